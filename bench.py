@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmarks of the MI355X light-curve likelihood engine.  One JSON line on stdout (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mcmc|companion|population|sed]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mcmc|companion|population|sed] [--dump-outputs DIR]
 
 Headline (`--workload mcmc`, the default): walker-steps/s of the ensemble sampler on BASELINE.json configs[1]
 (ShockCooling, 1024 walkers per GPU, 500 synthetic epochs x {U,B,V,g,r,i} = 3000 points, float64).  A "step" is one
@@ -92,7 +92,8 @@ def parse_args(argv=None):
                     help="'mcmc' (default) = the headline configs[1] line; the others print their own line")
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2000,
-                    help='ensemble steps in the timed region (BASELINE configs[1] runs 2000)')
+                    help='ensemble steps in the timed region (BASELINE configs[1] runs 2000); mcmc / companion repeat '
+                         'it LCF_BENCH_REPS times (5) and report the median repetition')
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--scaling', choices=['weak', 'strong'], default=None,
                     help='mcmc: weak (1024 walkers per GPU, default) or strong (1024 in all); companion: strong (the '
@@ -112,7 +113,32 @@ def parse_args(argv=None):
                     help='(internal) a fresh process times lightcurve_mcmc() calls from call to chain and prints them')
     ap.add_argument('--launch-check', action='store_true',
                     help='only start the ranks, let them find each other (gloo) and print what they saw')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step (the arrays its '
+                         'caller receives) as DIR/<name>.npy in float64; the inputs are seeded, so the files of two '
+                         'builds can be compared output for output')
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as float64 DIR/<name>.npy, at most DUMP_MAX_BYTES in all (rank 0 only)."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})')
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
+def last_step_outputs(sampler):
+    """What a caller of the timed run receives from its last step: every walker's position and log-posterior (the last
+    row of the stored chain, = the state run_mcmc returns) and the acceptance fraction the sampler reports after it."""
+    return {'coords': sampler.get_chain()[-1], 'log_prob': sampler.get_log_prob()[-1],
+            'acceptance_fraction': sampler.acceptance_fraction}
 
 
 def free_port():
@@ -567,6 +593,7 @@ def run_mcmc(args):
     t0 = time.perf_counter()
     chain_shape = sampler.get_chain().shape                                # 48 bytes per walker and step over PCIe
     download_s = time.perf_counter() - t0
+    outputs = last_step_outputs(sampler) if args.dump_outputs and rank == 0 else None  # (before the next run drops the chain)
     elapsed_nochain, _, _ = timed_run(sampler, dist, args.warmup, args.steps, None, store=False)
     coll = collective_info(sampler, dist, world)
     if coll is not None:
@@ -626,6 +653,8 @@ def run_mcmc(args):
                 out['cpu_baseline_c'] = {'error': repr(exc)}
         if world == 1 and os.environ.get('LCF_BENCH_NO_E2E') != '1':
             out['end_to_end'] = end_to_end_block(lc)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         emit(out)
     if dist is not None:
         dist.barrier()
@@ -758,6 +787,7 @@ def run_companion(args):
     elapsed, elapsed_all, device_ms = timed_run(sampler, dist, args.warmup, args.steps, x0)
     value = nw * args.steps / elapsed
     ran = {'kernel': sampler._native.last_run_kernel(), 'launches': sampler._native.last_run_launches()}
+    outputs = last_step_outputs(sampler) if args.dump_outputs and rank == 0 else None
     coll = collective_info(sampler, dist, world)
     if coll is not None:
         coll['probe'] = probe
@@ -797,6 +827,8 @@ def run_companion(args):
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline_companion(lc, lum0)
             out['speedup_vs_cpu_baseline'] = value / out['cpu_baseline']['value']
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         emit(out)
     if dist is not None:
         dist.barrier()
@@ -842,11 +874,15 @@ def run_population(args):
     if dist is not None:
         dist.barrier()
     t0 = time.perf_counter()
-    pop.run_mcmc(None, args.steps, store=True)    # every ensemble keeps its chain in HBM, as the reference's run does
+    states = pop.run_mcmc(None, args.steps, store=True)    # every ensemble keeps its chain in HBM, as the reference's run does
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = max_over_ranks(dist, time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:   # (this rank's transients: the states the timed run returned, transient-major)
+        dump_outputs(args.dump_outputs, {'coords': np.stack([states[k].coords for k in pop.indices]),
+                                         'log_prob': np.stack([states[k].log_prob for k in pop.indices]),
+                                         'acceptance_fraction': np.stack([pop[k].acceptance_fraction for k in pop.indices])})
     if rank == 0:
         eng = pop[pop.indices[0]].engine
         eng._variant = args.variant
@@ -925,6 +961,8 @@ def run_sed(args):
             res = like(cand, precision=prec)
             ms.append(like.engine.last_kernel_ms)
         out[prec] = (res, float(np.median(ms)))
+    if args.dump_outputs:    # (the log-likelihoods of every candidate from each precision's last timed call)
+        dump_outputs(args.dump_outputs, {'log_likelihood_' + prec.replace('-', '_'): res for prec, (res, _) in out.items()})
     alg_samples = n_ep * n_c * (13 + 11 + 15 + 89 + 75 + 89)
     # quads the sample-table kernels walk per candidate: the compressed ("cool") table of a filter where the candidate is
     # hot enough
