@@ -349,6 +349,24 @@ lcf_status lcf_sed_set_observations(lcf_sed* s, int64_t n_epochs, const int32_t*
 lcf_status lcf_sed_log_likelihood(lcf_sed* s, int64_t n_cand, int32_t n_par, int32_t sigma_type, const double* cand,
                                   int32_t precision, int32_t use_compressed, double* out, double* kernel_ms);
 
+/* ---- bolometric light curves (bolometric.py:483-534, 32-59, 422-453) ------------------------------------------ */
+/* blackbody_lstsq for many epochs in one launch: for epoch e, points ep_off[e] .. ep_off[e+1]-1 (observed freq_eff
+ * [THz], luminosity density lum [W/Hz]), the bounded, unweighted least-squares fit of planck_fast(freq (1+z), T, R,
+ * cutoff_freq) from p0[e] = (T, R) within lo[e] <= (T, R) <= hi[e] (projected Levenberg-Marquardt, analytic Jacobian),
+ * until no variable moves by more than xtol relative or max_iter iterations.  out[e][8] = T, R, cost = 1/2 sum r^2,
+ * cov_TT, cov_TR, cov_RR (curve_fit's: pinv(J^T J) 2 cost / (m - 2), +inf when m <= 2), iterations, 0.
+ * status[e]: 1 converged (step below xtol), 2 converged (projected gradient zero), 0 iteration cap, -1 no points or a
+ * non-finite input or cost.  p0 outside [lo, hi] is LCF_ERR_INVALID_ARGUMENT. */
+lcf_status lcf_bb_lstsq(int32_t device, int64_t n_epochs, const int32_t* ep_off, const double* freq, const double* lum,
+                        const double* p0, const double* lo, const double* hi, double z, double cutoff_freq,
+                        int32_t max_iter, double xtol, double* out, int32_t* status);
+/* pseudo() and stefan_boltzmann() of n samples (T [kK], R [1000 Rsun]): L_pseudo[k] = 1e12 x the trapezoid (end
+ * weights 1/2) of planck_fast((freq0 + j)(1+z), T, R, cutoff_freq) over j < n_grid, where the host passes
+ * freq0 = I.freq_eff - I.dfreq/2 and n_grid = len(np.arange(freq0, U.freq_eff + U.dfreq/2)); L_bol[k] = 4 pi R^2
+ * sigma_SB T^4 [W]. */
+lcf_status lcf_bb_luminosity(int32_t device, int64_t n, const double* T, const double* R, double z, double freq0,
+                             int32_t n_grid, double cutoff_freq, double* L_pseudo, double* L_bol);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,10 @@ SIGNATURES = [
     ('lcf_sed_set_observations', C.c_int, [C.c_void_p, C.c_int64, _ip, _ip, _dp, _dp]),
     ('lcf_sed_log_likelihood', C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp,
                                          _dp]),
+    ('lcf_bb_lstsq', C.c_int, [C.c_int32, C.c_int64, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32,
+                               C.c_double, _dp, _ip]),
+    ('lcf_bb_luminosity', C.c_int, [C.c_int32, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_int32, C.c_double, _dp,
+                                    _dp]),
 ]
 
 
@@ -639,3 +643,32 @@ class SedEngine:
                                                 int(precision), int(bool(compressed)), _ptr(out), C.byref(ms)))
         self.last_kernel_ms = ms.value
         return out
+
+
+def bb_lstsq(ep_off, freq, lum, p0, lo, hi, z=0., cutoff_freq=np.inf, max_iter=500, xtol=1e-12, device=0):
+    """``lcf_bb_lstsq``: bounded least-squares blackbody fits of many epochs in one launch.  ``p0``, ``lo``, ``hi``:
+    (n_epochs, 2).  Returns ``(out[n_epochs, 8], status[n_epochs])`` (columns: T, R, cost, cov_TT, cov_TR, cov_RR,
+    iterations, 0)."""
+    lib = load_library()
+    off, freq, lum = _i32(ep_off), _f64(freq), _f64(lum)
+    n = len(off) - 1
+    if n < 0 or off[0] != 0 or not (len(freq) == len(lum) == off[-1]):
+        raise ValueError('freq and lum must have ep_off[-1] entries, ep_off[0] == 0')
+    p0, lo, hi = (_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n, 2))) for a in (p0, lo, hi))
+    out = np.empty((n, 8))
+    status = np.empty(n, dtype=np.int32)
+    _check(lib.lcf_bb_lstsq(int(device), n, _ptr(off, _ip), _ptr(freq), _ptr(lum), _ptr(p0), _ptr(lo), _ptr(hi),
+                            float(z), float(cutoff_freq), int(max_iter), float(xtol), _ptr(out), _ptr(status, _ip)))
+    return out, status
+
+
+def bb_luminosity(T, R, z, freq0, n_grid, cutoff_freq=np.inf, device=0):
+    """``lcf_bb_luminosity``: (L_pseudo, L_bol) [W] of every (T, R) sample."""
+    lib = load_library()
+    T, R = _f64(T), _f64(R)
+    if T.shape != R.shape:
+        raise ValueError('T and R must have the same shape')
+    Lp, Lb = np.empty(T.shape), np.empty(T.shape)
+    _check(lib.lcf_bb_luminosity(int(device), T.size, _ptr(T), _ptr(R), float(z), float(freq0), int(n_grid),
+                                 float(cutoff_freq), _ptr(Lp), _ptr(Lb)))
+    return Lp, Lb

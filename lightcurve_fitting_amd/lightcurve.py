@@ -4,9 +4,13 @@ Host-side, one-off work: the step *before* the hot 
 store (dict of NumPy arrays + ``meta``) exposing the part of the reference's ``LC(astropy.table.Table)`` API that
 ``lightcurve_mcmc`` and the models touch (``lightcurve.py:62-360, 677-681, 912-941`` in the reference):
 ``LC.read``, ``lc[col]``, ``lc.colnames``, ``lc.meta``, ``where``, ``filters_to_objects``, ``zp``, ``calcAbsMag``,
-``calcLum``, ``calcFlux`` and the free functions ``mag2flux`` / ``flux2mag``.
+``calcLum``, ``calcFlux``, ``calcMag``, ``findNondet``, ``bin`` and the free functions ``mag2flux`` / ``flux2mag`` /
+``binflux`` (``lightcurve.py:206-270, 944-1000``).
 
-Not reproduced: plotting, binning and the Planck18 distance modulus (pass ``dm``).  E(B-V)-based extinction uses
+The reference's table is an astropy ``Table`` with masked columns; this one has no masks.  A missing entry of the
+``epoch`` column (``bolometric.group_by_epoch``) is ``NaN``, and an output value the reference masks is ``NaN``.
+
+Not reproduced: plotting and the Planck18 distance modulus (pass ``dm``).  E(B-V)-based extinction uses
 ``extinction.py`` (the Fitzpatrick 1999 law restated; third-party arithmetic for the reference).
 """
 import numpy as np
@@ -53,6 +57,56 @@ def flux2mag(flux, dflux=np.array(np.nan), zp=0., nondet=None, nondetSigmas=3.):
     return mag, dmag
 
 
+def binflux(time, flux, dflux, delta=0.2, include_zero=True):
+    """Bin a light curve by averaging points within ``delta`` of the first remaining point (lightcurve.py:944-1000):
+    inverse-variance weighted fluxes; a bin holding a point without an error bar (0, 999, 9999, -1 or NaN) is the plain
+    mean with uncertainty 0 when ``include_zero``, else such points are left out."""
+    time, flux, dflux = (np.asarray(a, dtype=float) for a in (time, flux, dflux))
+    bin_time, bin_flux, bin_dflux = [], [], []
+    while len(flux) > 0:
+        grp = np.abs(time - time[0]) <= delta
+        time_grp, flux_grp, dflux_grp = time[grp], flux[grp], dflux[grp]
+        zeros = (dflux_grp == 0) | (dflux_grp == 999) | (dflux_grp == 9999) | (dflux_grp == -1) | np.isnan(dflux_grp)
+        if any(zeros) and include_zero:
+            x, y, z = np.mean(time_grp), np.mean(flux_grp), 0.
+        else:
+            time_grp, flux_grp, dflux_grp = time_grp[~zeros], flux_grp[~zeros], dflux_grp[~zeros]
+            x = np.mean(time_grp)
+            y = np.sum(flux_grp * dflux_grp ** -2) / np.sum(dflux_grp ** -2)
+            z = np.sum(dflux_grp ** -2) ** -0.5
+        bin_time.append(x)
+        bin_flux.append(y)
+        bin_dflux.append(z)
+        time, flux, dflux = time[~grp], flux[~grp], dflux[~grp]
+    return np.array(bin_time), np.array(bin_flux), np.array(bin_dflux)
+
+
+def _group_keys(column):
+    """Sort key of a grouping column's entries: filters by their own order, everything else as it compares."""
+    return np.array([str(v) for v in column]) if column.dtype == object and not all(
+        isinstance(v, Filter) for v in column) else column
+
+
+def _group_rows(lc, keys):
+    """Row indices of each distinct combination of ``keys`` (astropy ``group_by``: groups sorted by the keys, rows in
+    table order within a group)."""
+    if not keys:
+        return [np.arange(len(lc))]
+    codes = []
+    for k in keys:
+        col = lc[k]
+        if col.dtype == object and all(isinstance(v, Filter) for v in col):
+            uniq = sorted(set(col))
+            lookup = {f: i for i, f in enumerate(uniq)}
+            codes.append(np.array([lookup[v] for v in col]))
+        else:
+            codes.append(np.unique(_group_keys(col), return_inverse=True)[1].ravel())
+    order = np.lexsort(codes[::-1])   # (lexsort: the last key is the primary one; stable)
+    stacked = np.column_stack(codes)[order]
+    bounds = np.flatnonzero(np.any(np.diff(stacked, axis=0) != 0, axis=1)) + 1
+    return np.split(order, bounds)
+
+
 def _convert(tokens):
     """Column of strings -> float, bool or str array."""
     try:
@@ -71,9 +125,11 @@ class LC:
         self.columns = {}
         self.meta = dict(meta or {})
         self.nondetSigmas = 3.
+        self.groupby = {'filter', 'source'}
         if isinstance(data, LC):
             self.meta = dict(data.meta)
             self.nondetSigmas = data.nondetSigmas
+            self.groupby = set(data.groupby)
             data = data.columns
         for k, v in (data or {}).items():
             self[k] = v
@@ -117,6 +173,7 @@ class LC:
         out = LC.__new__(LC)
         out.meta = dict(self.meta)
         out.nondetSigmas = self.nondetSigmas
+        out.groupby = set(getattr(self, 'groupby', {'filter', 'source'}))
         out.columns = {k: v[item] for k, v in self.columns.items()}
         return out
 
@@ -197,6 +254,49 @@ class LC:
             zp = self.zp
         nondet = self['nondet'] if 'nondet' in self else None
         self['flux'], self['dflux'] = mag2flux(self['mag'], self['dmag'], zp, nondet, self.nondetSigmas)
+
+    def bin(self, delta=0.3, groupby=None):
+        """Light curve binned by :func:`binflux` within each group of ``groupby`` (default ``{'filter', 'source'}``;
+        only the columns present count) (lightcurve.py:206-251).  The result holds ``MJD``, ``flux``, ``dflux`` and
+        the grouping columns, groups in the order of their keys; its ``meta`` is this light curve's (the same
+        dictionary, as in the reference)."""
+        if groupby is not None:
+            self.groupby = groupby
+        keys = sorted(set(self.groupby) & set(self.colnames))
+        self.groupby = set(keys)
+        parts = {k: [] for k in ['MJD', 'flux', 'dflux'] + keys}
+        for rows in _group_rows(self, keys):
+            if not len(rows):
+                continue
+            mjd, flux, dflux = binflux(self['MJD'][rows], self['flux'][rows], self['dflux'][rows], delta)
+            for name, v in (('MJD', mjd), ('flux', flux), ('dflux', dflux)):
+                parts[name].append(v)
+            for k in keys:
+                col = np.empty(len(mjd), dtype=self[k].dtype)
+                col[:] = [self[k][rows[0]]] * len(mjd)
+                parts[k].append(col)
+        out = LC.__new__(LC)
+        out.columns = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in parts.items()}
+        out.meta = self.meta
+        out.nondetSigmas = self.nondetSigmas
+        out.groupby = set(keys)
+        return out
+
+    def findNondet(self, nondetSigmas=None):
+        """Boolean ``'nondet'``: flux below ``nondetSigmas`` times its uncertainty (lightcurve.py:253-264)."""
+        if nondetSigmas is not None:
+            self.nondetSigmas = nondetSigmas
+        self['nondet'] = np.asarray(self['flux'] < self.nondetSigmas * np.asarray(self['dflux']), dtype=bool)
+
+    def calcMag(self, nondetSigmas=None, zp=None):
+        """``'mag'`` / ``'dmag'`` from ``'flux'`` / ``'dflux'`` after :meth:`findNondet` (lightcurve.py:266-282);
+        a nondetection's magnitude is the ``nondetSigmas`` limit and its ``dmag`` is NaN."""
+        if nondetSigmas is not None:
+            self.nondetSigmas = nondetSigmas
+        self.findNondet()
+        if zp is None:
+            zp = self.zp
+        self['mag'], self['dmag'] = flux2mag(self['flux'], self['dflux'], zp, self['nondet'], self.nondetSigmas)
 
     def calcAbsMag(self, dm=None, extinction=None, hostext=None, ebv=None, rv=None, host_ebv=None, host_rv=None,
                    redshift=None):

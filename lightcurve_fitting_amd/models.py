@@ -146,6 +146,8 @@ class Model:
     reddened = False
     #: photometry-bound engines one model keeps (each holds a copy of a light curve on the device)
     max_bound_engines = 8
+    #: cutoff frequency [THz] of a modified blackbody (filters.py:308-310); only Blackbody takes another value
+    cutoff_freq = np.inf
 
     def __init__(self, lc=None, redshift=0.):
         if redshift:
@@ -200,7 +202,8 @@ class Model:
         t0 = time.perf_counter()
         filts = [as_filter(f) for f in filts]
         uniq, idx = _index_filters(filts)
-        tabs = PackedTables(uniq, z=self.z, compress=not self.reddened, reddening=self.reddened)
+        tabs = PackedTables(uniq, z=self.z, cutoff_freq=self.cutoff_freq, compress=not self.reddened,
+                            reddening=self.reddened)
         t1 = time.perf_counter()
         pri = None if priors is None else [p.descriptor() for p in priors]
         eng = _eng.Engine(self.model_id, self.n_model_params, self._consts(), t, y, dy, idx, tabs.off, tabs.a, tabs.w,
@@ -518,6 +521,10 @@ class Blackbody(Model):
     model_id = _eng.MODEL_BLACKBODY
     input_names = ['T', 'R']
     units = ['kK', '1000 Rsun']
+
+    def __init__(self, lc=None, redshift=0., cutoff_freq=np.inf):
+        super().__init__(lc, redshift)
+        self.cutoff_freq = cutoff_freq   # (the band tables of every engine this model makes)
 
     def _eval_engine(self, t_in, f, scalar_params=True):
         # not a reference Model: one (filter, time) point per entry even for arrays of candidates, result (npoints, n)
