@@ -367,6 +367,19 @@ lcf_status lcf_bb_lstsq(int32_t device, int64_t n_epochs, const int32_t* ep_off,
 lcf_status lcf_bb_luminosity(int32_t device, int64_t n, const double* T, const double* R, double z, double freq0,
                              int32_t n_grid, double cutoff_freq, double* L_pseudo, double* L_bol);
 
+/* ---- integrated autocorrelation time (emcee.autocorr.integrated_time, without its tol check) ------------------ */
+/* Per parameter d: f[tau] = mean over walkers of the walker's autocorrelation at lag tau normalised by its lag 0,
+ * taus = 2 cumsum(f) - 1, window[d] = argmin(k < c taus[k]) if any k satisfies it, else n_t - 1, and
+ * tau[d] = taus[window[d]] (NaN with window n_t - 1 where a walker's series is constant).  Only the lags up to the
+ * window are computed.  Host chain[n_t][n_w][n_d]; uploaded, processed and freed. */
+lcf_status lcf_autocorr_time(int32_t device, const double* chain, int64_t n_t, int32_t n_w, int32_t n_d, double c,
+                             double* tau, int64_t* window);
+/* The same for the stored chains of n samplers (one device), read in place on the device: rows discard,
+ * discard + thin, ... of each sampler's last stored run.  tau / window hold each sampler's n_dim entries one after
+ * another.  LCF_ERR_STATE when a sampler has no stored chain; discard past the chain is LCF_ERR_INVALID_ARGUMENT. */
+lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double c,
+                                      double* tau, int64_t* window);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5509,6 +5509,28 @@ lcf_status lcf_sampler_get_chain(lcf_sampler* s, double* chain, double* log_prob
     return LCF_OK;
 }
 
+lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double c,
+                                      double* tau, int64_t* window) {
+    if (!s || n < 1 || !tau || !window) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
+    if (!std::isfinite(c)) return fail(LCF_ERR_INVALID_ARGUMENT, "c must be finite");
+    for (int32_t i = 0; i < n; ++i) {
+        if (!s[i]) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
+        if (!s[i]->ds.store_chain || s[i]->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
+        if (discard >= s[i]->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
+        if (s[i]->e->device != s[0]->e->device) return fail(LCF_ERR_UNSUPPORTED, "the samplers are on different devices");
+    }
+    std::vector<AutocorrSeries> series(n);
+    for (int32_t i = 0; i < n; ++i) {
+        if (lcf_status st = settle(s[i])) return st;  // (the trailing commit writes the last chain row)
+        const DevSampler& ds = s[i]->ds;
+        const int64_t row = (int64_t)ds.n_walkers * ds.n_dim;
+        series[i] = AutocorrSeries{ds.chain + discard * row, (s[i]->run_steps - discard + thin - 1) / thin, thin * row,
+                                   ds.n_walkers, ds.n_dim};
+    }
+    return autocorr_run(s[0]->e->device, series.data(), n, c, tau, window);
+}
+
 lcf_status lcf_sampler_get_naccepted(lcf_sampler* s, int64_t* n_accepted) {
     if (!s || !n_accepted) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = settle(s)) return st;

@@ -73,4 +73,13 @@ lcf_status upload(const std::vector<T>& h, T** d, UploadArena& arena) {
     return arena.put(h.data(), h.size() * sizeof(T), (void**)d);
 }
 
+// Autocorrelation time (lcf_autocorr.hip): one series per walker and parameter; element t of series (w, d) at
+// chain[t * row_stride + w * n_d + d] in device memory.  tau / window receive n_d entries per entry of `in`, in order.
+struct AutocorrSeries {
+    const double* chain;
+    int64_t n_t, row_stride;
+    int32_t n_w, n_d;
+};
+lcf_status autocorr_run(int32_t device, const AutocorrSeries* in, int32_t n, double c, double* tau, int64_t* window);
+
 }  // namespace lcf

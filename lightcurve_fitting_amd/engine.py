@@ -134,6 +134,10 @@ SIGNATURES = [
                                C.c_double, _dp, _ip]),
     ('lcf_bb_luminosity', C.c_int, [C.c_int32, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_int32, C.c_double, _dp,
                                     _dp]),
+    ('lcf_autocorr_time', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_double, _dp,
+                                    C.POINTER(C.c_int64)]),
+    ('lcf_samplers_autocorr_time', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp,
+                                             C.POINTER(C.c_int64)]),
 ]
 
 
@@ -672,3 +676,34 @@ def bb_luminosity(T, R, z, freq0, n_grid, cutoff_freq=np.inf, device=0):
     _check(lib.lcf_bb_luminosity(int(device), T.size, _ptr(T), _ptr(R), float(z), float(freq0), int(n_grid),
                                  float(cutoff_freq), _ptr(Lp), _ptr(Lb)))
     return Lp, Lb
+
+
+def autocorr_time(chain, c=5., device=0):
+    """``lcf_autocorr_time``: emcee's integrated autocorrelation time (without the ``tol`` check) of a host chain
+    (n_t, n_w, n_d).  Returns ``(tau[n_d], window[n_d])``."""
+    lib = load_library()
+    x = _f64(chain)
+    if x.ndim != 3:
+        raise ValueError('chain must have shape (n_t, n_w, n_d)')
+    n_t, n_w, n_d = x.shape
+    tau, window = np.empty(n_d), np.empty(n_d, dtype=np.int64)
+    _check(lib.lcf_autocorr_time(int(device), _ptr(x), n_t, n_w, n_d, float(c), _ptr(tau),
+                                 window.ctypes.data_as(C.POINTER(C.c_int64))))
+    return tau, window
+
+
+def samplers_autocorr_time(native_samplers, discard=0, thin=1, c=5.):
+    """``lcf_samplers_autocorr_time``: the same for the device-resident chains of the last stored run of several
+    :class:`NativeSampler` objects (one sequence of launches for all).  Returns a list of ``(tau, window)``."""
+    lib = load_library()
+    n = len(native_samplers)
+    arr = (C.c_void_p * n)(*[s._h for s in native_samplers])
+    total = sum(s.ndim for s in native_samplers)
+    tau, window = np.empty(total), np.empty(total, dtype=np.int64)
+    _check(lib.lcf_samplers_autocorr_time(arr, n, int(discard), int(thin), float(c), _ptr(tau),
+                                          window.ctypes.data_as(C.POINTER(C.c_int64))))
+    out, k = [], 0
+    for s in native_samplers:
+        out.append((tau[k:k + s.ndim].copy(), window[k:k + s.ndim].copy()))
+        k += s.ndim
+    return out

@@ -237,6 +237,41 @@ class PopulationSampler:
             s._finish(nsteps, store)
         return {k: s._state for k, s in self.samplers.items()}
 
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False, has_walkers=True):
+        """``{index: tau}`` of this rank's transients, each as ``EnsembleSampler.get_autocorr_time`` gives it; the
+        chains still on the device go through one native call together.  If any transient fails the ``tol`` test,
+        ``quiet=False`` raises one :class:`~lightcurve_fitting_amd.autocorr.AutocorrError` whose ``.tau`` is the
+        whole dict (``quiet=True`` logs one warning per such transient)."""
+        from .autocorr import AutocorrError, convergence_message, logger
+        from .engine import samplers_autocorr_time
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        resident = [k for k, s in self.samplers.items() if len(s._chain_host) == 0 and s._chain_on_device > 0]
+        est = {}
+        for k, s in self.samplers.items():
+            if k not in resident:
+                est[k] = s._autocorr(discard, thin, c)
+            elif len(range(discard, s.iteration, thin)) == 0:
+                raise ValueError(f'discard={discard} leaves no steps of the {s.iteration} stored (transient {k})')
+        if resident:
+            got = samplers_autocorr_time([self.samplers[k]._native for k in resident], discard, thin, c)
+            for k, (tau, window) in zip(resident, got):
+                est[k] = (tau, window, len(range(discard, self.samplers[k].iteration, thin)))
+        taus, raw, msgs = {}, {}, []
+        for k in self.samplers:
+            tau, _, n_t = est[k]
+            raw[k] = tau
+            msg = convergence_message(tau, n_t, tol)
+            if msg is not None:
+                if quiet:
+                    logger.warning(msg)
+                msgs.append(f'transient {k}: {msg}')
+            taus[k] = thin * tau
+        if msgs and not quiet:
+            raise AutocorrError(raw, '\n'.join(msgs))
+        return taus
+
     def __getitem__(self, k):
         return self.samplers[k]
 
@@ -629,6 +664,31 @@ class EnsembleSampler:
     def get_chain(self, flat=False, thin=1, discard=0):
         c = self._chain[discard::thin]
         return c.reshape(-1, self.ndim) if flat else c
+
+    def _autocorr(self, discard, thin, c):
+        """``(tau, window, n_t)`` of the stored chain's rows ``discard::thin``, without the ``tol`` check: on the
+        device chain in place when the whole stored chain is the last run's, else on ``get_chain`` (host entry)."""
+        from .engine import autocorr_time, samplers_autocorr_time
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        if self.iteration == 0:
+            raise ValueError('no chain is stored: run the sampler with store=True first')
+        n_t = len(range(discard, self.iteration, thin))
+        if n_t == 0:
+            raise ValueError(f'discard={discard} leaves no steps of the {self.iteration} stored')
+        if len(self._chain_host) == 0 and self._chain_on_device > 0:
+            tau, window = samplers_autocorr_time([self._native], discard, thin, c)[0]
+        else:
+            tau, window = autocorr_time(self.get_chain(discard=discard, thin=thin), c, device=self.engine.device)
+        return tau, window, n_t
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False, has_walkers=True):
+        """``thin * integrated_time(self.get_chain(discard=discard, thin=thin), c, tol, quiet)``, emcee's definition
+        (``lightcurve_fitting_amd.autocorr``).  The chain of the last run is read where it lies in device memory."""
+        from .autocorr import check_convergence
+        tau, _, n_t = self._autocorr(discard, thin, c)
+        return thin * check_convergence(tau, n_t, tol, quiet)
 
     def get_log_prob(self, flat=False, thin=1, discard=0):
         lp = self._lp[discard::thin]
