@@ -2664,28 +2664,81 @@ lcf_status lcf_engine::sync_dp() {
 
 namespace {
 
-// More than the default 64 KiB of dynamic LDS must be granted per kernel function -- and per DEVICE: the attribute
-// belongs to the current device's copy of the function, so it is set before every such launch (cheap next to one; a
-// per-process flag would leave the second device of a process without it).
-template <class K>
-inline void allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// ---- the instantiation table: which kernels exist ---------------------------------------------------------------------
+// A launch site takes its family's instantiation for the fit dimension through dispatch(); a dimension outside the
+// family's list takes the generic kernel, ND = 0 (the dimension at run time).  Models with kernels of their own take
+// them through dispatch_model() at their own dimension.  Every instantiation costs compile time.
+template <int... V> struct Dims {};
+template <int M, int ND> struct Model {};              // model M's own kernels, at fit dimension ND
+template <class... S> struct Models {};
+template <int ND, int NP, int M> struct RunRow {};     // k_solo_run<ND, 1, true, NP, M, ...>
+template <class... R> struct RunRows {};
+// (k_solo, k_solo_run and k_pop; 0 = none, the generic kernel)
+using SpecialisedModels = Models<Model<kShockCooling, 5>, Model<kShockCooling2, 4>>;
+#ifndef LCF_DEV_BUILD
+using StepDims = Dims<2, 3, 4, 5, 6, 7, 8, 9>;   // k_step: the fit dimensions of the supported models (+ sigma)
+using SoloDims = Dims<4, 5, 6, 7, 8, 9>;         // k_fused, k_solo, k_solo_run
+using PopDims = Dims<4, 5, 6, 8>;                // k_pop, k_step_multi
+using PopRunModels = SpecialisedModels;          // k_pop_run (otherwise generic only)
+// k_solo_run between ranks (RANKS), row by row: the benchmark shapes' own kernels and the companion fit's dimension;
+// everything else takes the generic kernel
+using RanksRuns = RunRows<RunRow<5, 2, kShockCooling>, RunRow<4, 2, kShockCooling2>, RunRow<8, 2, 0>, RunRow<8, 8, 0>,
+                          RunRow<8, 4, 0>>;
+#else   // the device-only compile of the ISA report: the benchmarks' dimensions, the counted kernels
+using StepDims = Dims<5, 8>;
+using SoloDims = Dims<5, 8>;
+using PopDims = Dims<5, 8>;
+using PopRunModels = Models<Model<kShockCooling, 5>>;
+using RanksRuns = RunRows<RunRow<5, 2, kShockCooling>>;
+#endif
+using WideRuns = RunRows<RunRow<8, 8, 0>>;   // k_solo_run of 1024 threads on one GPU: the eight-parameter models
+#ifdef LCF_POP_GROUPS_ALL
+using PopRunGroups = Dims<4, 10, 12>;        // k_pop_run's proposals per workgroup besides kPopRunGroup (LCF_POP_GROUP)
+#else
+using PopRunGroups = Dims<>;
+#endif
+
+template <int V> using Int = std::integral_constant<int, V>;
+
+// f(Int<V>) for the entry V of the list equal to v; f(Int<OTHER>) when there is none.
+template <int OTHER = 0, int... V, class F>
+void dispatch(Dims<V...>, int v, F&& f) {
+    if (!((v == V && (f(Int<V>{}), true)) || ...)) f(Int<OTHER>{});
+}
+
+// f(Int<ND>, Int<M>) for the entry of the list with M = spec and ND = n_dim; false when there is none.
+template <int... M, int... ND, class F>
+bool dispatch_model(Models<Model<M, ND>...>, int n_dim, int spec, F&& f) {
+    return ((n_dim == ND && spec == M && (f(Int<ND>{}, Int<M>{}), true)) || ...);
+}
+
+// f(Int<ND>, Int<NP>, Int<M>) for the row (n_dim, np, spec) of the list; false when there is none.
+template <int... ND, int... NP, int... M, class F>
+bool dispatch_row(RunRows<RunRow<ND, NP, M>...>, int n_dim, int np, int spec, F&& f) {
+    return ((n_dim == ND && np == NP && spec == M && (f(Int<ND>{}, Int<NP>{}, Int<M>{}), true)) || ...);
+}
+
+template <int... ND, int... NP, int... M>
+constexpr bool has_dim(RunRows<RunRow<ND, NP, M>...>, int n_dim) {
+    return ((n_dim == ND) || ...);
+}
+
+template <int... M, int... ND>
+constexpr int table_model(Models<Model<M, ND>...>, int model, int n_dim) {
+    return ((model == M && n_dim == ND ? M : 0) + ...);
 }
 
 template <int VARIANT, int MODE>
 void launch_points_v(const DevProblem& pb, dim3 grid, size_t lds, hipStream_t st, int w_lo, int n, const double* dP,
                      const double* coef, const double* lprior, const double2* therm, double* out0, double* out1) {
-    const dim3 block(kBlock);
-#define LCF_GO(L, T) do { allow_lds(k_points<VARIANT, MODE, L, T>, lds);                                               \
-                          hipLaunchKernelGGL((k_points<VARIANT, MODE, L, T>), grid, block, lds, st, pb, w_lo, n, dP, coef, \
-                                             lprior, therm, out0, out1); } while (0)
-    if (pb.tab_in_lds) {
-        if (pb.use_therm) LCF_GO(true, true); else LCF_GO(true, false);
-    } else {
-        if (pb.use_therm) LCF_GO(false, true); else LCF_GO(false, false);
-    }
-#undef LCF_GO
+    const auto go = [&](auto kernel) {
+        prepare_kernel(kernel, lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, st, pb, w_lo, n, dP, coef, lprior, therm, out0, out1);
+    };
+    if (pb.tab_in_lds)
+        pb.use_therm ? go(k_points<VARIANT, MODE, true, true>) : go(k_points<VARIANT, MODE, true, false>);
+    else
+        pb.use_therm ? go(k_points<VARIANT, MODE, false, true>) : go(k_points<VARIANT, MODE, false, false>);
 }
 
 // Launches the per-point kernel for walkers [w_lo, w_lo + n) (absolute indices into P / coef / lprior / therm).
@@ -3484,8 +3537,6 @@ struct lcf_sampler {
     DevSampler rows_image_host{};
     bool rows_image_valid = false;
     unsigned int rows_arrivals = 0;          // the same count for the resident launches of row-board runs (cleared per run)
-    int run_capacity = -1;                   // workgroups of k_solo_run the device holds at once (-1: not asked yet)
-    int run_capacity_wide = -1;              // ... of its 1024-thread form (NPARTS = 8)
     size_t run_board_bytes() const {
         return board_rows_bytes(kRunRing, ds.n_walkers, ds.n_dim) + (size_t)kBoardTail * sizeof(unsigned int);
     }
@@ -3548,6 +3599,18 @@ struct lcf_sampler {
         const int64_t b = block_of_step(rel / 2);
         return d_draws[b & 1] + (size_t)(rel - 2 * block_start(b)) * ds.n_half;
     }
+    // half-steps of a resident launch from the run's half-step `rel` on: up to `max_span`, never past the end of the
+    // current block of draw records
+    int block_span(long long rel, int max_span) const {
+        return (int)std::min<long long>(max_span, 2 * (block_start(blk_current) + block_len(blk_current)) - rel);
+    }
+    // the other set of state buffers holds the state now (see alt_X)
+    void flip_state_sets() {
+        std::swap(ds.X, alt_X);
+        std::swap(ds.LP, alt_LP);
+        std::swap(ds.nacc, alt_nacc);
+        run_flip = !run_flip;
+    }
 };
 
 namespace {
@@ -3563,6 +3626,7 @@ lcf_status generate_steps(lcf_sampler* s, int buf, int64_t step0, int64_t len, i
         int n_pad = 2;
         while (n_pad < ds.n_walkers) n_pad <<= 1;
         const int threads = std::min(1024, std::max(64, n_pad / 2));
+        LCF_HIP(prepare_kernel(k_make_perm, (size_t)n_pad * 8));
         hipLaunchKernelGGL(k_make_perm, dim3((unsigned)len), dim3(threads), (size_t)n_pad * 8, gs, ds.n_walkers, n_pad,
                            ds.key0, ds.key1, (long long)step0, s->d_perm[buf], ds.n_half,
                            need_slots ? s->d_slot[buf] : nullptr, front);
@@ -3661,23 +3725,10 @@ lcf_status launch_next(lcf_sampler* s, bool have_next, int lo, int hi, hipStream
         if (lcf_status r = enter_half_step(s, rel, st)) return r;
     const DrawRec* draws = have_next ? s->rows(rel) : nullptr;
     const DrawRec* prev_draws = have_prev ? s->rows(rel - 1) : nullptr;
-#define LCF_STEP(ND) hipLaunchKernelGGL(k_step<ND>, dim3((unsigned)ds.n_half), dim3(64), 0, st, \
-                                        e->dp, ds, have_prev, prev_row, have_next ? 1 : 0, draws, prev_draws, g, lo, hi, \
-                                        s->coef, s->lprior)
-    switch (ds.n_dim) {  // the fit dimensions of the supported models (+ sigma) get dedicated instantiations
-#ifndef LCF_DEV_BUILD
-        case 2: LCF_STEP(2); break;
-        case 3: LCF_STEP(3); break;
-        case 4: LCF_STEP(4); break;
-        case 6: LCF_STEP(6); break;
-        case 7: LCF_STEP(7); break;
-        case 9: LCF_STEP(9); break;
-#endif
-        case 5: LCF_STEP(5); break;
-        case 8: LCF_STEP(8); break;
-        default: LCF_STEP(0); break;
-    }
-#undef LCF_STEP
+    dispatch(StepDims{}, ds.n_dim, [&](auto nd) {
+        hipLaunchKernelGGL(k_step<decltype(nd)::value>, dim3((unsigned)ds.n_half), dim3(64), 0, st, e->dp, ds, have_prev, prev_row,
+                           have_next ? 1 : 0, draws, prev_draws, g, lo, hi, s->coef, s->lprior);
+    });
     LCF_HIP(hipGetLastError());
     if (have_next)
         if (lcf_status r = leave_half_step(s, st)) return r;
@@ -3731,27 +3782,17 @@ lcf_status launch_fused(lcf_sampler* s, int lo, int hi, hipStream_t st) {
     const dim3 grid((unsigned)((size_t)(hi - lo) * e->dp.n_parts + (foreign + kBlock / 64 - 1) / (kBlock / 64)));
     const size_t lds = fused_lds_bytes(e);
     double* lprior = ds.inline_finalize ? nullptr : s->lprior;  // the finalize launch of a sharded run reads it
-#define LCF_FUSED3(ND, V, T) do { allow_lds(k_fused<ND, V, T>, lds);                                                     \
-                                  hipLaunchKernelGGL((k_fused<ND, V, T>), grid, dim3(kBlock), lds, st, e->dp, ds,       \
-                                                     have_prev, prev_row, draws, prev_draws, g, lo, hi, lprior); } while (0)
-#define LCF_FUSED(ND)                                                                             \
-    do {                                                                                          \
-        if (e->dp.variant == 0) { if (e->dp.use_therm) LCF_FUSED3(ND, 0, true); else LCF_FUSED3(ND, 0, false); } \
-        else { if (e->dp.use_therm) LCF_FUSED3(ND, 1, true); else LCF_FUSED3(ND, 1, false); }      \
-    } while (0)
-    switch (ds.n_dim) {
-#ifndef LCF_DEV_BUILD
-        case 4: LCF_FUSED(4); break;
-        case 6: LCF_FUSED(6); break;
-        case 7: LCF_FUSED(7); break;
-        case 9: LCF_FUSED(9); break;
-#endif
-        case 5: LCF_FUSED(5); break;
-        case 8: LCF_FUSED(8); break;
-        default: LCF_FUSED(0); break;
-    }
-#undef LCF_FUSED
-#undef LCF_FUSED3
+    const auto go = [&](auto kernel) {
+        prepare_kernel(kernel, lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, st, e->dp, ds, have_prev, prev_row, draws, prev_draws, g, lo, hi,
+                           lprior);
+    };
+    const bool v1 = e->dp.variant != 0, therm = e->dp.use_therm;
+    dispatch(SoloDims{}, ds.n_dim, [&](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        if (v1) therm ? go(k_fused<ND, 1, true>) : go(k_fused<ND, 1, false>);
+        else therm ? go(k_fused<ND, 0, true>) : go(k_fused<ND, 0, false>);
+    });
     LCF_HIP(hipGetLastError());
     if (lcf_status r = leave_half_step(s, st)) return r;
     s->pending = true;
@@ -3783,9 +3824,7 @@ int specialised_model(const DevProblem& dp) {
     static const bool disabled = std::getenv("LCF_NO_SPECIALISED") != nullptr;
     if (disabled || !dp.use_therm || !dp.use_itab || dp.variant == 0 || !dp.em_dense || !dp.itab_uniform || dp.use_sigma)
         return 0;
-    if (dp.model == kShockCooling && dp.n_dim == 5) return kShockCooling;
-    if (dp.model == kShockCooling2 && dp.n_dim == 4) return kShockCooling2;
-    return 0;
+    return table_model(SpecialisedModels{}, dp.model, dp.n_dim);
 }
 
 // One half-step of a single-GPU run: ONE launch, one workgroup per proposal, accept test and commit included.
@@ -3802,49 +3841,27 @@ lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board
     const dim3 grid((unsigned)(board ? hi - lo : ds.n_half));
     if (board && hi <= lo) return leave_half_step(s, st);
     const int spec = specialised_model(e->dp);
-#define LCF_SOLO6(ND, V, T, NP, B, M)                                                                                 \
-    do {                                                                                                              \
-        if (lds > 64 * 1024) /* allow more than the default 64 KiB of dynamic LDS (per function and device) */       \
-            LCF_HIP(hipFuncSetAttribute((const void*)k_solo<ND, V, T, NP, B, M>,                                      \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCU));                 \
-        hipLaunchKernelGGL((k_solo<ND, V, T, NP, B, M>), grid, dim3(kBlock * (NP == 8 ? 4 : 2)), lds, st, e->d_dp, ds, row, \
-                           draws, draws_next, G, g_run0, lo);                                                         \
-    } while (0)
-#define LCF_SOLO5(ND, V, T, NP, B)                                                                                    \
-    do {                                                                                                              \
-        if (NP != 8 && ND == 5 && spec == kShockCooling) LCF_SOLO6(5, V, T, (NP == 8 ? 4 : NP), B, kShockCooling);    \
-        else if (NP != 8 && ND == 4 && spec == kShockCooling2) LCF_SOLO6(4, V, T, (NP == 8 ? 4 : NP), B, kShockCooling2); \
-        else LCF_SOLO6(ND, V, T, NP, B, 0);                                                                           \
-    } while (0)
-#define LCF_SOLO4(ND, V, T, NP)                                                                                       \
-    do {                                                                                                              \
-        if (board) LCF_SOLO5(ND, V, T, NP, true); else LCF_SOLO5(ND, V, T, NP, false);                                \
-    } while (0)
     // workgroups of 512 threads: one part per 256 threads (up to two parts) or two (three or four)
     // ... or four (1024 threads) where the launch has at most one workgroup per CU
     static const bool no_wide = std::getenv("LCF_NO_WIDE_SOLO") != nullptr;
     const bool wide = !no_wide && e->dp.n_parts > 2 && (int)grid.x <= e->n_cus;
-#define LCF_SOLO3(ND, V, T)                                                                                           \
-    do {                                                                                                              \
-        if (e->dp.n_parts <= 2) LCF_SOLO4(ND, V, T, 2); else if (wide) LCF_SOLO4(ND, V, T, 8); else LCF_SOLO4(ND, V, T, 4); \
-    } while (0)
-#define LCF_SOLO(ND) LCF_SOLO3(ND, 1, true)
-    switch (ds.n_dim) {
-#ifndef LCF_DEV_BUILD
-        case 4: LCF_SOLO(4); break;
-        case 6: LCF_SOLO(6); break;
-        case 7: LCF_SOLO(7); break;
-        case 9: LCF_SOLO(9); break;
-#endif
-        case 5: LCF_SOLO(5); break;
-        case 8: LCF_SOLO(8); break;
-        default: LCF_SOLO(0); break;
-    }
-#undef LCF_SOLO
-#undef LCF_SOLO3
-#undef LCF_SOLO4
-#undef LCF_SOLO5
-#undef LCF_SOLO6
+    const int np = e->dp.n_parts <= 2 ? 2 : wide ? 8 : 4;   // (NP: parts per workgroup, 8 = the four of a proposal)
+    hipError_t err = hipSuccess;
+    const auto go = [&](auto nd, auto np_, auto m) {
+        constexpr int ND = decltype(nd)::value, NP = decltype(np_)::value, M = decltype(m)::value;
+        const auto kernel = board ? k_solo<ND, 1, true, NP, true, M> : k_solo<ND, 1, true, NP, false, M>;
+        if ((err = prepare_kernel(kernel, lds)) == hipSuccess)
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock * (NP == 8 ? 4 : 2)), lds, st, e->d_dp, ds, row, draws, draws_next, G,
+                               g_run0, lo);
+    };
+    dispatch(SoloDims{}, ds.n_dim, [&](auto nd) {
+        dispatch<8>(Dims<2, 4>{}, np, [&](auto np_) {
+            const auto own = [&](auto snd, auto m) { go(snd, np_, m); };
+            if constexpr (decltype(np_)::value == 8) go(nd, np_, Int<0>{});   // (no model has a 1024-thread kernel)
+            else if (!dispatch_model(SpecialisedModels{}, nd, spec, own)) go(nd, np_, Int<0>{});
+        });
+    });
+    LCF_HIP(err);
     LCF_HIP(hipGetLastError());
     return leave_half_step(s, st);
 }
@@ -3876,15 +3893,19 @@ bool wide_runs() {
 }
 bool run_wide(const lcf_sampler* s, int proposals) {
     static const bool no_wide = std::getenv("LCF_NO_WIDE_SOLO") != nullptr;
-    return !no_wide && s->e->dp.n_parts > 2 && proposals <= s->e->n_cus && s->ds.n_dim == 8;
+    return !no_wide && s->e->dp.n_parts > 2 && proposals <= s->e->n_cus && has_dim(WideRuns{}, s->ds.n_dim);
+}
+// Launches of `width` proposals that take resident workgroups: up to `slots` proposals where a light curve has more
+// than two parts (the rank's share of a row-board run: up to two slots per workgroup, rows_resident_eligible).
+bool resident_size(const lcf_sampler* s, int width, int slots) {
+    if (s->e->dp.n_parts <= 2) return width <= 4 * kRunSlots;
+    return (width > s->e->n_cus || (wide_runs() && run_wide(s, width))) && width <= slots;
 }
 bool run_eligible(const lcf_sampler* s) {
     static const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr;
     static const bool any_size = std::getenv("LCF_RUN_ANY_SIZE") != nullptr;   // (tests: several slots per workgroup)
     return !disabled && !s->run_off && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) && s->ds.n_peers == 0 &&
-           ((s->e->dp.n_parts <= 2 ? s->ds.n_half <= 4 * kRunSlots
-                                   : (s->ds.n_half > s->e->n_cus || (wide_runs() && run_wide(s, s->ds.n_half))) && s->ds.n_half <= kRunSlots) ||
-            any_size);
+           (resident_size(s, s->ds.n_half, kRunSlots) || any_size);
 }
 
 struct RunBusy { hipEvent_t ev = nullptr; hipStream_t stream = nullptr; bool used = false; bool enqueuing = false; };
@@ -3926,26 +3947,20 @@ struct RunClaim {   // releases on every path out of the enqueue
     ~RunClaim() { if (held) run_release(dev, st); }
 };
 
-template <class K>
-lcf_status run_capacity(lcf_sampler* s, K kernel, int threads, size_t lds) {
-    int& cap = threads > kBlock * 2 ? s->run_capacity_wide : s->run_capacity;
-    if (cap >= 0) return LCF_OK;
-    if (lds > 64 * 1024)   // (what the launch asks for, not the CU's whole LDS: the kernel may hold static words of its own)
-        LCF_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int per_cu = 0;
-    LCF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
-    // (the compute units this stream may use: a CU mask on the stream -- or on the process -- leaves fewer than the device has)
-    int cus = s->e->n_cus;
+// Workgroups of a resident launch, `per_cu` of them per CU: all on the device at once, on the compute units the engine's
+// stream may use (a CU mask on the stream -- or on the process -- leaves fewer than the device has).
+int run_capacity(const lcf_engine* e, int per_cu) {
+    int cus = e->n_cus;
     uint32_t mask[16] = {0};
-    if (hipExtStreamGetCUMask(s->e->stream, 16, mask) == hipSuccess) {
+    if (hipExtStreamGetCUMask(e->stream, 16, mask) == hipSuccess) {
         int bits = 0;
         for (uint32_t m : mask) bits += __builtin_popcount(m);
         if (bits > 0 && bits < cus) cus = bits;
     }
     (void)hipGetLastError();
-    cap = per_cu * cus;
+    int cap = per_cu * cus;
     if (const char* env = std::getenv("LCF_RUN_GRID")) cap = std::min(cap, std::atoi(env));  // (tests)
-    return LCF_OK;
+    return cap;
 }
 
 // The sampler as k_solo_run reads it, in device memory (a constant-address-space pointer in the kernel): written when a
@@ -4055,65 +4070,47 @@ lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, b
     const bool test_missing = std::getenv("LCF_RUN_TEST_MISSING") != nullptr;
     const int spec = specialised_model(e->dp);
     unsigned int& arrivals = ranks ? s->rows_arrivals : s->run_arrivals;
-#define LCF_RUN6(ND, NP, M, R)                                                                                        \
-    do {                                                                                                              \
-        constexpr int kThr = kBlock * (NP == 8 ? 4 : 2);                                                              \
-        if (lcf_status r = run_capacity(s, k_solo_run<ND, 1, true, NP, M, R>, kThr, lds)) return r;                   \
-        const int cap = NP == 8 ? s->run_capacity_wide : s->run_capacity;                                             \
-        if (cap < 1) return fail(LCF_ERR_UNSUPPORTED, "k_solo_run does not fit the device");                          \
-        if (dry) break;                                                                                               \
-        const int n_wg = std::min(hi - lo, cap);                                                                      \
-        const dim3 grid((unsigned)(test_missing && n_wg > 1 ? n_wg - 1 : n_wg));                                      \
-        arrivals += (unsigned int)n_wg;   /* (0 = "no check": skipped when the count wraps onto it) */                 \
-        if (arrivals == 0u) arrivals = 1u;                                                                            \
-        hipLaunchKernelGGL((k_solo_run<ND, 1, true, NP, M, R>), grid, dim3(kThr), lds, st, e->d_dp, rs, rel, draws,    \
-                           g_run0, n_hs, state_from, n_wg, run_flags, arrivals, lo, hi - lo, need_progress);          \
-    } while (0)
-#define LCF_RUN5(ND, NP, M) LCF_RUN6(ND, NP, M, false)
-#define LCF_RUN4(ND, NP)                                                                                              \
-    do {                                                                                                              \
-        if (ND == 5 && spec == kShockCooling) LCF_RUN5(5, NP, kShockCooling);                                         \
-        else if (ND == 4 && spec == kShockCooling2) LCF_RUN5(4, NP, kShockCooling2);                                  \
-        else LCF_RUN5(ND, NP, 0);                                                                                     \
-    } while (0)
-#define LCF_RUN(ND) do { if (e->dp.n_parts <= 2) LCF_RUN4(ND, 2); else LCF_RUN4(ND, 4); } while (0)
+    lcf_status rc = LCF_OK;
+    const auto go = [&](auto nd, auto np_, auto m, auto ranks_) {
+        constexpr int ND = decltype(nd)::value, NP = decltype(np_)::value, M = decltype(m)::value;
+        const auto kernel = k_solo_run<ND, 1, true, NP, M, decltype(ranks_)::value>;
+        const int threads = kBlock * (NP == 8 ? 4 : 2);
+        int per_cu = 0;
+        if (hipError_t err = prepare_kernel(kernel, lds, threads, &per_cu)) {
+            rc = fail(LCF_ERR_HIP, std::string("preparing k_solo_run: ") + hipGetErrorString(err));
+            return;
+        }
+        const int cap = run_capacity(e, per_cu);
+        if (cap < 1) {
+            rc = fail(LCF_ERR_UNSUPPORTED, "k_solo_run does not fit the device");
+            return;
+        }
+        if (dry) return;
+        const int n_wg = std::min(hi - lo, cap);
+        const dim3 grid((unsigned)(test_missing && n_wg > 1 ? n_wg - 1 : n_wg));
+        arrivals += (unsigned int)n_wg;   // (0 = "no check": skipped when the count wraps onto it)
+        if (arrivals == 0u) arrivals = 1u;
+        hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, e->d_dp, rs, rel, draws, g_run0, n_hs, state_from, n_wg,
+                           run_flags, arrivals, lo, hi - lo, need_progress);
+    };
+    // (NP = 8: 1024-thread workgroups, the four parts of a proposal side by side -- where the table has a row for it,
+    // else the 512-thread form)
+    const int np = e->dp.n_parts <= 2 ? 2 : run_wide(s, hi - lo) ? 8 : 4;
     if (ranks) {
-        // (between ranks: the benchmark shapes' own kernels, the companion fit's dimension, and the generic kernel with the
-        // dimension at run time for everything else -- every instantiation is a minute of compile time)
-        const bool two = e->dp.n_parts <= 2;
-        const bool wide = run_wide(s, hi - lo);   // (1024-thread workgroups, the four parts of a proposal side by side)
-        if (s->ds.n_dim == 5 && spec == kShockCooling && two) LCF_RUN6(5, 2, kShockCooling, true);
-#ifndef LCF_DEV_BUILD
-        else if (s->ds.n_dim == 4 && spec == kShockCooling2 && two) LCF_RUN6(4, 2, kShockCooling2, true);
-        else if (s->ds.n_dim == 8 && two) LCF_RUN6(8, 2, 0, true);
-        else if (s->ds.n_dim == 8 && wide) LCF_RUN6(8, 8, 0, true);
-        else if (s->ds.n_dim == 8) LCF_RUN6(8, 4, 0, true);
-#endif
-        else if (two) LCF_RUN6(0, 2, 0, true);
-        else LCF_RUN6(0, 4, 0, true);
-        LCF_HIP(hipGetLastError());
-        return LCF_OK;
+        const auto row = [&](auto nd, auto np_, auto m) { go(nd, np_, m, std::true_type{}); };
+        if (!dispatch_row(RanksRuns{}, s->ds.n_dim, np, spec, row))
+            dispatch<4>(Dims<2>{}, np, [&](auto np_) { go(Int<0>{}, np_, Int<0>{}, std::true_type{}); });
+    } else {
+        const auto row = [&](auto nd, auto np_, auto m) { go(nd, np_, m, std::false_type{}); };
+        if (!dispatch_row(WideRuns{}, s->ds.n_dim, np, spec, row))
+            dispatch(SoloDims{}, s->ds.n_dim, [&](auto nd) {
+                dispatch<4>(Dims<2>{}, np, [&](auto np_) {
+                    const auto own = [&](auto snd, auto m) { go(snd, np_, m, std::false_type{}); };
+                    if (!dispatch_model(SpecialisedModels{}, nd, spec, own)) go(nd, np_, Int<0>{}, std::false_type{});
+                });
+            });
     }
-    if (s->ds.n_dim == 8 && run_wide(s, hi - lo)) {
-        LCF_RUN6(8, 8, 0, false);
-        LCF_HIP(hipGetLastError());
-        return LCF_OK;
-    }
-    switch (s->ds.n_dim) {
-#ifndef LCF_DEV_BUILD
-        case 4: LCF_RUN(4); break;
-        case 6: LCF_RUN(6); break;
-        case 7: LCF_RUN(7); break;
-        case 9: LCF_RUN(9); break;
-#endif
-        case 5: LCF_RUN(5); break;
-        case 8: LCF_RUN(8); break;
-        default: LCF_RUN(0); break;
-    }
-#undef LCF_RUN
-#undef LCF_RUN4
-#undef LCF_RUN5
-#undef LCF_RUN6
+    if (rc) return rc;
     LCF_HIP(hipGetLastError());
     return LCF_OK;
 }
@@ -4289,10 +4286,6 @@ lcf_status sampler_begin(lcf_sampler* s, int64_t first_step, int64_t n_steps, in
             LCF_HIP(hipMalloc((void**)&s->d_slot[b], (size_t)(1 + 2 * cap) * ds.n_walkers * sizeof(int)));
         }
         s->blk_cap = cap;
-        int n_pad = 2;
-        while (n_pad < ds.n_walkers) n_pad <<= 1;
-        if ((size_t)n_pad * 8 > 65536)
-            LCF_HIP(hipFuncSetAttribute((const void*)k_make_perm, hipFuncAttributeMaxDynamicSharedMemorySize, n_pad * 8));
     }
     s->blk_steps = s->blk_cap;
     s->blk_first = std::min<int64_t>(s->blk_cap, LCF_FIRST_BLOCK);
@@ -4307,45 +4300,6 @@ lcf_status sampler_begin(lcf_sampler* s, int64_t first_step, int64_t n_steps, in
     return generate_block(s, 0, gen ? gen : e->stream);
 }
 
-// k_pop_run<ND, 1, G, M> for the population's shape: `L` null = its LDS attribute set and the workgroups a CU holds asked;
-// else the launch.
-struct PopRunLaunch {
-    dim3 grid;
-    hipStream_t st;
-    const MultiItem* items;
-    long long rel, state_from;
-    int n_hs, store_chain, launch_no, n_wg;
-};
-template <int ND, int G, int M>
-hipError_t pop_run_do(const PopRunLaunch* L, size_t lds, int* per_cu) {
-    const auto kernel = k_pop_run<ND, 1, G, M>;
-    if (!L) {
-        if (lds > 64 * 1024)
-            if (hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, 64 * G, lds);
-    }
-    hipLaunchKernelGGL(kernel, L->grid, dim3(64 * G), lds, L->st, L->items, L->rel, L->n_hs, L->state_from, L->store_chain,
-                       L->launch_no, L->n_wg);
-    return hipGetLastError();
-}
-template <int G>
-hipError_t pop_run_shape(int same_dim, int spec, const PopRunLaunch* L, size_t lds, int* per_cu) {
-    if (same_dim == 5 && spec == kShockCooling) return pop_run_do<5, G, kShockCooling>(L, lds, per_cu);
-#ifndef LCF_DEV_BUILD
-    if (same_dim == 4 && spec == kShockCooling2) return pop_run_do<4, G, kShockCooling2>(L, lds, per_cu);
-#endif
-    return pop_run_do<0, G, 0>(L, lds, per_cu);
-}
-hipError_t pop_run_kernel(int group, int same_dim, int spec, const PopRunLaunch* L, size_t lds, int* per_cu) {
-    switch (group) {
-#ifdef LCF_POP_GROUPS_ALL
-        case 4: return pop_run_shape<4>(same_dim, spec, L, lds, per_cu);
-        case 10: return pop_run_shape<10>(same_dim, spec, L, lds, per_cu);
-        case 12: return pop_run_shape<12>(same_dim, spec, L, lds, per_cu);
-#endif
-        default: return pop_run_shape<kPopRunGroup>(same_dim, spec, L, lds, per_cu);
-    }
-}
 
 }  // namespace
 
@@ -4543,10 +4497,7 @@ lcf_status lcf_sampler_check(lcf_sampler* s) {
             // last step.  Take the state it started from, drop what it reported, and run the same steps again with a
             // launch per half-step (as every later run of this sampler).
             LCF_HIP(hipStreamSynchronize(s->e->stream));
-            std::swap(s->ds.X, s->alt_X);
-            std::swap(s->ds.LP, s->alt_LP);
-            std::swap(s->ds.nacc, s->alt_nacc);
-            s->run_flip = !s->run_flip;
+            s->flip_state_sets();
             int sticky = 0;
             std::memcpy(&sticky, s->snap, sizeof(int));
             sticky &= 1;                                   // (a NaN of an earlier run stays reported)
@@ -4856,8 +4807,7 @@ bool rows_resident_eligible(const lcf_sampler* s, int width) {
     const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr || std::getenv("LCF_ROWS_PER_HALF_STEP") != nullptr;
     const bool any_size = std::getenv("LCF_RUN_ANY_SIZE") != nullptr;
     return !disabled && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) &&
-           ((s->e->dp.n_parts <= 2 ? width <= 4 * kRunSlots
-                                   : (width > s->e->n_cus || (wide_runs() && run_wide(s, width))) && width <= 2 * kRunSlots) || any_size);
+           (resident_size(s, width, 2 * kRunSlots) || any_size);
 }
 
 lcf_status board_alloc(lcf_sampler* s) {
@@ -4973,9 +4923,7 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
         for (long long rel = 0; rel < 2 * n_steps;) {
             ++s->last_launches;
             if (lcf_status r = enter_half_step(s, rel, st)) return r;
-            const int64_t b = s->blk_current;
-            const long long end = 2 * (s->block_start(b) + s->block_len(b));
-            const int n = (int)std::min<long long>(kRunSpan, end - rel);
+            const int n = s->block_span(rel, kRunSpan);
             const long long need = starts[0] >= 0 ? s->g_run0 + starts[0] : 0;
             if (lcf_status r = launch_run(s, rel, n, st, true, lo, hi, need)) return r;
             mark("resident launch enqueued");
@@ -5042,18 +4990,13 @@ lcf_status lcf_sampler_run_async(lcf_sampler* s, int64_t first_step, int64_t n_s
         for (long long rel = 0; rel < 2 * n_steps;) {   // (the first launch posts the start state on the board itself)
             ++s->last_launches;
             if (lcf_status r = enter_half_step(s, rel, st)) return r;
-            const int64_t b = s->blk_current;
-            const long long end = 2 * (s->block_start(b) + s->block_len(b));
-            const int n = (int)std::min<long long>(kRunSpanSolo, end - rel);
+            const int n = s->block_span(rel, kRunSpanSolo);
             if (lcf_status r = launch_run(s, rel, n, st)) return r;
             if (lcf_status r = leave_half_step(s, st)) return r;
             rel += n;
         }
         s->g_next += 2 * n_steps;
-        std::swap(s->ds.X, s->alt_X);          // the state behind this run is in the other set now
-        std::swap(s->ds.LP, s->alt_LP);
-        std::swap(s->ds.nacc, s->alt_nacc);
-        s->run_flip = !s->run_flip;
+        s->flip_state_sets();                  // the state behind this run is in the other set now
         LCF_HIP(hipEventRecord(s->ev1, st));
         claim.held = false;
         run_release(s->e->device, st);
@@ -5178,8 +5121,7 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         while (n_pad < d0.n_walkers) n_pad <<= 1;
         const int threads = std::min(1024, std::max(64, n_pad / 2));
         const long long front_row = b > 0 ? 2 * (long long)s0->block_len(b - 1) : -1;
-        if ((size_t)n_pad * 8 > 65536)
-            LCF_HIP(hipFuncSetAttribute((const void*)k_make_perm_multi, hipFuncAttributeMaxDynamicSharedMemorySize, n_pad * 8));
+        LCF_HIP(prepare_kernel(k_make_perm_multi, (size_t)n_pad * 8));
         hipLaunchKernelGGL(k_make_perm_multi, dim3((unsigned)len, (unsigned)n), dim3(threads), (size_t)n_pad * 8, pop_stream, dgen,
                            d0.n_walkers, n_pad, (long long)(s0->run_first + k0), buf, d0.n_half, front_row);
         const long long recs = (long long)len * 2 * d0.n_half;
@@ -5319,8 +5261,16 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         // gridDim.x workgroups per transient, all of them on the device at once: what the device holds, shared evenly --
         // and no more than give every workgroup the same number of groups of proposals per half-step
         const int n_groups = (nh + run_group - 1) / run_group;
+        // k_pop_run<ND, 1, G, M> for the population's shape: f(kernel, G)
+        const auto with_kernel = [&](auto f) {
+            dispatch<kPopRunGroup>(PopRunGroups{}, run_group, [&](auto g_) {
+                constexpr int G = decltype(g_)::value;
+                const auto own = [&](auto nd, auto m) { f(k_pop_run<decltype(nd)::value, 1, G, decltype(m)::value>, G); };
+                if (!dispatch_model(PopRunModels{}, same_dim, pop_spec, own)) f(k_pop_run<0, 1, G, 0>, G);
+            });
+        };
         int per_cu = 0;
-        err = pop_run_kernel(run_group, same_dim, pop_spec, nullptr, run_lds, &per_cu);
+        with_kernel([&](auto kernel, int G) { err = prepare_kernel(kernel, run_lds, 64 * G, &per_cu); });
         int cap = per_cu * s0->e->n_cus;
         if (const char* env = std::getenv("LCF_RUN_GRID")) cap = std::min(cap, std::atoi(env));  // (tests)
         const int chunk = std::min<int>(n, std::max(cap, 1));          // transients per launch
@@ -5333,14 +5283,14 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         for (long long rel = 0; rel < 2 * n_steps && err == hipSuccess;) {
             if (pop_enter(rel) != LCF_OK) err = hipErrorUnknown;
             if (err != hipSuccess) break;
-            const int64_t b = s0->blk_current;
-            const long long end = 2 * (s0->block_start(b) + s0->block_len(b));
-            const int n_hs = (int)std::min<long long>(kRunSpanSolo, end - rel);
+            const int n_hs = s0->block_span(rel, kRunSpanSolo);
             for (int c0 = 0; c0 < n && err == hipSuccess; c0 += chunk) {
-                const int nc = std::min(chunk, n - c0);
-                const PopRunLaunch L{dim3((unsigned)(test_missing && run_grid > 1 ? run_grid - 1 : run_grid), (unsigned)nc), st,
-                                     ditems + c0, rel, state_from, n_hs, store_chain ? 1 : 0, run_launches, run_grid};
-                err = pop_run_kernel(run_group, same_dim, pop_spec, &L, run_lds, nullptr);
+                const dim3 grid((unsigned)(test_missing && run_grid > 1 ? run_grid - 1 : run_grid), (unsigned)std::min(chunk, n - c0));
+                with_kernel([&](auto kernel, int G) {
+                    hipLaunchKernelGGL(kernel, grid, dim3(64 * G), run_lds, st, ditems + c0, rel, n_hs, state_from,
+                                       store_chain ? 1 : 0, run_launches, run_grid);
+                });
+                err = hipGetLastError();
             }
             ++run_launches;
             for (int t = 0; t < n; ++t)
@@ -5349,12 +5299,8 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
             rel += n_hs;
         }
         for (int t = 0; t < n; ++t) {   // the state behind this run is in the other set of buffers now
-            lcf_sampler* s = ss[t];
-            s->run_arrivals += (unsigned int)(run_launches * run_grid);
-            std::swap(s->ds.X, s->alt_X);
-            std::swap(s->ds.LP, s->alt_LP);
-            std::swap(s->ds.nacc, s->alt_nacc);
-            s->run_flip = !s->run_flip;
+            ss[t]->run_arrivals += (unsigned int)(run_launches * run_grid);
+            ss[t]->flip_state_sets();
         }
         claim.held = false;
         run_release(s0->e->device, st);
@@ -5363,24 +5309,14 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         for (int64_t k = 0; k < 2 * n_steps && err == hipSuccess; ++k) {
             if (pop_enter(k) != LCF_OK) err = hipErrorUnknown;
             if (err != hipSuccess) break;
-#define LCF_POP3(ND, G, M) do { allow_lds(k_pop<ND, 1, G, M>, pop_lds);                                             \
-                                hipLaunchKernelGGL((k_pop<ND, 1, G, M>), gq, bq, pop_lds, st, ditems, (long long)k); } while (0)
-#define LCF_POP2(ND, G) do { if (ND == 5 && pop_spec == kShockCooling) LCF_POP3(5, G, kShockCooling);               \
-                             else if (ND == 4 && pop_spec == kShockCooling2) LCF_POP3(4, G, kShockCooling2);        \
-                             else LCF_POP3(ND, G, 0); } while (0)
-#define LCF_POP(ND) LCF_POP2(ND, pop_group)
-            switch (same_dim) {
-#ifndef LCF_DEV_BUILD
-                case 4: LCF_POP(4); break;
-                case 6: LCF_POP(6); break;
-#endif
-                case 5: LCF_POP(5); break;
-                case 8: LCF_POP(8); break;
-                default: LCF_POP(0); break;
-            }
-#undef LCF_POP2
-#undef LCF_POP3
-#undef LCF_POP
+            const auto go = [&](auto nd, auto m) {
+                const auto kernel = k_pop<decltype(nd)::value, 1, pop_group, decltype(m)::value>;
+                if ((err = prepare_kernel(kernel, pop_lds)) == hipSuccess)
+                    hipLaunchKernelGGL(kernel, gq, bq, pop_lds, st, ditems, (long long)k);
+            };
+            dispatch(PopDims{}, same_dim, [&](auto nd) {
+                if (!dispatch_model(SpecialisedModels{}, nd, pop_spec, go)) go(nd, Int<0>{});
+            });
             for (int t = 0; t < n; ++t)
                 if (st != ss[t]->e->stream) ss[t]->foreign_stream = true;
             if (err == hipSuccess && pop_leave() != LCF_OK) err = hipErrorUnknown;
@@ -5392,18 +5328,10 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         if (!have_next && !have_prev) break;
         if (have_next && pop_enter(k) != LCF_OK) err = hipErrorUnknown;   // (every transient's block of draw records)
         if (err != hipSuccess) break;
-#define LCF_STEPM(ND) hipLaunchKernelGGL(k_step_multi<ND>, gs, bs, 0, st, ditems, have_prev ? 1 : 0,                      \
-                                         (long long)((k - 1) / 2), have_next ? 1 : 0, (long long)k, (long long)(g + k))
-        switch (same_dim) {
-#ifndef LCF_DEV_BUILD
-            case 4: LCF_STEPM(4); break;
-            case 6: LCF_STEPM(6); break;
-#endif
-            case 5: LCF_STEPM(5); break;
-            case 8: LCF_STEPM(8); break;
-            default: LCF_STEPM(0); break;
-        }
-#undef LCF_STEPM
+        dispatch(PopDims{}, same_dim, [&](auto nd) {
+            hipLaunchKernelGGL(k_step_multi<decltype(nd)::value>, gs, bs, 0, st, ditems, have_prev ? 1 : 0,
+                               (long long)((k - 1) / 2), have_next ? 1 : 0, (long long)k, (long long)(g + k));
+        });
         if (have_next) {
             for (int t = 0; t < n; ++t)
                 if (st != ss[t]->e->stream) ss[t]->foreign_stream = true;
@@ -5411,16 +5339,17 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         }
         if (!have_next) break;
         const int parity = (int)((g + k) & 1);
-#define LCF_PM(V, L, T) do { allow_lds(k_points_multi<V, L, T>, lds);                                       \
-                             hipLaunchKernelGGL((k_points_multi<V, L, T>), gp, bp, lds, st, ditems, parity); } while (0)
+        const auto go = [&](auto kernel) {
+            prepare_kernel(kernel, lds);
+            hipLaunchKernelGGL(kernel, gp, bp, lds, st, ditems, parity);
+        };
         if (p0.variant == 0) {
-            if (p0.tab_in_lds) { if (thermal) LCF_PM(0, true, true); else LCF_PM(0, true, false); }
-            else { if (thermal) LCF_PM(0, false, true); else LCF_PM(0, false, false); }
+            if (p0.tab_in_lds) thermal ? go(k_points_multi<0, true, true>) : go(k_points_multi<0, true, false>);
+            else thermal ? go(k_points_multi<0, false, true>) : go(k_points_multi<0, false, false>);
         } else {
-            if (p0.tab_in_lds) { if (thermal) LCF_PM(1, true, true); else LCF_PM(1, true, false); }
-            else { if (thermal) LCF_PM(1, false, true); else LCF_PM(1, false, false); }
+            if (p0.tab_in_lds) thermal ? go(k_points_multi<1, true, true>) : go(k_points_multi<1, true, false>);
+            else thermal ? go(k_points_multi<1, false, true>) : go(k_points_multi<1, false, false>);
         }
-#undef LCF_PM
         err = hipGetLastError();
     }
     if (err == hipSuccess) err = hipEventRecord(ev1, st);
@@ -5465,10 +5394,7 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         if (gave_up) {
             for (int t = 0; t < n; ++t) {
                 lcf_sampler* s = ss[t];
-                std::swap(s->ds.X, s->alt_X);
-                std::swap(s->ds.LP, s->alt_LP);
-                std::swap(s->ds.nacc, s->alt_nacc);
-                s->run_flip = !s->run_flip;
+                s->flip_state_sets();
                 int sticky = 0;
                 std::memcpy(&sticky, s->snap, sizeof(int));
                 sticky &= 1;                                   // (a NaN of an earlier run stays reported)

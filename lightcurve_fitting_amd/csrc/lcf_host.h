@@ -4,7 +4,10 @@
 
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "lcf.h"
@@ -21,6 +24,41 @@ lcf_status fail(lcf_status st, const std::string& msg);
             return lcf::fail(e_ == hipErrorOutOfMemory ? LCF_ERR_OUT_OF_MEMORY : LCF_ERR_HIP,              \
                              std::string(#call) + ": " + hipGetErrorString(e_));                           \
     } while (0)
+
+// Every launch with dynamic LDS is prepared here, on the device it goes to.  More than the default 64 KiB must be granted
+// per kernel function and device: it is, once (again only should a later launch of the function ask for more -- what
+// the launch asks for, not the CU's whole LDS: the kernel may hold static words of its own).  `per_cu`: the workgroups
+// of `threads` threads with that LDS one CU holds, asked once per (device, function, threads, LDS bytes).
+inline hipError_t prepare_kernel(const void* kernel, size_t lds, int threads = 0, int* per_cu = nullptr) {
+    if (lds <= 64 * 1024 && !per_cu) return hipSuccess;
+    static std::mutex mutex;
+    static std::map<std::pair<int, const void*>, size_t> granted;
+    static std::map<std::tuple<int, const void*, int, size_t>, int> occupancy;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    std::lock_guard<std::mutex> lock(mutex);
+    if (lds > 64 * 1024) {
+        size_t& g = granted[{dev, kernel}];
+        if (lds > g) {
+            if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+            g = lds;
+        }
+    }
+    if (!per_cu) return hipSuccess;
+    const auto key = std::make_tuple(dev, kernel, threads, lds);
+    auto it = occupancy.find(key);
+    if (it == occupancy.end()) {
+        int n = 0;
+        if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, lds)) return e;
+        it = occupancy.emplace(key, n).first;
+    }
+    *per_cu = it->second;
+    return hipSuccess;
+}
+template <class... A>
+hipError_t prepare_kernel(void (*kernel)(A...), size_t lds, int threads = 0, int* per_cu = nullptr) {
+    return prepare_kernel(reinterpret_cast<const void*>(kernel), lds, threads, per_cu);
+}
 
 template <class T>
 lcf_status upload(const std::vector<T>& h, T** d, std::vector<void*>& owned) {

@@ -561,8 +561,7 @@ lcf_status lcf_sed_log_likelihood(lcf_sed* s, int64_t n_cand, int32_t n_par, int
     }
     if (precision == 2) {
         const size_t lds2 = kExpTabSize * sizeof(double) + (size_t)s->sd.n_filters * s->sd.itab_m * 16 * kSedRowLds;
-        if (lds2 > 64 * 1024)
-            LCF_HIP(hipFuncSetAttribute((const void*)k_sed_interp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        LCF_HIP(prepare_kernel(k_sed_interp, lds2));
         // workgroups of 256 with a grid stride over the (epoch, tile) items: as many as keep every CU busy with the
         // waves its LDS allows, and no more (each stages the interpolants once)
         const long long items = ne * ((n_cand + 63) / 64);   // one per wave

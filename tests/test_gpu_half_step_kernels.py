@@ -656,6 +656,46 @@ def test_row_boards_companion_several_slots_per_workgroup(monkeypatch):
         assert np.array_equal(s.naccepted(), ref.naccepted())
 
 
+def test_resident_run_after_board_connect_in_a_fresh_process():
+    """A sampler's board_connect resolves its row-board kernel ahead of the first run (k_solo_run<8, 1, true, 8, 0, RANKS>:
+    LDS granted, occupancy asked); a single-GPU run of the same sampler then takes the other resident kernel,
+    k_solo_run<8, 1, true, 8, 0>, which needs a grant and an occupancy of its own.  The companion engine's launches ask
+    for 71 600 bytes of dynamic LDS, more than the default 64 KiB: its staging image holds 596 band-table pairs, eight
+    filter descriptors, 32 KiB of interpolants and 25.5 KiB of SiFTO splines (4308 double2), behind the 2304-byte head
+    and in front of 368 bytes of scratch.  In a fresh process, so that no earlier sampler can have granted it: the
+    resident run's chain is the one of k_solo, a launch per half-step, bit for bit."""
+    import os
+    import subprocess
+    import sys
+    code = """
+import sys
+import numpy as np
+sys.path.insert(0, %r)
+import bench
+from lightcurve_fitting_amd.engine import NativeSampler
+model, lc, priors, _ = bench.build_companion(0)
+eng = model.engine_for(lc, priors=priors)
+x0 = bench.companion_walkers(40)
+s = NativeSampler(eng, 40, 9)
+s.board_connect(1, 0, local_ptrs=[s.board_export()[1]])
+s.set_state(x0)
+assert s.set_half_step_kernel('auto') == 'run'
+s.run(0, 4, 'random', True)
+assert s.last_run_kernel() == 'run', s.last_run_kernel()
+ref = NativeSampler(eng, 40, 9)
+assert ref.set_half_step_kernel('solo') == 'solo'
+ref.set_state(x0)
+ref.run(0, 4, 'random', True)
+assert ref.last_run_kernel() == 'solo'
+for a, b in zip(s.get_chain(), ref.get_chain()):
+    assert np.array_equal(a, b)
+assert np.array_equal(s.naccepted(), ref.naccepted())
+print('OK')
+""" % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.startswith('OK'), (out.stdout[-1500:], out.stderr[-3000:])
+
+
 @pytest.mark.parametrize('form', ['resident', 'per half-step'])
 def test_row_boards_missing_rank_ends_with_an_error(monkeypatch, form):
     """A rank that never runs: the waits of the other one are bounded (LCF_PEER_WAIT_S, here 0.5 s; 5 s by default), the
