@@ -1134,9 +1134,12 @@ __global__ __launch_bounds__(1024) void k_make_perm(int n_walkers, int n_pad, ui
 }
 
 // Population mode: the same for MANY samplers in one launch (blockIdx.y = sampler; equal walker counts and blocks).  What
-// differs from sampler to sampler -- the key of its RNG, its buffers -- comes from an array in device memory.
+// differs from sampler to sampler -- the key of its RNG, its walker dimension (the accept test's (n_dim - 1) ln z), its
+// stretch scale, its buffers -- comes from an array in device memory.
 struct GenItem {
     uint32_t key0, key1;
+    int n_dim;
+    double a;
     int* perm[2];
     int* slot[2];
     DrawRec* draws[2];
@@ -1227,12 +1230,15 @@ __global__ void k_draws(DevSampler sm, const int* __restrict__ perm, const int* 
                         long long first_step, long long n_steps, DrawRec* __restrict__ draws) {
     draws_body(sm, perm, slot_of, first_step, n_steps, draws);
 }
-// (population mode, blockIdx.y = sampler: `sm` = the samplers' common shape, the key from the item)
+// (population mode, blockIdx.y = sampler: `sm` = the samplers' common walker count; key, dimension and stretch scale
+// from the item)
 __global__ void k_draws_multi(const GenItem* __restrict__ items, DevSampler sm, int buf, long long first_step,
                               long long n_steps) {
     const GenItem it = items[blockIdx.y];
     sm.key0 = it.key0;
     sm.key1 = it.key1;
+    sm.n_dim = it.n_dim;
+    sm.a = it.a;
     draws_body(sm, it.perm[buf], it.slot[buf], first_step, n_steps, it.draws[buf]);
 }
 
@@ -5099,8 +5105,9 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
     if (batched_gen) {
         std::vector<GenItem> gen(n);
         for (int t = 0; t < n; ++t)
-            gen[t] = GenItem{ss[t]->ds.key0, ss[t]->ds.key1, {ss[t]->d_perm[0], ss[t]->d_perm[1]},
-                             {ss[t]->d_slot[0], ss[t]->d_slot[1]}, {ss[t]->d_draws[0], ss[t]->d_draws[1]}};
+            gen[t] = GenItem{ss[t]->ds.key0, ss[t]->ds.key1, ss[t]->ds.n_dim, ss[t]->ds.a,
+                             {ss[t]->d_perm[0], ss[t]->d_perm[1]}, {ss[t]->d_slot[0], ss[t]->d_slot[1]},
+                             {ss[t]->d_draws[0], ss[t]->d_draws[1]}};
         LCF_HIP(hipMalloc((void**)&dgen, (size_t)n * sizeof(GenItem)));
         if (hipMemcpy(dgen, gen.data(), (size_t)n * sizeof(GenItem), hipMemcpyHostToDevice) != hipSuccess) {
             hipFree(dgen);

@@ -35,17 +35,24 @@ def small_problem(npts=60, seed=5):
 
 
 def oracle_log_posterior(pb):
+    """(n, ndim) block -> (n,) oracle log-posteriors.  ``pb``: ``t``, ``bands``, ``y``, ``dy``, ``priors`` (descriptors)
+    and the oracle model tuple ``model`` (default ``('ShockCooling', pb['orc'])``); optional ``use_sigma`` and
+    ``sigma_type`` (a fitted sigma as the last parameter)."""
     model = pb.get('model') or ('ShockCooling', pb['orc'])
+    kw = dict(use_sigma=pb.get('use_sigma', False), sigma_type=pb.get('sigma_type', 'relative'))
+    args = (model, pb['t'], pb['bands'], pb['y'], pb['dy'])
 
     def fn(block):
         block = np.atleast_2d(block)
         out = np.full(len(block), -np.inf)
         lp = np.array([O.log_prior(pb['priors'], p) for p in block])
         ok = np.isfinite(lp)
-        if ok.sum() == 1:  # a single column would be squeezed away (np.squeeze in temperature_radius)
-            out[ok] = lp[ok] + O.log_likelihood(model, pb['t'], pb['bands'], pb['y'], pb['dy'], block[ok][0])
+        if model[0] == 'CompanionShocking':  # (its oracle evaluates one parameter vector at a time)
+            out[ok] = lp[ok] + np.array([O.log_likelihood(*args, p, **kw) for p in block[ok]])
+        elif ok.sum() == 1:  # a single column would be squeezed away (np.squeeze in temperature_radius)
+            out[ok] = lp[ok] + O.log_likelihood(*args, block[ok][0], **kw)
         elif ok.any():
-            out[ok] = lp[ok] + O.log_likelihood(model, pb['t'], pb['bands'], pb['y'], pb['dy'], block[ok].T)
+            out[ok] = lp[ok] + O.log_likelihood(*args, block[ok].T, **kw)
         return out
     return fn
 

@@ -11,7 +11,7 @@ from lightcurve_fitting_amd import engine as E
 from lightcurve_fitting_amd import models as M
 from lightcurve_fitting_amd.autocorr import AutocorrError, integrated_time
 from lightcurve_fitting_amd.fitting import lightcurve_mcmc
-from lightcurve_fitting_amd.sampler import PopulationSampler
+from lightcurve_fitting_amd.sampler import EnsembleSampler, PopulationSampler
 from test_autocorr_host import ar1, oracle_autocorr
 
 pytestmark = pytest.mark.gpu
@@ -141,3 +141,9 @@ def test_population_equals_each_transient():
     assert all(np.array_equal(err.value.tau[k], plain[k], equal_nan=True) for k in range(3))
     for k in range(3):
         assert _rel(plain[k], oracle_autocorr(pop[k].get_chain())[0]) <= 1e-10
+    # the 4-D transient behind a 5-D one samples its own posterior: its chain is that of a solo run
+    model, lc2, pri = problems[1]
+    solo = EnsembleSampler(48, 4, model.engine_for(lc2, priors=pri), seed=3 + 1)
+    solo.run_mcmc(x0[1], 300)
+    assert np.array_equal(pop[1].get_chain(), solo.get_chain())
+    np.testing.assert_allclose(pop[1].get_log_prob(), solo.get_log_prob(), rtol=1e-12, atol=1e-9)
