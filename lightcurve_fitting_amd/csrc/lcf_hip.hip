@@ -2698,11 +2698,6 @@ using PopRunModels = Models<Model<kShockCooling, 5>>;
 using RanksRuns = RunRows<RunRow<5, 2, kShockCooling>>;
 #endif
 using WideRuns = RunRows<RunRow<8, 8, 0>>;   // k_solo_run of 1024 threads on one GPU: the eight-parameter models
-#ifdef LCF_POP_GROUPS_ALL
-using PopRunGroups = Dims<4, 10, 12>;        // k_pop_run's proposals per workgroup besides kPopRunGroup (LCF_POP_GROUP)
-#else
-using PopRunGroups = Dims<>;
-#endif
 
 template <int V> using Int = std::integral_constant<int, V>;
 
@@ -3655,18 +3650,42 @@ lcf_status generate_steps(lcf_sampler* s, int buf, int64_t step0, int64_t len, i
     return LCF_OK;
 }
 
-// Block b of the current run (block b lives in buffer b & 1).
-lcf_status generate_block(lcf_sampler* s, int64_t b, hipStream_t consumer) {
+// Block b of the current run (block b lives in buffer b & 1) for a GROUP of samplers ss[0, n) that share their block
+// geometry -- a population's transients, or one sampler on its own; so do enter_half_step and leave_half_step.  `gen`:
+// the group's GenItems in device memory, the block of all of them from one launch of each batched generation kernel;
+// null: sampler by sampler.
+lcf_status generate_block(lcf_sampler* const* ss, int n, int64_t b, hipStream_t consumer, const GenItem* gen = nullptr) {
     const int buf = (int)(b & 1);
-    const int64_t k0 = s->block_start(b);
-    const int* host_perm = s->split_mode == LCF_SPLIT_HOST ? s->d_perm_host + (size_t)k0 * s->ds.n_walkers : nullptr;
-    // the half-step in front of a later block: the last row of the previous block (the other buffer)
-    const int* front = (b > 0 && s->need_slots)
-                           ? s->d_slot[buf ^ 1] + (size_t)2 * s->block_len(b - 1) * s->ds.n_walkers : nullptr;
-    if (lcf_status r = generate_steps(s, buf, s->run_first + k0, s->block_len(b), s->split_mode, host_perm, s->need_slots,
-                                      front, consumer))
-        return r;
-    s->blk_generated = b;
+    if (gen) {
+        const lcf_sampler* s0 = ss[0];
+        const DevSampler& d0 = s0->ds;
+        const int64_t k0 = s0->block_start(b), len = s0->block_len(b);
+        int n_pad = 2;
+        while (n_pad < d0.n_walkers) n_pad <<= 1;
+        const int threads = std::min(1024, std::max(64, n_pad / 2));
+        const long long front_row = b > 0 ? 2 * (long long)s0->block_len(b - 1) : -1;
+        LCF_HIP(prepare_kernel(k_make_perm_multi, (size_t)n_pad * 8));
+        hipLaunchKernelGGL(k_make_perm_multi, dim3((unsigned)len, (unsigned)n), dim3(threads), (size_t)n_pad * 8, consumer, gen,
+                           d0.n_walkers, n_pad, (long long)(s0->run_first + k0), buf, d0.n_half, front_row);
+        const long long recs = (long long)len * 2 * d0.n_half;
+        hipLaunchKernelGGL(k_draws_multi, dim3((unsigned)((recs + 255) / 256), (unsigned)n), dim3(256), 0, consumer, gen, d0,
+                           buf, (long long)(s0->run_first + k0), (long long)len);
+        LCF_HIP(hipGetLastError());
+    }
+    for (int t = 0; t < n; ++t) {
+        lcf_sampler* s = ss[t];
+        if (!gen) {
+            const int64_t k0 = s->block_start(b);
+            const int* host_perm = s->split_mode == LCF_SPLIT_HOST ? s->d_perm_host + (size_t)k0 * s->ds.n_walkers : nullptr;
+            // the half-step in front of a later block: the last row of the previous block (the other buffer)
+            const int* front = (b > 0 && s->need_slots)
+                                   ? s->d_slot[buf ^ 1] + (size_t)2 * s->block_len(b - 1) * s->ds.n_walkers : nullptr;
+            if (lcf_status r = generate_steps(s, buf, s->run_first + k0, s->block_len(b), s->split_mode, host_perm,
+                                              s->need_slots, front, consumer))
+                return r;
+        }
+        s->blk_generated = b;
+    }
     return LCF_OK;
 }
 
@@ -3691,21 +3710,23 @@ lcf_status speculate_continuation(lcf_sampler* s, hipStream_t st) {
 
 // Before launching the run's half-step `rel` on stream `st`: its block of draw records must be generated (it is,
 // unless the caller jumped ahead).
-lcf_status enter_half_step(lcf_sampler* s, long long rel, hipStream_t st) {
-    const int64_t b = s->block_of_step(rel / 2);
-    if (b == s->blk_current) return LCF_OK;
-    while (s->blk_generated < b)
-        if (lcf_status r = generate_block(s, s->blk_generated + 1, st)) return r;
-    s->blk_current = b;
+lcf_status enter_half_step(lcf_sampler* const* ss, int n, long long rel, hipStream_t st, const GenItem* gen = nullptr) {
+    const lcf_sampler* s0 = ss[0];
+    const int64_t b = s0->block_of_step(rel / 2);
+    if (b == s0->blk_current) return LCF_OK;
+    while (s0->blk_generated < b)
+        if (lcf_status r = generate_block(ss, n, s0->blk_generated + 1, st, gen)) return r;
+    for (int t = 0; t < n; ++t) ss[t]->blk_current = b;
     return LCF_OK;
 }
 
 // After that launch (the last reader of the block left behind, through the previous half-step's records): generate
 // the next block into the buffer that is now free.
-lcf_status leave_half_step(lcf_sampler* s, hipStream_t st) {
-    const int64_t last = s->block_of_step(s->run_steps - 1);
-    if (s->blk_generated == s->blk_current && s->blk_current < last)
-        return generate_block(s, s->blk_current + 1, st);
+lcf_status leave_half_step(lcf_sampler* const* ss, int n, hipStream_t st, const GenItem* gen = nullptr) {
+    const lcf_sampler* s0 = ss[0];
+    const int64_t last = s0->block_of_step(s0->run_steps - 1);
+    if (s0->blk_generated == s0->blk_current && s0->blk_current < last)
+        return generate_block(ss, n, s0->blk_current + 1, st, gen);
     return LCF_OK;
 }
 
@@ -3728,7 +3749,7 @@ lcf_status launch_next(lcf_sampler* s, bool have_next, int lo, int hi, hipStream
     const long long rel = g - s->g_run0;
     if (st != e->stream) s->foreign_stream = true;
     if (have_next)
-        if (lcf_status r = enter_half_step(s, rel, st)) return r;
+        if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
     const DrawRec* draws = have_next ? s->rows(rel) : nullptr;
     const DrawRec* prev_draws = have_prev ? s->rows(rel - 1) : nullptr;
     dispatch(StepDims{}, ds.n_dim, [&](auto nd) {
@@ -3737,7 +3758,7 @@ lcf_status launch_next(lcf_sampler* s, bool have_next, int lo, int hi, hipStream
     });
     LCF_HIP(hipGetLastError());
     if (have_next)
-        if (lcf_status r = leave_half_step(s, st)) return r;
+        if (lcf_status r = leave_half_step(&s, 1, st)) return r;
     s->pending = have_next;
     if (have_next) s->g_next = g + 1;
     return LCF_OK;
@@ -3781,7 +3802,7 @@ lcf_status launch_fused(lcf_sampler* s, int lo, int hi, hipStream_t st) {
     const long long prev_row = have_prev ? (g - 1 - s->g_run0) / 2 : 0;
     const long long rel = g - s->g_run0;
     if (st != e->stream) s->foreign_stream = true;
-    if (lcf_status r = enter_half_step(s, rel, st)) return r;
+    if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
     const DrawRec* draws = s->rows(rel);
     const DrawRec* prev_draws = have_prev ? s->rows(rel - 1) : nullptr;
     const int foreign = ds.n_half - (hi - lo);
@@ -3800,7 +3821,7 @@ lcf_status launch_fused(lcf_sampler* s, int lo, int hi, hipStream_t st) {
         else therm ? go(k_fused<ND, 0, true>) : go(k_fused<ND, 0, false>);
     });
     LCF_HIP(hipGetLastError());
-    if (lcf_status r = leave_half_step(s, st)) return r;
+    if (lcf_status r = leave_half_step(&s, 1, st)) return r;
     s->pending = true;
     s->g_next = g + 1;
     return LCF_OK;
@@ -3838,14 +3859,14 @@ int specialised_model(const DevProblem& dp) {
 lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board = false, int lo = 0, int hi = 0) {
     lcf_engine* e = s->e;
     const DevSampler& ds = s->ds;
-    if (lcf_status r = enter_half_step(s, rel, st)) return r;
+    if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
     const DrawRec* draws = s->rows(rel);
     const bool next_here = rel + 1 < 2 * s->run_steps && s->block_of_step((rel + 1) / 2) == s->blk_current;
     const DrawRec* draws_next = next_here ? draws + ds.n_half : nullptr;
     const size_t lds = solo_lds_bytes(e);
     const long long row = rel / 2, G = s->g_run0 + rel, g_run0 = s->g_run0;
     const dim3 grid((unsigned)(board ? hi - lo : ds.n_half));
-    if (board && hi <= lo) return leave_half_step(s, st);
+    if (board && hi <= lo) return leave_half_step(&s, 1, st);
     const int spec = specialised_model(e->dp);
     // workgroups of 512 threads: one part per 256 threads (up to two parts) or two (three or four)
     // ... or four (1024 threads) where the launch has at most one workgroup per CU
@@ -3869,7 +3890,7 @@ lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board
     });
     LCF_HIP(err);
     LCF_HIP(hipGetLastError());
-    return leave_half_step(s, st);
+    return leave_half_step(&s, 1, st);
 }
 
 // ---- a block of half-steps in ONE launch (k_solo_run) ---------------------------------------------------------------
@@ -3950,7 +3971,8 @@ struct RunClaim {   // releases on every path out of the enqueue
     int dev;
     hipStream_t st;
     bool held;
-    ~RunClaim() { if (held) run_release(dev, st); }
+    void release() { if (held) run_release(dev, st); held = false; }
+    ~RunClaim() { release(); }
 };
 
 // Workgroups of a resident launch, `per_cu` of them per CU: all on the device at once, on the compute units the engine's
@@ -4201,6 +4223,34 @@ lcf_status settle(lcf_sampler* s) {
 // Whatever changes the state on the device makes the host's copy stale.
 void invalidate_snapshot(lcf_sampler* s) { s->snap_enqueued = s->snap_valid = false; }
 
+// What the settled snapshot of a run reports: its error word and the words of the workgroups of one-launch runs.
+int reported_error(const lcf_sampler* s) {
+    int err = 0;
+    std::memcpy(&err, s->snap, sizeof(int));
+    const unsigned int* flags = s->snap_flags();
+    for (int k = 0; k < 2 * kSnapFlags; ++k) err |= (int)flags[k];
+    return err;
+}
+
+// A resident launch whose workgroups were not all on the device (somebody else's resident kernel holds CUs) has given
+// up within the bound of its waits and written no state -- that goes into the other set of buffers, in the run's last
+// step.  Put the sampler back on the state its resident run started from and drop what the run reported; the board's
+// tail words and count of started workgroups start again from zero.  (The run's stream must have been waited for.)
+lcf_status rewind_resident_run(lcf_sampler* s) {
+    s->flip_state_sets();
+    int sticky = 0;
+    std::memcpy(&sticky, s->snap, sizeof(int));
+    sticky &= 1;                                   // (a NaN of an earlier run stays reported)
+    LCF_HIP(hipMemcpy(s->ds.err, &sticky, sizeof(int), hipMemcpyHostToDevice));
+    std::memcpy(s->snap, &sticky, sizeof(int));
+    std::memset(s->snap_flags(), 0, 2 * kSnapFlags * sizeof(unsigned int));
+    LCF_HIP(hipMemset(static_cast<unsigned char*>(s->run_board_mem) + s->run_board_bytes() - kBoardClear * sizeof(unsigned int), 0,
+                      kBoardClear * sizeof(unsigned int)));
+    s->run_arrivals = 0;
+    invalidate_snapshot(s);
+    return LCF_OK;
+}
+
 // Device memory for the chain of a run of n_steps steps (kept until a longer run needs more).
 lcf_status reserve_chain(lcf_sampler* s, int64_t n_steps) {
     DevSampler& ds = s->ds;
@@ -4303,7 +4353,7 @@ lcf_status sampler_begin(lcf_sampler* s, int64_t first_step, int64_t n_steps, in
     }
     s->spec_first = -1;
     if (defer) return LCF_OK;
-    return generate_block(s, 0, gen ? gen : e->stream);
+    return generate_block(&s, 1, 0, gen ? gen : e->stream);
 }
 
 
@@ -4477,14 +4527,7 @@ void* lcf_sampler_rows_ptr(lcf_sampler* s, int32_t* row_doubles) {
 lcf_status lcf_sampler_check(lcf_sampler* s) {
     if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = settle(s)) return st;
-    int err = 0;
-    std::memcpy(&err, s->snap, sizeof(int));
-    {   // (what the workgroups of one-launch runs reported themselves)
-        const unsigned int* flags = s->snap_flags();
-        unsigned int any = 0;
-        for (int k = 0; k < 2 * kSnapFlags; ++k) any |= flags[k];
-        err |= (int)any;
-    }
+    const int err = reported_error(s);
     if (err & 2) {
         // (an aborted multi-rank run leaves the ranks with different states -- a rank has committed its own walkers of
         // the half-step the others gave up on: the ensemble must be set again, on every rank, before the next run)
@@ -4498,21 +4541,9 @@ lcf_status lcf_sampler_check(lcf_sampler* s) {
             hipMemcpy(w, reinterpret_cast<unsigned char*>(s->board_mem) + s->board_bytes() - kBoardClear * sizeof(unsigned int), sizeof w,
                       hipMemcpyDeviceToHost);
         if (run && s->replay_steps >= 0 && s->replay_split != LCF_SPLIT_HOST) {
-            // The launch's workgroups were not all resident (somebody else's resident kernel on this GPU): it gave up
-            // within the bound of its waits and has written no state -- that goes into the other set of buffers, in the
-            // last step.  Take the state it started from, drop what it reported, and run the same steps again with a
-            // launch per half-step (as every later run of this sampler).
+            // The launch gave up (rewind_resident_run): the same steps with a launch per half-step, as later runs.
             LCF_HIP(hipStreamSynchronize(s->e->stream));
-            s->flip_state_sets();
-            int sticky = 0;
-            std::memcpy(&sticky, s->snap, sizeof(int));
-            sticky &= 1;                                   // (a NaN of an earlier run stays reported)
-            LCF_HIP(hipMemcpy(s->ds.err, &sticky, sizeof(int), hipMemcpyHostToDevice));
-            std::memcpy(s->snap, &sticky, sizeof(int));
-            std::memset(s->snap_flags(), 0, 2 * kSnapFlags * sizeof(unsigned int));
-            LCF_HIP(hipMemset(static_cast<unsigned char*>(s->run_board_mem) + s->run_board_bytes() - kBoardClear * sizeof(unsigned int), 0,
-                              kBoardClear * sizeof(unsigned int)));
-            s->run_arrivals = 0;
+            if (lcf_status r = rewind_resident_run(s)) return r;
             static bool told = false;
             if (!told)
                 std::fprintf(stderr, "liblcf_hip: a one-launch run waited %.2f s for version %u of walker %u: its workgroups were "
@@ -4526,7 +4557,6 @@ lcf_status lcf_sampler_check(lcf_sampler* s) {
             told = true;
             s->run_off = true;
             s->spec_first = -1;
-            invalidate_snapshot(s);
             const int64_t n = s->replay_steps;
             s->replay_steps = -1;
             if (lcf_status st = lcf_sampler_run_async(s, s->replay_first, n, s->replay_split, nullptr, s->replay_store)) return st;
@@ -4928,7 +4958,7 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
         long long starts[2] = {-1, -1};   // first half-steps (relative) of the two launches in front
         for (long long rel = 0; rel < 2 * n_steps;) {
             ++s->last_launches;
-            if (lcf_status r = enter_half_step(s, rel, st)) return r;
+            if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
             const int n = s->block_span(rel, kRunSpan);
             const long long need = starts[0] >= 0 ? s->g_run0 + starts[0] : 0;
             if (lcf_status r = launch_run(s, rel, n, st, true, lo, hi, need)) return r;
@@ -4938,7 +4968,7 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
                                    (long long)(s->g_run0 + rel), (long long)(rel / 2), s->rows(rel), n, 0, 1);
                 LCF_HIP(hipGetLastError());
             }
-            if (lcf_status r = leave_half_step(s, st)) return r;
+            if (lcf_status r = leave_half_step(&s, 1, st)) return r;
             starts[0] = starts[1];
             starts[1] = rel;
             rel += n;
@@ -4995,17 +5025,16 @@ lcf_status lcf_sampler_run_async(lcf_sampler* s, int64_t first_step, int64_t n_s
         s->last_launches = 0;
         for (long long rel = 0; rel < 2 * n_steps;) {   // (the first launch posts the start state on the board itself)
             ++s->last_launches;
-            if (lcf_status r = enter_half_step(s, rel, st)) return r;
+            if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
             const int n = s->block_span(rel, kRunSpanSolo);
             if (lcf_status r = launch_run(s, rel, n, st)) return r;
-            if (lcf_status r = leave_half_step(s, st)) return r;
+            if (lcf_status r = leave_half_step(&s, 1, st)) return r;
             rel += n;
         }
         s->g_next += 2 * n_steps;
         s->flip_state_sets();                  // the state behind this run is in the other set now
         LCF_HIP(hipEventRecord(s->ev1, st));
-        claim.held = false;
-        run_release(s->e->device, st);
+        claim.release();
         // (the last step wrote the snapshot with the state: no snapshot kernel; the caller waits for this event)
         LCF_HIP(hipEventRecord(s->ev_snap, st));
         s->snap_enqueued = true;
@@ -5063,115 +5092,120 @@ lcf_status lcf_sampler_run(lcf_sampler* s, int64_t first_step, int64_t n_steps, 
     return r;
 }
 
-// Population mode: the same n_steps for `n` samplers (one transient each, same walker count) with ONE k_step and ONE
-// k_points launch per half-step covering all of them (blockIdx.y = transient).
-// (`resident`: the transients' workgroups may stay for blocks of half-steps, k_pop_run; false = a launch per half-step,
-// what a run falls back to -- for the rest of the process -- after a resident launch whose workgroups were not all there)
-static bool g_pop_run_off = false;
-static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step, int64_t n_steps, int32_t split_mode,
-                                 int32_t store_chain, double* elapsed_ms, bool resident) {
-    if (!ss || n <= 0) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (n > 65535) return fail(LCF_ERR_INVALID_ARGUMENT, "at most 65535 transients per call");
-    if (split_mode == LCF_SPLIT_HOST) return fail(LCF_ERR_UNSUPPORTED, "population runs use identity or random splits");
-    const lcf_sampler* s0 = ss[0];
-    if (!s0) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
-    for (int t = 0; t < n; ++t) {
-        const lcf_sampler* s = ss[t];
-        if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
-        const DevProblem &a = s->e->dp, &b = s0->e->dp;
-        if (s->e->device != s0->e->device || s->ds.n_walkers != s0->ds.n_walkers || a.variant != b.variant ||
-            a.use_therm != b.use_therm || a.tab_in_lds != b.tab_in_lds)
-            return fail(LCF_ERR_UNSUPPORTED, "transients of one batched run must agree on device, walker count, "
-                                             "band-sum variant, thermal sharing and table placement");
-    }
-    // Everything of this run -- every transient's draw records, the half-steps, the snapshots -- goes on ONE stream (the
-    // first transient's): stream order is all the synchronisation there is.  What the transients' own streams still hold
-    // (set_state, an earlier run of their own) is waited for once, here.
-    LCF_HIP(hipSetDevice(s0->e->device));
-    LCF_HIP(hipDeviceSynchronize());
-    hipStream_t pop_stream = s0->e->stream;
-    long long g = 0;
-    for (int t = 0; t < n; ++t) {
-        if (lcf_status st = sampler_begin(ss[t], first_step, n_steps, split_mode, nullptr, store_chain, true, pop_stream,
-                                          /*defer: see pop_generate*/ true)) return st;
-        g = std::max(g, ss[t]->g_next);
-    }
-    // The draw records of ALL transients come from one launch of each generation kernel per block of steps (random
-    // splits of samplers with the same block geometry -- what a population has; else sampler by sampler as before).
-    bool batched_gen = split_mode == LCF_SPLIT_RANDOM;
-    for (int t = 1; t < n; ++t)
-        batched_gen = batched_gen && ss[t]->blk_first == s0->blk_first && ss[t]->blk_steps == s0->blk_steps;
-    GenItem* dgen = nullptr;
-    if (batched_gen) {
-        std::vector<GenItem> gen(n);
-        for (int t = 0; t < n; ++t)
-            gen[t] = GenItem{ss[t]->ds.key0, ss[t]->ds.key1, ss[t]->ds.n_dim, ss[t]->ds.a,
-                             {ss[t]->d_perm[0], ss[t]->d_perm[1]}, {ss[t]->d_slot[0], ss[t]->d_slot[1]},
-                             {ss[t]->d_draws[0], ss[t]->d_draws[1]}};
-        LCF_HIP(hipMalloc((void**)&dgen, (size_t)n * sizeof(GenItem)));
-        if (hipMemcpy(dgen, gen.data(), (size_t)n * sizeof(GenItem), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(dgen);
-            return fail(LCF_ERR_HIP, "hipMemcpy of the generation items");
-        }
-    }
-    // block b of every sampler (enqueued on the population's stream)
-    auto pop_generate = [&](int64_t b) -> lcf_status {
-        if (!batched_gen) {
-            for (int t = 0; t < n; ++t)
-                if (lcf_status r = generate_block(ss[t], b, pop_stream)) return r;
-            return LCF_OK;
-        }
-        const DevSampler& d0 = s0->ds;
-        const int buf = (int)(b & 1);
-        const int64_t k0 = s0->block_start(b), len = s0->block_len(b);
-        int n_pad = 2;
-        while (n_pad < d0.n_walkers) n_pad <<= 1;
-        const int threads = std::min(1024, std::max(64, n_pad / 2));
-        const long long front_row = b > 0 ? 2 * (long long)s0->block_len(b - 1) : -1;
-        LCF_HIP(prepare_kernel(k_make_perm_multi, (size_t)n_pad * 8));
-        hipLaunchKernelGGL(k_make_perm_multi, dim3((unsigned)len, (unsigned)n), dim3(threads), (size_t)n_pad * 8, pop_stream, dgen,
-                           d0.n_walkers, n_pad, (long long)(s0->run_first + k0), buf, d0.n_half, front_row);
-        const long long recs = (long long)len * 2 * d0.n_half;
-        hipLaunchKernelGGL(k_draws_multi, dim3((unsigned)((recs + 255) / 256), (unsigned)n), dim3(256), 0, pop_stream, dgen, d0,
-                           buf, (long long)(s0->run_first + k0), (long long)len);
-        LCF_HIP(hipGetLastError());
-        for (int t = 0; t < n; ++t) ss[t]->blk_generated = b;
-        return LCF_OK;
-    };
-    auto pop_enter = [&](long long rel) -> lcf_status {      // (enter_half_step for all samplers)
-        const int64_t b = s0->block_of_step(rel / 2);
-        if (b == s0->blk_current) return LCF_OK;
-        while (s0->blk_generated < b)
-            if (lcf_status r = pop_generate(s0->blk_generated + 1)) return r;
-        for (int t = 0; t < n; ++t) ss[t]->blk_current = b;
-        return LCF_OK;
-    };
-    auto pop_leave = [&]() -> lcf_status {                    // (leave_half_step for all samplers)
-        const int64_t last = s0->block_of_step(s0->run_steps - 1);
-        if (s0->blk_generated == s0->blk_current && s0->blk_current < last) return pop_generate(s0->blk_current + 1);
-        return LCF_OK;
-    };
-    if (n_steps > 0)
-        if (lcf_status r = pop_generate(0)) {
-            if (dgen) hipFree(dgen);
-            return r;
-        }
-    std::vector<MultiItem> items(n);
-    size_t lds = 0;
+}  // extern "C"
+
+// ---- population mode: the same n_steps for `n` samplers (one transient each, same walker count) in lock step ---------
+// Every launch covers all transients (blockIdx.y = transient), in the first of three forms the population allows
+// (population_plan): resident workgroups for blocks of half-steps (k_pop_run), ONE launch per half-step (k_pop), or two
+// (k_step_multi + k_points_multi).  Each form is enqueued by a loop of its own over the run's half-steps.
+namespace {
+
+// Proposals per workgroup of k_pop: 4.  (Measured at 32 x 512 walkers x 600 points: 49.0 us per half-step; staging the
+// interpolants in LDS as well costs occupancy, 61.7 us; workgroups of 8 proposals that can afford it, 50.4 us;
+// five waves per SIMD at the price of 8 spilled registers, 47.0 us.)
+constexpr int kPopGroup = 4;
+
+bool g_pop_run_off = false;   // a resident launch of this process found its workgroups not all there
+
+// How a population run goes, decided before any of it is enqueued.
+struct PopPlan {
+    int form = LCF_KERNEL_POPULATION_PHASES;   // LCF_KERNEL_POPULATION_RUN, _POPULATION or _POPULATION_PHASES
+    std::vector<MultiItem> items;              // per transient: its sampler by value, the engine's parts merged
+    int same_dim = 0;                          // compile-time walker dimension when every transient has the same
+    int pop_spec = 0;                          // the model-specialised kernel when every transient takes the same
     int max_parts = 1;
-    const bool thermal = s0->e->dp.use_therm != 0;
-    int same_dim = s0->ds.n_dim;  // compile-time walker dimension when every transient has the same
+    size_t lds = 0, pop_lds = 0, run_lds = 0;  // of k_points_multi, k_pop and k_pop_run
+    // the resident form: k_pop_run<ND, 1, kPopRunGroup, M> of the population's shape, the workgroups of it the device
+    // holds, transients per launch, workgroups per transient, and the device's claim (run_claim)
+    decltype(&k_pop_run<0, 1, kPopRunGroup, 0>) run_kernel = nullptr;
+    int cap = 0, chunk = 0, run_grid = 0;
+    RunClaim claim{0, nullptr, false};
+    // the run's GenItems (batched generation only) and items in device memory, freed with the plan on every way out
+    GenItem* d_gen = nullptr;
+    MultiItem* d_items = nullptr;
+    ~PopPlan() { hipFree(d_gen); hipFree(d_items); }
+};
+
+// LDS of a workgroup of `group` proposals of k_pop / k_pop_run: the staged image, the proposals' scratch and wave sums
+size_t pop_lds_bytes(const DevProblem& pb, int group) {
+    return kLdsHead * sizeof(double) + (size_t)pb.stage_d2 * sizeof(double2) +
+           (size_t)group * (kPopScratch + 4 * kPopMaxParts) * sizeof(double);
+}
+
+// The resident form, if it fits: the workgroups stay for a block of half-steps and hand each other rows through the
+// transients' boards.  The launch stages the interpolants in LDS as well, where the engine's image leaves them out.
+lcf_status plan_resident(lcf_sampler** ss, int n, long long g, PopPlan& p) {
+    const lcf_sampler* s0 = ss[0];
+    // (a board of tagged rows and a second set of state buffers per transient -- 64 KB per walker: a population of
+    // thousands of transients stays with a launch per half-step rather than take more than half of the free memory)
+    size_t need = 0, free_b = 0, total_b = 0;
     for (int t = 0; t < n; ++t)
-        if (ss[t]->ds.n_dim != same_dim) same_dim = 0;
+        if (!ss[t]->run_board_mem) need += ss[t]->run_board_bytes() + (size_t)ss[t]->ds.n_walkers * (ss[t]->ds.n_dim + 2) * 8;
+    const bool memory = need == 0 || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2);
+    (void)hipGetLastError();
+    if (!memory) return LCF_OK;
+    const bool itab_lds = !(std::getenv("LCF_POP_ITAB_LDS") && std::atoi(std::getenv("LCF_POP_ITAB_LDS")) == 0);
+    std::vector<int> itab_extra(n, 0);
+    for (int t = 0; t < n; ++t) {
+        const DevProblem& ip = p.items[t].pb;
+        const size_t n_itab = ip.use_itab ? (size_t)ip.n_filters * ip.itab_m * 8 : 0;
+        if (itab_lds && n_itab > 0 && ip.n_itab_lds == 0 && ip.n_spl_lds == 0 && n_itab * sizeof(double) <= 40 * 1024)
+            itab_extra[t] = (int)n_itab;
+        p.run_lds = std::max(p.run_lds, pop_lds_bytes(ip, kPopRunGroup) + (size_t)(itab_extra[t] / 2) * sizeof(double2));
+    }
+    // fits: a CU's LDS, and at least one workgroup on the compute units the population's stream may use
+    if (p.run_lds > kLdsPerCU) return LCF_OK;
+    const auto own = [&](auto nd, auto m) {
+        p.run_kernel = k_pop_run<decltype(nd)::value, 1, kPopRunGroup, decltype(m)::value>;
+    };
+    if (!dispatch_model(PopRunModels{}, p.same_dim, p.pop_spec, own)) p.run_kernel = k_pop_run<0, 1, kPopRunGroup, 0>;
+    int per_cu = 0;
+    LCF_HIP(prepare_kernel(p.run_kernel, p.run_lds, 64 * kPopRunGroup, &per_cu));
+    p.cap = run_capacity(s0->e, per_cu);
+    if (p.cap < 1) return LCF_OK;
+    p.claim.dev = s0->e->device;
+    p.claim.st = s0->e->stream;
+    if (!(p.claim.held = run_claim(p.claim.dev, p.claim.st))) return LCF_OK;
     for (int t = 0; t < n; ++t) {
         lcf_sampler* s = ss[t];
-        s->g_next = s->g_run0 = g;  // lock-step half-step numbering across the population
+        if (lcf_status r = run_buffers(s)) return r;
+        MultiItem& it = p.items[t];
+        it.sm = run_struct(s);
+        it.g_run0 = g;
+        it.flip = s->run_flip ? 1 : 0;
+        it.arrive0 = s->run_arrivals;
+        if ((it.itab_extra = itab_extra[t])) {
+            it.pb.n_itab_lds = itab_extra[t];
+            it.pb.stage_d2 += itab_extra[t] / 2;
+        }
+    }
+    // gridDim.x workgroups per transient, all of them on the device at once: what the device holds, shared evenly -- and
+    // no more than give every workgroup the same number of groups of proposals per half-step
+    const int n_groups = (s0->ds.n_half + kPopRunGroup - 1) / kPopRunGroup;
+    p.chunk = std::min(n, p.cap);
+    const int room = std::min(std::max(1, p.cap / p.chunk), n_groups);
+    const int per_wg = (n_groups + room - 1) / room;
+    p.run_grid = (n_groups + per_wg - 1) / per_wg;
+    p.form = LCF_KERNEL_POPULATION_RUN;
+    return LCF_OK;
+}
+
+// The plan of a run that every transient's sampler has begun: the items, the half-steps numbered in lock step from g,
+// and the form (`resident`: the resident form may be taken).
+lcf_status population_plan(lcf_sampler** ss, int n, int64_t n_steps, long long g, bool resident, PopPlan& p) {
+    const DevProblem& p0 = ss[0]->e->dp;
+    p.items.resize(n);
+    p.same_dim = ss[0]->ds.n_dim;
+    for (int t = 0; t < n; ++t) {
+        lcf_sampler* s = ss[t];
+        s->g_next = s->g_run0 = g;
         s->ds.inline_finalize = 1;
-        items[t] = MultiItem{s->e->dp, s->ds, {s->d_draws[0], s->d_draws[1]}, (long long)s->blk_first,
-                             (long long)s->blk_steps, s->coef, s->lprior};
+        if (s->ds.n_dim != p.same_dim) p.same_dim = 0;
+        p.items[t] = MultiItem{s->e->dp, s->ds, {s->d_draws[0], s->d_draws[1]}, (long long)s->blk_first,
+                               (long long)s->blk_steps, s->coef, s->lprior};
         // With many transients in one launch a single workgroup per proposal already fills the chip, and it stages
         // the tables and reduces once for all of the proposal's chunks: fewer parts than the engine's default.
-        DevProblem& ip = items[t].pb;
+        DevProblem& ip = p.items[t].pb;
         const long long slots = (long long)n * s->ds.n_half;
         const int want = (int)std::max<long long>(1, (kTargetGroups + slots - 1) / slots);
         const int parts = std::min(ip.n_parts, want);
@@ -5183,197 +5217,162 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
             ip.part_col0[J] = J < np ? ep.part_col0[J * mg] : ep.em_cols;
         }
         ip.n_parts = np;
-        lds = std::max(lds, s->e->lds_bytes);
-        max_parts = std::max(max_parts, items[t].pb.n_parts);
+        p.lds = std::max(p.lds, s->e->lds_bytes);
+        p.max_parts = std::max(p.max_parts, np);
     }
-    // One launch per half-step (k_pop: a workgroup per four proposals, accept test included) where every transient has
-    // shared epochs, staged tables, the fast band sum, at most kPopMaxParts merged parts and tables that do not depend
-    // on the proposal (ShockCooling3's reddened tables do); else the two launches below.
-    const DevProblem& p0 = s0->e->dp;
-    bool one_launch = std::getenv("LCF_NO_POP") == nullptr && thermal && p0.variant != 0 && p0.tab_in_lds &&
-                      max_parts <= kPopMaxParts;
-    size_t pop_lds = 0;
-    // Proposals per workgroup: 4.  (Measured at 32 x 512 walkers x 600 points: 49.0 us per half-step; staging the
-    // interpolants in LDS as well costs occupancy, 61.7 us; workgroups of 8 proposals that can afford it, 50.4 us;
-    // five waves per SIMD at the price of 8 spilled registers, 47.0 us.)
-    constexpr int pop_group = 4;
-    for (int t = 0; t < n; ++t) one_launch = one_launch && ss[t]->e->dp.model != kShockCooling3;
-    for (int t = 0; t < n && one_launch; ++t) {
-        const DevProblem& ip = items[t].pb;
-        pop_lds = std::max(pop_lds, kLdsHead * sizeof(double) + (size_t)ip.stage_d2 * sizeof(double2) +
-                                        (size_t)pop_group * (kPopScratch + 4 * kPopMaxParts) * sizeof(double));
-    }
-    one_launch = one_launch && pop_lds <= kLdsPerCU;
-    int pop_spec = specialised_model(items[0].pb);   // every transient of the population of that shape, or the generic kernel
+    p.pop_spec = specialised_model(p.items[0].pb);
     for (int t = 1; t < n; ++t)
-        if (specialised_model(items[t].pb) != pop_spec) pop_spec = 0;
-    LCF_HIP(hipSetDevice(s0->e->device));
-    // Resident form (k_pop_run): the workgroups stay for a block of half-steps and hand each other rows through the
-    // transients' boards.  The launch stages the interpolants in LDS as well, where the engine's image leaves them out.
+        if (specialised_model(p.items[t].pb) != p.pop_spec) p.pop_spec = 0;
+    // k_pop where every transient has shared epochs, staged tables, the fast band sum, at most kPopMaxParts merged parts
+    // and tables that do not depend on the proposal (ShockCooling3's reddened tables do)
+    bool one_launch = std::getenv("LCF_NO_POP") == nullptr && p0.use_therm && p0.variant != 0 && p0.tab_in_lds &&
+                      p.max_parts <= kPopMaxParts;
+    for (int t = 0; t < n; ++t) {
+        one_launch = one_launch && ss[t]->e->dp.model != kShockCooling3;
+        p.pop_lds = std::max(p.pop_lds, pop_lds_bytes(p.items[t].pb, kPopGroup));
+    }
+    if (!one_launch || p.pop_lds > kLdsPerCU) return LCF_OK;
+    p.form = LCF_KERNEL_POPULATION;
     const bool no_pop_run = std::getenv("LCF_NO_POP_RUN") != nullptr || std::getenv("LCF_NO_RUN_KERNEL") != nullptr;
-    const bool pop_itab_lds = !(std::getenv("LCF_POP_ITAB_LDS") && std::atoi(std::getenv("LCF_POP_ITAB_LDS")) == 0);
-    resident = resident && one_launch && !no_pop_run && !g_pop_run_off && n_steps > 0;
-    if (resident) {
-        // (a board of tagged rows and a second set of state buffers per transient -- 64 KB per walker: a population of
-        // thousands of transients stays with a launch per half-step rather than take more than half of the free memory)
-        size_t need = 0, free_b = 0, total_b = 0;
-        for (int t = 0; t < n; ++t)
-            if (!ss[t]->run_board_mem) need += ss[t]->run_board_bytes() + (size_t)ss[t]->ds.n_walkers * (ss[t]->ds.n_dim + 2) * 8;
-        if (need > 0 && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b / 2)) resident = false;
-        (void)hipGetLastError();
-    }
-    resident = resident && run_claim(s0->e->device, pop_stream);
-    RunClaim claim{s0->e->device, pop_stream, resident};
-    size_t run_lds = 0;
-    int run_group = kPopRunGroup;   // proposals (= waves) per workgroup of the resident form
-#ifdef LCF_POP_GROUPS_ALL
-    if (const char* env = std::getenv("LCF_POP_GROUP")) run_group = std::atoi(env);   // (experiments: 4, 8, 10, 12)
-#endif
-    if (resident) {
-        for (int t = 0; t < n; ++t) {
-            lcf_sampler* s = ss[t];
-            if (lcf_status r = run_buffers(s)) {
-                hipFree(dgen);
-                return r;
-            }
-            MultiItem& it = items[t];
-            it.sm = run_struct(s);
-            it.g_run0 = g;
-            it.flip = s->run_flip ? 1 : 0;
-            it.itab_extra = 0;
-            it.arrive0 = s->run_arrivals;
-            it.pad = 0u;
-            DevProblem& ip = it.pb;
-            const size_t n_itab = ip.use_itab ? (size_t)ip.n_filters * ip.itab_m * 8 : 0;
-            if (pop_itab_lds && n_itab > 0 && ip.n_itab_lds == 0 && ip.n_spl_lds == 0 && n_itab * sizeof(double) <= 40 * 1024) {
-                it.itab_extra = (int)n_itab;
-                ip.n_itab_lds = (int)n_itab;
-                ip.stage_d2 += (int)(n_itab / 2);
-            }
-            run_lds = std::max(run_lds, kLdsHead * sizeof(double) + (size_t)ip.stage_d2 * sizeof(double2) +
-                                            (size_t)run_group * (kPopScratch + 4 * kPopMaxParts) * sizeof(double));
+    if (!resident || no_pop_run || g_pop_run_off || n_steps == 0) return LCF_OK;
+    return plan_resident(ss, n, g, p);
+}
+
+// Resident form: per block of draw records, launches of `chunk` transients at a time, run_grid workgroups each.
+lcf_status enqueue_pop_run(lcf_sampler** ss, int n, PopPlan& p, int64_t n_steps, int32_t store_chain, hipStream_t st,
+                           long long* launches) {
+    // (test of the recovery from a launch whose workgroups are not all resident: the last one is not launched at all)
+    const bool test_missing = std::getenv("LCF_RUN_TEST_MISSING") != nullptr;
+    const unsigned int n_wg = (unsigned int)(test_missing && p.run_grid > 1 ? p.run_grid - 1 : p.run_grid);
+    const long long state_from = 2 * (long long)(n_steps - 1);   // X / LP / counts: written by the run's last step
+    int run_launches = 0;
+    for (long long rel = 0; rel < 2 * n_steps; ++run_launches) {
+        if (lcf_status r = enter_half_step(ss, n, rel, st, p.d_gen)) return r;
+        const int n_hs = ss[0]->block_span(rel, kRunSpanSolo);
+        for (int c0 = 0; c0 < n; c0 += p.chunk) {
+            hipLaunchKernelGGL(p.run_kernel, dim3(n_wg, (unsigned)std::min(p.chunk, n - c0)), dim3(64 * kPopRunGroup), p.run_lds,
+                               st, p.d_items + c0, rel, n_hs, state_from, store_chain ? 1 : 0, run_launches, p.run_grid);
+            LCF_HIP(hipGetLastError());
         }
+        for (int t = 0; t < n; ++t) ss[t]->run_arrivals += (unsigned int)p.run_grid;   // (the board's count of them)
+        if (lcf_status r = leave_half_step(ss, n, st, p.d_gen)) return r;
+        rel += n_hs;
     }
-    MultiItem* ditems = nullptr;
-    LCF_HIP(hipMalloc((void**)&ditems, (size_t)n * sizeof(MultiItem)));
-    hipStream_t st = s0->e->stream;
-    hipError_t err = hipMemcpyAsync(ditems, items.data(), (size_t)n * sizeof(MultiItem), hipMemcpyHostToDevice, st);
-    const int nh = s0->ds.n_half;
-    hipEvent_t ev0 = s0->ev0, ev1 = s0->ev1;
-    if (err == hipSuccess) err = hipEventRecord(ev0, st);
-    const dim3 gs((unsigned)nh, (unsigned)n), gp((unsigned)(nh * max_parts), (unsigned)n);
-    const dim3 bs(64), bp(kBlock);
-    int run_launches = 0, run_grid = 0;
-    if (resident) {
-        // gridDim.x workgroups per transient, all of them on the device at once: what the device holds, shared evenly --
-        // and no more than give every workgroup the same number of groups of proposals per half-step
-        const int n_groups = (nh + run_group - 1) / run_group;
-        // k_pop_run<ND, 1, G, M> for the population's shape: f(kernel, G)
-        const auto with_kernel = [&](auto f) {
-            dispatch<kPopRunGroup>(PopRunGroups{}, run_group, [&](auto g_) {
-                constexpr int G = decltype(g_)::value;
-                const auto own = [&](auto nd, auto m) { f(k_pop_run<decltype(nd)::value, 1, G, decltype(m)::value>, G); };
-                if (!dispatch_model(PopRunModels{}, same_dim, pop_spec, own)) f(k_pop_run<0, 1, G, 0>, G);
+    for (int t = 0; t < n; ++t) ss[t]->flip_state_sets();   // the state behind this run is in the other set now
+    p.claim.release();
+    *launches = run_launches;
+    return LCF_OK;
+}
+
+// One launch per half-step: k_pop, a workgroup per kPopGroup proposals, accept test included.
+lcf_status enqueue_pop(lcf_sampler** ss, int n, const PopPlan& p, int64_t n_steps, hipStream_t st) {
+    const int nh = ss[0]->ds.n_half;
+    const dim3 grid((unsigned)((nh + kPopGroup - 1) / kPopGroup), (unsigned)n), block(64 * kPopGroup);
+    decltype(&k_pop<0, 1, kPopGroup, 0>) kernel = nullptr;   // k_pop<ND, 1, kPopGroup, M> of the population's shape
+    const auto own = [&](auto nd, auto m) { kernel = k_pop<decltype(nd)::value, 1, kPopGroup, decltype(m)::value>; };
+    dispatch(PopDims{}, p.same_dim, [&](auto nd) {
+        if (!dispatch_model(SpecialisedModels{}, nd, p.pop_spec, own)) own(nd, Int<0>{});
+    });
+    LCF_HIP(prepare_kernel(kernel, p.pop_lds));
+    for (int64_t k = 0; k < 2 * n_steps; ++k) {
+        if (lcf_status r = enter_half_step(ss, n, k, st, p.d_gen)) return r;
+        hipLaunchKernelGGL(kernel, grid, block, p.pop_lds, st, p.d_items, (long long)k);
+        LCF_HIP(hipGetLastError());
+        if (lcf_status r = leave_half_step(ss, n, st, p.d_gen)) return r;
+    }
+    return LCF_OK;
+}
+
+// Two launches per half-step: k_step_multi commits the previous half-step and draws the next one, k_points_multi
+// evaluates its proposals; one more k_step_multi commits the last.
+lcf_status enqueue_pop_phases(lcf_sampler** ss, int n, const PopPlan& p, int64_t n_steps, long long g, hipStream_t st) {
+    const DevProblem& p0 = ss[0]->e->dp;
+    const int nh = ss[0]->ds.n_half;
+    const dim3 gs((unsigned)nh, (unsigned)n), gp((unsigned)(nh * p.max_parts), (unsigned)n);
+    decltype(&k_step_multi<0>) step = nullptr;
+    dispatch(PopDims{}, p.same_dim, [&](auto nd) { step = k_step_multi<decltype(nd)::value>; });
+    decltype(&k_points_multi<0, false, false>) points = nullptr;   // <VARIANT, LDS_TAB, THERM> of the population
+    dispatch<1>(Dims<0>{}, p0.variant, [&](auto v) {
+        dispatch<1>(Dims<0>{}, p0.tab_in_lds, [&](auto tab) {
+            dispatch<1>(Dims<0>{}, p0.use_therm, [&](auto therm) {
+                points = k_points_multi<decltype(v)::value, decltype(tab)::value != 0, decltype(therm)::value != 0>;
             });
-        };
-        int per_cu = 0;
-        with_kernel([&](auto kernel, int G) { err = prepare_kernel(kernel, run_lds, 64 * G, &per_cu); });
-        int cap = per_cu * s0->e->n_cus;
-        if (const char* env = std::getenv("LCF_RUN_GRID")) cap = std::min(cap, std::atoi(env));  // (tests)
-        const int chunk = std::min<int>(n, std::max(cap, 1));          // transients per launch
-        const int room = std::max(1, cap / chunk);
-        const int per_wg = (n_groups + std::min(room, n_groups) - 1) / std::min(room, n_groups);
-        run_grid = (n_groups + per_wg - 1) / per_wg;
-        if (cap < 1 && err == hipSuccess) err = hipErrorInvalidConfiguration;
-        const bool test_missing = std::getenv("LCF_RUN_TEST_MISSING") != nullptr;
-        const long long state_from = 2 * (long long)(n_steps - 1);
-        for (long long rel = 0; rel < 2 * n_steps && err == hipSuccess;) {
-            if (pop_enter(rel) != LCF_OK) err = hipErrorUnknown;
-            if (err != hipSuccess) break;
-            const int n_hs = s0->block_span(rel, kRunSpanSolo);
-            for (int c0 = 0; c0 < n && err == hipSuccess; c0 += chunk) {
-                const dim3 grid((unsigned)(test_missing && run_grid > 1 ? run_grid - 1 : run_grid), (unsigned)std::min(chunk, n - c0));
-                with_kernel([&](auto kernel, int G) {
-                    hipLaunchKernelGGL(kernel, grid, dim3(64 * G), run_lds, st, ditems + c0, rel, n_hs, state_from,
-                                       store_chain ? 1 : 0, run_launches, run_grid);
-                });
-                err = hipGetLastError();
-            }
-            ++run_launches;
-            for (int t = 0; t < n; ++t)
-                if (st != ss[t]->e->stream) ss[t]->foreign_stream = true;
-            if (err == hipSuccess && pop_leave() != LCF_OK) err = hipErrorUnknown;
-            rel += n_hs;
-        }
-        for (int t = 0; t < n; ++t) {   // the state behind this run is in the other set of buffers now
-            ss[t]->run_arrivals += (unsigned int)(run_launches * run_grid);
-            ss[t]->flip_state_sets();
-        }
-        claim.held = false;
-        run_release(s0->e->device, st);
-    } else if (one_launch) {
-        const dim3 gq((unsigned)((nh + pop_group - 1) / pop_group), (unsigned)n), bq(64 * pop_group);
-        for (int64_t k = 0; k < 2 * n_steps && err == hipSuccess; ++k) {
-            if (pop_enter(k) != LCF_OK) err = hipErrorUnknown;
-            if (err != hipSuccess) break;
-            const auto go = [&](auto nd, auto m) {
-                const auto kernel = k_pop<decltype(nd)::value, 1, pop_group, decltype(m)::value>;
-                if ((err = prepare_kernel(kernel, pop_lds)) == hipSuccess)
-                    hipLaunchKernelGGL(kernel, gq, bq, pop_lds, st, ditems, (long long)k);
-            };
-            dispatch(PopDims{}, same_dim, [&](auto nd) {
-                if (!dispatch_model(SpecialisedModels{}, nd, pop_spec, go)) go(nd, Int<0>{});
-            });
-            for (int t = 0; t < n; ++t)
-                if (st != ss[t]->e->stream) ss[t]->foreign_stream = true;
-            if (err == hipSuccess && pop_leave() != LCF_OK) err = hipErrorUnknown;
-            if (err == hipSuccess) err = hipGetLastError();
-        }
-    }
-    for (int64_t k = 0; !one_launch && !resident && k <= 2 * n_steps && err == hipSuccess; ++k) {
-        const bool have_next = k < 2 * n_steps, have_prev = k > 0;
-        if (!have_next && !have_prev) break;
-        if (have_next && pop_enter(k) != LCF_OK) err = hipErrorUnknown;   // (every transient's block of draw records)
-        if (err != hipSuccess) break;
-        dispatch(PopDims{}, same_dim, [&](auto nd) {
-            hipLaunchKernelGGL(k_step_multi<decltype(nd)::value>, gs, bs, 0, st, ditems, have_prev ? 1 : 0,
-                               (long long)((k - 1) / 2), have_next ? 1 : 0, (long long)k, (long long)(g + k));
         });
-        if (have_next) {
-            for (int t = 0; t < n; ++t)
-                if (st != ss[t]->e->stream) ss[t]->foreign_stream = true;
-            if (err == hipSuccess && pop_leave() != LCF_OK) err = hipErrorUnknown;
-        }
+    });
+    LCF_HIP(prepare_kernel(points, p.lds));
+    for (int64_t k = 0; n_steps > 0 && k <= 2 * n_steps; ++k) {
+        const bool have_next = k < 2 * n_steps, have_prev = k > 0;
+        if (have_next)
+            if (lcf_status r = enter_half_step(ss, n, k, st, p.d_gen)) return r;
+        hipLaunchKernelGGL(step, gs, dim3(64), 0, st, p.d_items, have_prev ? 1 : 0, (long long)((k - 1) / 2), have_next ? 1 : 0,
+                           (long long)k, (long long)(g + k));
+        LCF_HIP(hipGetLastError());
         if (!have_next) break;
-        const int parity = (int)((g + k) & 1);
-        const auto go = [&](auto kernel) {
-            prepare_kernel(kernel, lds);
-            hipLaunchKernelGGL(kernel, gp, bp, lds, st, ditems, parity);
-        };
-        if (p0.variant == 0) {
-            if (p0.tab_in_lds) thermal ? go(k_points_multi<0, true, true>) : go(k_points_multi<0, true, false>);
-            else thermal ? go(k_points_multi<0, false, true>) : go(k_points_multi<0, false, false>);
-        } else {
-            if (p0.tab_in_lds) thermal ? go(k_points_multi<1, true, true>) : go(k_points_multi<1, true, false>);
-            else thermal ? go(k_points_multi<1, false, true>) : go(k_points_multi<1, false, false>);
-        }
-        err = hipGetLastError();
+        if (lcf_status r = leave_half_step(ss, n, st, p.d_gen)) return r;
+        hipLaunchKernelGGL(points, gp, dim3(kBlock), p.lds, st, p.d_items, (int)((g + k) & 1));
+        LCF_HIP(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipEventRecord(ev1, st);
+    return LCF_OK;
+}
+
+// One pass of lcf_population_run (`resident`: the resident form may be taken).  *repeat: a resident launch gave up;
+// every transient is back on the state the run started from, and the caller repeats the steps without that form.
+lcf_status population_run(lcf_sampler** ss, int n, int64_t first_step, int64_t n_steps, int32_t split_mode,
+                          int32_t store_chain, double* elapsed_ms, bool resident, bool* repeat) {
+    const lcf_sampler* s0 = ss[0];
+    hipStream_t st = s0->e->stream;
+    // Everything of this run -- every transient's draw records, the half-steps, the snapshots -- goes on ONE stream (the
+    // first transient's): stream order is all the synchronisation there is.  What the transients' own streams still hold
+    // (set_state, an earlier run of their own) is waited for once, here.
+    LCF_HIP(hipSetDevice(s0->e->device));
+    LCF_HIP(hipDeviceSynchronize());
+    long long g = 0;
+    for (int t = 0; t < n; ++t) {
+        lcf_sampler* s = ss[t];
+        if (lcf_status r = sampler_begin(s, first_step, n_steps, split_mode, nullptr, store_chain, true, st,
+                                         /*defer: generated for all transients below*/ true)) return r;
+        g = std::max(g, s->g_next);
+        if (s->e->stream != st) s->foreign_stream = true;   // (until the stream has been waited for)
+    }
+    // The draw records of ALL transients come from one launch of each generation kernel per block of steps (random
+    // splits of samplers with the same block geometry -- what a population has; else sampler by sampler).
+    PopPlan p;
+    bool batched_gen = split_mode == LCF_SPLIT_RANDOM;
+    for (int t = 1; t < n; ++t)
+        batched_gen = batched_gen && ss[t]->blk_first == s0->blk_first && ss[t]->blk_steps == s0->blk_steps;
+    if (batched_gen) {
+        std::vector<GenItem> gen(n);
+        for (int t = 0; t < n; ++t)
+            gen[t] = GenItem{ss[t]->ds.key0, ss[t]->ds.key1, ss[t]->ds.n_dim, ss[t]->ds.a,
+                             {ss[t]->d_perm[0], ss[t]->d_perm[1]}, {ss[t]->d_slot[0], ss[t]->d_slot[1]},
+                             {ss[t]->d_draws[0], ss[t]->d_draws[1]}};
+        LCF_HIP(hipMalloc((void**)&p.d_gen, (size_t)n * sizeof(GenItem)));
+        LCF_HIP(hipMemcpy(p.d_gen, gen.data(), (size_t)n * sizeof(GenItem), hipMemcpyHostToDevice));
+    }
+    if (n_steps > 0)
+        if (lcf_status r = generate_block(ss, n, 0, st, p.d_gen)) return r;
+    if (lcf_status r = population_plan(ss, n, n_steps, g, resident, p)) return r;
+    LCF_HIP(hipMalloc((void**)&p.d_items, (size_t)n * sizeof(MultiItem)));
+    LCF_HIP(hipMemcpyAsync(p.d_items, p.items.data(), (size_t)n * sizeof(MultiItem), hipMemcpyHostToDevice, st));
+    LCF_HIP(hipEventRecord(s0->ev0, st));
+    long long launches = 2 * n_steps * (p.form == LCF_KERNEL_POPULATION_PHASES ? 2 : 1);
+    const lcf_status rc = p.form == LCF_KERNEL_POPULATION_RUN ? enqueue_pop_run(ss, n, p, n_steps, store_chain, st, &launches)
+                          : p.form == LCF_KERNEL_POPULATION   ? enqueue_pop(ss, n, p, n_steps, st)
+                                                              : enqueue_pop_phases(ss, n, p, n_steps, g, st);
+    if (rc) return rc;
+    LCF_HIP(hipEventRecord(s0->ev1, st));
     // every transient's snapshot (error word, state, counts) behind the run, on the same stream: ONE wait below serves
     // the 32 state / count / check calls that follow (each of them used to synchronise and launch on its own)
-    for (int t = 0; t < n && err == hipSuccess; ++t) {
+    for (int t = 0; t < n; ++t) {
         const long long words = (long long)(ss[t]->snap_bytes() / 8);
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ss[t]->ds,
                            reinterpret_cast<unsigned long long*>(ss[t]->snap));
-        err = hipGetLastError();
+        LCF_HIP(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    hipFree(ditems);
-    if (dgen) hipFree(dgen);
-    LCF_HIP(err);
+    LCF_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && elapsed_ms) *elapsed_ms = ms;
+    if (hipEventElapsedTime(&ms, s0->ev0, s0->ev1) == hipSuccess && elapsed_ms) *elapsed_ms = ms;
+    bool gave_up = false;
     for (int t = 0; t < n; ++t) {
         ss[t]->g_next = g + 2 * n_steps;
         ss[t]->pending = false;
@@ -5382,52 +5381,49 @@ static lcf_status population_run(lcf_sampler** ss, int32_t n, int64_t first_step
         ss[t]->snap_valid = true;
         ss[t]->last_ms = ms;
         ss[t]->last_rows = false;
-        ss[t]->last_kernel = resident ? LCF_KERNEL_POPULATION_RUN : one_launch ? LCF_KERNEL_POPULATION : LCF_KERNEL_POPULATION_PHASES;
-        ss[t]->last_launches = resident ? run_launches : 2 * n_steps * (one_launch ? 1 : 2);
+        ss[t]->last_kernel = p.form;
+        ss[t]->last_launches = launches;
+        gave_up = gave_up || (p.form == LCF_KERNEL_POPULATION_RUN && (reported_error(ss[t]) & 2));
     }
-    if (resident) {
-        // A resident launch whose workgroups were not all on the device (somebody else's resident kernel holds CUs) has
-        // given up within the bound of its waits.  No state has been written -- that goes into the other set of buffers,
-        // in the last step: take the states the run started from, drop what it reported, and run the same steps with a
-        // launch per half-step, as every later population run of this process.
-        bool gave_up = false;
-        for (int t = 0; t < n; ++t) {
-            int e = 0;
-            std::memcpy(&e, ss[t]->snap, sizeof(int));
-            const unsigned int* flags = ss[t]->snap_flags();
-            for (int k = 0; k < 2 * kSnapFlags; ++k) e |= (int)flags[k];
-            gave_up = gave_up || (e & 2);
-        }
-        if (gave_up) {
-            for (int t = 0; t < n; ++t) {
-                lcf_sampler* s = ss[t];
-                s->flip_state_sets();
-                int sticky = 0;
-                std::memcpy(&sticky, s->snap, sizeof(int));
-                sticky &= 1;                                   // (a NaN of an earlier run stays reported)
-                LCF_HIP(hipMemcpy(s->ds.err, &sticky, sizeof(int), hipMemcpyHostToDevice));
-                std::memcpy(s->snap, &sticky, sizeof(int));
-                std::memset(s->snap_flags(), 0, 2 * kSnapFlags * sizeof(unsigned int));
-                LCF_HIP(hipMemset(static_cast<unsigned char*>(s->run_board_mem) + s->run_board_bytes() - kBoardClear * sizeof(unsigned int),
-                                  0, kBoardClear * sizeof(unsigned int)));
-                s->run_arrivals = 0;
-                invalidate_snapshot(s);
-            }
-            std::fprintf(stderr, "liblcf_hip: a resident population launch gave up waiting for a row: its workgroups were not all "
-                         "resident (another resident kernel on this GPU?); the steps are repeated with a launch per half-step, as are "
-                         "this process's later population runs (LCF_NO_POP_RUN=1 avoids the wait)\n");
-            g_pop_run_off = true;
-            return population_run(ss, n, first_step, n_steps, split_mode, store_chain, elapsed_ms, false);
-        }
+    if (gave_up) {   // (rewind_resident_run; the caller repeats the steps with a launch per half-step)
+        for (int t = 0; t < n; ++t)
+            if (lcf_status r = rewind_resident_run(ss[t])) return r;
+        std::fprintf(stderr, "liblcf_hip: a resident population launch gave up waiting for a row: its workgroups were not all "
+                     "resident (another resident kernel on this GPU?); the steps are repeated with a launch per half-step, as are "
+                     "this process's later population runs (LCF_NO_POP_RUN=1 avoids the wait)\n");
+        g_pop_run_off = true;
+        *repeat = true;
+        return LCF_OK;
     }
     for (int t = 0; t < n; ++t)
         if (lcf_status r = lcf_sampler_check(ss[t])) return r;
     return LCF_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 lcf_status lcf_population_run(lcf_sampler** ss, int32_t n, int64_t first_step, int64_t n_steps, int32_t split_mode,
                               int32_t store_chain, double* elapsed_ms) {
-    return population_run(ss, n, first_step, n_steps, split_mode, store_chain, elapsed_ms, true);
+    if (!ss || n <= 0) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > 65535) return fail(LCF_ERR_INVALID_ARGUMENT, "at most 65535 transients per call");
+    if (split_mode == LCF_SPLIT_HOST) return fail(LCF_ERR_UNSUPPORTED, "population runs use identity or random splits");
+    const lcf_sampler* s0 = ss[0];
+    for (int t = 0; t < n; ++t) {
+        const lcf_sampler* s = ss[t];
+        if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
+        const DevProblem &a = s->e->dp, &b = s0->e->dp;
+        if (s->e->device != s0->e->device || s->ds.n_walkers != s0->ds.n_walkers || a.variant != b.variant ||
+            a.use_therm != b.use_therm || a.tab_in_lds != b.tab_in_lds)
+            return fail(LCF_ERR_UNSUPPORTED, "transients of one batched run must agree on device, walker count, "
+                                             "band-sum variant, thermal sharing and table placement");
+    }
+    bool repeat = false;   // (a resident launch gave up: the same steps again, without the resident form)
+    lcf_status r = population_run(ss, n, first_step, n_steps, split_mode, store_chain, elapsed_ms, true, &repeat);
+    if (r == LCF_OK && repeat)
+        r = population_run(ss, n, first_step, n_steps, split_mode, store_chain, elapsed_ms, false, &repeat);
+    return r;
 }
 
 lcf_status lcf_sampler_get_chain(lcf_sampler* s, double* chain, double* log_prob) {

@@ -211,9 +211,11 @@ class PopulationSampler:
     def run_mcmc(self, initial_states, nsteps, store=True, batched=True):
         """``initial_states``: mapping/sequence index -> (nwalkers, ndim) coordinates, or None to continue.
 
-        ``batched`` (default): one native call runs all transients in lock step with one proposal launch and one
-        likelihood launch per half-step for the whole population; if the transients cannot share launches (mixed
-        table placement etc.) or ``batched`` is false, every ensemble is enqueued on its own stream instead."""
+        ``batched`` (default): one native call runs all transients in lock step, every launch covering the whole
+        population: resident workgroups for blocks of half-steps where the transients and the device allow them, else
+        one launch per half-step, else one proposal launch and one likelihood launch per half-step; if the transients
+        cannot share launches (mixed table placement etc.) or ``batched`` is false, every ensemble is enqueued on its
+        own stream instead."""
         from .engine import LcfError, population_run
         samplers = list(self.samplers.values())
         for k, s in self.samplers.items():

@@ -420,7 +420,8 @@ def test_population_one_launch_per_half_step(nwalkers, monkeypatch):
     (k_pop: a workgroup per four proposals, accept test included).  Their chains are bitwise those of the two-launch path
     (LCF_NO_POP=1), and the oracle-driven chain of a transient; 21 walkers = 11 slots per half-step: a partly filled last
     workgroup and, in every second half-step, an empty slot.  Resident launches also with blocks of 2 steps of draw
-    records (several launches per run) and with 2 workgroups per transient (several groups of proposals per workgroup)."""
+    records (several launches per run) and with 2 workgroups per transient (several groups of proposals per workgroup);
+    where the device holds no resident workgroup (LCF_RUN_GRID=0) the run takes a launch per half-step."""
     from lightcurve_fitting_amd.sampler import PopulationSampler
     problems, x0, pbs = [], {}, []
     for k in range(4):
@@ -440,7 +441,8 @@ def test_population_one_launch_per_half_step(nwalkers, monkeypatch):
     forms = {'population-run': {}, 'population': {'LCF_NO_POP_RUN': '1'}, 'population-phases': {'LCF_NO_POP': '1'},
              'population-run, blocks of 2 steps': {'LCF_DRAW_BLOCK': '2'},
              'population-run, 8 workgroups': {'LCF_RUN_GRID': '8'},
-             'population-run, interpolants from L2': {'LCF_POP_ITAB_LDS': '0'}}
+             'population-run, interpolants from L2': {'LCF_POP_ITAB_LDS': '0'},
+             'population, no room for resident workgroups': {'LCF_RUN_GRID': '0'}}
     for form, env in forms.items():
         for name in ('LCF_NO_POP_RUN', 'LCF_NO_POP', 'LCF_DRAW_BLOCK', 'LCF_RUN_GRID', 'LCF_POP_ITAB_LDS'):
             monkeypatch.delenv(name, raising=False)
