@@ -380,6 +380,28 @@ lcf_status lcf_autocorr_time(int32_t device, const double* chain, int64_t n_t, i
 lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double c,
                                       double* tau, int64_t* window);
 
+/* ---- posterior-predictive quantiles (what lightcurve_model_plot draws, fitting.py:337-360, over ALL samples) ---- */
+/* `grid` is an evaluation engine built for the grid points (dummy photometry, no sigma, no priors; every (time,
+ * filter) pair at most once).  For every point: the model values of all samples, NaNs dropped (n_valid of them
+ * remain), sorted, interpolated linearly between the order statistics around h = (n_valid - 1) q / 100 -- NumPy's
+ * nanpercentile, default method; NaN where n_valid = 0.  No value is stored per (sample, point): device memory beyond
+ * the samples is at most workspace_bytes (LCF_ERR_INVALID_ARGUMENT, with the amount needed, if that is too little for
+ * the samples' coefficients and one time of the grid) and the times are worked through in as many tiles as that takes.
+ * Results do not depend on the tiling and are bitwise reproducible.
+ * component: 0 = the model, 1 = the SiFTO term alone (companion-shocking models only): the template at the model's
+ * stretch and offsets times the filter's factor, 0 outside the template (fitting.py:355-360).
+ * q[n_q]: percentiles in [0, 100]; n_filters * n_q <= 512.
+ * Quantiles of the model over n host samples P[n][ld] (the first n_par columns are used) on the points of `grid`: */
+lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t component,
+                                 const double* q, int32_t n_q, int64_t workspace_bytes,
+                                 double* out /* [n_q][n_points] */, int64_t* n_valid /* [n_points] */);
+/* The same over rows discard, discard + thin, ... of the sampler's last stored run, read in place (every walker of a
+ * kept step is a sample, in the order of get_chain).  LCF_ERR_STATE without a stored chain, LCF_ERR_UNSUPPORTED when
+ * sampler and grid engine are on different devices, LCF_ERR_INVALID_ARGUMENT for discard past the chain. */
+lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin,
+                                         int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
+                                         double* out, int64_t* n_valid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5460,6 +5460,74 @@ lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discar
     return autocorr_run(s[0]->e->device, series.data(), n, c, tau, window);
 }
 
+// What both predictive entry points check before the device is touched.
+static lcf_status predict_check(const lcf_engine* grid, int32_t component, const double* q, int32_t n_q,
+                                const double* out, const int64_t* n_valid) {
+    if (!grid || !q || !out || !n_valid) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_q < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one percentile");
+    for (int32_t j = 0; j < n_q; ++j)
+        if (!(q[j] >= 0. && q[j] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");
+    const bool companion = grid->dp.model >= kCompanion && grid->dp.model <= kCompanion3;
+    if (component != 0 && !(component == 1 && companion))
+        return fail(LCF_ERR_INVALID_ARGUMENT, "component: 0 = the model, 1 = the SiFTO term of a companion-shocking model");
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no points");
+    return LCF_OK;
+}
+
+// The grid engine's points as a (time, filter) table and the run itself.
+static lcf_status predict_impl(lcf_engine* grid, const PredictSamples& in, int32_t component, const double* q,
+                               int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points, NF = dp.n_filters;
+    std::vector<int> filt(N), orig(N), epoch(N);
+    LCF_HIP(hipMemcpy(filt.data(), dp.pt_filt, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int32_t> table((size_t)dp.n_epochs * NF, -1);
+    for (int i = 0; i < N; ++i) {
+        int32_t& slot = table[(size_t)epoch[i] * NF + filt[i]];
+        if (slot >= 0) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine holds a (time, filter) pair twice");
+        slot = orig[i];
+    }
+    return predict_run(grid->device, dp, in, table.data(), component, q, n_q, workspace_bytes, out, n_valid);
+}
+
+lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t component,
+                                 const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
+    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+    if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
+    if (ld < 1 || ld < grid->dp.n_par) return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than the model's parameter count");
+    if (n > (1LL << 40) / ld) return fail(LCF_ERR_INVALID_ARGUMENT, "too many samples");
+    LCF_HIP(hipSetDevice(grid->device));
+    double* dP = nullptr;
+    LCF_HIP(hipMalloc((void**)&dP, (size_t)n * ld * sizeof(double)));
+    lcf_status st = LCF_OK;
+    if (hipMemcpy(dP, P, (size_t)n * ld * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        st = fail(LCF_ERR_HIP, "copying the samples to the device failed");
+    if (!st) st = predict_impl(grid, PredictSamples{dP, n, n, 0, ld}, component, q, n_q, workspace_bytes, out, n_valid);
+    hipFree(dP);
+    return st;
+}
+
+lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin,
+                                         int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
+                                         double* out, int64_t* n_valid) {
+    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
+    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
+    if (!s->ds.store_chain || s->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
+    if (discard >= s->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
+    if (s->e->device != grid->device) return fail(LCF_ERR_UNSUPPORTED, "sampler and grid engine are on different devices");
+    if (s->ds.n_dim < grid->dp.n_par)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the chain has fewer columns than the model has parameters");
+    if (lcf_status st = settle(s)) return st;  // (the trailing commit writes the last chain row)
+    LCF_HIP(hipSetDevice(grid->device));
+    const DevSampler& ds = s->ds;
+    const int64_t row = (int64_t)ds.n_walkers * ds.n_dim, steps = (s->run_steps - discard + thin - 1) / thin;
+    const PredictSamples in{ds.chain + discard * row, steps * ds.n_walkers, ds.n_walkers, thin * row, ds.n_dim};
+    return predict_impl(grid, in, component, q, n_q, workspace_bytes, out, n_valid);
+}
+
 lcf_status lcf_sampler_get_naccepted(lcf_sampler* s, int64_t* n_accepted) {
     if (!s || !n_accepted) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = settle(s)) return st;

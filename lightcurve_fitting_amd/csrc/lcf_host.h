@@ -120,4 +120,18 @@ struct AutocorrSeries {
 };
 lcf_status autocorr_run(int32_t device, const AutocorrSeries* in, int32_t n, double c, double* tau, int64_t* window);
 
+// Posterior-predictive quantiles (lcf_predict.hip): n samples in device memory, sample s being the ld-strided row at
+// base + (s / n_w) * step_stride + (s % n_w) * ld (a stored chain read in place: n_w walkers per kept step).
+struct DevProblem;
+struct PredictSamples {
+    const double* base;
+    int64_t n, n_w, step_stride;
+    int32_t ld;
+};
+// `dp`: the engine of the grid points; orig[n_epochs][n_filters] (host): the index of the point (time, filter) in the
+// caller's order, -1 where the grid has no such point.  out[n_q][n_points], n_valid[n_points] (host).
+lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig,
+                       int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
+                       int64_t* n_valid);
+
 }  // namespace lcf

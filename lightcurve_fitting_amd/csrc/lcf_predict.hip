@@ -1,0 +1,557 @@
+// Posterior-predictive quantiles on gfx950: for every grid point (observation time x filter) the percentiles, over ALL
+// samples of a chain, of the model light curve -- np.nanpercentile(Y, q, axis=samples) with Y[point][sample] never
+// stored.  The value of a (sample, point) pair is recomputed in every pass; device memory beyond the chain is the
+// samples' derived coefficients (64 bytes each) plus a per-time block that does not depend on the number of samples.
+//
+// Every value becomes an order-preserving 64-bit key (IEEE bits, sign folded), NaNs are dropped, and the wanted order
+// statistics are found by radix selection on the key, most significant bits first:
+//   k_pq_coef     walker_coefficients of every sample, once, [8][n] (consecutive lanes = consecutive samples)
+//   k_pq_pass     workgroup = (one time, all its filters, a chunk of samples), lanes = samples: thermal state once per
+//                 (sample, time), then the filters.  mode 0: histogram of the keys' top bits per point; mode 1: per
+//                 search (point, percentile) the histogram of the next bits among the keys that carry the search's
+//                 prefix; mode 2: the keys with the prefix go to the search's buffer, the smallest key above them is kept.
+//                 Histograms are 32-bit counters in LDS (ds_add), merged into device memory with integer atomic adds.
+//   k_pq_pick     per search: the bin that holds the wanted rank -> longer prefix, rank inside it, number of keys left
+//   k_pq_finish   per search: bitonic sort of the (at most kPqCap) collected keys in LDS, order statistics rank and
+//                 rank + 1 (the latter possibly the kept successor), NumPy's linear interpolation
+// The host repeats mode 1 until every search holds at most kPqCap keys or its prefix is a whole key (ties: the answer is
+// that key).  All counts are integers and the collected keys are sorted, so no result depends on the order in which
+// workgroups arrive, on the sample chunks or on how the times are tiled over the workspace; there is no floating-point
+// atomic and no workgroup waits for another.  (DESIGN.md "Posterior-predictive quantiles".)
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "lcf.h"
+#include "lcf_device.h"
+#include "lcf_host.h"
+
+using namespace lcf;
+
+namespace {
+
+constexpr int kPqThreads = 512;            // lanes of a pass workgroup (8 waves)
+constexpr int kPqCap = 2048;               // keys a search sorts in LDS
+constexpr int kPqHistBytes = 48 * 1024;    // LDS histogram counters of a pass workgroup
+constexpr int kPqMaxSearch = 512;          // filters x percentiles of one call
+constexpr int kPqMinBits = 4, kPqMaxBits = 11;
+constexpr unsigned long long kNoKey = ~0ull;
+
+struct PqSearch {
+    unsigned long long prefix;   // the top `pbits` bits shared by the keys still in question
+    unsigned long long succ;     // smallest key above all of them (mode 2)
+    long long rank;              // wanted order statistic among the keys with the prefix
+    long long count;             // keys with the prefix
+    double gamma;                // weight of order statistic rank + 1
+    int pbits;                   // -1: the point has no valid value
+    unsigned int fill;           // keys collected so far (mode 2)
+    int active;                  // still more than kPqCap keys and bits left: another histogram pass
+    int collect;                 // at most kPqCap keys: they are collected and sorted
+};
+
+struct PqArgs {
+    const double* base;          // sample s = the row at base + (s / n_w) * step_stride + (s % n_w) * ld
+    long long n, n_w, step_stride;
+    int ld;
+    const double* coef;          // [kNCoef][n]
+    const int* orig;             // [n_epochs][n_filters]: the point's index in the caller's order, -1 = no such point
+    int ep0;                     // first time of the tile
+    int n_q, component, mode, shift, bits;
+    long long chunk;             // samples per workgroup
+    unsigned int* hist;          // mode 0: [tile time][filter][1 << bits], mode 1: [search][1 << bits]
+    PqSearch* search;            // [tile time][filter][percentile]
+    unsigned long long* buf;     // [search][kPqCap]
+};
+
+// doubles ordered as unsigned integers (-inf < ... < -0 < +0 < ... < +inf)
+__device__ __forceinline__ unsigned long long pq_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double pq_value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// ln S_f(e^u) from the filter's interpolant in device memory (the form of the likelihood kernels: interval of the
+// coordinate r, Horner's rule on 8 coefficients)
+__device__ __forceinline__ double pq_interp(const DevProblem& pb, int filt, double r) {
+    const int j = (int)r;
+    const double s = fma(__builtin_amdgcn_fract(r), 2., -1.);
+    const double2* q = reinterpret_cast<const double2*>(pb.itab + filt * pb.itab_m * 8 + 8 * j);
+    const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    double g = fma(q0.x, s, q0.y);
+    g = fma(g, s, q1.x);
+    g = fma(g, s, q1.y);
+    g = fma(g, s, q2.x);
+    g = fma(g, s, q2.y);
+    g = fma(g, s, q3.x);
+    return fma(g, s, q3.y);
+}
+
+// Band sum over the shortest table that is valid at 1/T, chosen per LANE (lanes are samples here: a value must not
+// depend on which samples share a wave).
+__device__ __forceinline__ double pq_band_sum(const DevProblem& pb, const FiltDesc& fd, double invT, const ExpTab et) {
+    int off = fd.off, cnt = fd.cnt;
+    if (pb.use_ctab && fd.ccnt > 0 && invT <= fd.inv_tmin) off = fd.coff, cnt = fd.ccnt;
+    if (pb.use_ctab && fd.hcnt > 0 && invT <= fd.inv_tmin2) off = fd.hoff, cnt = fd.hcnt;
+    if (cnt <= 0) return 0.;
+    const double2* tab = pb.tab + off;
+    if (pb.variant == 0) return band_sum_ref(tab, cnt, invT);
+    const double amax = fmax(tab[0].x, tab[cnt - 1].x);
+    if (amax * invT < 170.) return band_sum_main(tab, cnt, invT * kInvLn2N, et);
+    return band_sum_safe(tab, cnt, -(invT * kInvLn2N), et);
+}
+
+// The model at (sample, time t_in, filter f) from the thermal state (x, p) in the encoding of thermal_state_log.
+// component 1 (companion-shocking models): the SiFTO term alone.
+template <int MODEL>
+__device__ __forceinline__ double pq_point(const DevProblem& pb, const double* __restrict__ c,
+                                           const double* __restrict__ prow, double t_in, int f, double x, double p,
+                                           const ExpTab et, int component) {
+    const int model = MODEL ? MODEL : pb.model;
+    const bool companion = model >= kCompanion && model <= kCompanion3;
+    const FiltDesc fd = pb.f_desc[f];
+    double y = 0.;
+    if (!(companion && component == 1)) {
+        double invT = 0., pref = 0.;
+        bool done = false;
+        if (__double2hiint(x) >= 0) {   // log-space state: x = interval coordinate of ln T, p = ln R_bb^2
+            // (ShockCooling4 also needs the band sum at 0.74 T: ln 0.74 / h intervals lower)
+            const double r_low = model == kShockCooling4 ? x - 0.3011050927839216 * pb.itab_inv_h : x;
+            if (r_low >= (double)fd.r_min) {
+                double L = pq_interp(pb, f, x);
+                if (model == kShockCooling4)   // min(blackbody, suppressed blackbody at 0.74 T), models.py:629-631
+                    L = fmin(L, pq_interp(pb, f, x - 0.3011050927839216 * pb.itab_inv_h) + 1.2044203711356864);
+                y = exp_scaled<false>(fma(L, kInvLn2N, p * kInvLn2N), et);
+                done = true;
+            } else {   // outside this filter's proved range: the sample tables, in linear space
+                invT = exp(-fma(x, 1. / pb.itab_inv_h, pb.itab_u0));
+                pref = exp(p);
+            }
+        } else {
+            invT = -x;
+            pref = p;
+        }
+        if (!done) {
+            double S = 0.;
+            if (invT > 0.) {
+                if (model == kShockCooling3) {   // the sample's reddening, sample by sample over the full table
+                    for (int k = 0; k < fd.cnt; ++k) {
+                        const double2 aw = pb.tab[fd.off + k];
+                        S += aw.y * exp2(-c[6] * pb.tab_ext[fd.off + k]) / expm1(aw.x * invT);
+                    }
+                } else {
+                    S = pq_band_sum(pb, fd, invT, et);
+                    if (model == kShockCooling4)
+                        S = fmin(S, pq_band_sum(pb, fd, invT * (1. / 0.74), et) * (1. / (0.74 * 0.74 * 0.74 * 0.74)));
+                }
+            }
+            y = (pref != pref) ? pref : pref * S;   // (pref may be NaN, or 0 with 1/T == 0)
+        }
+        if (model == kShockCooling3) y *= c[5];   // models.py:495
+    }
+    if (companion) {   // models.py:909-917, 977-980, 1040-1045
+        const double kfac = c[5] * (fd.kpar >= 0 ? prow[fd.kpar] : 1.);
+        const double sfac = fd.spar >= 0 ? prow[fd.spar] : 1.;
+        const double dt = fd.dtpar >= 0 ? prow[fd.dtpar] : 0.;
+        const double u = (t_in - c[3] - dt) * (1. / c[4]);
+        double tmpl;
+        if (pb.knot_h > 0.)
+            tmpl = spline_eval_uniform(pb, reinterpret_cast<const double2*>(pb.spl) + f * (pb.n_knots - 1) * 2, u);
+        else
+            tmpl = spline_eval(pb.knots, pb.n_knots, pb.spl + (size_t)f * (pb.n_knots - 1) * 4, u, pb.knot_inv_h);
+        y = component == 1 ? tmpl * sfac : y * kfac + tmpl * sfac;
+    }
+    return y;
+}
+
+__device__ __forceinline__ const double* pq_row(const PqArgs& a, long long s) {
+    return a.base + (s / a.n_w) * a.step_stride + (s % a.n_w) * a.ld;
+}
+
+__global__ __launch_bounds__(256) void k_pq_coef(const DevProblem pb, const PqArgs a, double* __restrict__ coef) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.n) return;
+    double c[kNCoef];
+    walker_coefficients(pb, pq_row(a, s), c);
+    for (int i = 0; i < kNCoef; ++i) coef[(long long)i * a.n + s] = c[i];
+}
+
+// blockIdx.x = time of the tile, blockIdx.y = chunk of samples.  Dynamic LDS: exp table | per search prefix, successor,
+// prefix bits, collect flag | histogram counters.
+template <int MODEL>
+__global__ __launch_bounds__(kPqThreads) void k_pq_pass(const DevProblem pb, const PqArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nf = pb.n_filters, ns = nf * a.n_q;
+    double* exptab = reinterpret_cast<double*>(smem);
+    unsigned long long* s_prefix = reinterpret_cast<unsigned long long*>(exptab + kExpTabSize);
+    unsigned long long* s_succ = s_prefix + ns;
+    int* s_pbits = reinterpret_cast<int*>(s_succ + ns);
+    int* s_col = s_pbits + ns;
+    unsigned int* s_hist = reinterpret_cast<unsigned int*>(s_col + ns);
+
+    const int model = MODEL ? MODEL : pb.model;
+    const bool companion = model >= kCompanion && model <= kCompanion3;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ep = a.ep0 + blockIdx.x;
+    const int n_hist = a.mode == 0 ? nf << a.bits : a.mode == 1 ? ns << a.bits : 0;
+    PqSearch* search = a.search + (size_t)blockIdx.x * ns;
+    for (int k = tid; k < kExpTabSize; k += kPqThreads) exptab[k] = pb.exp2tab[k];
+    for (int k = tid; k < n_hist; k += kPqThreads) s_hist[k] = 0u;
+    if (a.mode != 0)
+        for (int k = tid; k < ns; k += kPqThreads) {
+            const PqSearch sr = search[k];
+            s_prefix[k] = sr.prefix;
+            s_succ[k] = kNoKey;
+            s_pbits[k] = (a.mode == 1 ? sr.active != 0 : sr.pbits > 0) ? sr.pbits : -1;
+            s_col[k] = sr.collect;
+        }
+    __syncthreads();
+
+    const ExpTab et{exptab};
+    const double t_in = pb.epoch_t[ep];
+    const int* orig = a.orig + (size_t)ep * nf;
+    const bool log_state = pb.variant != 0 && pb.use_itab && model != kShockCooling3;
+    const bool sifto_only = companion && a.component == 1;
+    const unsigned int mask = (1u << a.bits) - 1u;
+    const long long s0 = (long long)blockIdx.y * a.chunk, s1 = min(a.n, s0 + a.chunk);
+    for (long long sb = s0; sb < s1; sb += kPqThreads) {
+        const long long s = sb + tid;
+        if (s >= s1) continue;
+        double c[kNCoef];
+#pragma unroll
+        for (int i = 0; i < kNCoef; ++i) c[i] = a.coef[(long long)i * a.n + s];
+        const double* prow = companion ? pq_row(a, s) : a.base;
+        double x = -0., p = 0.;
+        if (!sifto_only) {
+            if (log_state) {
+                thermal_state_log<MODEL>(pb, c, t_in, x, p, et);
+            } else {
+                double T, invT, pref;
+                thermal_state<MODEL>(pb, c, t_in, T, invT, pref);
+                encode_linear(invT, pref, x, p);
+            }
+        }
+        for (int f = 0; f < nf; ++f) {
+            if (orig[f] < 0) continue;
+            const double v = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, a.component);
+            const bool valid = v == v;
+            const unsigned long long key = pq_key(v);
+            if (a.mode == 0) {
+                // (the values of a point mostly share their exponent: lanes with the same bin add once, together)
+                const int bin = (int)(key >> a.shift);
+                unsigned long long m = __builtin_amdgcn_ballot_w64(valid);
+                while (m) {
+                    const int leader = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m));
+                    const int b0 = __builtin_amdgcn_readlane(bin, leader);
+                    const unsigned long long peers = __builtin_amdgcn_ballot_w64(valid && bin == b0);
+                    if (lane == leader) atomicAdd(&s_hist[(f << a.bits) + b0], (unsigned int)__popcll(peers));
+                    m &= ~peers;
+                }
+            } else if (valid) {
+                for (int j = 0; j < a.n_q; ++j) {
+                    const int k = f * a.n_q + j, pbits = s_pbits[k];
+                    if (pbits < 0) continue;
+                    const unsigned long long pre = s_prefix[k];
+                    if (a.mode == 1) {   // (every active search has the same 64 - shift - bits prefix bits)
+                        // One ds_add per lane.  (Measured and not kept: a round of the sharing above in front of it --
+                        // the first refinement, whose keys still crowd into a few bins, 76 -> 66 ms, the second, whose
+                        // keys are spread, 46 -> 60 ms at 2 048 000 samples x 6000 points.)
+                        if ((key >> (a.shift + a.bits)) == pre)
+                            atomicAdd(&s_hist[(k << a.bits) + (int)((unsigned int)(key >> a.shift) & mask)], 1u);
+                    } else {
+                        const unsigned long long head = pbits >= 64 ? key : key >> (64 - pbits);
+                        if (head == pre) {
+                            if (s_col[k]) {
+                                const unsigned int at = atomicAdd(&search[k].fill, 1u);
+                                if (at < (unsigned int)kPqCap)
+                                    a.buf[((size_t)blockIdx.x * ns + k) * kPqCap + at] = key;
+                            }
+                        } else if (head > pre && key < s_succ[k]) {
+                            atomicMin(&s_succ[k], key);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (a.mode == 2) {
+        for (int k = tid; k < ns; k += kPqThreads)
+            if (s_succ[k] != kNoKey) atomicMin(&search[k].succ, s_succ[k]);
+    } else {
+        unsigned int* g = a.hist + (size_t)blockIdx.x * n_hist;
+        for (int k = tid; k < n_hist; k += kPqThreads) {
+            const unsigned int v = s_hist[k];
+            if (v) atomicAdd(&g[k], v);
+        }
+    }
+}
+
+struct PqPick {
+    const unsigned int* hist;
+    PqSearch* search;
+    const int* orig;             // of the tile's first time
+    const double* qf;            // [n_q] percentiles / 100
+    long long* n_valid;          // [n_points]
+    unsigned int* n_active;
+    int n_q, bits, mode;
+};
+
+// One workgroup per search of the tile.  mode 0: the point's histogram of the top bits -> n_valid, the wanted rank
+// h = (n_valid - 1) q / 100 (NumPy's virtual index, default method) and its bin; mode 1: the search's own histogram.
+__global__ __launch_bounds__(256) void k_pq_pick(const PqPick a) {
+    __shared__ unsigned long long part[256];
+    const int g = blockIdx.x, j = g % a.n_q, pf = g / a.n_q, tid = threadIdx.x;
+    PqSearch* sr = a.search + g;
+    if (a.mode == 1 && !sr->active) return;
+    const int nb = 1 << a.bits, seg = (nb + 255) / 256;
+    const unsigned int* row = a.hist + ((size_t)(a.mode == 0 ? pf : g) << a.bits);
+    unsigned long long sum = 0;
+    for (int b = tid * seg; b < min(nb, (tid + 1) * seg); ++b) sum += row[b];
+    part[tid] = sum;
+    __syncthreads();
+    if (tid != 0) return;
+    long long rank;
+    int pbits;
+    unsigned long long prefix;
+    if (a.mode == 0) {
+        unsigned long long total = 0;
+        for (int t = 0; t < 256; ++t) total += part[t];
+        const int o = a.orig[pf];
+        if (j == 0 && o >= 0) a.n_valid[o] = (long long)total;
+        sr->succ = kNoKey;
+        sr->fill = 0u;
+        if (total == 0) {
+            sr->prefix = 0;
+            sr->rank = sr->count = 0;
+            sr->gamma = 0.;
+            sr->pbits = -1;
+            sr->active = sr->collect = 0;
+            return;
+        }
+        const double h = (double)(long long)(total - 1) * a.qf[j], lo = floor(h);
+        rank = (long long)lo;
+        sr->gamma = h - lo;
+        pbits = 0;
+        prefix = 0;
+    } else {
+        rank = sr->rank;
+        pbits = sr->pbits;
+        prefix = sr->prefix;
+    }
+    unsigned long long cum = 0;
+    int t = 0;
+    while (t < 255 && cum + part[t] <= (unsigned long long)rank) cum += part[t++];
+    int b = min(t * seg, nb - 1);
+    while (b < nb - 1 && cum + row[b] <= (unsigned long long)rank) cum += row[b++];
+    const long long count = row[b];
+    pbits += a.bits;
+    sr->prefix = (prefix << a.bits) | (unsigned long long)b;
+    sr->pbits = pbits;
+    sr->rank = rank - (long long)cum;
+    sr->count = count;
+    sr->active = count > kPqCap && pbits < 64;
+    sr->collect = count <= kPqCap;
+    if (sr->active) atomicAdd(a.n_active, 1u);
+}
+
+// One workgroup per search: sort what was collected, take the order statistics, interpolate as NumPy's _lerp does.
+__global__ __launch_bounds__(256) void k_pq_finish(const PqSearch* __restrict__ search,
+                                                   const unsigned long long* __restrict__ buf,
+                                                   const int* __restrict__ orig, int n_q, long long n_points,
+                                                   double* __restrict__ out) {
+    __shared__ unsigned long long keys[kPqCap];
+    const int g = blockIdx.x, j = g % n_q, o = orig[g / n_q], tid = threadIdx.x;
+    if (o < 0) return;
+    const PqSearch sr = search[g];
+    double* dst = out + (long long)j * n_points + o;
+    if (sr.pbits < 0) {
+        if (tid == 0) *dst = qnan();
+        return;
+    }
+    unsigned long long k_lo, k_hi;
+    if (sr.collect) {
+        const int n = (int)min((long long)kPqCap, min(sr.count, (long long)sr.fill));
+        int np2 = 2;
+        while (np2 < n) np2 <<= 1;
+        for (int i = tid; i < np2; i += 256) keys[i] = i < n ? buf[(size_t)g * kPqCap + i] : kNoKey;
+        __syncthreads();
+        for (int k = 2; k <= np2; k <<= 1)
+            for (int d = k >> 1; d > 0; d >>= 1) {
+                for (int i = tid; i < np2; i += 256) {
+                    const int l = i ^ d;
+                    if (l > i) {
+                        const unsigned long long x = keys[i], y = keys[l];
+                        if ((x > y) == ((i & k) == 0)) {
+                            keys[i] = y;
+                            keys[l] = x;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        if (tid != 0) return;
+        const int r = (int)min(sr.rank, (long long)max(n - 1, 0));
+        k_lo = keys[r];
+        k_hi = r + 1 < n ? keys[r + 1] : sr.succ;
+    } else {   // more than kPqCap keys and every bit decided: they all are the key `prefix`
+        if (tid != 0) return;
+        k_lo = sr.prefix;
+        k_hi = sr.rank + 1 < sr.count ? sr.prefix : sr.succ;
+    }
+    const double lo = pq_value(k_lo);
+    if (sr.gamma == 0.) {   // the result is an evaluated value itself
+        *dst = lo;
+        return;
+    }
+    const double hi = pq_value(k_hi), t = sr.gamma, diff = __dsub_rn(hi, lo);
+    *dst = t >= 0.5 ? __dsub_rn(hi, __dmul_rn(diff, __dsub_rn(1., t))) : __dadd_rn(lo, __dmul_rn(diff, t));
+}
+
+struct PqBuf {
+    std::vector<void*> p;
+    ~PqBuf() {
+        for (void* q : p) hipFree(q);
+    }
+    template <class T>
+    lcf_status alloc(T** d, size_t n) {
+        *d = nullptr;
+        LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
+        p.push_back(*d);
+        return LCF_OK;
+    }
+};
+
+int hist_bits(long long n_hist, int max_bits) {
+    int b = kPqMinBits;
+    while (b < max_bits && (n_hist << (b + 1)) * 4 <= kPqHistBytes) ++b;
+    return b;
+}
+
+template <int MODEL>
+lcf_status launch_pass(const DevProblem& dp, const PqArgs& a, int n_ep, size_t lds) {
+    const unsigned chunks = (unsigned)((a.n + a.chunk - 1) / a.chunk);
+    hipLaunchKernelGGL(k_pq_pass<MODEL>, dim3((unsigned)n_ep, chunks), dim3(kPqThreads), lds, 0, dp, a);
+    LCF_HIP(hipGetLastError());
+    return LCF_OK;
+}
+
+lcf_status run_pass(const DevProblem& dp, const PqArgs& a, int n_ep, size_t lds) {
+    if (dp.model == kShockCooling) return launch_pass<kShockCooling>(dp, a, n_ep, lds);
+    return launch_pass<0>(dp, a, n_ep, lds);
+}
+
+}  // namespace
+
+namespace lcf {
+
+lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig_host,
+                       int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
+                       int64_t* n_valid) {
+    LCF_HIP(hipSetDevice(device));
+    const int nf = dp.n_filters, n_ep_all = dp.n_epochs, ns = nf * n_q;
+    const long long n_points = dp.n_points;
+    if (ns > kPqMaxSearch)
+        return fail(LCF_ERR_UNSUPPORTED, "filters x percentiles of one call must not exceed 512");
+    const int bits0 = hist_bits(nf, kPqMaxBits), bits1 = hist_bits(ns, kPqMaxBits);
+    const size_t lds_head = kExpTabSize * sizeof(double) + (size_t)ns * 24;
+    // device memory: per sample the coefficients, per point the results, per time of a tile the rest
+    const size_t fixed = (size_t)in.n * kNCoef * sizeof(double) + (size_t)n_points * (n_q + 1) * 8 +
+                         (size_t)n_ep_all * nf * 4 + 4096;
+    const size_t hist_ep = std::max((size_t)nf << bits0, (size_t)ns << bits1) * 4;
+    const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8);
+    if (workspace_bytes < 0 || (size_t)workspace_bytes < fixed + per_ep)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "workspace_bytes too small: this call needs at least " +
+                                                  std::to_string(fixed + per_ep) + " bytes");
+    const int tile = (int)std::min<size_t>(((size_t)workspace_bytes - fixed) / per_ep, (size_t)n_ep_all);
+
+    PqBuf mem;
+    double *d_coef, *d_q, *d_out;
+    long long* d_nv;
+    int* d_orig;
+    unsigned int *d_hist, *d_active;
+    PqSearch* d_search;
+    unsigned long long* d_buf;
+    lcf_status st;
+    if ((st = mem.alloc(&d_coef, (size_t)in.n * kNCoef)) || (st = mem.alloc(&d_q, n_q)) ||
+        (st = mem.alloc(&d_out, (size_t)n_points * n_q)) || (st = mem.alloc(&d_nv, n_points)) ||
+        (st = mem.alloc(&d_orig, (size_t)n_ep_all * nf)) || (st = mem.alloc(&d_hist, (size_t)tile * hist_ep / 4)) ||
+        (st = mem.alloc(&d_active, 1)) || (st = mem.alloc(&d_search, (size_t)tile * ns)) ||
+        (st = mem.alloc(&d_buf, (size_t)tile * ns * kPqCap)))
+        return st;
+    std::vector<double> qf(q, q + n_q);
+    for (double& v : qf) v = v / 100.;
+    LCF_HIP(hipMemcpy(d_q, qf.data(), n_q * sizeof(double), hipMemcpyHostToDevice));
+    LCF_HIP(hipMemcpy(d_orig, orig_host, (size_t)n_ep_all * nf * sizeof(int), hipMemcpyHostToDevice));
+    LCF_HIP(hipMemset(d_nv, 0, n_points * sizeof(long long)));
+
+    PqArgs a{};
+    a.base = in.base;
+    a.n = in.n;
+    a.n_w = in.n_w;
+    a.step_stride = in.step_stride;
+    a.ld = in.ld;
+    a.coef = d_coef;
+    a.orig = d_orig;
+    a.n_q = n_q;
+    a.component = component;
+    a.hist = d_hist;
+    a.search = d_search;
+    a.buf = d_buf;
+    hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((in.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
+    LCF_HIP(hipGetLastError());
+
+    for (int ep0 = 0; ep0 < n_ep_all; ep0 += tile) {
+        const int n_ep = std::min(tile, n_ep_all - ep0);
+        // samples per workgroup: enough workgroups to fill the device, few enough that merging a workgroup's
+        // histogram stays small next to its evaluations (whole multiples of the workgroup; at most 65535 chunks)
+        long long chunk = (in.n * n_ep / 4096 + kPqThreads - 1) / kPqThreads * kPqThreads;
+        chunk = std::min<long long>(std::max<long long>(chunk, 4 * kPqThreads), 64 * kPqThreads);
+        chunk = std::max<long long>(chunk, ((in.n + 65534) / 65535 + kPqThreads - 1) / kPqThreads * kPqThreads);
+        a.ep0 = ep0;
+        a.chunk = chunk;
+        PqPick pk{d_hist, d_search, d_orig + (size_t)ep0 * nf, d_q, d_nv, d_active, n_q, bits0, 0};
+        // pass 0: the keys' top bits, one histogram per point
+        a.mode = 0;
+        a.bits = bits0;
+        a.shift = 64 - bits0;
+        LCF_HIP(hipMemsetAsync(d_hist, 0, (size_t)n_ep * ((size_t)nf << bits0) * 4, 0));
+        LCF_HIP(hipMemsetAsync(d_active, 0, 4, 0));
+        if ((st = run_pass(dp, a, n_ep, lds_head + ((size_t)nf << bits0) * 4))) return st;
+        hipLaunchKernelGGL(k_pq_pick, dim3((unsigned)(n_ep * ns)), dim3(256), 0, 0, pk);
+        LCF_HIP(hipGetLastError());
+        // passes 1, 2, ...: the next bits of the keys under every search's prefix, while a search holds too many keys
+        for (int pbits = bits0; pbits < 64;) {
+            unsigned int active = 0;
+            LCF_HIP(hipMemcpy(&active, d_active, 4, hipMemcpyDeviceToHost));
+            if (!active) break;
+            const int bits = std::min(bits1, 64 - pbits);
+            a.mode = 1;
+            a.bits = bits;
+            a.shift = 64 - pbits - bits;
+            LCF_HIP(hipMemsetAsync(d_hist, 0, (size_t)n_ep * ((size_t)ns << bits) * 4, 0));
+            LCF_HIP(hipMemsetAsync(d_active, 0, 4, 0));
+            if ((st = run_pass(dp, a, n_ep, lds_head + ((size_t)ns << bits) * 4))) return st;
+            pk.bits = bits;
+            pk.mode = 1;
+            hipLaunchKernelGGL(k_pq_pick, dim3((unsigned)(n_ep * ns)), dim3(256), 0, 0, pk);
+            LCF_HIP(hipGetLastError());
+            pbits += bits;
+        }
+        // last pass: collect the keys of every search that is down to kPqCap, and every search's successor key
+        a.mode = 2;
+        a.bits = 0;
+        a.shift = 0;
+        if ((st = run_pass(dp, a, n_ep, lds_head))) return st;
+        hipLaunchKernelGGL(k_pq_finish, dim3((unsigned)(n_ep * ns)), dim3(256), 0, 0, d_search, d_buf,
+                           d_orig + (size_t)ep0 * nf, n_q, n_points, d_out);
+        LCF_HIP(hipGetLastError());
+    }
+    LCF_HIP(hipMemcpy(out, d_out, (size_t)n_points * n_q * sizeof(double), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(n_valid, d_nv, (size_t)n_points * sizeof(long long), hipMemcpyDeviceToHost));
+    return LCF_OK;
+}
+
+}  // namespace lcf

@@ -138,6 +138,10 @@ SIGNATURES = [
                                     C.POINTER(C.c_int64)]),
     ('lcf_samplers_autocorr_time', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, C.c_double, _dp,
                                              C.POINTER(C.c_int64)]),
+    ('lcf_predict_quantiles', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int64,
+                                        _dp, C.POINTER(C.c_int64)]),
+    ('lcf_sampler_predict_quantiles', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp,
+                                                C.c_int32, C.c_int64, _dp, C.POINTER(C.c_int64)]),
 ]
 
 
@@ -707,3 +711,33 @@ def samplers_autocorr_time(native_samplers, discard=0, thin=1, c=5.):
         out.append((tau[k:k + s.ndim].copy(), window[k:k + s.ndim].copy()))
         k += s.ndim
     return out
+
+
+#: ``component`` of the predictive entry points
+COMPONENT_MODEL, COMPONENT_SIFTO = 0, 1
+#: filters x percentiles one native predictive call takes (include/lcf.h)
+PREDICT_MAX_SEARCHES = 512
+#: device memory of a predictive call beyond the samples, unless the caller says otherwise
+PREDICT_WORKSPACE_BYTES = 1 << 30
+
+
+def predict_quantiles(grid_engine, samples, percentiles, component=COMPONENT_MODEL, workspace_bytes=None, discard=0,
+                      thin=1):
+    """``lcf_predict_quantiles`` / ``lcf_sampler_predict_quantiles``: percentiles over all samples of the model on
+    the points of ``grid_engine`` (an evaluation engine).  ``samples``: a host array (n, ld), or a
+    :class:`NativeSampler` whose last stored run is read in place (rows ``discard::thin``).  Returns
+    ``(quantiles[n_q, n_points], n_valid[n_points])``."""
+    lib = load_library()
+    q = _f64(percentiles)
+    out = np.empty((len(q), grid_engine.npoints))
+    n_valid = np.empty(grid_engine.npoints, dtype=np.int64)
+    ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    tail = (int(component), _ptr(q), len(q), ws, _ptr(out), n_valid.ctypes.data_as(C.POINTER(C.c_int64)))
+    if isinstance(samples, NativeSampler):
+        _check(lib.lcf_sampler_predict_quantiles(grid_engine.handle, samples._h, int(discard), int(thin), *tail))
+    else:
+        P = _f64(samples)
+        if P.ndim != 2:
+            raise ValueError('samples must have shape (n, n_columns)')
+        _check(lib.lcf_predict_quantiles(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
+    return out, n_valid

@@ -1,14 +1,19 @@
 """``lightcurve_mcmc`` counterpart (reference fitting.py:16-168): same keyword signature, checks and return
 conventions; the ensemble runs on the MI355X instead of inside emcee's Python loop.
 
-Plotting (``show`` / ``save_plot_as``), ``lightcurve_corner`` and ``lightcurve_model_plot`` are outside the hot path
-(SURVEY.md section 8): they only consume ``sampler.chain`` / ``sampler.flatchain``, which the returned object provides.
+Plotting (``show`` / ``save_plot_as``, ``lightcurve_corner``, ``lightcurve_model_plot``) stays outside the package: the
+figures only consume ``sampler.chain`` / ``sampler.flatchain``, which the returned object provides.  The NUMBERS behind
+``lightcurve_model_plot`` (fitting.py:337-360) are here: :func:`posterior_predictive` gives the percentile bands of
+the model light curves -- and, for the companion-shocking models, of the SiFTO term the reference draws dashed -- over
+every sample of the chain instead of 100 random draws, computed on the device without storing a value per (sample,
+grid point).
 """
 import warnings
 
 import numpy as np
 
-from .models import UniformPrior
+from .models import BaseCompanionShocking, Model, UniformPrior, _column
+from .filters import as_filter
 from .sampler import EnsembleSampler
 
 PRIOR_WARNING = 'The p_max/p_min keywords are deprecated. Use the priors keyword instead.'
@@ -129,3 +134,145 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
         print('saving sampler.flatchain as ' + save_sampler_as)
         np.save(save_sampler_as, sampler.flatchain)
     return sampler
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# posterior-predictive light-curve bands (the numbers of lightcurve_model_plot, reference fitting.py:337-360)
+# ---------------------------------------------------------------------------------------------------------------
+def quantile_ranks(n_valid, q):
+    """Which order statistics percentile ``q`` of ``n_valid`` sorted values lies between, and how far: ``(lo, hi,
+    gamma)`` with ``h = (n_valid - 1) * q / 100``, ``lo = floor(h)``, ``hi = min(lo + 1, n_valid - 1)`` and
+    ``gamma = h - lo`` -- NumPy's default (``'linear'``) method, and the definition the device kernels implement
+    (``k_pq_pick``).  Arguments broadcast."""
+    n = np.asarray(n_valid, dtype=np.int64)
+    h = (n - 1) * (np.asarray(q, dtype=np.float64) / 100.)
+    lo = np.floor(h)
+    gamma = h - lo
+    lo = lo.astype(np.int64)
+    return lo, np.minimum(lo + 1, n - 1), gamma
+
+
+def quantile_lerp(a, b, gamma):
+    """The value ``gamma`` of the way from order statistic ``a`` to the next one ``b``, in the form NumPy evaluates it
+    (and ``k_pq_finish`` does): from ``a`` below one half, from ``b`` above; ``a`` itself where ``gamma`` is 0."""
+    a, b, gamma = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64),
+                                      np.asarray(gamma, dtype=np.float64))
+    with np.errstate(invalid='ignore'):
+        diff = b - a
+        out = np.where(gamma >= 0.5, b - diff * (1. - gamma), a + diff * gamma)
+    return np.where(gamma == 0., a, out)
+
+
+def predictive_grid(lc, t=None, tmin=None, tmax=None, num=1000, xscale='linear', filters_to_model=None):
+    """The ``filters x times`` grid of ``lightcurve_model_plot`` (fitting.py:340-348): ``t`` if given, else ``num``
+    points from ``tmin`` to ``tmax`` (default: the range of ``lc['MJD']``), equally spaced (``xscale='linear'``) or
+    geometrically (``'log'``); the filters of ``filters_to_model``, else the distinct filters of ``lc``, sorted.
+    Returns ``(times, filters)``."""
+    if t is not None:
+        times = np.array(t, dtype=np.float64).ravel()
+    else:
+        if tmin is None:
+            tmin = np.min(_column(lc, 'MJD'))
+        if tmax is None:
+            tmax = np.max(_column(lc, 'MJD'))
+        if xscale not in ('linear', 'log'):
+            raise ValueError("xscale must be 'linear' or 'log'")
+        times = np.geomspace(tmin, tmax, int(num)) if xscale == 'log' else np.linspace(tmin, tmax, int(num))
+    if len(times) == 0 or not np.all(np.isfinite(times)):
+        raise ValueError('the grid needs at least one time, all finite')
+    if filters_to_model is None:
+        filters = sorted(set(as_filter(f) for f in _column(lc, 'filter')))
+    else:
+        filters = [as_filter(f) for f in filters_to_model]
+    if len(filters) == 0:
+        raise ValueError('the grid needs at least one filter')
+    return times, filters
+
+
+class PosteriorPredictive:
+    """Result of :func:`posterior_predictive`: ``t`` (nt,), ``filters`` (nf Filter objects), ``percentiles`` (nq,),
+    ``quantiles`` (nq, nf, nt), ``n_valid`` (nf, nt) -- the samples whose model value at the point is not NaN -- and
+    ``n_samples``."""
+    __slots__ = ('t', 'filters', 'percentiles', 'quantiles', 'n_valid', 'n_samples')
+
+    def __init__(self, t, filters, percentiles, quantiles, n_valid, n_samples):
+        self.t, self.filters, self.percentiles = t, filters, percentiles
+        self.quantiles, self.n_valid, self.n_samples = quantiles, n_valid, n_samples
+
+    def __repr__(self):
+        return (f'<PosteriorPredictive: {len(self.percentiles)} percentiles x {len(self.filters)} filters x '
+                f'{len(self.t)} times over {self.n_samples} samples>')
+
+
+def _predictive_samples(samples, discard, thin):
+    """``(sampler or None, host array or None, n_samples, n_columns)`` after the checks that need no device."""
+    if isinstance(samples, EnsembleSampler) or (hasattr(samples, '_native') and hasattr(samples, 'get_chain')):
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        if samples.iteration == 0:
+            raise ValueError('no chain is stored: run the sampler with store=True first')
+        n_t = len(range(discard, samples.iteration, thin))
+        if n_t == 0:
+            raise ValueError(f'discard={discard} leaves no steps of the {samples.iteration} stored')
+        return samples, None, n_t * samples.nwalkers, samples.ndim
+    if discard != 0 or thin != 1:
+        raise ValueError('discard and thin apply to a sampler; slice the array of samples instead')
+    P = np.ascontiguousarray(samples, dtype=np.float64)
+    if P.ndim != 2:
+        raise ValueError('samples must be a sampler or an array of shape (n_samples, n_columns)')
+    if P.shape[0] == 0:
+        raise ValueError('no samples')
+    return None, P, P.shape[0], P.shape[1]
+
+
+def posterior_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=None, tmin=None, tmax=None,
+                         num=1000, xscale='linear', filters_to_model=None, discard=0, thin=1, use_sigma=False,
+                         component='model', workspace_bytes=None):
+    """Percentile bands of the model light curves over ALL samples of a chain, on the dense ``filters x times`` grid
+    of ``lightcurve_model_plot`` (fitting.py:337-360; see :func:`predictive_grid` for ``t`` ... ``filters_to_model``).
+
+    ``samples``: the sampler ``lightcurve_mcmc`` returned -- rows ``discard::thin`` of its stored chain, read where
+    they lie in device memory when the whole stored chain is the last run's, else uploaded from ``get_chain`` -- or a
+    host array ``(n_samples, n_columns)`` such as a saved ``flatchain`` (``discard`` / ``thin`` do not apply).
+    ``use_sigma``: the last column is the intrinsic scatter and does not enter the model (fitting.py:349-352).
+    ``component``: ``'model'``, or ``'sifto'`` for the SiFTO term of a companion-shocking model alone (the template at the
+    sample's stretch and offsets times the filter's factor, 0 outside the template; fitting.py:355-360).
+
+    For every grid point the values of all samples are taken, NaNs dropped (``n_valid`` remain), and the percentiles
+    interpolated linearly between order statistics: ``np.nanpercentile(Y, percentiles, axis=samples)`` with NumPy's
+    default method, NaN where ``n_valid`` is 0.  No value is stored per (sample, point): device memory beyond the
+    samples stays below ``workspace_bytes`` (default 1 GiB), the times being worked through in tiles.  Results are
+    bitwise reproducible and do not depend on ``workspace_bytes``.  Returns a :class:`PosteriorPredictive`."""
+    from . import engine as _eng
+    q = np.array(percentiles, dtype=np.float64).ravel()
+    if q.size == 0:
+        raise ValueError('percentiles must not be empty')
+    if not np.all((q >= 0.) & (q <= 100.)):
+        raise ValueError('percentiles must be in the range [0, 100]')
+    if component not in ('model', 'sifto'):
+        raise ValueError("component must be 'model' or 'sifto'")
+    if component == 'sifto' and not isinstance(model, BaseCompanionShocking):
+        raise ValueError("component='sifto' needs a companion-shocking model")
+    sampler, P, n_samples, n_col = _predictive_samples(samples, discard, thin)
+    want = model.n_model_params + int(bool(use_sigma))
+    if n_col != want:
+        raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
+                         + (' and one for sigma' if use_sigma else ''))
+    times, filters = predictive_grid(lc, t, tmin, tmax, num, xscale, filters_to_model)
+    if len(filters) > _eng.PREDICT_MAX_SEARCHES:
+        raise ValueError(f'at most {_eng.PREDICT_MAX_SEARCHES} filters')
+
+    grid_engine, shape = Model._eval_engine(model, times, filters, False)   # the dense grid, filter-major
+    if sampler is not None and not (len(sampler._chain_host) == 0 and sampler._chain_on_device > 0):
+        P, sampler = sampler.get_chain(discard=int(discard), thin=int(thin), flat=True), None
+    source = sampler._native if sampler is not None else P
+    comp = _eng.COMPONENT_SIFTO if component == 'sifto' else _eng.COMPONENT_MODEL
+    per_call = max(1, _eng.PREDICT_MAX_SEARCHES // len(filters))
+    quantiles, n_valid = [], None
+    for k in range(0, len(q), per_call):
+        out, n_valid = _eng.predict_quantiles(grid_engine, source, q[k:k + per_call], comp, workspace_bytes,
+                                              discard=int(discard), thin=int(thin))
+        quantiles.append(out)
+    quantiles = np.concatenate(quantiles).reshape((len(q),) + shape)
+    return PosteriorPredictive(times, filters, q, quantiles, n_valid.reshape(shape), n_samples)

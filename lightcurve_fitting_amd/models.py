@@ -482,6 +482,17 @@ class BaseCompanionShocking(Model):
     def _n_tr_params(self):
         return 3
 
+    def companion_shocking(self, t_in, f, t_exp, a13, Mc_v9_7, kappa=1.):
+        """The shock component alone at times ``t_in`` in filters ``f`` (models.py:757-784): ``temperature_radius``
+        followed by ``blackbody_to_filters``.  An opacity ``kappa`` other than 1 enters as the separation ``a13 / kappa``
+        and the product ``kappa * Mc_v9_7`` (models.py:753-754 depend on these two combinations only)."""
+        a13 = np.asarray(a13, dtype=np.float64) / kappa
+        Mc_v9_7 = np.asarray(Mc_v9_7, dtype=np.float64) * kappa
+        if self.model_id == _eng.MODEL_COMPANION_SHOCKING3 and np.any(Mc_v9_7 != 1.):
+            raise NotImplementedError('CompanionShocking3 fixes kappa * Mc_v9_7 = 1 (models.py:1040)')
+        T, R = self.temperature_radius(t_in, t_exp, a13, Mc_v9_7)
+        return blackbody_to_filters(f, T, R, self.z)
+
     @staticmethod
     def t_min(p):
         return p[3] + p[4] * sifto_template()[:, 0].min()
