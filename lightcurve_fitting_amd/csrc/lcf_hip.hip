@@ -13,9 +13,11 @@
 // 256; lane = one data point.  The exp table and all band tables are staged in LDS once per
 // workgroup; lanes of a wave read the same LDS address (broadcast) because neighbouring points share a filter.
 // Reductions are wave shuffles + a fixed-order LDS sum: no float atomics anywhere, results are bitwise reproducible
-// run to run and independent of the GPU count.  The sampler (k_fused = a whole half-step in one launch; k_step,
-// k_draws, k_make_perm), the multi-transient launches (k_*_multi) and the RCCL-driven sharded run live further down;
-// the SED engine is in lcf_sed.hip.
+// run to run and independent of the GPU count.  The sampler's kernels (k_fused = a whole half-step in one launch; k_step,
+// k_solo, k_solo_run) and what launches them, the multi-transient launches (k_*_multi, k_pop*) and the runs over several
+// ranks live further down: this file holds everything that instantiates a kernel template.  The bookkeeping of runs
+// (draw records, begin / snapshot / check, lcf_sampler_run) is in lcf_sampler.hip, which shares lcf_internal.h with
+// this file; the SED engine is in lcf_sed.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +35,7 @@
 #include "lcf.h"
 #include "lcf_device.h"
 #include "lcf_host.h"
+#include "lcf_internal.h"
 
 // Tuning knobs of the likelihood loop (measured on the 1024-walker, 3000-point fit: 2-6 chunks of prefetch and 4-6
 // waves per SIMD are within 1 % of each other; 8 waves per SIMD spill and lose 40 %).
@@ -41,9 +44,6 @@
 #endif
 #ifndef LCF_KPRE_SOLO
 #define LCF_KPRE_SOLO 2  // the same in the one-workgroup-per-proposal kernel (4: 3.73e7 walker-steps/s, 3: 3.74e7, 2: 3.78e7)
-#endif
-#ifndef LCF_FIRST_BLOCK
-#define LCF_FIRST_BLOCK 32  // steps in the first block of draw records of a run (the later ones: up to 256)
 #endif
 #ifndef LCF_HEAD_START
 #define LCF_HEAD_START 0  // k_solo: the waves beside the serial head wait 64 x this many cycles before their first loads
@@ -944,96 +944,6 @@ __global__ __launch_bounds__(kBlock) void k_bb_pointwise(const DevProblem pb, in
     out[i] = r * r * S;
 }
 
-// ---- ensemble sampler ---------------------------------------------------------------------------------------------
-// Half-steps are numbered globally (g = 0, 1, 2, ...).  Everything a proposal needs later for its accept/reject is
-// kept per proposal slot in buffers double-buffered by the parity of g, so that ONE kernel (k_next) can, fully in
-// parallel and without any inter-workgroup hand-off, (i) commit the previous half-step and (ii) draw the next
-// proposals: a thread that needs the position of a walker whose previous move is not committed yet simply evaluates
-// that walker's accept test itself (a pure function of immutable per-slot data).
-// Per proposal slot: what its accept test needs besides the new log-posterior (one 32-byte load).
-struct SlotRec {
-    double zl;      // (n_dim - 1) ln z
-    double lnu;     // ln u of the accept test
-    double lp_old;  // log-posterior of the walker when the proposal was drawn
-    double lpri;    // log-prior of the proposal
-};
-// Per (step, half, slot): the state-independent part of the stretch move, drawn for the whole run in advance.
-struct DrawRec {
-    int wid, pid;      // active walker and its partner from the complementary colour
-    int wprev, pprev;  // their proposal slots in the previous half-step of the run (-1: not active there)
-    double z;          // stretch factor
-    double zl;         // (n_dim - 1) ln z
-    double lnu;        // ln u
-    int wage, page;    // half-steps since the walker / the partner last moved (1..3; 0 without slot bookkeeping)
-};
-
-struct DevSampler {
-    int n_walkers, n_half, n_dim, store_chain;
-    uint32_t key0, key1;
-    int inline_finalize;  // 1: accept tests sum the chi^2 partials themselves; 0: they read the gathered newlp
-    int n_peers;          // > 0: the rows travel through peer mailboxes (below) instead of part2 + a collective
-    double a;
-    double* X;          // [n_walkers][n_dim]  committed positions
-    double* LP;         // [n_walkers]         committed log-posteriors
-    double* Q[2];       // [n_half][n_dim]     proposals
-    SlotRec* rec[2];    // [n_half]
-    double* newlp[2];   // [n_half]            log-posterior of the proposal (finalize kernel / all-gather)
-    double* part2[2];   // [n_half][n_parts + 1] per slot: chi^2 partial sums, then the log-prior; half-step parity 0 / 1
-    double* chain;      // [n_steps][n_walkers][n_dim]
-    double* chain_lp;   // [n_steps][n_walkers]
-    long long* nacc;    // [n_walkers]
-    int* err;
-    // Peer mailboxes (multi-GPU without a collective): every rank owns a mailbox [4 generations][n_half][row] of
-    // 16-byte entries; a rank that has evaluated a proposal writes the entry of each of the row's numbers straight into
-    // EVERY rank's mailbox (peer memory mapped through IPC; over xGMI on a node), and whoever needs the row polls its
-    // own copy.  mbox = this rank's, peer_mbox[r] = rank r's as mapped here (own included).
-    unsigned long long* mbox;
-    unsigned long long* peer_mbox[kMaxPeers];
-    // Row boards (multi-GPU, one workgroup per proposal: lcf_sampler_run_rows).  Every rank owns a board
-    // [kRing versions][n_walkers][n_dim + 2] of 16-byte entries in uncached memory -- a walker's position, its
-    // log-posterior and its acceptance count after each of its moves, tagged with the half-step -- followed by one
-    // progress word per rank, an abort word and four words that say what an aborted launch was waiting for.  The rank
-    // that moves a walker posts the row on EVERY rank's board; nobody else computes anything about that walker.
-    unsigned long long* board;
-    unsigned long long* peer_board[kMaxPeers];
-    int n_board_ranks, board_rank;
-    int ring, pad_ring;   // versions a board keeps (a power of two): kRing between ranks, kRunRing for one-launch runs
-    // One-launch runs write the snapshot the host reads after a run -- [error word | X | LP | n_accepted] in pinned host
-    // memory -- themselves, with the state, in their last step; a workgroup that meets a NaN or gives up a wait says so in
-    // a word of its own behind it (snap_flags[blockIdx.x & (kSnapFlags - 1)] = 1 / snap_flags[kSnapFlags + ...] = 2;
-    // plain stores, cleared with the state only: errors stay until set_state).  Null: the snapshot kernel does it.
-    unsigned long long* snap_out;
-    unsigned int* snap_flags;
-    // ... and write the state into a second set of buffers (the host then swaps the two sets): a launch that gives up
-    // leaves the state it started from untouched, and the host runs the same steps again, a launch per half-step.
-    double* X_out;
-    double* LP_out;
-    long long* nacc_out;
-    // Bound of every wait for another rank (mailbox entries, board rows, progress words), in ticks of the 100 MHz wall
-    // clock: peer_wait_ticks().  A rank's stream holds only a few ms of launches, so a host that stalls longer than
-    // this on ONE rank ends the run on ALL of them -- the default is therefore seconds, not the 0.5 s of round 2.
-    unsigned long long wait_ticks;
-    // ... and of the wait of a resident launch (k_solo_run) for the REST OF ITSELF: LCF_RESIDENT_WAIT_S, default 0.05 s.
-    unsigned long long resident_ticks;
-};
-
-// LCF_RESIDENT_WAIT_S (seconds, default 0.05): how long a workgroup of a resident launch waits for a row before it asks
-// whether the launch's other workgroups have started at all (board_take)
-unsigned long long resident_wait_ticks() {
-    double sec = 0.05;
-    if (const char* env = std::getenv("LCF_RESIDENT_WAIT_S")) sec = std::atof(env);
-    if (!(sec > 0.)) sec = 0.05;
-    return (unsigned long long)(std::min(sec, 600.) * 1e8);
-}
-
-// LCF_PEER_WAIT_S (seconds, default 5; the tests of the bounded waits set 0.5)
-unsigned long long peer_wait_ticks() {
-    double sec = 5.;
-    if (const char* env = std::getenv("LCF_PEER_WAIT_S")) sec = std::atof(env);
-    if (!(sec > 0.)) sec = 5.;
-    return (unsigned long long)(std::min(sec, 600.) * 1e8);
-}
-
 // One float64 as two 8-byte granules {32 data bits, 32-bit generation tag}: an 8-byte store is the largest that
 // arrives whole, so a reader that sees the tag of the generation it waits for in both granules has the value -- no
 // flag, no fence, no ordering between stores needed (the "LL" protocol of the collective libraries).  Mailbox
@@ -1067,179 +977,6 @@ __device__ inline double mbox_take(const DevSampler& sm, long long g, int slot, 
         }
         __builtin_amdgcn_s_sleep(2);
     }
-}
-
-// Random red/blue colouring of each step (emcee's randomize_split): one workgroup per step ranks the walkers by a
-// 50-bit Philox key (ties impossible: the walker id fills the low 14 bits) with a bitonic sort in LDS.
-// perm[step][0 .. n/2) is colour 0.  Deterministic in (seed, step): every rank of a multi-GPU run derives the same
-// split without communicating.
-// `slot_of` (or null): the slot table of k_slots, written here as well -- the step's two rows, and by the block's first
-// workgroup the row in front of the block (`front`, or all -1) -- so that the records need no launch in between.
-__device__ __forceinline__ void make_perm_body(int n_walkers, int n_pad, uint32_t key0, uint32_t key1,
-                                               long long first_step, int* __restrict__ perm, int n_half,
-                                               int* __restrict__ slot_of, const int* __restrict__ front) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
-    const long long step = first_step + blockIdx.x;
-    for (int w = threadIdx.x; w < n_pad; w += blockDim.x) {
-        unsigned long long k = ~0ull;
-        if (w < n_walkers) {
-            uint32_t r[4];
-            philox4x32((uint32_t)w, (uint32_t)step, 2u, 7u, key0, key1, r);
-            const unsigned long long h = ((unsigned long long)r[0] << 32) | r[1];
-            k = (h & ~0x3fffull) | (unsigned long long)w;
-        }
-        keys[w] = k;
-    }
-    __syncthreads();
-    // Pairs [64 m, 64 m + 64) -- one wave's share of a stage (blockDim.x is a multiple of 64) -- touch keys
-    // [128 m, 128 m + 128) only while the stride is at most 64: such stages follow each other without a workgroup
-    // barrier (a wave's LDS operations execute in order); 6 of the 55 stages of 1024 keys need one on either side.
-    for (int size = 2; size <= n_pad; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < (n_pad >> 1); i += blockDim.x) {
-                const int lo = 2 * i - (i & (stride - 1));  // index with bit `stride` clear
-                const int hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a > b) == up) {
-                    keys[lo] = b;
-                    keys[hi] = a;
-                }
-            }
-            const int next = stride > 1 ? stride >> 1 : size;   // the stride of the stage that follows
-            if (stride > 64 || next > 64)
-                __syncthreads();
-            else
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-    }
-    __syncthreads();
-    for (int w = threadIdx.x; w < n_walkers; w += blockDim.x) {
-        const int wid = (int)(keys[w] & 0x3fffull);
-        perm[(size_t)blockIdx.x * n_walkers + w] = wid;
-        if (slot_of) {   // (position w of the permutation: colour 0 = the first n_half entries -- as k_slots)
-            const int half = w < n_half ? 0 : 1, slot = w < n_half ? w : w - n_half;
-            slot_of[((size_t)blockIdx.x * 2 + 1 + half) * n_walkers + wid] = slot;
-            slot_of[((size_t)blockIdx.x * 2 + 1 + (1 - half)) * n_walkers + wid] = -1;
-            if (blockIdx.x == 0) slot_of[w] = front ? front[w] : -1;
-        }
-    }
-}
-
-__global__ __launch_bounds__(1024) void k_make_perm(int n_walkers, int n_pad, uint32_t key0, uint32_t key1,
-                                                    long long first_step, int* __restrict__ perm, int n_half,
-                                                    int* __restrict__ slot_of, const int* __restrict__ front) {
-    make_perm_body(n_walkers, n_pad, key0, key1, first_step, perm, n_half, slot_of, front);
-}
-
-// Population mode: the same for MANY samplers in one launch (blockIdx.y = sampler; equal walker counts and blocks).  What
-// differs from sampler to sampler -- the key of its RNG, its walker dimension (the accept test's (n_dim - 1) ln z), its
-// stretch scale, its buffers -- comes from an array in device memory.
-struct GenItem {
-    uint32_t key0, key1;
-    int n_dim;
-    double a;
-    int* perm[2];
-    int* slot[2];
-    DrawRec* draws[2];
-};
-// `front_row` >= 0: the half-step in front of the block is row `front_row` of the OTHER buffer's slot table (-1: none)
-__global__ __launch_bounds__(1024) void k_make_perm_multi(const GenItem* __restrict__ items, int n_walkers, int n_pad,
-                                                          long long first_step, int buf, int n_half, long long front_row) {
-    const GenItem it = items[blockIdx.y];
-    make_perm_body(n_walkers, n_pad, it.key0, it.key1, first_step, it.perm[buf], n_half, it.slot[buf],
-                   front_row >= 0 ? it.slot[buf ^ 1] + (size_t)front_row * n_walkers : nullptr);
-}
-
-// Slot of every walker in each half-step of a block of steps (-1 where it is not active).  Rows of `slot_of`
-// ([1 + 2 n_steps][n_walkers]): row 0 = the half-step in front of the block (copied from the previous block, or all
-// -1 at the start of a run), row 1 + 2 k + half = half-step (k, half) of the block.
-__global__ void k_slots(int n_walkers, int n_half, const int* __restrict__ perm, long long n_steps,
-                        int* __restrict__ slot_of, const int* __restrict__ front) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < n_walkers) slot_of[idx] = front ? front[idx] : -1;   // row 0 (nobody in this launch reads it)
-    if (idx >= n_steps * n_walkers) return;
-    const long long row = idx / n_walkers;
-    const int pos = (int)(idx % n_walkers);  // position in the permutation: colour 0 = first n_half entries
-    const int wid = perm ? perm[idx] : pos;
-    const int half = pos < n_half ? 0 : 1, slot = pos < n_half ? pos : pos - n_half;
-    slot_of[((size_t)row * 2 + 1 + half) * n_walkers + wid] = slot;
-    slot_of[((size_t)row * 2 + 1 + (1 - half)) * n_walkers + wid] = -1;
-}
-
-// The state-independent half of every stretch move of a block of steps, one thread per (step, half, slot).
-// n_half = ceil(n_walkers / 2) slots per half-step: colour 0 (the first n_half entries of the step's permutation)
-// moves in half 0 against the n_walkers - n_half walkers of colour 1, then colour 1 against colour 0 -- the larger
-// colour first, as emcee's red-blue split does for an odd ensemble; the slot an odd ensemble leaves empty in half 1
-// gets wid = -1.  `slot_of` null: no slot bookkeeping (the one-workgroup-per-proposal half-step does not need it).
-__device__ __forceinline__ void draws_body(const DevSampler& sm, const int* __restrict__ perm, const int* __restrict__ slot_of,
-                                           long long first_step, long long n_steps, DrawRec* __restrict__ draws) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n_steps * 2 * sm.n_half) return;
-    const int i = (int)(idx % sm.n_half), half = (int)((idx / sm.n_half) & 1);
-    const long long row = idx / (2 * sm.n_half);
-    const int* pr = perm ? perm + (size_t)row * sm.n_walkers : nullptr;
-    const int n_act = half == 0 ? sm.n_half : sm.n_walkers - sm.n_half, n_other = sm.n_walkers - n_act;
-    DrawRec d;
-    if (i >= n_act) {
-        d.wid = d.pid = d.wprev = d.pprev = -1;
-        d.z = 1.;
-        d.zl = d.lnu = 0.;
-        d.wage = d.page = 0;
-        draws[idx] = d;
-        return;
-    }
-    const int my_slot = half == 0 ? i : sm.n_half + i;  // colour 0 = first n_half entries of the permutation
-    const int wid = pr ? pr[my_slot] : my_slot;
-    uint32_t r[4], s2[4];
-    philox4x32((uint32_t)wid, (uint32_t)(first_step + row), (uint32_t)half, 0u, sm.key0, sm.key1, r);
-    philox4x32((uint32_t)wid, (uint32_t)(first_step + row), (uint32_t)half, 1u, sm.key0, sm.key1, s2);
-    const double zr = (sm.a - 1.) * u01(r[0], r[1]) + 1.;
-    const double z = zr * zr / sm.a;
-    int j = (int)(u01(r[2], r[3]) * (double)n_other);
-    j = min(j, n_other - 1);
-    const int other_slot = half == 0 ? sm.n_half + j : j;
-    d.wid = wid;
-    d.pid = pr ? pr[other_slot] : other_slot;
-    const int* before = slot_of ? slot_of + (size_t)(row * 2 + half) * sm.n_walkers : nullptr;  // the half-step in front
-    d.wprev = before ? before[d.wid] : -1;
-    d.pprev = before ? before[d.pid] : -1;
-    d.z = z;
-    d.zl = (double)(sm.n_dim - 1) * log(z);
-    d.lnu = log(u01(s2[0], s2[1]));
-    // Every walker moves once per step, in one of its two half-steps: a walker that was not active in the half-step in
-    // front (half-step G - 1) moved in the one before it, or -- the walker of a step's SECOND half-step only -- three
-    // half-steps ago (first half of the previous step).  The sharded one-workgroup-per-proposal run waits for exactly
-    // that version of each row.  (Before the first step of a run every age points in front of the run: its start state.)
-    d.wage = d.page = 0;
-    if (slot_of) {
-        if (half == 0) {
-            d.wage = before[d.wid] >= 0 ? 1 : 2;
-            d.page = before[d.pid] >= 0 ? 1 : 2;
-        } else {
-            const int* two_back = slot_of + (size_t)(row * 2) * sm.n_walkers;  // second half of the previous step
-            d.wage = two_back[d.wid] >= 0 ? 2 : 3;
-            d.page = 1;
-        }
-    }
-    draws[idx] = d;
-}
-
-__global__ void k_draws(DevSampler sm, const int* __restrict__ perm, const int* __restrict__ slot_of,
-                        long long first_step, long long n_steps, DrawRec* __restrict__ draws) {
-    draws_body(sm, perm, slot_of, first_step, n_steps, draws);
-}
-// (population mode, blockIdx.y = sampler: `sm` = the samplers' common walker count; key, dimension and stretch scale
-// from the item)
-__global__ void k_draws_multi(const GenItem* __restrict__ items, DevSampler sm, int buf, long long first_step,
-                              long long n_steps) {
-    const GenItem it = items[blockIdx.y];
-    sm.key0 = it.key0;
-    sm.key1 = it.key1;
-    sm.n_dim = it.n_dim;
-    sm.a = it.a;
-    draws_body(sm, it.perm[buf], it.slot[buf], first_step, n_steps, it.draws[buf]);
 }
 
 // The serial part of a half-step for slot i, executed by ONE wave (lane = 0..63): accept tests of the previous
@@ -1499,46 +1236,6 @@ __global__ __launch_bounds__(kBlock, LCF_WAVES) void k_fused(const DevProblem pb
     if (sm.n_peers > 0 && tid == 0) mbox_post(sm, g, i, part, part_stride(pb), psum);  // straight into every rank's mailbox
 }
 
-// ---- row boards: tagged words in device memory ---------------------------------------------------------------------
-// One float64 = ONE 16-byte entry of two 8-byte granules {32 data bits, 32-bit tag}, tag = half-step after which the row
-// holds + 1 (the LL protocol of the mailboxes above, the entry posted with one 16-byte store and polled with one 16-byte
-// load: each granule carries its own tag, so an entry that arrives in two halves is still never mistaken for complete).
-// A row = the walker's n_dim + 2 numbers in consecutive entries, padded to whole 128-byte lines (board_row_entries):
-// the lanes of ONE store instruction post a row, into one line (n_dim <= 6) of each board it goes to.
-// Between ranks (k_solo<BOARD> per half-step, k_solo_run<..., RANKS> per block of half-steps): a ring of kRing versions.
-// Safe because (a) a reader asks for exactly the version the draw record names (DrawRec::wage / page) and waits,
-// bounded, until both granules carry its tag; (b) progress words bound how far ranks drift apart: with a launch per
-// half-step no rank starts half-step G before every rank has finished G - 2; with a launch per block of up to kRunSpan
-// half-steps no rank starts a launch before every rank has STARTED the launch before the previous one (a rank's
-// progress word = the first half-step of the launch it has reached, posted by that launch itself: stream order proves
-// that everything in front of it, its row collection included, is complete).  Everything a rank still reads is then at
-// most 3 kRunSpan + 2 versions behind anything another rank writes: kRing = 256 versions are never overrun.
-constexpr int kRing = 256;
-constexpr int kSnapFlags = 1024;
-// One-launch runs of ONE GPU (k_solo_run, k_pop_run): a launch covers at most kRunSpanSolo half-steps, reads versions >= G - 3 and
-// writes G + 1: kRunRing versions are never overrun however far the workgroups of a launch drift apart.
-// (Between ranks a launch covers at most kRunSpan half-steps -- the ring of the inter-rank boards bounds it, below; on one
-// GPU up to kRunSpanSolo: a launch's start-up -- staging, first fetch, every workgroup arriving, ~18 us at configs[1] --
-// is then paid once per 256 half-steps instead of once per 64: 5.41 -> 5.31 us per half-step over a 1000-step run.)
-#ifndef LCF_RUN_SPAN_SOLO
-#define LCF_RUN_SPAN_SOLO 256
-#endif
-constexpr int kRunSpanSolo = LCF_RUN_SPAN_SOLO;
-constexpr int kRunRing = 2 * kRunSpanSolo;
-constexpr int kRunSpan = 64;
-static_assert((kRunRing & (kRunRing - 1)) == 0 && kRunRing >= kRunSpanSolo + 8, "the ring of a one-launch run covers a launch");
-constexpr int kRunStoreChain = 1, kRunFlip = 2;   // k_solo_run's run_flags: the run stores its chain; its start state is in X_out / LP_out / nacc_out
-// 32-bit words behind the rows: progress per rank, abort, 4 x diagnosis, arrivals (workgroups of resident launches that
-// have started, counted up from launch to launch: a launch knows the count that says "all of mine are there")
-constexpr int kBoardTail = kMaxPeers + 1 + 4 + 1 + 4;
-constexpr int kBoardClear = 10;                 // the last words of the tail that set_state clears: abort ... arrivals, and
-                                                // the four words of the entry a given-up wait last saw (diagnosis)
-static_assert(kRing >= 3 * kRunSpan + 8, "the ring of the inter-rank boards must cover three launches");
-
-__host__ __device__ inline int board_row_entries(int n_dim) { return (n_dim + 2 + 7) & ~7; }   // 16-byte entries per row
-__host__ __device__ inline size_t board_rows_bytes(int ring, int n_walkers, int n_dim) {
-    return (size_t)ring * n_walkers * board_row_entries(n_dim) * 16;
-}
 __device__ inline unsigned long long* board_entry(unsigned long long* board, const DevSampler& sm, unsigned int tag, int wid,
                                                   int col) {
     return board + 2 * ((((size_t)(tag & (unsigned int)(sm.ring - 1)) * sm.n_walkers) + wid) * board_row_entries(sm.n_dim) + col);
@@ -1718,17 +1415,7 @@ __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSample
         const bool own = lane >= 16;
         const int col = own ? lane - 16 : lane;
         if (own ? col <= nd + 1 : col < nd) {
-#ifdef LCF_EXPERIMENT_NOPOLL   // (timing experiment, wrong chain: the state in memory instead of the rows the half-step needs:
-            // one load past the caches, as a poll that finds its row at once, and no waiting for anybody)
-            {
-                const int w_ = own ? dr.wid : dr.pid;
-                const double* src_ = col < nd ? sm.X + (size_t)w_ * nd + col : col == nd ? sm.LP + w_ : sm.LP + w_;
-                h.got = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(src_),
-                                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-            }
-#else
             h.got = board_take<BOARD == 2>(sm, board_tag(G, own ? dr.wage : dr.page, g_run0), own ? dr.wid : dr.pid, col, arrive_goal);
-#endif
         }
     }
     h.lp_i = BOARD ? lane_value(h.got, 16 + nd) : sm.LP[dr.wid];
@@ -1952,11 +1639,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             double acc = 0.;
             if (c0 + (ltid & ~63) < c1) {   // (a virtual wave without columns adds nothing)
                 const bool live = c0 + ltid < c1;
-#ifdef LCF_EXPERIMENT_NOCOLUMNS   // (timing experiment, wrong chain: no likelihood arithmetic)
-                if (false)
-#else
                 if (!lean_column<MODEL>(pb, sc, first_col, ExpTab{exptab}, itab_at, acc))
-#endif
                     acc = cold_column_with_state<VARIANT, MODEL>(pbp, sc, sq, first_col.t, min(c0 + ltid, c1 - 1), live);
                 term = live ? acc : 0.;     // (lanes beyond the part repeated its last column)
             }
@@ -1985,23 +1668,9 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                 if ((tid & 63) == 0) red[4 * pp + (ltid >> 6)] = ws;
             }
         } else {
-#ifdef LCF_TWICE   // diagnostic: the column phase twice through the SAME code (second pass: warm instruction cache)
-            {
-                int reps_;
-                asm volatile("s_mov_b32 %0, 2" : "=s"(reps_));
-#pragma unroll 1
-                for (int rep = 0; rep < reps_; ++rep) {
-                    if (part < pb.n_parts)
-                        term = epochs_loop<VARIANT, true, kFetch, MODEL, true>(pb, part, sq, cs, ltab, fdesc, ExpTab{exptab}, ltid,
-                                                                               itab_at, first_col, true, pbp, sc);
-                    if (rep == 0) LCF_STAMP(0, 7);
-                }
-            }
-#else
             if (part < pb.n_parts)
                 term = epochs_loop<VARIANT, true, kFetch, MODEL, true>(pb, part, sq, cs, ltab, fdesc, ExpTab{exptab}, ltid, itab_at,
                                                                        first_col, true, pbp, sc);
-#endif
             LCF_STAMP(0, 8);
             LCF_STAMP(1, 12);
             const double ws = wave_sum(term);
@@ -2236,16 +1905,6 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
 template <class T>
 __global__ void k_put_image(T* __restrict__ dst, const T src) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *dst = src;
-}
-
-// State of the sampler as 8-byte words into (mapped, pinned) host memory: [error flag | X | LP | n_accepted].
-__global__ void k_snapshot(const DevSampler sm, unsigned long long* __restrict__ out) {
-    const long long nx = (long long)sm.n_walkers * sm.n_dim, nw = sm.n_walkers;
-    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w == 0) out[0] = (unsigned long long)(unsigned int)*sm.err;
-    else if (w <= nx) out[w] = reinterpret_cast<const unsigned long long*>(sm.X)[w - 1];
-    else if (w <= nx + nw) out[w] = reinterpret_cast<const unsigned long long*>(sm.LP)[w - 1 - nx];
-    else if (w <= nx + 2 * nw) out[w] = (unsigned long long)sm.nacc[w - 1 - nx - nw];
 }
 
 // ---- population mode: one launch covers the same half-step of MANY independent transients (blockIdx.y) --------------
@@ -2587,74 +2246,6 @@ lcf_status fail(lcf_status st, const std::string& msg) {
 }
 }  // namespace lcf
 
-namespace {
-
-}  // namespace
-
-struct lcf_engine {
-    int device = 0;
-    DevProblem dp{};
-    std::vector<void*> owned;
-    hipStream_t stream = nullptr;
-    int64_t samples_per_eval = 0;
-    size_t lds_bytes = 0;
-    int* d_tab_off = nullptr;   // per filter: (offset, count) of the full table in the device table
-    int* d_ctab_off = nullptr;  // per filter: (offset, count) of the compressed table
-    double* d_ctmin = nullptr;
-    bool have_ctab = false, have_itab = false;
-    int n_cus = 256;             // compute units of the device (launch shapes depend on it)
-    DevProblem* d_dp = nullptr;  // `dp` in device memory, for the kernels that read it through a pointer
-    lcf_status sync_dp();        // after every change of `dp`
-    // workspace for n walkers
-    int64_t cap = 0;
-    double *wP = nullptr, *wcoef = nullptr, *wlprior = nullptr, *wpart = nullptr, *wout = nullptr;
-    double2* wtherm = nullptr;
-    // scratch for evaluate-type calls
-    size_t big_bytes = 0;
-    double* wbig = nullptr;
-
-    ~lcf_engine() {
-        hipSetDevice(device);
-        for (void* p : owned) hipFree(p);
-        free_ws();
-        if (wbig) hipFree(wbig);
-        if (stream) hipStreamDestroy(stream);
-    }
-    void free_ws() {
-        for (double** p : {&wP, &wcoef, &wlprior, &wpart, &wout}) {
-            if (*p) hipFree(*p);
-            *p = nullptr;
-        }
-        if (wtherm) hipFree(wtherm);
-        wtherm = nullptr;
-        cap = 0;
-    }
-    lcf_status reserve(int64_t n) {
-        if (n <= cap) return LCF_OK;
-        LCF_HIP(hipStreamSynchronize(stream));
-        free_ws();
-        const int64_t c = std::max<int64_t>(n, 64);
-        LCF_HIP(hipMalloc((void**)&wP, c * dp.n_dim * sizeof(double)));
-        LCF_HIP(hipMalloc((void**)&wcoef, c * kNCoef * sizeof(double)));
-        LCF_HIP(hipMalloc((void**)&wlprior, c * sizeof(double)));
-        LCF_HIP(hipMalloc((void**)&wpart, c * (dp.n_parts + 1) * sizeof(double)));
-        LCF_HIP(hipMalloc((void**)&wout, c * sizeof(double)));
-        if (dp.use_therm) LCF_HIP(hipMalloc((void**)&wtherm, c * dp.n_epochs * sizeof(double2)));
-        cap = c;
-        return LCF_OK;
-    }
-    lcf_status reserve_big(size_t bytes) {
-        if (bytes <= big_bytes) return LCF_OK;
-        LCF_HIP(hipStreamSynchronize(stream));
-        if (wbig) hipFree(wbig);
-        wbig = nullptr;
-        big_bytes = 0;
-        LCF_HIP(hipMalloc((void**)&wbig, bytes));
-        big_bytes = bytes;
-        return LCF_OK;
-    }
-};
-
 // `dp` into its image in device memory: by a kernel on the engine's stream (see k_put_image), complete on return.
 lcf_status lcf_engine::sync_dp() {
     if (!d_dp) {
@@ -2759,6 +2350,9 @@ void launch_points(const lcf_engine* e, int w_lo, int n, const double* dP, const
         launch_points_v<1, MODE>(pb, grid, e->lds_bytes, st, w_lo, n, dP, coef, lprior, therm, out0, out1);
 }
 
+}  // namespace
+
+namespace lcf {
 // log-likelihood / log-posterior of n walkers, device pointers, enqueue only.
 lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout, hipStream_t st, int with_prior) {
     if (n == 0) return LCF_OK;
@@ -2771,6 +2365,9 @@ lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout,
     LCF_HIP(hipGetLastError());
     return LCF_OK;
 }
+}  // namespace lcf
+
+namespace {
 
 lcf_status logprob_host(lcf_engine* e, int64_t n, const double* P, double* out, int with_prior) {
     if (!e || n < 0 || (n > 0 && (!P || !out))) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
@@ -3431,311 +3028,9 @@ extern "C" lcf_status lcf_profile_loglike_kernel(lcf_engine* e, int64_t n, const
     return LCF_OK;
 }
 
-namespace {
-// ---- memory that kernels POLL (row boards, mailboxes) is never handed back to the driver ---------------------------------
-// A board that was freed (hipFree) and whose address range the driver then gave to the next sampler's board left single
-// workgroups of the next launches reading the OLD contents of those addresses for as long as they polled -- rows that
-// every other workgroup (and the host) could see never arrived for them, 5 s waits, once also a stale row with a valid
-// tag (a wrong chain).  Reproduced deterministically by tools/debug/rows_mismatch.py once the inter-rank boards were
-// megabytes (freed uncached memory recycled into the next board); gone when such memory is not freed.  So: polled
-// memory goes back to a list of this process and is taken from there by the next sampler that needs the same size;
-// whoever takes it clears it (stale tags of an earlier life would be valid tags of the next) before anything reads it.
-struct PolledBlock { int dev; bool uncached; size_t bytes; void* p; };
-std::mutex g_polled_mutex;
-std::vector<PolledBlock> g_polled;
-
-void* polled_take(int dev, bool uncached, size_t bytes) {
-    std::lock_guard<std::mutex> lock(g_polled_mutex);
-    for (size_t k = 0; k < g_polled.size(); ++k)
-        if (g_polled[k].dev == dev && g_polled[k].uncached == uncached && g_polled[k].bytes == bytes) {
-            void* p = g_polled[k].p;
-            g_polled.erase(g_polled.begin() + (long)k);
-            return p;
-        }
-    return nullptr;
-}
-void polled_give(int dev, bool uncached, size_t bytes, void* p) {
-    std::lock_guard<std::mutex> lock(g_polled_mutex);
-    g_polled.push_back(PolledBlock{dev, uncached, bytes, p});
-}
-// `bytes` of polled memory on the current device, cleared (complete on return).
-lcf_status polled_alloc(int dev, bool uncached, size_t bytes, void** out) {
-    void* p = polled_take(dev, uncached, bytes);
-    if (!p) {
-        if (uncached)   // fine-grained device memory: peers' stores over the fabric and this rank's polls meet in memory
-            LCF_HIP(hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached));
-        else
-            LCF_HIP(hipMalloc(&p, bytes));
-    }
-    *out = p;
-    LCF_HIP(hipMemset(p, 0, bytes));        // tag 0: no version / generation (half-steps are numbered from 2)
-    LCF_HIP(hipDeviceSynchronize());
-    return LCF_OK;
-}
-
-}  // namespace
-
-// =================================================================================================================
-// sampler
-// =================================================================================================================
-struct lcf_sampler {
-    lcf_engine* e = nullptr;
-    int device = 0;           // e->device, kept for the destructor
-    DevSampler ds{};
-    std::vector<void*> owned;
-    double *coef = nullptr, *lprior = nullptr;
-    // The state-independent draws of a run are produced in BLOCKS of steps, two buffers (block b lives in buffer b & 1):
-    // device memory does not grow with the run, the first half-step starts after a short first block, and nothing on
-    // the host waits for the generation.  The generation kernels go on the SAME stream as the half-steps, between two
-    // of them: block b + 1 right behind the first launch of block b (the last reader of the buffer it overwrites), so
-    // stream order is all the synchronisation there is.  (Measured at 1024 walkers x 2000 steps: a low- or
-    // normal-priority side stream with events cost 3-4 % of the whole run however rarely it was used; the inline
-    // kernels cost 40 us per 256 steps.)
-    int64_t blk_first = 0, blk_steps = 0;          // steps in block 0 and in every later block
-    int64_t blk_cap = 0;                           // steps a buffer holds
-    int* d_perm[2] = {nullptr, nullptr};           // [blk_cap][n_walkers]
-    DrawRec* d_draws[2] = {nullptr, nullptr};      // [blk_cap][2][n_half]
-    int* d_slot[2] = {nullptr, nullptr};           // [1 + 2 blk_cap][n_walkers] (row 0: the half-step in front)
-    int* d_perm_host = nullptr;                    // LCF_SPLIT_HOST: the caller's permutations of the whole run
-    int64_t perm_host_rows = 0;
-    int split_mode = LCF_SPLIT_IDENTITY;
-    bool need_slots = true;                        // draw records carry the slots of the previous half-step
-    int64_t blk_generated = -1;                    // last block whose generation is enqueued
-    int64_t blk_current = -1;                      // block the half-steps are in
-    int64_t run_first = 0, run_steps = 0;
-    int64_t spec_first = -1;   // >= 0: buffer 0 holds the first block of a run starting at this step (speculated)
-    int spec_mode = 0;
-    bool spec_slots = false;
-    int64_t chain_cap = 0;
-    bool has_state = false;
-    long long g_next = 2;     // global half-step counter (never reused: see lcf_sampler_begin)
-    long long g_run0 = 2;     // first half-step of the current run
-    bool pending = false;     // the last proposed half-step is not committed yet
-    bool foreign_stream = false;  // half-steps of the current run were enqueued on a caller's stream
-    int half_step_kernel = LCF_HALF_STEP_AUTO;
-    int last_kernel = -1;     // what the last run's half-steps were (lcf_sampler_last_run_kernel)
-    bool last_rows = false;   // ... and whether it was a row-board run (between ranks)
-    long long last_launches = 0;   // launches of that kernel in the last run (lcf_sampler_last_run_launches)
-    unsigned long long* mailbox = nullptr;   // this rank's peer mailbox (uncached device memory), see DevSampler
-    size_t mailbox_cap = 0;
-    void* board_mem = nullptr;               // this rank's row board (uncached device memory), see DevSampler
-    std::vector<void*> board_opened;         // peers' boards mapped through IPC
-    // One-launch runs write their final state into the other of two sets of state buffers (DevSampler::X_out ...):
-    // ds.X / LP / nacc name the set that holds the state behind everything enqueued so far.
-    double* alt_X = nullptr;
-    double* alt_LP = nullptr;
-    long long* alt_nacc = nullptr;
-    bool run_off = false;                    // a one-launch run of this sampler gave up once: launches per half-step from then on
-    int replay_split = 0, replay_store = 0;  // the last one-launch run, should it have to be repeated
-    int64_t replay_first = 0, replay_steps = -1;
-    void* run_board_mem = nullptr;           // the board of one-launch runs (k_solo_run): kRunRing versions, this GPU only
-    DevSampler* d_run_image = nullptr;       // the sampler as k_solo_run reads it (run_image)
-    DevSampler run_image_host{};
-    bool run_image_valid = false;
-    bool run_flip = false;                   // ds.X / LP / nacc name the SECOND set of state buffers
-    unsigned int run_arrivals = 0;           // workgroups of resident launches enqueued so far (the board's arrivals word)
-    DevSampler* d_rows_image = nullptr;      // the sampler as k_solo_run<..., RANKS> reads it (rows_image)
-    DevSampler rows_image_host{};
-    bool rows_image_valid = false;
-    unsigned int rows_arrivals = 0;          // the same count for the resident launches of row-board runs (cleared per run)
-    size_t run_board_bytes() const {
-        return board_rows_bytes(kRunRing, ds.n_walkers, ds.n_dim) + (size_t)kBoardTail * sizeof(unsigned int);
-    }
-    size_t board_bytes() const {
-        return board_rows_bytes(kRing, ds.n_walkers, ds.n_dim) + (size_t)kBoardTail * sizeof(unsigned int);
-    }
-    std::vector<void*> opened;               // peers' mailboxes mapped through IPC
-    int peer_ranks = 0, peer_rank = 0;
-    // Snapshot of (error flag, positions, log-posteriors, acceptance counts) in pinned host memory, copied behind the
-    // last launch of a run: the calls that read them back after the run wait for nothing more.
-    unsigned char* snap = nullptr;
-    bool snap_enqueued = false, snap_valid = false;
-    size_t snap_x() const { return 8; }
-    size_t snap_lp() const { return snap_x() + (size_t)ds.n_walkers * ds.n_dim * sizeof(double); }
-    size_t snap_acc() const { return snap_lp() + (size_t)ds.n_walkers * sizeof(double); }
-    size_t snap_bytes() const { return snap_acc() + (size_t)ds.n_walkers * sizeof(long long); }
-    size_t snap_alloc() const { return snap_bytes() + 2 * kSnapFlags * sizeof(unsigned int); }   // + the workgroups' error words
-    unsigned int* snap_flags() const { return reinterpret_cast<unsigned int*>(snap + snap_bytes()); }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_snap = nullptr;   // behind the snapshot kernel: what a caller of a finished run waits for
-    double last_ms = 0.;
-
-    ~lcf_sampler() {
-        // (the device is remembered here: a garbage collector may destroy the engine first, and nothing below needs it)
-        hipSetDevice(device);
-        for (void* p : owned) hipFree(p);
-        if (ds.chain) hipFree(ds.chain);
-        if (ds.chain_lp) hipFree(ds.chain_lp);
-        free_blocks();
-        for (void* p : opened) hipIpcCloseMemHandle(p);
-        if (mailbox) polled_give(device, true, mailbox_cap, mailbox);
-        for (void* p : board_opened) hipIpcCloseMemHandle(p);
-        if (board_mem) polled_give(device, true, board_bytes(), board_mem);
-        if (run_board_mem) polled_give(device, false, run_board_bytes(), run_board_mem);
-        if (snap) hipHostFree(snap);
-        if (d_perm_host) hipFree(d_perm_host);
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-        if (ev_snap) hipEventDestroy(ev_snap);
-    }
-    void free_blocks() {
-        for (int b = 0; b < 2; ++b) {
-            if (d_perm[b]) hipFree(d_perm[b]);
-            if (d_draws[b]) hipFree(d_draws[b]);
-            if (d_slot[b]) hipFree(d_slot[b]);
-            d_perm[b] = nullptr;
-            d_draws[b] = nullptr;
-            d_slot[b] = nullptr;
-        }
-        blk_cap = 0;
-    }
-    // block of the run's step k (relative), and the block's first step / length
-    int64_t block_of_step(int64_t k) const { return k < blk_first ? 0 : 1 + (k - blk_first) / blk_steps; }
-    int64_t block_start(int64_t b) const { return b == 0 ? 0 : blk_first + (b - 1) * blk_steps; }
-    int64_t block_len(int64_t b) const {
-        return std::min(run_steps, block_start(b) + (b == 0 ? blk_first : blk_steps)) - block_start(b);
-    }
-    // draw records of the run's half-step `rel` (its block must be resident)
-    const DrawRec* rows(long long rel) const {
-        const int64_t b = block_of_step(rel / 2);
-        return d_draws[b & 1] + (size_t)(rel - 2 * block_start(b)) * ds.n_half;
-    }
-    // half-steps of a resident launch from the run's half-step `rel` on: up to `max_span`, never past the end of the
-    // current block of draw records
-    int block_span(long long rel, int max_span) const {
-        return (int)std::min<long long>(max_span, 2 * (block_start(blk_current) + block_len(blk_current)) - rel);
-    }
-    // the other set of state buffers holds the state now (see alt_X)
-    void flip_state_sets() {
-        std::swap(ds.X, alt_X);
-        std::swap(ds.LP, alt_LP);
-        std::swap(ds.nacc, alt_nacc);
-        run_flip = !run_flip;
-    }
-};
-
-namespace {
-
-// Enqueue, on stream `gs` (the one the half-steps run on: behind the last reader of the buffer), the generation of
-// `len` steps of draw records starting at absolute step `step0` into buffer `buf`.  `front`: where the slots of the
-// half-step in front of the block come from (null: nothing in front, the start of a run).
-lcf_status generate_steps(lcf_sampler* s, int buf, int64_t step0, int64_t len, int split_mode, const int* host_perm,
-                          bool need_slots, const int* front, hipStream_t gs) {
-    const DevSampler& ds = s->ds;
-    const int* perm = nullptr;
-    if (split_mode == LCF_SPLIT_RANDOM) {
-        int n_pad = 2;
-        while (n_pad < ds.n_walkers) n_pad <<= 1;
-        const int threads = std::min(1024, std::max(64, n_pad / 2));
-        LCF_HIP(prepare_kernel(k_make_perm, (size_t)n_pad * 8));
-        hipLaunchKernelGGL(k_make_perm, dim3((unsigned)len), dim3(threads), (size_t)n_pad * 8, gs, ds.n_walkers, n_pad,
-                           ds.key0, ds.key1, (long long)step0, s->d_perm[buf], ds.n_half,
-                           need_slots ? s->d_slot[buf] : nullptr, front);
-        perm = s->d_perm[buf];
-    } else if (split_mode == LCF_SPLIT_HOST) {
-        perm = host_perm;
-    }
-    const long long total = (long long)len * ds.n_walkers;
-    int* slots = nullptr;
-    if (need_slots) {
-        slots = s->d_slot[buf];
-        if (split_mode != LCF_SPLIT_RANDOM)   // (a random split's table comes with its permutations, from k_make_perm)
-            hipLaunchKernelGGL(k_slots, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, gs, ds.n_walkers, ds.n_half, perm,
-                               (long long)len, slots, front);
-    }
-    const long long recs = (long long)len * 2 * ds.n_half;
-    hipLaunchKernelGGL(k_draws, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, gs, ds, perm, slots,
-                       (long long)step0, (long long)len, s->d_draws[buf]);
-    LCF_HIP(hipGetLastError());
-    return LCF_OK;
-}
-
-// Block b of the current run (block b lives in buffer b & 1) for a GROUP of samplers ss[0, n) that share their block
-// geometry -- a population's transients, or one sampler on its own; so do enter_half_step and leave_half_step.  `gen`:
-// the group's GenItems in device memory, the block of all of them from one launch of each batched generation kernel;
-// null: sampler by sampler.
-lcf_status generate_block(lcf_sampler* const* ss, int n, int64_t b, hipStream_t consumer, const GenItem* gen = nullptr) {
-    const int buf = (int)(b & 1);
-    if (gen) {
-        const lcf_sampler* s0 = ss[0];
-        const DevSampler& d0 = s0->ds;
-        const int64_t k0 = s0->block_start(b), len = s0->block_len(b);
-        int n_pad = 2;
-        while (n_pad < d0.n_walkers) n_pad <<= 1;
-        const int threads = std::min(1024, std::max(64, n_pad / 2));
-        const long long front_row = b > 0 ? 2 * (long long)s0->block_len(b - 1) : -1;
-        LCF_HIP(prepare_kernel(k_make_perm_multi, (size_t)n_pad * 8));
-        hipLaunchKernelGGL(k_make_perm_multi, dim3((unsigned)len, (unsigned)n), dim3(threads), (size_t)n_pad * 8, consumer, gen,
-                           d0.n_walkers, n_pad, (long long)(s0->run_first + k0), buf, d0.n_half, front_row);
-        const long long recs = (long long)len * 2 * d0.n_half;
-        hipLaunchKernelGGL(k_draws_multi, dim3((unsigned)((recs + 255) / 256), (unsigned)n), dim3(256), 0, consumer, gen, d0,
-                           buf, (long long)(s0->run_first + k0), (long long)len);
-        LCF_HIP(hipGetLastError());
-    }
-    for (int t = 0; t < n; ++t) {
-        lcf_sampler* s = ss[t];
-        if (!gen) {
-            const int64_t k0 = s->block_start(b);
-            const int* host_perm = s->split_mode == LCF_SPLIT_HOST ? s->d_perm_host + (size_t)k0 * s->ds.n_walkers : nullptr;
-            // the half-step in front of a later block: the last row of the previous block (the other buffer)
-            const int* front = (b > 0 && s->need_slots)
-                                   ? s->d_slot[buf ^ 1] + (size_t)2 * s->block_len(b - 1) * s->ds.n_walkers : nullptr;
-            if (lcf_status r = generate_steps(s, buf, s->run_first + k0, s->block_len(b), s->split_mode, host_perm,
-                                              s->need_slots, front, consumer))
-                return r;
-        }
-        s->blk_generated = b;
-    }
-    return LCF_OK;
-}
-
-// A run usually continues where the last one stopped (burn-in -> sampling; run_mcmc(None, ...) in a loop).  Behind the
-// last launch of a run, generate the first block of such a continuation, so that its first half-step finds its draw
-// records ready: sampler_begin adopts them when the new run matches (first step, split mode, slot bookkeeping).
-// (Measured and dropped: the same BESIDE a one-block run instead of behind it -- into the other buffer, on a stream of the
-// sampler's own, of the lowest priority, enqueued before or after the run's launch -- so that the caller's
-// synchronisation does not wait for it.  The 20 us it takes behind the run disappear, but the resident launch beside it
-// takes 16-36 us longer -- its workgroups arrive later: 14.4-15.0 against 14.2 us per step of a 20-step run.)
-lcf_status speculate_continuation(lcf_sampler* s, hipStream_t st) {
-    s->spec_first = -1;
-    if (s->pending || s->split_mode == LCF_SPLIT_HOST || s->run_steps == 0) return LCF_OK;
-    const int64_t first = s->run_first + s->run_steps;
-    if (lcf_status r = generate_steps(s, 0, first, s->blk_first, s->split_mode, nullptr, s->need_slots, nullptr, st))
-        return r;
-    s->spec_first = first;
-    s->spec_mode = s->split_mode;
-    s->spec_slots = s->need_slots;
-    return LCF_OK;
-}
-
-// Before launching the run's half-step `rel` on stream `st`: its block of draw records must be generated (it is,
-// unless the caller jumped ahead).
-lcf_status enter_half_step(lcf_sampler* const* ss, int n, long long rel, hipStream_t st, const GenItem* gen = nullptr) {
-    const lcf_sampler* s0 = ss[0];
-    const int64_t b = s0->block_of_step(rel / 2);
-    if (b == s0->blk_current) return LCF_OK;
-    while (s0->blk_generated < b)
-        if (lcf_status r = generate_block(ss, n, s0->blk_generated + 1, st, gen)) return r;
-    for (int t = 0; t < n; ++t) ss[t]->blk_current = b;
-    return LCF_OK;
-}
-
-// After that launch (the last reader of the block left behind, through the previous half-step's records): generate
-// the next block into the buffer that is now free.
-lcf_status leave_half_step(lcf_sampler* const* ss, int n, hipStream_t st, const GenItem* gen = nullptr) {
-    const lcf_sampler* s0 = ss[0];
-    const int64_t last = s0->block_of_step(s0->run_steps - 1);
-    if (s0->blk_generated == s0->blk_current && s0->blk_current < last)
-        return generate_block(ss, n, s0->blk_current + 1, st, gen);
-    return LCF_OK;
-}
-
-template <class T>
-lcf_status dalloc(T** p, size_t n, std::vector<void*>& owned) {
-    LCF_HIP(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-    owned.push_back(*p);
-    return LCF_OK;
-}
+// (In namespace lcf: the functions lcf_internal.h declares, which lcf_sampler.hip calls; everything `static` stays
+// internal to this file.)
+namespace lcf {
 
 // Commit half-step g_next - 1 (if pending) and draw half-step g_next (if have_next); coefficients and log-priors of the
 // slots [lo, hi) for the likelihood launch behind it.
@@ -3764,24 +3059,30 @@ lcf_status launch_next(lcf_sampler* s, bool have_next, int lo, int hi, hipStream
     return LCF_OK;
 }
 
-// Likelihood of the proposals [lo, hi) of the half-step drawn last.
+// Log-posteriors of the shard's proposals from their partial sums (sharded runs: the all-gather sends these).
+static lcf_status launch_finalize(lcf_sampler* s, int lo, int hi, hipStream_t st) {
+    if (hi <= lo) return LCF_OK;
+    lcf_engine* e = s->e;
+    const int par = (int)((s->g_next - 1) & 1), bs = 128;
+    hipLaunchKernelGGL(k_finalize, dim3((hi - lo + bs - 1) / bs), dim3(bs), 0, st, e->dp, hi - lo,
+                       s->ds.part2[par] + (size_t)lo * (e->dp.n_parts + 1), s->lprior + lo, s->ds.newlp[par] + lo);
+    LCF_HIP(hipGetLastError());
+    return LCF_OK;
+}
+
+// Likelihood of the proposals [lo, hi) of the half-step drawn last; `finalize`: and their log-posteriors.
 lcf_status launch_eval(lcf_sampler* s, int lo, int hi, bool finalize, hipStream_t st) {
     lcf_engine* e = s->e;
     if (hi <= lo) return LCF_OK;
     double* part = s->ds.part2[(s->g_next - 1) & 1];
     launch_points<0>(e, lo, hi - lo, s->ds.Q[(s->g_next - 1) & 1], s->coef, s->lprior, nullptr, part, nullptr, st);
-    if (finalize) {
-        const int bs = 128;
-        hipLaunchKernelGGL(k_finalize, dim3((hi - lo + bs - 1) / bs), dim3(bs), 0, st, e->dp, hi - lo,
-                           part + (size_t)lo * (e->dp.n_parts + 1), s->lprior + lo, s->ds.newlp[(s->g_next - 1) & 1] + lo);
-    }
     LCF_HIP(hipGetLastError());
-    return LCF_OK;
+    return finalize ? launch_finalize(s, lo, hi, st) : LCF_OK;
 }
 
 constexpr size_t kLdsPerCU = 160 * 1024;
 
-size_t fused_lds_bytes(const lcf_engine* e) {
+static size_t fused_lds_bytes(const lcf_engine* e) {
     return e->lds_bytes + kFusedScratch * sizeof(double);
 }
 
@@ -3828,7 +3129,7 @@ lcf_status launch_fused(lcf_sampler* s, int lo, int hi, hipStream_t st) {
 }
 
 // ---- one workgroup per proposal (k_solo): single-GPU runs whose parts fit one workgroup -----------------------------
-size_t solo_lds_bytes(const lcf_engine* e) {
+static size_t solo_lds_bytes(const lcf_engine* e) {
     return kLdsHead * sizeof(double) + (size_t)e->dp.stage_d2 * sizeof(double2) +
            (kSoloScratch + 4) * sizeof(double);
 }
@@ -3847,7 +3148,7 @@ bool solo_eligible(const lcf_sampler* s) {
 // The model-specialised kernels (k_solo / k_pop <..., MODEL>) take engines of the shape the benchmarks have: a power-law
 // model (ShockCooling, ShockCooling2) without a fitted sigma, dense columns, interpolated band sums proved from their
 // first interval.  0: the generic kernel.
-int specialised_model(const DevProblem& dp) {
+static int specialised_model(const DevProblem& dp) {
     static const bool disabled = std::getenv("LCF_NO_SPECIALISED") != nullptr;
     if (disabled || !dp.use_therm || !dp.use_itab || dp.variant == 0 || !dp.em_dense || !dp.itab_uniform || dp.use_sigma)
         return 0;
@@ -3856,7 +3157,7 @@ int specialised_model(const DevProblem& dp) {
 
 // One half-step of a single-GPU run: ONE launch, one workgroup per proposal, accept test and commit included.
 // `board`: this rank's slots [lo, hi) only, rows from / to the row boards (lcf_sampler_run_rows).
-lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board = false, int lo = 0, int hi = 0) {
+lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board, int lo, int hi) {
     lcf_engine* e = s->e;
     const DevSampler& ds = s->ds;
     if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
@@ -3914,17 +3215,17 @@ constexpr int kRunSlots = 512;
 // ensemble: configs[2] on 8 GPUs, 256 proposals): 1024-thread workgroups, all four parts of a proposal side by side, as
 // k_solo uses for such launches -- resident, for the eight-parameter models (the instantiation that exists).
 // (LCF_WIDE_RUNS=0: launches that k_solo's 1024-thread workgroups would take keep a launch per half-step)
-bool wide_runs() {
+static bool wide_runs() {
     const char* env = std::getenv("LCF_WIDE_RUNS");
     return !(env && env[0] == '0');
 }
-bool run_wide(const lcf_sampler* s, int proposals) {
+static bool run_wide(const lcf_sampler* s, int proposals) {
     static const bool no_wide = std::getenv("LCF_NO_WIDE_SOLO") != nullptr;
     return !no_wide && s->e->dp.n_parts > 2 && proposals <= s->e->n_cus && has_dim(WideRuns{}, s->ds.n_dim);
 }
 // Launches of `width` proposals that take resident workgroups: up to `slots` proposals where a light curve has more
 // than two parts (the rank's share of a row-board run: up to two slots per workgroup, rows_resident_eligible).
-bool resident_size(const lcf_sampler* s, int width, int slots) {
+static bool resident_size(const lcf_sampler* s, int width, int slots) {
     if (s->e->dp.n_parts <= 2) return width <= 4 * kRunSlots;
     return (width > s->e->n_cus || (wide_runs() && run_wide(s, width))) && width <= slots;
 }
@@ -3936,8 +3237,8 @@ bool run_eligible(const lcf_sampler* s) {
 }
 
 struct RunBusy { hipEvent_t ev = nullptr; hipStream_t stream = nullptr; bool used = false; bool enqueuing = false; };
-RunBusy g_run_busy[64];
-std::mutex g_run_mutex;
+static RunBusy g_run_busy[64];
+static std::mutex g_run_mutex;
 
 // May a one-launch run go on stream `st` of device `dev` now?  Yes unless another stream's is being enqueued (between its
 // claim and its release: the device counts as busy from the claim on, not only once the release has recorded the event)
@@ -3967,17 +3268,10 @@ void run_release(int dev, hipStream_t st) {   // behind the last launch of the r
     b.used = hipEventRecord(b.ev, st) == hipSuccess;
     b.enqueuing = false;
 }
-struct RunClaim {   // releases on every path out of the enqueue
-    int dev;
-    hipStream_t st;
-    bool held;
-    void release() { if (held) run_release(dev, st); held = false; }
-    ~RunClaim() { release(); }
-};
 
 // Workgroups of a resident launch, `per_cu` of them per CU: all on the device at once, on the compute units the engine's
 // stream may use (a CU mask on the stream -- or on the process -- leaves fewer than the device has).
-int run_capacity(const lcf_engine* e, int per_cu) {
+static int run_capacity(const lcf_engine* e, int per_cu) {
     int cus = e->n_cus;
     uint32_t mask[16] = {0};
     if (hipExtStreamGetCUMask(e->stream, 16, mask) == hipSuccess) {
@@ -3995,7 +3289,7 @@ int run_capacity(const lcf_engine* e, int per_cu) {
 // sampler's first one-launch run is enqueued and again only when something in it has changed (a longer chain).  The
 // two sets of state buffers keep their places in it -- X / LP / nacc = the set the sampler was created with -- and the
 // launch's flags say which of them holds the run's start state.
-DevSampler run_struct(const lcf_sampler* s) {
+static DevSampler run_struct(const lcf_sampler* s) {
     DevSampler rs = s->ds;
     const bool flip = s->run_flip;
     rs.X = flip ? s->alt_X : s->ds.X;
@@ -4025,29 +3319,36 @@ lcf_status run_buffers(lcf_sampler* s) {
     return dalloc(&s->alt_nacc, nw, s->owned);
 }
 
-lcf_status run_image(lcf_sampler* s, hipStream_t st, const DevSampler** out, int* flags) {
-    const DevSampler rs = run_struct(s);
-    const bool flip = s->run_flip;
-    if (!s->d_run_image) {
-        LCF_HIP(hipMalloc((void**)&s->d_run_image, sizeof(DevSampler)));
-        s->owned.push_back(s->d_run_image);
-        s->run_image_valid = false;
+// An image of the sampler in device memory (lcf_sampler::Image): allocated when first asked for, and rewritten when `rs`,
+// what a launch is about to read there, is not what was written last.  `rs` null: allocated only.
+static lcf_status put_image(lcf_sampler* s, lcf_sampler::Image& im, const DevSampler* rs, hipStream_t st) {
+    if (!im.dev) {
+        LCF_HIP(hipMalloc((void**)&im.dev, sizeof(DevSampler)));
+        s->owned.push_back(im.dev);
+        im.valid = false;
     }
-    if (!s->run_image_valid || std::memcmp(&rs, &s->run_image_host, sizeof rs) != 0) {
+    if (rs && (!im.valid || std::memcmp(rs, &im.host, sizeof *rs) != 0)) {
         // (by a kernel, in stream order behind the launches that read the old image: k_put_image)
-        hipLaunchKernelGGL(k_put_image<DevSampler>, dim3(1), dim3(64), 0, st, s->d_run_image, rs);
+        hipLaunchKernelGGL(k_put_image<DevSampler>, dim3(1), dim3(64), 0, st, im.dev, *rs);
         LCF_HIP(hipGetLastError());
-        std::memcpy(&s->run_image_host, &rs, sizeof rs);
-        s->run_image_valid = true;
+        std::memcpy(&im.host, rs, sizeof *rs);
+        im.valid = true;
     }
-    *out = s->d_run_image;
-    *flags = (s->ds.store_chain ? kRunStoreChain : 0) | (flip ? kRunFlip : 0);
+    return LCF_OK;
+}
+
+// The image k_solo_run reads (run_struct), and the launch's flags.
+static lcf_status run_image(lcf_sampler* s, hipStream_t st, const DevSampler** out, int* flags) {
+    const DevSampler rs = run_struct(s);
+    if (lcf_status r = put_image(s, s->run_image, &rs, st)) return r;
+    *out = s->run_image.dev;
+    *flags = (s->ds.store_chain ? kRunStoreChain : 0) | (s->run_flip ? kRunFlip : 0);
     return LCF_OK;
 }
 
 // The same for a rank of a row-board run (k_solo_run<..., RANKS>): the rank's own board and its peers', no second set of
 // state buffers (state and chain are collected from the board), no snapshot words.
-lcf_status rows_image(lcf_sampler* s, hipStream_t st, const DevSampler** out) {
+static lcf_status rows_image(lcf_sampler* s, hipStream_t st, const DevSampler** out) {
     DevSampler rs = s->ds;
     rs.store_chain = rs.inline_finalize = rs.n_peers = 0;
     rs.X_out = nullptr;
@@ -4055,18 +3356,8 @@ lcf_status rows_image(lcf_sampler* s, hipStream_t st, const DevSampler** out) {
     rs.nacc_out = nullptr;
     rs.snap_out = nullptr;
     rs.snap_flags = nullptr;
-    if (!s->d_rows_image) {
-        LCF_HIP(hipMalloc((void**)&s->d_rows_image, sizeof(DevSampler)));
-        s->owned.push_back(s->d_rows_image);
-        s->rows_image_valid = false;
-    }
-    if (!s->rows_image_valid || std::memcmp(&rs, &s->rows_image_host, sizeof rs) != 0) {
-        hipLaunchKernelGGL(k_put_image<DevSampler>, dim3(1), dim3(64), 0, st, s->d_rows_image, rs);
-        LCF_HIP(hipGetLastError());
-        std::memcpy(&s->rows_image_host, &rs, sizeof rs);
-        s->rows_image_valid = true;
-    }
-    *out = s->d_rows_image;
+    if (lcf_status r = put_image(s, s->rows_image, &rs, st)) return r;
+    *out = s->rows_image.dev;
     return LCF_OK;
 }
 
@@ -4076,8 +3367,8 @@ lcf_status rows_image(lcf_sampler* s, hipStream_t st, const DevSampler** out) {
 // `dry`: nothing is launched -- the kernel the launch would take is resolved, its LDS attribute set and its capacity on this
 // device asked (what a process pays ONCE per kernel: lcf_sampler_board_connect does it ahead of the first run, so that no
 // rank's first launch makes such calls while another rank's resident workgroups already wait for it).
-lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, bool ranks = false, int lo = 0, int hi = 0,
-                      long long need_progress = 0, bool dry = false) {
+lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, bool ranks, int lo, int hi,
+                      long long need_progress, bool dry) {
     lcf_engine* e = s->e;
     const DevSampler* rs = nullptr;
     int run_flags = 0;
@@ -4143,17 +3434,6 @@ lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, b
     return LCF_OK;
 }
 
-// Log-posteriors of the shard's proposals from their partial sums (sharded runs: the all-gather sends these).
-lcf_status launch_finalize(lcf_sampler* s, int lo, int hi, hipStream_t st) {
-    if (hi <= lo) return LCF_OK;
-    lcf_engine* e = s->e;
-    const int par = (int)((s->g_next - 1) & 1), bs = 128;
-    hipLaunchKernelGGL(k_finalize, dim3((hi - lo + bs - 1) / bs), dim3(bs), 0, st, e->dp, hi - lo,
-                       s->ds.part2[par] + (size_t)lo * (e->dp.n_parts + 1), s->lprior + lo, s->ds.newlp[par] + lo);
-    LCF_HIP(hipGetLastError());
-    return LCF_OK;
-}
-
 // One half-step of a sharded run on this rank, up to the log-posteriors of its shard [lo, hi).
 lcf_status launch_half_step_sharded(lcf_sampler* s, int lo, int hi, hipStream_t st) {
     if (fused_eligible(s) && hi > lo) {
@@ -4171,431 +3451,9 @@ lcf_status launch_half_step_rows(lcf_sampler* s, int lo, int hi, hipStream_t st)
     return launch_eval(s, lo, hi, false, st);
 }
 
-lcf_status flush_pending(lcf_sampler* s, hipStream_t st) {
-    if (!s->pending) return LCF_OK;
-    return launch_next(s, false, 0, 0, st);
-}
-
-// Commit what is pending and copy the snapshot behind it, all on the engine's stream; enqueue only.
-lcf_status enqueue_snapshot(lcf_sampler* s) {
-    lcf_engine* e = s->e;
-    hipStream_t st = e->stream;
-    if (s->foreign_stream) {  // half-steps were driven on a caller's stream: order this stream behind them
-        LCF_HIP(hipDeviceSynchronize());
-        s->foreign_stream = false;
-    }
-    if (lcf_status r = flush_pending(s, st)) return r;
-    const DevSampler& ds = s->ds;
-    // one small kernel writes the snapshot straight into the pinned host buffer (four separate copies cost 4x the
-    // fixed price of a device-to-host transfer)
-    const long long words = (long long)(s->snap_bytes() / 8);
-    hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ds,
-                       reinterpret_cast<unsigned long long*>(s->snap));
-    LCF_HIP(hipGetLastError());
-    LCF_HIP(hipEventRecord(s->ev_snap, st));
-    s->snap_enqueued = true;
-    s->snap_valid = false;
-    return LCF_OK;
-}
-
-// The snapshot of the sampler's present state, complete in host memory on return.
-lcf_status settle(lcf_sampler* s) {
-    LCF_HIP(hipSetDevice(s->e->device));
-    if (s->snap_valid && !s->pending && !s->foreign_stream) return LCF_OK;
-    if (!s->snap_enqueued || s->pending || s->foreign_stream)
-        if (lcf_status r = enqueue_snapshot(s)) return r;
-    // Wait for the snapshot, not for the stream: what a run enqueues behind it (the draw records of a possible
-    // continuation, 30-40 us of kernels) is nobody's business here -- everything later on the stream is ordered behind
-    // it anyway.  A short run ends within a millisecond of this call: poll for that long before handing the wait to
-    // the driver.
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        while (hipEventQuery(s->ev_snap) == hipErrorNotReady &&
-               std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2)) {
-        }
-    }
-    LCF_HIP(hipEventSynchronize(s->ev_snap));
-    s->snap_enqueued = false;
-    s->snap_valid = true;
-    return LCF_OK;
-}
-
-// Whatever changes the state on the device makes the host's copy stale.
-void invalidate_snapshot(lcf_sampler* s) { s->snap_enqueued = s->snap_valid = false; }
-
-// What the settled snapshot of a run reports: its error word and the words of the workgroups of one-launch runs.
-int reported_error(const lcf_sampler* s) {
-    int err = 0;
-    std::memcpy(&err, s->snap, sizeof(int));
-    const unsigned int* flags = s->snap_flags();
-    for (int k = 0; k < 2 * kSnapFlags; ++k) err |= (int)flags[k];
-    return err;
-}
-
-// A resident launch whose workgroups were not all on the device (somebody else's resident kernel holds CUs) has given
-// up within the bound of its waits and written no state -- that goes into the other set of buffers, in the run's last
-// step.  Put the sampler back on the state its resident run started from and drop what the run reported; the board's
-// tail words and count of started workgroups start again from zero.  (The run's stream must have been waited for.)
-lcf_status rewind_resident_run(lcf_sampler* s) {
-    s->flip_state_sets();
-    int sticky = 0;
-    std::memcpy(&sticky, s->snap, sizeof(int));
-    sticky &= 1;                                   // (a NaN of an earlier run stays reported)
-    LCF_HIP(hipMemcpy(s->ds.err, &sticky, sizeof(int), hipMemcpyHostToDevice));
-    std::memcpy(s->snap, &sticky, sizeof(int));
-    std::memset(s->snap_flags(), 0, 2 * kSnapFlags * sizeof(unsigned int));
-    LCF_HIP(hipMemset(static_cast<unsigned char*>(s->run_board_mem) + s->run_board_bytes() - kBoardClear * sizeof(unsigned int), 0,
-                      kBoardClear * sizeof(unsigned int)));
-    s->run_arrivals = 0;
-    invalidate_snapshot(s);
-    return LCF_OK;
-}
-
-// Device memory for the chain of a run of n_steps steps (kept until a longer run needs more).
-lcf_status reserve_chain(lcf_sampler* s, int64_t n_steps) {
-    DevSampler& ds = s->ds;
-    if (n_steps <= s->chain_cap) return LCF_OK;
-    LCF_HIP(hipStreamSynchronize(s->e->stream));
-    if (ds.chain) hipFree(ds.chain);
-    if (ds.chain_lp) hipFree(ds.chain_lp);
-    ds.chain = nullptr;
-    ds.chain_lp = nullptr;
-    s->chain_cap = 0;
-    LCF_HIP(hipMalloc((void**)&ds.chain, (size_t)n_steps * ds.n_walkers * ds.n_dim * sizeof(double)));
-    LCF_HIP(hipMalloc((void**)&ds.chain_lp, (size_t)n_steps * ds.n_walkers * sizeof(double)));
-    s->chain_cap = n_steps;
-    return LCF_OK;
-}
-
-// Start a run of n_steps steps: settle what the previous run left pending, size the chain and the draw blocks, and
-// enqueue the generation of the first block.  Nothing here waits for the device unless a buffer has to grow.
-// `need_slots`: the draw records carry each walker's slot in the previous half-step (every path except k_solo).
-// `gen`: the stream the first block of draw records is generated on (default: the engine's own -- where a single
-// sampler's half-steps follow; a population's half-steps all run on ONE stream, and so do its samplers' records).
-// `defer`: the first block is NOT generated here (a population generates the blocks of all its samplers in one launch).
-lcf_status sampler_begin(lcf_sampler* s, int64_t first_step, int64_t n_steps, int32_t split_mode, const int32_t* perm,
-                         int32_t store_chain, bool need_slots, hipStream_t gen = nullptr, bool defer = false) {
-    if (!s || n_steps < 0 || first_step < 0) return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument");
-    if (split_mode < LCF_SPLIT_IDENTITY || split_mode > LCF_SPLIT_HOST)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad split_mode");
-    if (split_mode == LCF_SPLIT_HOST && !perm && n_steps > 0)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "LCF_SPLIT_HOST needs perm");
-    if (split_mode == LCF_SPLIT_RANDOM && s->ds.n_walkers > 16384)
-        return fail(LCF_ERR_UNSUPPORTED, "device-generated splits support at most 16384 walkers; pass perm");
-    if (split_mode != LCF_SPLIT_HOST) perm = nullptr;
-    if (!s->has_state) return fail(LCF_ERR_STATE, "lcf_sampler_set_state must be called first");
-    lcf_engine* e = s->e;
-    LCF_HIP(hipSetDevice(e->device));
-    if (s->foreign_stream) {  // the previous run was driven on a caller's stream: order everything behind it
-        LCF_HIP(hipDeviceSynchronize());
-        s->foreign_stream = false;
-    }
-    if (lcf_status st = flush_pending(s, e->stream)) return st;  // with the previous run's chain and draw records
-    DevSampler& ds = s->ds;
-    // leave a gap in the half-step numbering: no stale (last_g == g - 1) match across runs or set_state calls
-    s->g_next += 2;
-    s->g_run0 = s->g_next;
-    ds.store_chain = store_chain ? 1 : 0;
-    if (store_chain)
-        if (lcf_status st = reserve_chain(s, n_steps)) return st;
-    if (perm && n_steps > 0) {
-        // validate: every row must be a permutation of 0..n_walkers-1 (out-of-range ids would fault the GPU)
-        std::vector<char> seen(ds.n_walkers);
-        for (int64_t r = 0; r < n_steps; ++r) {
-            std::fill(seen.begin(), seen.end(), 0);
-            const int32_t* row = perm + (size_t)r * ds.n_walkers;
-            for (int i = 0; i < ds.n_walkers; ++i) {
-                if (row[i] < 0 || row[i] >= ds.n_walkers || seen[row[i]])
-                    return fail(LCF_ERR_INVALID_ARGUMENT, "perm rows must be permutations of the walker ids");
-                seen[row[i]] = 1;
-            }
-        }
-        LCF_HIP(hipStreamSynchronize(e->stream));
-        if (n_steps > s->perm_host_rows) {
-            if (s->d_perm_host) hipFree(s->d_perm_host);
-            s->d_perm_host = nullptr;
-            s->perm_host_rows = 0;
-            LCF_HIP(hipMalloc((void**)&s->d_perm_host, (size_t)n_steps * ds.n_walkers * sizeof(int)));
-            s->perm_host_rows = n_steps;
-        }
-        LCF_HIP(hipMemcpy(s->d_perm_host, perm, (size_t)n_steps * ds.n_walkers * sizeof(int), hipMemcpyHostToDevice));
-    }
-    invalidate_snapshot(s);
-    s->run_first = first_step;
-    s->run_steps = n_steps;
-    s->split_mode = split_mode;
-    s->need_slots = need_slots;
-    s->blk_generated = s->blk_current = -1;
-    if (n_steps == 0) return LCF_OK;
-    // Block geometry: about 2^18 draw records (12 MiB) per buffer however long the run; a short first block, so that
-    // the first half-step waits for a few steps' worth of records only.
-    int64_t cap = std::max<int64_t>(4, std::min<int64_t>(256, (int64_t)(1 << 18) / ds.n_walkers));
-    if (const char* env = std::getenv("LCF_DRAW_BLOCK")) cap = std::max<int64_t>(1, std::atoll(env));  // (tests: tiny blocks)
-    bool grown = false;
-    if (cap > s->blk_cap) {
-        grown = true;
-        LCF_HIP(hipStreamSynchronize(e->stream));
-        s->free_blocks();
-        for (int b = 0; b < 2; ++b) {
-            LCF_HIP(hipMalloc((void**)&s->d_perm[b], (size_t)cap * ds.n_walkers * sizeof(int)));
-            LCF_HIP(hipMalloc((void**)&s->d_draws[b], (size_t)cap * 2 * ds.n_half * sizeof(DrawRec)));
-            LCF_HIP(hipMalloc((void**)&s->d_slot[b], (size_t)(1 + 2 * cap) * ds.n_walkers * sizeof(int)));
-        }
-        s->blk_cap = cap;
-    }
-    s->blk_steps = s->blk_cap;
-    s->blk_first = std::min<int64_t>(s->blk_cap, LCF_FIRST_BLOCK);
-    if (s->spec_first == first_step && s->spec_mode == split_mode && s->spec_slots == need_slots && !grown && !defer &&
-        (gen == nullptr || gen == e->stream)) {   // (a block speculated on the engine's stream is not ordered with another)
-        s->spec_first = -1;  // the previous run left this run's first block behind (speculate_continuation)
-        s->blk_generated = 0;
-        return LCF_OK;
-    }
-    s->spec_first = -1;
-    if (defer) return LCF_OK;
-    return generate_block(&s, 1, 0, gen ? gen : e->stream);
-}
-
-
-}  // namespace
+}  // namespace lcf
 
 extern "C" {
-
-lcf_status lcf_sampler_create(lcf_engine* e, int32_t n_walkers, uint64_t seed, double a, lcf_sampler** out) {
-    if (!e || !out) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    if (n_walkers < 2) return fail(LCF_ERR_INVALID_ARGUMENT, "n_walkers must be >= 2");
-    if (!(a > 1.)) return fail(LCF_ERR_INVALID_ARGUMENT, "stretch scale a must be > 1");
-    LCF_HIP(hipSetDevice(e->device));
-    auto* s = new lcf_sampler();
-    s->e = e;
-    s->device = e->device;
-    DevSampler& ds = s->ds;
-    ds.n_walkers = n_walkers;
-    ds.n_half = (n_walkers + 1) / 2;  // slots per half-step: the larger colour of an odd ensemble
-    ds.n_dim = e->dp.n_dim;
-    ds.key0 = (uint32_t)(seed & 0xffffffffu);
-    ds.key1 = (uint32_t)(seed >> 32);
-    ds.a = a;
-    ds.wait_ticks = peer_wait_ticks();
-    ds.resident_ticks = resident_wait_ticks();
-    ds.ring = kRing;
-    const size_t nw = n_walkers, nh = ds.n_half, nd = ds.n_dim;
-    lcf_status st;
-#define AL(p, n) if ((st = dalloc(&p, n, s->owned)) != LCF_OK) { delete s; return st; }
-    AL(ds.X, nw * nd); AL(ds.LP, nw); AL(ds.nacc, nw); AL(ds.err, 1);
-    for (int b = 0; b < 2; ++b) {
-        AL(ds.Q[b], nh * nd); AL(ds.rec[b], nh); AL(ds.newlp[b], nh);
-    }
-    AL(s->coef, nh * kNCoef); AL(s->lprior, nh);
-    for (int b = 0; b < 2; ++b) AL(ds.part2[b], nh * (e->dp.n_parts + 1));
-#undef AL
-    LCF_HIP(hipMemset(ds.nacc, 0, nw * sizeof(long long)));
-    LCF_HIP(hipMemset(ds.err, 0, sizeof(int)));
-    LCF_HIP(hipEventCreate(&s->ev0));
-    LCF_HIP(hipEventCreate(&s->ev1));
-    LCF_HIP(hipEventCreateWithFlags(&s->ev_snap, hipEventDisableTiming));
-    LCF_HIP(hipHostMalloc((void**)&s->snap, s->snap_alloc(), hipHostMallocDefault));
-    std::memset(s->snap, 0, s->snap_alloc());
-    *out = s;
-    return LCF_OK;
-}
-
-void lcf_sampler_destroy(lcf_sampler* s) { delete s; }
-
-lcf_status lcf_sampler_reserve_chain(lcf_sampler* s, int64_t n_steps) {
-    if (!s || n_steps < 0) return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument");
-    LCF_HIP(hipSetDevice(s->e->device));
-    if (s->ds.store_chain && s->run_steps > 0 && n_steps > s->chain_cap)
-        return fail(LCF_ERR_STATE, "the stored chain of the last run must be read (lcf_sampler_get_chain) before its buffer grows");
-    return reserve_chain(s, n_steps);
-}
-
-lcf_status lcf_sampler_set_state(lcf_sampler* s, const double* coords) {
-    if (!s || !coords) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    lcf_engine* e = s->e;
-    LCF_HIP(hipSetDevice(e->device));
-    LCF_HIP(hipDeviceSynchronize());
-    s->pending = false;  // an uncommitted move of the old state is dropped with it
-    s->foreign_stream = false;
-    invalidate_snapshot(s);
-    const DevSampler& ds = s->ds;
-    if (lcf_status st = e->reserve(ds.n_walkers)) return st;
-    LCF_HIP(hipMemcpyAsync(ds.X, coords, (size_t)ds.n_walkers * ds.n_dim * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    if (lcf_status st = logprob_dev(e, ds.n_walkers, ds.X, ds.LP, e->stream, 1)) return st;
-    LCF_HIP(hipMemsetAsync(ds.nacc, 0, (size_t)ds.n_walkers * sizeof(long long), e->stream));
-    LCF_HIP(hipMemsetAsync(ds.err, 0, sizeof(int), e->stream));
-    std::memset(s->snap_flags(), 0, 2 * kSnapFlags * sizeof(unsigned int));   // (after the device synchronisation above)
-    if (s->run_board_mem)   // (the abort word and its diagnosis behind the rows of the one-launch runs' board)
-    {
-        LCF_HIP(hipMemsetAsync(static_cast<unsigned char*>(s->run_board_mem) + s->run_board_bytes() - kBoardClear * sizeof(unsigned int), 0,
-                               kBoardClear * sizeof(unsigned int), e->stream));
-        s->run_arrivals = 0;
-    }
-    LCF_HIP(hipStreamSynchronize(e->stream));
-    s->has_state = true;
-    return LCF_OK;
-}
-
-lcf_status lcf_sampler_get_state(lcf_sampler* s, double* coords, double* log_prob) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = settle(s)) return st;
-    if (coords) std::memcpy(coords, s->snap + s->snap_x(), s->snap_lp() - s->snap_x());
-    if (log_prob) std::memcpy(log_prob, s->snap + s->snap_lp(), s->snap_acc() - s->snap_lp());
-    return LCF_OK;
-}
-
-lcf_status lcf_sampler_begin(lcf_sampler* s, int64_t first_step, int64_t n_steps, int32_t split_mode,
-                             const int32_t* perm, int32_t store_chain) {
-    if (lcf_status st = sampler_begin(s, first_step, n_steps, split_mode, perm, store_chain, true)) return st;
-    // the half-steps of the phase API may be enqueued on a caller's stream, which is not ordered with the engine's own:
-    // the first block of draw records (generated on the engine's stream) must be complete before this returns
-    LCF_HIP(hipStreamSynchronize(s->e->stream));
-    return LCF_OK;
-}
-
-// ---- phase-by-phase API (multi-GPU): propose -> evaluate(shard) -> [all-gather newlp] -> accept -------------------
-lcf_status lcf_sampler_propose(lcf_sampler* s, int64_t step, int32_t half, void* stream) {
-    if (!s || half < 0 || half > 1 || step < s->run_first || step >= s->run_first + s->run_steps)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad step/half");
-    const long long g = s->g_run0 + 2 * (step - s->run_first) + half;
-    if (g != s->g_next) return fail(LCF_ERR_STATE, "half-steps must be proposed in order, each exactly once");
-    s->ds.inline_finalize = 0;  // accept tests read the gathered newlp
-    // the shard is not known yet: every slot gets its coefficients (lcf_sampler_half_step knows it and is cheaper)
-    return launch_next(s, true, 0, s->ds.n_half, stream ? (hipStream_t)stream : s->e->stream);
-}
-// propose + evaluate in one call: the shard is known, so the thermal states of [lo, hi) are computed by the same
-// launch that draws the proposals (3 launches per half-step and rank: k_step, k_points, k_finalize).
-lcf_status lcf_sampler_half_step(lcf_sampler* s, int64_t step, int32_t half, int32_t lo, int32_t hi, void* stream) {
-    if (!s || half < 0 || half > 1 || step < s->run_first || step >= s->run_first + s->run_steps)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad step/half");
-    if (lo < 0 || hi < lo || hi > s->ds.n_half) return fail(LCF_ERR_INVALID_ARGUMENT, "bad shard range");
-    const long long g = s->g_run0 + 2 * (step - s->run_first) + half;
-    if (g != s->g_next) return fail(LCF_ERR_STATE, "half-steps must be proposed in order, each exactly once");
-    hipStream_t st = stream ? (hipStream_t)stream : s->e->stream;
-    s->ds.inline_finalize = 0;
-    return launch_half_step_sharded(s, lo, hi, st);
-}
-
-lcf_status lcf_sampler_evaluate(lcf_sampler* s, int32_t lo, int32_t hi, void* stream) {
-    if (!s || lo < 0 || hi < lo || hi > s->ds.n_half) return fail(LCF_ERR_INVALID_ARGUMENT, "bad shard range");
-    if (!s->pending) return fail(LCF_ERR_STATE, "lcf_sampler_propose must precede lcf_sampler_evaluate");
-    return launch_eval(s, lo, hi, true, stream ? (hipStream_t)stream : s->e->stream);
-}
-lcf_status lcf_sampler_accept(lcf_sampler* s, int64_t step, int32_t half, void* stream) {
-    if (!s || half < 0 || half > 1 || step < s->run_first || step >= s->run_first + s->run_steps)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad step/half");
-    // The accept/reject of a half-step is applied by the kernel that draws the next one (it needs the gathered
-    // newlp, which is complete once this call is reached); only the run's last half-step is committed here.
-    if (step == s->run_first + s->run_steps - 1 && half == 1)
-        return flush_pending(s, stream ? (hipStream_t)stream : s->e->stream);
-    return LCF_OK;
-}
-void* lcf_sampler_newlp_ptr(lcf_sampler* s) { return s ? s->ds.newlp[(s->g_next - 1) & 1] : nullptr; }
-lcf_status lcf_sampler_set_half_step_kernel(lcf_sampler* s, int32_t choice, int32_t* used) {
-    if (!s || choice < LCF_HALF_STEP_AUTO || choice > LCF_HALF_STEP_SOLO)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad half-step kernel choice");
-    s->half_step_kernel = choice;
-    if (used) *used = run_eligible(s) ? 3 : solo_eligible(s) ? 2 : fused_eligible(s) ? 1 : 0;
-    return LCF_OK;
-}
-
-int32_t lcf_sampler_last_run_kernel(const lcf_sampler* s) { return s ? s->last_kernel : -1; }
-
-int64_t lcf_sampler_last_run_launches(const lcf_sampler* s) { return s ? s->last_launches : 0; }
-
-int32_t lcf_sampler_one_launch(const lcf_sampler* s) { return s && (solo_eligible(s) || fused_eligible(s)) ? 1 : 0; }
-
-lcf_status lcf_sampler_half_step_rows(lcf_sampler* s, int64_t step, int32_t half, int32_t lo, int32_t hi,
-                                      void* stream) {
-    if (!s || half < 0 || half > 1 || step < s->run_first || step >= s->run_first + s->run_steps)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad step/half");
-    if (lo < 0 || hi < lo || hi > s->ds.n_half) return fail(LCF_ERR_INVALID_ARGUMENT, "bad shard range");
-    const long long g = s->g_run0 + 2 * (step - s->run_first) + half;
-    if (g != s->g_next) return fail(LCF_ERR_STATE, "half-steps must be proposed in order, each exactly once");
-    hipStream_t st = stream ? (hipStream_t)stream : s->e->stream;
-    s->ds.inline_finalize = 1;  // accept tests add up the gathered rows
-    return launch_half_step_rows(s, lo, hi, st);
-}
-
-void* lcf_sampler_rows_ptr(lcf_sampler* s, int32_t* row_doubles) {
-    if (!s) return nullptr;
-    if (row_doubles) *row_doubles = s->e->dp.n_parts + 1;
-    return s->ds.part2[(s->g_next - 1) & 1];
-}
-
-lcf_status lcf_sampler_check(lcf_sampler* s) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = settle(s)) return st;
-    const int err = reported_error(s);
-    if (err & 2) {
-        // (an aborted multi-rank run leaves the ranks with different states -- a rank has committed its own walkers of
-        // the half-step the others gave up on: the ensemble must be set again, on every rank, before the next run)
-        const double sec = (double)s->ds.wait_ticks / 1e8;
-        unsigned int w[kBoardClear] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const bool run = s->last_kernel == LCF_KERNEL_RUN && s->run_board_mem && !s->last_rows;
-        if (run)
-            hipMemcpy(w, reinterpret_cast<unsigned char*>(s->run_board_mem) + s->run_board_bytes() - kBoardClear * sizeof(unsigned int),
-                      sizeof w, hipMemcpyDeviceToHost);
-        else if (s->board_mem)
-            hipMemcpy(w, reinterpret_cast<unsigned char*>(s->board_mem) + s->board_bytes() - kBoardClear * sizeof(unsigned int), sizeof w,
-                      hipMemcpyDeviceToHost);
-        if (run && s->replay_steps >= 0 && s->replay_split != LCF_SPLIT_HOST) {
-            // The launch gave up (rewind_resident_run): the same steps with a launch per half-step, as later runs.
-            LCF_HIP(hipStreamSynchronize(s->e->stream));
-            if (lcf_status r = rewind_resident_run(s)) return r;
-            static bool told = false;
-            if (!told)
-                std::fprintf(stderr, "liblcf_hip: a one-launch run waited %.2f s for version %u of walker %u: its workgroups were "
-                             "not all resident (another resident kernel on this GPU?); the steps are repeated with a launch per "
-                             "half-step, as are this sampler's later runs (LCF_NO_RUN_KERNEL=1 avoids the wait)\n",
-                             w[1] == 3 ? (double)s->ds.resident_ticks / 1e8 : sec, w[2], w[3]);
-            if (!told && std::getenv("LCF_TRACE_RUN"))
-                std::fprintf(stderr, "liblcf_hip: (what %u, column %u, workgroups started %u; the entry held {%08x tag %u | %08x tag %u}; host: "
-                             "%d walkers, board %08x)\n", w[1], w[4], w[5], w[6], w[7], w[8], w[9], s->ds.n_walkers,
-                             (unsigned int)(unsigned long long)s->run_board_mem);
-            told = true;
-            s->run_off = true;
-            s->spec_first = -1;
-            const int64_t n = s->replay_steps;
-            s->replay_steps = -1;
-            if (lcf_status st = lcf_sampler_run_async(s, s->replay_first, n, s->replay_split, nullptr, s->replay_store)) return st;
-            return lcf_sampler_check(s);
-        }
-        if (run) {
-            char msg[260];
-            std::snprintf(msg, sizeof msg, "one-launch run: version %u of walker %u (column %u) was not posted within %.1f s: "
-                          "the launch's workgroups were not all resident (another process's persistent kernel on this "
-                          "GPU?); set the state again and run with LCF_NO_RUN_KERNEL=1", w[2], w[3], w[4], sec);
-            return fail(LCF_ERR_STATE, msg);
-        }
-        if (w[0]) {
-            char msg[300];
-            if (w[1] == 1)
-                std::snprintf(msg, sizeof msg, "row-board run: version %u of walker %u (column %u) was not posted within "
-                              "%.1f s: a rank is missing or behind (set_state is required on all ranks before the next run)",
-                              w[2], w[3], w[4], sec);
-            else if (w[1] == 3)
-                std::snprintf(msg, sizeof msg, "row-board run: version %u of walker %u did not arrive within %.2f s and only "
-                              "%u workgroups of this rank's resident launch had started: another resident kernel holds this "
-                              "GPU (set_state is required on all ranks before the next run)", w[2], w[3],
-                              (double)s->ds.resident_ticks / 1e8, w[4]);
-            else if (s->last_kernel == LCF_KERNEL_RUN)
-                std::snprintf(msg, sizeof msg, "row-board run: the launch from half-step %u waited %.1f s for rank %u to "
-                              "reach half-step %u (set_state is required on all ranks before the next run)", w[2], sec, w[3], w[4]);
-            else
-                std::snprintf(msg, sizeof msg, "row-board run: half-step %u waited %.1f s for rank %u to finish half-step "
-                              "%u (set_state is required on all ranks before the next run)", w[2], sec, w[3], w[2] - 2);
-            return fail(LCF_ERR_STATE, msg);
-        }
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "a peer's rows did not arrive within %.1f s (peer-mailbox run; set_state is required "
-                      "on all ranks before the next run)", sec);
-        return fail(LCF_ERR_STATE, msg);
-    }
-    if (err) return fail(LCF_ERR_NAN_LOGPROB, "Probability function returned NaN");
-    return LCF_OK;
-}
 
 // ---- RCCL, bound at run time (no link-time dependency; the library PyTorch ships is reused when torch is loaded) ----
 namespace {
@@ -4743,6 +3601,41 @@ lcf_status lcf_sampler_run_sharded(lcf_sampler* s, lcf_comm* c, int64_t first_st
 
 // ---- peer mailboxes: a sharded run without a collective ---------------------------------------------------------------
 namespace {
+// What the mailboxes and the row boards have in common.  A rank's block of polled memory for the other ranks: its IPC
+// handle (`out`) and, for ranks emulated inside one process, its address (`local_ptr`).
+lcf_status export_block(void* block, lcf_ipc_handle* out, void** local_ptr) {
+    if (out) {
+        static_assert(sizeof(hipIpcMemHandle_t) <= sizeof(lcf_ipc_handle), "IPC handle size");
+        hipIpcMemHandle_t h;
+        LCF_HIP(hipIpcGetMemHandle(&h, block));
+        std::memset(out, 0, sizeof(*out));
+        std::memcpy(out, &h, sizeof(h));
+    }
+    if (local_ptr) *local_ptr = block;
+    return LCF_OK;
+}
+// Every rank's block as this rank addresses it, into peers[0, n_ranks): its own (`mine`), plain device pointers
+// (`local_ptrs`), or the handles opened through IPC and remembered in `opened` (closed with the sampler).
+lcf_status map_blocks(void* mine, int n_ranks, int rank, const lcf_ipc_handle* handles, void* const* local_ptrs,
+                      std::vector<void*>& opened, unsigned long long** peers, const char* what_null) {
+    for (int r = 0; r < n_ranks; ++r) {
+        void* p = nullptr;
+        if (r == rank) {
+            p = mine;
+        } else if (local_ptrs) {  // ranks emulated inside one process: plain device pointers
+            p = local_ptrs[r];
+        } else {
+            hipIpcMemHandle_t h;
+            std::memcpy(&h, &handles[r], sizeof(h));
+            LCF_HIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
+            opened.push_back(p);
+        }
+        if (!p) return fail(LCF_ERR_INVALID_ARGUMENT, what_null);
+        peers[r] = static_cast<unsigned long long*>(p);
+    }
+    return LCF_OK;
+}
+
 size_t mailbox_bytes(const lcf_sampler* s) {
     return (size_t)4 * s->ds.n_half * (s->e->dp.n_parts + 1) * 2 * sizeof(unsigned long long);
 }
@@ -4759,15 +3652,7 @@ lcf_status mailbox_alloc(lcf_sampler* s) {
 lcf_status lcf_sampler_mailbox_export(lcf_sampler* s, lcf_ipc_handle* out, void** local_ptr) {
     if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = mailbox_alloc(s)) return st;
-    if (out) {
-        static_assert(sizeof(hipIpcMemHandle_t) <= sizeof(lcf_ipc_handle), "IPC handle size");
-        hipIpcMemHandle_t h;
-        LCF_HIP(hipIpcGetMemHandle(&h, s->mailbox));
-        std::memset(out, 0, sizeof(*out));
-        std::memcpy(out, &h, sizeof(h));
-    }
-    if (local_ptr) *local_ptr = s->mailbox;
-    return LCF_OK;
+    return export_block(s->mailbox, out, local_ptr);
 }
 
 lcf_status lcf_sampler_mailbox_connect(lcf_sampler* s, int32_t n_ranks, int32_t rank, const lcf_ipc_handle* handles,
@@ -4779,21 +3664,9 @@ lcf_status lcf_sampler_mailbox_connect(lcf_sampler* s, int32_t n_ranks, int32_t 
     if (!fused_eligible(s)) return fail(LCF_ERR_UNSUPPORTED, "peer-mailbox runs need the one-launch half-step (k_fused)");
     if (lcf_status st = mailbox_alloc(s)) return st;
     LCF_HIP(hipSetDevice(s->e->device));
-    for (int r = 0; r < n_ranks; ++r) {
-        void* p = nullptr;
-        if (r == rank) {
-            p = s->mailbox;
-        } else if (local_ptrs) {  // ranks emulated inside one process: plain device pointers
-            p = local_ptrs[r];
-        } else {
-            hipIpcMemHandle_t h;
-            std::memcpy(&h, &handles[r], sizeof(h));
-            LCF_HIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-            s->opened.push_back(p);
-        }
-        if (!p) return fail(LCF_ERR_INVALID_ARGUMENT, "null peer mailbox");
-        s->ds.peer_mbox[r] = static_cast<unsigned long long*>(p);
-    }
+    if (lcf_status st = map_blocks(s->mailbox, n_ranks, rank, handles, local_ptrs, s->opened, s->ds.peer_mbox,
+                                   "null peer mailbox"))
+        return st;
     s->ds.mbox = s->mailbox;
     s->peer_ranks = n_ranks;
     s->peer_rank = rank;
@@ -4861,14 +3734,7 @@ extern "C" {
 lcf_status lcf_sampler_board_export(lcf_sampler* s, lcf_ipc_handle* out, void** local_ptr) {
     if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = board_alloc(s)) return st;
-    if (out) {
-        hipIpcMemHandle_t h;
-        LCF_HIP(hipIpcGetMemHandle(&h, s->board_mem));
-        std::memset(out, 0, sizeof(*out));
-        std::memcpy(out, &h, sizeof(h));
-    }
-    if (local_ptr) *local_ptr = s->board_mem;
-    return LCF_OK;
+    return export_block(s->board_mem, out, local_ptr);
 }
 
 lcf_status lcf_sampler_board_connect(lcf_sampler* s, int32_t n_ranks, int32_t rank, const lcf_ipc_handle* handles,
@@ -4881,31 +3747,15 @@ lcf_status lcf_sampler_board_connect(lcf_sampler* s, int32_t n_ranks, int32_t ra
         return fail(LCF_ERR_UNSUPPORTED, "row-board runs need the one-workgroup-per-proposal half-step (k_solo)");
     if (lcf_status st = board_alloc(s)) return st;
     LCF_HIP(hipSetDevice(s->e->device));
-    for (int r = 0; r < n_ranks; ++r) {
-        void* p = nullptr;
-        if (r == rank) {
-            p = s->board_mem;
-        } else if (local_ptrs) {  // ranks emulated inside one process: plain device pointers
-            p = local_ptrs[r];
-        } else {
-            hipIpcMemHandle_t h;
-            std::memcpy(&h, &handles[r], sizeof(h));
-            LCF_HIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-            s->board_opened.push_back(p);
-        }
-        if (!p) return fail(LCF_ERR_INVALID_ARGUMENT, "null peer board");
-        s->ds.peer_board[r] = static_cast<unsigned long long*>(p);
-    }
+    if (lcf_status st = map_blocks(s->board_mem, n_ranks, rank, handles, local_ptrs, s->board_opened, s->ds.peer_board,
+                                   "null peer board"))
+        return st;
     s->ds.n_board_ranks = n_ranks;
     s->ds.board_rank = rank;
     // (the kernel a resident run of this rank will take, resolved now: see launch_run's `dry`; and the image of the
     // sampler it reads, allocated now: an allocation made by one rank of a process while another rank's resident
     // workgroups already wait for it can hold its launch back for seconds)
-    if (!s->d_rows_image) {
-        LCF_HIP(hipMalloc((void**)&s->d_rows_image, sizeof(DevSampler)));
-        s->owned.push_back(s->d_rows_image);
-        s->rows_image_valid = false;
-    }
+    if (lcf_status st = put_image(s, s->rows_image, nullptr, nullptr)) return st;
     const int width = s->ds.n_half / n_ranks;
     if (rows_resident_eligible(s, width))
         if (lcf_status st = launch_run(s, 0, 0, s->e->stream, true, rank * width, rank * width + width, 0, true)) return st;
@@ -5000,96 +3850,6 @@ lcf_status lcf_sampler_run_rows(lcf_sampler* s, int64_t first_step, int64_t n_st
                                 const int32_t* perm, int32_t store_chain) {
     if (lcf_status st = lcf_sampler_run_rows_async(s, first_step, n_steps, split_mode, perm, store_chain)) return st;
     return lcf_sampler_wait(s);
-}
-
-// Enqueue a whole run on the engine's stream and return: several samplers (one engine each = one transient of a
-// population) then execute concurrently on the device.  lcf_sampler_wait() completes it.
-lcf_status lcf_sampler_run_async(lcf_sampler* s, int64_t first_step, int64_t n_steps, int32_t split_mode,
-                                 const int32_t* perm, int32_t store_chain) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    const bool one_launch = run_eligible(s) && n_steps > 0 && run_claim(s->e->device, s->e->stream);
-    RunClaim claim{s->e->device, s->e->stream, one_launch};
-    s->last_rows = false;
-    if (lcf_status st = sampler_begin(s, first_step, n_steps, split_mode, perm, store_chain,
-                                      !solo_eligible(s) || run_eligible(s))) return st;
-    hipStream_t st = s->e->stream;
-    s->ds.inline_finalize = 1;  // single GPU: no separate finalize / accept launches
-    LCF_HIP(hipEventRecord(s->ev0, st));
-    if (one_launch) {   // the workgroups stay for a block of half-steps and hand each other rows (k_solo_run)
-        if (lcf_status r = run_buffers(s)) return r;
-        s->replay_first = first_step;
-        s->replay_steps = n_steps;
-        s->replay_split = split_mode;
-        s->replay_store = store_chain;
-        s->last_kernel = LCF_KERNEL_RUN;
-        s->last_launches = 0;
-        for (long long rel = 0; rel < 2 * n_steps;) {   // (the first launch posts the start state on the board itself)
-            ++s->last_launches;
-            if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
-            const int n = s->block_span(rel, kRunSpanSolo);
-            if (lcf_status r = launch_run(s, rel, n, st)) return r;
-            if (lcf_status r = leave_half_step(&s, 1, st)) return r;
-            rel += n;
-        }
-        s->g_next += 2 * n_steps;
-        s->flip_state_sets();                  // the state behind this run is in the other set now
-        LCF_HIP(hipEventRecord(s->ev1, st));
-        claim.release();
-        // (the last step wrote the snapshot with the state: no snapshot kernel; the caller waits for this event)
-        LCF_HIP(hipEventRecord(s->ev_snap, st));
-        s->snap_enqueued = true;
-        s->snap_valid = false;
-        return speculate_continuation(s, st);
-    }
-    // per half-step: ONE launch (k_fused) when everything a workgroup needs fits in LDS, else
-    // [commit previous + draw + thermal states] -> [per-point likelihood]; one trailing commit
-    const bool fused = fused_eligible(s);
-    s->last_kernel = solo_eligible(s) ? LCF_KERNEL_SOLO : fused ? LCF_KERNEL_FUSED : LCF_KERNEL_PHASES;
-    s->last_launches = 2 * n_steps;
-    if (solo_eligible(s)) {  // one workgroup per proposal, nothing pending between launches
-        for (int64_t k = 0; k < 2 * n_steps; ++k)
-            if (lcf_status r = launch_solo(s, k, st)) return r;
-        s->g_next += 2 * n_steps;
-        LCF_HIP(hipEventRecord(s->ev1, st));
-        if (lcf_status r = enqueue_snapshot(s)) return r;
-        return speculate_continuation(s, st);
-    }
-    for (int64_t k = 0; k < 2 * n_steps; ++k) {
-        if (fused) {
-            if (lcf_status r = launch_fused(s, 0, s->ds.n_half, st)) return r;
-            continue;
-        }
-        if (lcf_status r = launch_next(s, true, 0, s->ds.n_half, st)) return r;
-        if (lcf_status r = launch_eval(s, 0, s->ds.n_half, false, st)) return r;
-    }
-    if (lcf_status r = flush_pending(s, st)) return r;
-    LCF_HIP(hipEventRecord(s->ev1, st));
-    if (lcf_status r = enqueue_snapshot(s)) return r;
-    return speculate_continuation(s, st);
-}
-
-lcf_status lcf_sampler_wait(lcf_sampler* s) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = lcf_sampler_check(s)) return st;  // (waits for the run and its snapshot)
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess) s->last_ms = ms;
-    return LCF_OK;
-}
-
-lcf_status lcf_sampler_run(lcf_sampler* s, int64_t first_step, int64_t n_steps, int32_t split_mode,
-                           const int32_t* perm, int32_t store_chain) {
-    static const bool trace = std::getenv("LCF_TRACE_RUN") != nullptr;   // (diagnostic: host time of the two halves)
-    const auto t0 = std::chrono::steady_clock::now();
-    if (lcf_status st = lcf_sampler_run_async(s, first_step, n_steps, split_mode, perm, store_chain)) return st;
-    const auto t1 = std::chrono::steady_clock::now();
-    const lcf_status r = lcf_sampler_wait(s);
-    if (trace) {
-        const auto t2 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "lcf_sampler_run: %lld steps enqueued in %.1f us, waited %.1f us, device %.1f us\n",
-                     (long long)n_steps, std::chrono::duration<double, std::micro>(t1 - t0).count(),
-                     std::chrono::duration<double, std::micro>(t2 - t1).count(), 1e3 * s->last_ms);
-    }
-    return r;
 }
 
 }  // extern "C"
@@ -5363,12 +4123,8 @@ lcf_status population_run(lcf_sampler** ss, int n, int64_t first_step, int64_t n
     LCF_HIP(hipEventRecord(s0->ev1, st));
     // every transient's snapshot (error word, state, counts) behind the run, on the same stream: ONE wait below serves
     // the 32 state / count / check calls that follow (each of them used to synchronise and launch on its own)
-    for (int t = 0; t < n; ++t) {
-        const long long words = (long long)(ss[t]->snap_bytes() / 8);
-        hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ss[t]->ds,
-                           reinterpret_cast<unsigned long long*>(ss[t]->snap));
-        LCF_HIP(hipGetLastError());
-    }
+    for (int t = 0; t < n; ++t)
+        if (lcf_status r = launch_snapshot(ss[t], st)) return r;
     LCF_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s0->ev0, s0->ev1) == hipSuccess && elapsed_ms) *elapsed_ms = ms;
@@ -5424,40 +4180,6 @@ lcf_status lcf_population_run(lcf_sampler** ss, int32_t n, int64_t first_step, i
     if (r == LCF_OK && repeat)
         r = population_run(ss, n, first_step, n_steps, split_mode, store_chain, elapsed_ms, false, &repeat);
     return r;
-}
-
-lcf_status lcf_sampler_get_chain(lcf_sampler* s, double* chain, double* log_prob) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (!s->ds.store_chain || s->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
-    if (lcf_status st = settle(s)) return st;  // (the trailing commit writes the last chain row)
-    const DevSampler& ds = s->ds;
-    if (chain)
-        LCF_HIP(hipMemcpy(chain, ds.chain, (size_t)s->run_steps * ds.n_walkers * ds.n_dim * sizeof(double), hipMemcpyDeviceToHost));
-    if (log_prob)
-        LCF_HIP(hipMemcpy(log_prob, ds.chain_lp, (size_t)s->run_steps * ds.n_walkers * sizeof(double), hipMemcpyDeviceToHost));
-    return LCF_OK;
-}
-
-lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double c,
-                                      double* tau, int64_t* window) {
-    if (!s || n < 1 || !tau || !window) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
-    if (!std::isfinite(c)) return fail(LCF_ERR_INVALID_ARGUMENT, "c must be finite");
-    for (int32_t i = 0; i < n; ++i) {
-        if (!s[i]) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
-        if (!s[i]->ds.store_chain || s[i]->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
-        if (discard >= s[i]->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
-        if (s[i]->e->device != s[0]->e->device) return fail(LCF_ERR_UNSUPPORTED, "the samplers are on different devices");
-    }
-    std::vector<AutocorrSeries> series(n);
-    for (int32_t i = 0; i < n; ++i) {
-        if (lcf_status st = settle(s[i])) return st;  // (the trailing commit writes the last chain row)
-        const DevSampler& ds = s[i]->ds;
-        const int64_t row = (int64_t)ds.n_walkers * ds.n_dim;
-        series[i] = AutocorrSeries{ds.chain + discard * row, (s[i]->run_steps - discard + thin - 1) / thin, thin * row,
-                                   ds.n_walkers, ds.n_dim};
-    }
-    return autocorr_run(s[0]->e->device, series.data(), n, c, tau, window);
 }
 
 // What both predictive entry points check before the device is touched.
@@ -5528,33 +4250,8 @@ lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64
     return predict_impl(grid, in, component, q, n_q, workspace_bytes, out, n_valid);
 }
 
-lcf_status lcf_sampler_get_naccepted(lcf_sampler* s, int64_t* n_accepted) {
-    if (!s || !n_accepted) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = settle(s)) return st;
-    std::memcpy(n_accepted, s->snap + s->snap_acc(), s->snap_bytes() - s->snap_acc());
-    return LCF_OK;
-}
-
-lcf_status lcf_sampler_get_snapshot(lcf_sampler* s, double* coords, double* log_prob, int64_t* n_accepted) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = settle(s)) return st;
-    if (coords) std::memcpy(coords, s->snap + s->snap_x(), s->snap_lp() - s->snap_x());
-    if (log_prob) std::memcpy(log_prob, s->snap + s->snap_lp(), s->snap_acc() - s->snap_lp());
-    if (n_accepted) std::memcpy(n_accepted, s->snap + s->snap_acc(), s->snap_bytes() - s->snap_acc());
-    return LCF_OK;
-}
-
-double lcf_sampler_last_run_ms(const lcf_sampler* s) { return s ? s->last_ms : 0.; }
-
 }  // extern "C"
 
-// (diagnostic, not in lcf.h) a copy of the board of the sampler's one-launch runs: rows, then the tail words
-extern "C" long long lcf_debug_read_run_board(lcf_sampler* s, void* out, long long max_bytes) {
-    if (!s || !s->run_board_mem) return -1;
-    const long long n = std::min<long long>(max_bytes, (long long)s->run_board_bytes());
-    if (hipMemcpy(out, s->run_board_mem, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return -2;
-    return n;
-}
 #ifdef LCF_PROGRESS
 extern "C" int lcf_debug_read_progress(unsigned int* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_progress), sizeof(unsigned int) * 64 * 16);

@@ -292,6 +292,8 @@ def test_hot_kernels_neither_spill_nor_lose_occupancy():
     blocks = {}
     for m in re.finditer(r'Function Name: (\S+)(.*?)(?=Function Name:|\Z)', text, re.S):
         fields = dict(re.findall(r'remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)', m.group(2)))
+        # (the report is the objects' reports one after the other: a kernel must be compiled into one of them only)
+        assert m.group(1) not in blocks, f'{m.group(1)} is compiled into two translation units'
         blocks[m.group(1)] = fields
     # k_solo<ND = 4..9, fast band sum, epoch-major likelihood, two / four parts, single-GPU and row-board form, generic
     # model> + its model-specialised instantiations (ShockCooling: ND 5, ShockCooling2: ND 4 -- the benchmark kernels),
