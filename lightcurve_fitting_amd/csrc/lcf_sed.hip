@@ -8,8 +8,10 @@
 //                logarithm per candidate, and per observation four 16-byte LDS reads, a degree-7 Horner and one table
 //                exponential instead of the filter's 11-89 Planck samples.  Workgroups of 256 walk (epoch, tile) items
 //                with a grid stride, so the 2 + 4 n_filters KiB they stage are paid once per workgroup, not per tile.
-//                A candidate outside the range the interpolants are proved for (T < 2 kK, > 256 kK) is appended to a
-//                list and finished by k_sed_rest over the sample tables: a few cold lanes do not stall their waves.
+//                A candidate outside the range the interpolants are proved for (below the largest t_min of its epoch's
+//                filters or at and above the table's upper end: 0.94 and 256 kK (1 + z) for the shipped tables that
+//                SpectrumLikelihood extends by 10 intervals) is appended to a list and finished by k_sed_rest over
+//                the sample tables: a few cold lanes do not stall their waves.
 //   precision 0: float64 over the sample tables (same band sum as the light-curve engine's levels 1 / 2)
 //   precision 1: float32 over the sample tables (v_exp_f32 / v_rcp_f32, accumulate in f32) -- BASELINE configs[3] as
 //                specified; precision 2 is both faster and exact to 1e-12, so it is what the bench line reports
@@ -429,8 +431,9 @@ lcf_status lcf_sed_create(int32_t n_filters, const int32_t* tab_off, const doubl
     auto* s = new lcf_sed();
     s->device = device;
     s->have_ctab = have_ctab;
-    // the interpolants fit the fast kernel's LDS up to 19 filters (2 + 4 KiB each of 160); beyond that precision 2 is
-    // not offered and the callers get the sample-table sums
+    // the interpolants fit the fast kernel's LDS (2 KiB + 80 bytes per row, 80 KiB so that two workgroups share a CU) up
+    // to 15 filters of 64 intervals, 13 of the 74 that SpectrumLikelihood passes; beyond that precision 2 is not
+    // offered and the callers get the sample-table sums (engine.py's SedEngine.interpolants_fit restates this rule)
     s->have_itab = have_itab && (size_t)n_filters * itab_m * 16 * kSedRowLds + kExpTabSize * sizeof(double) <= 80 * 1024;
     std::vector<double2> hitab;
     s->rmin.assign(n_filters, INFINITY);

@@ -619,11 +619,20 @@ class SedEngine:
             if ic.ndim != 3 or ic.shape[0] != len(off) - 1 or ic.shape[2] != 8 or it.shape != (len(off) - 1,):
                 raise ValueError('inconsistent interpolants')
             iargs = (_ptr(ic), _ptr(it), ic.shape[1], float(itab[2]), float(itab[3]))
-        self.has_interpolants = itab is not None
+        #: whether precision 2 runs through the interpolants.  The library stages them in the fast kernel's LDS
+        #: (lcf_sed_create: 80-byte rows, 2 KiB of exponential table, 80 KiB in all -- 13 filters of the per-epoch
+        #: engine's 74 intervals); a set that does not fit is not used, and precision 2 then computes what precision 0
+        #: does, sample by sample.  (tests/test_gpu_sed_edges.py holds this flag to the library's behaviour.)
+        self.has_interpolants = itab is not None and self.interpolants_fit(len(off) - 1, iargs[2])
         _check(self._lib.lcf_sed_create(len(off) - 1, _ptr(off, _ip), _ptr(a), _ptr(w), *cargs, *iargs, int(device),
                                         C.byref(self._h)))
         self.n_epochs = 0
         self.last_kernel_ms = 0.
+
+    @staticmethod
+    def interpolants_fit(n_filters, m):
+        """lcf_sed_create's rule: ``n_filters`` interpolants of ``m`` intervals fit the fast kernel's LDS."""
+        return n_filters * m * 80 + 256 * 8 <= 80 * 1024
 
     def close(self):
         h = getattr(self, '_h', None)

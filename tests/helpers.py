@@ -112,3 +112,434 @@ class OracleBackend:
 
     def finish(self):
         pass
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Per-epoch SED likelihood: an extended-precision reference and the input families of tests/test_gpu_sed_edges.py
+# (tests/test_sed_reference_host.py checks both without a GPU)
+# ---------------------------------------------------------------------------------------------------------------
+LD = np.longdouble
+#: np.longdouble is the x87 80-bit format here (eps 1.1e-19); where it is plain float64 the reference proves nothing
+LD_OK = bool(np.finfo(LD).eps < 1e-18)
+SED_FORMS = (None, 'relative', 'absolute')   # the three conventions of O.log_likelihood: no sigma, relative, absolute
+SED_TOL = 1e-11                              # the project's bound on SED log-likelihoods (tests/test_gpu_sed.py)
+
+_sed_tables = {}
+
+
+def sed_band_table(name, z=0., cutoff_freq=np.inf):
+    """``(a_k, W_k)`` of one band in np.longdouble: ``S(T) = sum_k W_k / expm1(a_k / T)`` is the band average of a
+    blackbody of unit radius.  ``a_k = C1 nu_k``, ``W_k = tw_k tnorm_k C2 nu_k^3 min(1, nu_cut / nu_k)`` with
+    ``nu_k = freq_k (1 + z)`` and ``tw_k`` the trapezoid weights of the band's own (unshifted) frequency grid."""
+    key = (O.band(name).name, float(z), float(cutoff_freq))
+    if key not in _sed_tables:
+        b = O.band(name)
+        fr = b.freq.astype(LD)
+        tw = np.empty_like(fr)
+        tw[1:-1] = (fr[2:] - fr[:-2]) / 2
+        tw[0], tw[-1] = (fr[1] - fr[0]) / 2, (fr[-1] - fr[-2]) / 2
+        nu = fr * (1 + LD(z))
+        _sed_tables[key] = (LD(O.C1) * nu,
+                            tw * b.tnorm.astype(LD) * LD(O.C2) * nu ** 3 * np.minimum(LD(1), LD(cutoff_freq) / nu))
+    return _sed_tables[key]
+
+
+def sed_band_sum(name, T, z=0., cutoff_freq=np.inf):
+    """Band average per unit R^2 at temperatures ``T`` (any shape), np.longdouble.  Zero for ``T <= 0``, ``T = inf``
+    and NaN, as the oracle's ``pw()`` makes it."""
+    a, w = sed_band_table(name, z, cutoff_freq)
+    T = np.asarray(T, dtype=LD)
+    hot = (T > 0) & np.isfinite(T)
+    inv_t = 1 / np.where(hot, T, 1)
+    s = np.zeros(T.shape, dtype=LD)
+    for ak, wk in zip(a, w):
+        s += wk / np.expm1(ak * inv_t)
+    return np.where(hot, s, 0)
+
+
+class SedCase:
+    """Observed epochs and candidates of one test input.  ``names[e]``, ``y[e]``, ``dy[e]``: the epoch's observations;
+    ``cand``: (n_epochs, n_cand, 3) of (T, R, sigma) -- the form without sigma uses the first two columns."""
+
+    def __init__(self, names, y, dy, cand, z=0., cutoff_freq=np.inf):
+        self.names, self.y, self.dy, self.cand, self.z, self.cutoff_freq = names, y, dy, cand, z, cutoff_freq
+        self._ref, self._orc, self._model = {}, {}, []
+
+    @property
+    def epochs(self):
+        return list(zip(self.names, self.y, self.dy))
+
+    @property
+    def unique(self):
+        """The distinct filters in SpectrumLikelihood's order (first appearance)."""
+        return list(dict.fromkeys(n for ep in self.names for n in ep))
+
+    def with_cand(self, cand):
+        return SedCase(self.names, self.y, self.dy, cand, self.z, self.cutoff_freq)
+
+    def candidates(self, form):
+        return self.cand if form else np.ascontiguousarray(self.cand[..., :2])
+
+    def zero_model(self):
+        """Candidates whose model is zero whatever the data: T <= 0, inf, NaN, or R == 0."""
+        T, R = self.cand[..., 0], self.cand[..., 1]
+        return ~((T > 0) & np.isfinite(T)) | (R == 0)
+
+    def model(self, e):
+        """The reference's band fluxes of epoch ``e``: (n_obs, n_cand), np.longdouble (the same for all forms)."""
+        if not self._model:   # band by band for all the epochs that observe it (the exponentials are the whole cost)
+            self._model = [np.empty((len(n), self.cand.shape[1]), dtype=LD) for n in self.names]
+            T, r2 = self.cand[..., 0].astype(LD), self.cand[..., 1].astype(LD) ** 2
+            for name in self.unique:
+                eps = np.array([k for k, n in enumerate(self.names) if name in n])
+                flux = sed_band_sum(name, T[eps], self.z, self.cutoff_freq) * r2[eps]
+                for k, row in zip(eps, flux):
+                    for o in np.nonzero(np.array(self.names[k]) == name)[0]:
+                        self._model[k][o] = row
+        return self._model[e]
+
+    def empty(self):
+        """(n_epochs, 1): the epoch has no observation (its log-likelihood is -0.0 for every candidate)."""
+        return np.array([[len(n) == 0] for n in self.names])
+
+    def reference(self, form, model_scale=1):
+        """Extended-precision log-likelihoods (n_epochs, n_cand), computed once per form."""
+        if (form, model_scale) not in self._ref:
+            self._ref[form, model_scale] = sed_reference(self, form, model_scale)
+        return self._ref[form, model_scale]
+
+    def oracle(self, form, epochs=None):
+        """The float64 oracle's log-likelihoods (n_epochs, n_cand); with ``epochs``, NaN in all other rows."""
+        m = ('Blackbody', type('Z', (), {'z': self.z})())
+        out = self._orc.setdefault(form, np.full(self.cand.shape[:2], np.nan))
+        p = self.candidates(form)
+        for e in (range(len(self.names)) if epochs is None else epochs):
+            names, y, dy = self.names[e], self.y[e], self.dy[e]
+            if not np.isnan(out[e]).all():
+                continue
+            if not len(names):
+                out[e] = -0.
+                continue
+            bands = [O.band(n) for n in names]
+            if not np.isfinite(self.cutoff_freq):
+                out[e] = O.log_likelihood(m, None, bands, y, dy, p[e].T, form is not None, form or 'relative')
+                continue
+            # (the oracle's 'Blackbody' front end has no cut-off frequency: its band averages, its likelihood)
+            T = np.broadcast_to(p[e, :, 0], (len(bands), p.shape[1]))
+            yfit = O.blackbody_to_filters_batch(bands, T, np.broadcast_to(p[e, :, 1], T.shape), self.z,
+                                                self.cutoff_freq)
+            y, dy = np.asarray(y, dtype=np.float64)[:, None], np.asarray(dy, dtype=np.float64)[:, None]
+            units = dy if form != 'absolute' else np.median(dy)
+            sigma = np.sqrt(dy ** 2. + (units * p[e, :, 2][None, :]) ** 2.) if form else dy
+            with np.errstate(all='ignore'):
+                out[e] = -0.5 * np.sum(np.log(2 * np.pi * sigma ** 2.) + ((y - yfit) / sigma) ** 2., axis=0)
+        return out
+
+    def expected(self, form):
+        """What the device is compared with: the reference, or the float64 oracle where np.longdouble is float64."""
+        return self.reference(form) if LD_OK else self.oracle(form)
+
+    def live(self):
+        """Candidates whose log-likelihood depends on the model: not the zero model, not an empty epoch."""
+        return ~self.zero_model() & ~self.empty()
+
+
+def sed_reference(case, form=None, model_scale=1):
+    """np.longdouble reference of SpectrumLikelihood: the band averages of :func:`sed_band_sum` times R^2, then the
+    Gaussian log-likelihood in the convention ``form`` (None: no sigma; 'relative'; 'absolute': sigma in units of the
+    epoch's ``np.median(dy)``).  ``model_scale`` multiplies every model value (the sensitivity check's perturbation)."""
+    n_obs = np.array([len(n) for n in case.names])
+    off = np.concatenate([[0], np.cumsum(n_obs)])
+    out = np.full(case.cand.shape[:2], -0., dtype=LD)      # (an epoch without observations: -1/2 of an empty sum)
+    if off[-1] == 0:
+        return out
+    case.model(0)
+    ep = np.repeat(np.arange(len(n_obs)), n_obs)            # the epoch of every observation
+    yfit = np.concatenate(case._model) * LD(model_scale)    # (n_obs, n_cand)
+    y, dy = np.concatenate(case.y).astype(LD)[:, None], np.concatenate(case.dy).astype(LD)[:, None]
+    sig2 = dy ** 2 + np.zeros_like(yfit)
+    if form is not None:
+        med = np.array([np.median(d) if len(d) else 0. for d in case.dy])   # float64, as np.median(dy) gives it
+        units = dy if form == 'relative' else med[ep].astype(LD)[:, None]
+        sig2 = dy ** 2 + (units * case.cand[ep, :, 2].astype(LD)) ** 2
+    term = np.log(2 * (4 * np.arctan(LD(1))) * sig2) + (y - yfit) ** 2 / sig2
+    some = n_obs > 0
+    out[some] = -0.5 * np.add.reduceat(term, off[:-1][some], axis=0)
+    return out
+
+
+# --- input families ----------------------------------------------------------------------------------------------
+SED7 = ['UVW2', 'U', 'B', 'V', 'g', 'r', 'i']
+SED14 = ['UVW2', 'UVM2', 'UVW1', 'U', 'B', 'V', 'g', 'r', 'i', 'z', 'J', 'H', 'K', 'y']
+
+
+def sed_tables(unique, z=0., cutoff_freq=np.inf):
+    """``(PackedTables, (coef, t_min, u0, h))`` as SpectrumLikelihood builds them for these filters."""
+    from lightcurve_fitting_amd.filters import PackedTables
+    tabs = PackedTables(unique, z=z, cutoff_freq=cutoff_freq)
+    return tabs, tabs.interpolants(below=10)
+
+
+def sed_range(itab):
+    """(t_lo, t_hi) [kK] of the interpolants' table: ``exp(u0)`` and ``exp(u0 + m h)``."""
+    coef, _, u0, h = itab
+    return float(np.exp(u0)), float(np.exp(u0 + coef.shape[1] * h))
+
+
+def sed_listed(T, t_min, itab):
+    """Which hot candidates the interpolated kernel hands to the list, by the engine's own rule: the interval
+    coordinate ``x = (ln T - u0) / h`` is below the threshold made from ``t_min`` (lcf_sed_create) or not below
+    ``m``.  ``t_min``: scalar or an array that broadcasts against ``T`` (the epoch's largest)."""
+    coef, _, u0, h = itab
+    with np.errstate(all='ignore'):
+        x = (np.log(T) - u0) * (1. / h)
+        rmin = np.nextafter(np.maximum((np.log(t_min) - u0) / h, 0.).astype(np.float32), np.float32(np.inf))
+    return (T > 0) & np.isfinite(T) & ~((x >= rmin) & (x < coef.shape[1]))
+
+
+def sed_cold_edge(z):
+    """Below this temperature [kK] the float64 oracle itself is no longer within 1e-12 of the reference (its
+    exponentials have arguments near 100 and beyond): the lower end of the shipped interpolants, 0.937 kK (1 + z)."""
+    from lightcurve_fitting_amd import filters as F
+    return float(np.exp(np.log(F.INTERP_TMIN) - 10 * np.log(F.INTERP_TMAX / F.INTERP_TMIN) / F.INTERP_M) * (1. + z))
+
+
+def sed_observe(rng, names, Tt, Rt, z=0., cutoff_freq=np.inf):
+    """Data of the epochs ``names`` for the truths (Tt[e], Rt[e]): the truth's band fluxes with 1 % noise, ``dy`` 1 %
+    of them.  -> (y, dy), lists over epochs."""
+    Tt, Rt = np.asarray(Tt, dtype=np.float64), np.asarray(Rt, dtype=np.float64)
+    flux = [np.empty(len(ep)) for ep in names]
+    for name in dict.fromkeys(n for ep in names for n in ep):
+        eps = np.array([k for k, ep in enumerate(names) if name in ep])
+        s = np.asarray(sed_band_sum(name, Tt[eps], z, cutoff_freq), dtype=np.float64) * Rt[eps] ** 2
+        for k, v in zip(eps, s):
+            flux[k][np.array(names[k]) == name] = v
+    y, dy = [], []
+    for f in flux:
+        assert np.all(f > 1e-140), 'a flux this small has a variance below the float64 range'
+        y.append(f * (1. + 0.01 * rng.standard_normal(len(f))))
+        dy.append(0.01 * f)
+    return y, dy
+
+
+def sed_scatter(rng, Tt, Rt, n_cand, lo=0., hi=np.inf):
+    """(n_epochs, n_cand, 3) candidates about the truths: 0.3 % in T (clipped to [lo, hi]), 1 % in R, sigma in 0-2."""
+    Tt, Rt = np.asarray(Tt, float)[:, None], np.asarray(Rt, float)[:, None]
+    n = (len(Tt), n_cand)
+    return np.stack([np.clip(Tt * (1. + 0.003 * rng.standard_normal(n)), lo, hi),
+                     Rt * (1. + 0.01 * rng.standard_normal(n)), rng.uniform(0., 2., n)], axis=-1)
+
+
+def _log_uniform(rng, lo, hi, size=None):
+    return np.exp(rng.uniform(np.log(lo), np.log(hi), size))
+
+
+_cases = {}
+
+
+def sed_case(name, *args):
+    """The input family ``name`` (built once per process, together with the references it caches)."""
+    if (name, args) not in _cases:
+        _cases[name, args] = globals()['_case_' + name](*args)
+    return _cases[name, args]
+
+
+def _case_listed():
+    """12 epochs x 101 candidates, UVW2 U B V g r i at z = 0.01.  Candidates hotter than the truth are far from the
+    data but still sensitive to the model (chi^2 ~ (model / sigma)^2), so each epoch mixes its own scatter with
+    candidates from the regimes ABOVE its truth; the few colder than the truth (almost no model: insensitive) are one
+    per epoch at the most."""
+    rng = np.random.default_rng(301)
+    z, n_c = 0.01, 101
+    tabs, itab = sed_tables(SED7, z)
+    t_lo, t_hi = sed_range(itab)
+    #        cold, cold, all cold, at t_lo x3,                 inside: one cold lane, inside, at t_hi x2, above x2
+    Tt = np.array([0.35, 0.6, 0.8, t_lo, t_lo * 1.001, t_lo * 0.999, 5., 20., t_hi, t_hi * 0.999, 400., 1500.])
+    Rt = _log_uniform(rng, 0.5, 20., len(Tt))
+    names = [SED7] * len(Tt)
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    cand = sed_scatter(rng, Tt, Rt, n_c)
+    edges = np.array([np.nextafter(t_lo, 0.), t_lo, np.nextafter(t_lo, 9.), np.nextafter(t_hi, 0.), t_hi,
+                      np.nextafter(t_hi, 1e9)])
+    for e in range(len(Tt)):
+        if e in (2, 6):      # all cold / exactly one cold lane
+            continue
+        # a third from each regime above the truth's, at random lanes of both waves; then the range's edges
+        hotter = [r for r in ((0.3, t_lo), (t_lo, t_hi), (t_hi, 2000.)) if r[1] > Tt[e] * 1.05]
+        lanes = rng.permutation(n_c)
+        for k, (a, b) in enumerate(hotter):
+            sel = lanes[k * 24:(k + 1) * 24]
+            cand[e, sel, 0] = _log_uniform(rng, max(a, Tt[e] * 1.02), b, len(sel))
+        sel = lanes[80:80 + len(edges)]
+        cand[e, sel, 0] = edges
+        if Tt[e] > 100.:     # (all the above are listed here: four lanes inside the range, two per wave)
+            cand[e, [5, 40, 70, 95], 0] = _log_uniform(rng, 2., 200., 4)
+    cand[2, :, 0] = np.minimum(cand[2, :, 0], np.nextafter(t_lo, 0.))
+    cand[6, 17, 0] = 0.7
+    case = SedCase(names, y, dy, cand, z)
+    case.tabs, case.itab = tabs, itab
+    return case
+
+
+def _case_state():
+    """Three candidate sets for ONE set of observations (6 epochs whose truths lie at the lower end of the range):
+    one that lists about half its candidates, one that lists none, one with more candidates that lists all."""
+    rng = np.random.default_rng(302)
+    z = 0.01
+    tabs, itab = sed_tables(SED7, z)
+    t_lo, _ = sed_range(itab)
+    Tt = t_lo * (1. + 0.001 * rng.uniform(-1., 1., 6))
+    Rt = _log_uniform(rng, 0.5, 20., 6)
+    names = [SED7, SED7[:4], SED7[2:], SED7, SED7[1:6], SED7[::2]]
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    half = SedCase(names, y, dy, sed_scatter(rng, Tt, Rt, 90), z)
+    none = half.with_cand(sed_scatter(rng, Tt * 1.02, Rt, 90, lo=t_lo * 1.001))
+    every = half.with_cand(sed_scatter(rng, Tt * 0.98, Rt, 150, hi=t_lo * 0.999))
+    for c in (half, none, every):
+        c.tabs, c.itab = tabs, itab
+    return half, none, every
+
+
+SED_ALTERED = {'U': 3., 'g': 10., 'i': np.inf}   # the per-filter validity test's raised thresholds [kK]
+
+
+def _case_validity():
+    """Epochs around the raised thresholds of SED_ALTERED (and the table's own lower end), so that candidates fall on
+    both sides of each; the last three epochs have no ``i`` (whose interpolant is declared absent)."""
+    rng = np.random.default_rng(303)
+    z = 0.01
+    tabs, itab = sed_tables(SED7, z)
+    t_lo, _ = sed_range(itab)
+    names = [SED7, SED7, SED7, ['UVW2', 'U', 'B', 'V', 'g'], ['B', 'V', 'g', 'r'], ['UVW2', 'U', 'g', 'r', 'B'],
+             ['UVW2', 'B', 'V', 'r']]
+    Tt = np.array([3., 10., 30., 3., 10., 10., t_lo])
+    Rt = _log_uniform(rng, 0.5, 20., len(Tt))
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    cand = sed_scatter(rng, Tt, Rt, 80)
+    cand[5, 70:, 0] = _log_uniform(rng, 12., 200., 10)             # above every threshold
+    case = SedCase(names, y, dy, cand, z)
+    case.tabs, case.itab = tabs, itab
+    return case
+
+
+def _case_stride():
+    """4200 epochs x 65 candidates: 8400 wave items, more than the 8192 waves of the largest launch.  1-3 observations
+    per epoch from U, B, V; truths at 5-50 kK; in 40 epochs (the first, the last and 38 between) the truth sits just
+    above the range's lower end and one candidate just below it (listed)."""
+    rng = np.random.default_rng(304)
+    z, n_ep, n_c = 0., 4200, 65
+    tabs, itab = sed_tables(['U', 'B', 'V'], z)
+    t_lo, _ = sed_range(itab)
+    names = [list(rng.permutation(['U', 'B', 'V'])[:rng.integers(1, 4)]) for _ in range(n_ep)]
+    names[0], names[1], names[2] = ['U', 'B', 'V'], ['B', 'V', 'U'], ['V', 'U', 'B']   # (every filter is in use)
+    Tt = _log_uniform(rng, 5., 50., n_ep)
+    Rt = _log_uniform(rng, 0.5, 20., n_ep)
+    cold = np.concatenate([[0, n_ep - 1], rng.choice(np.arange(1, n_ep - 1), 38, replace=False)])
+    Tt[cold] = t_lo * 1.012
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    cand = sed_scatter(rng, Tt, Rt, n_c, lo=t_lo * 1.0001)
+    cand[cold, rng.integers(0, n_c, len(cold)), 0] = t_lo * 0.98 * (1. + 0.003 * rng.standard_normal(len(cold)))
+    case = SedCase(names, y, dy, cand, z)
+    case.tabs, case.itab = tabs, itab
+    return case
+
+
+def _case_shapes(n_cand):
+    """Epochs with 0, 1, 2 and 7 observations in one engine (one names ``g`` twice; one sits at the range's lower end,
+    so that the list sees these shapes too)."""
+    rng = np.random.default_rng(305 + n_cand)
+    z = 0.01
+    tabs, itab = sed_tables(SED7, z)
+    t_lo, _ = sed_range(itab)
+    names = [[], ['V'], ['g', 'g'], SED7, ['B'], [], ['r', 'UVW2'], SED7]
+    Tt = np.array([8., 12., 6., 25., t_lo, 9., t_lo, 0.7])
+    Rt = _log_uniform(rng, 0.5, 20., len(Tt))
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    case = SedCase(names, y, dy, sed_scatter(rng, Tt, Rt, n_cand), z)
+    case.tabs, case.itab = tabs, itab
+    return case
+
+
+def _case_zero():
+    """Waves of ordinary candidates (truths inside the range and at its lower end) with zero-model temperatures and
+    radii mixed in: T in {0, -1, +inf, NaN}, R in {0, -2}."""
+    rng = np.random.default_rng(306)
+    z = 0.01
+    tabs, itab = sed_tables(SED7, z)
+    t_lo, _ = sed_range(itab)
+    names = [SED7, ['B', 'V', 'r'], ['g'], SED7[1:]]
+    Tt = np.array([9., 15., 30., t_lo])
+    Rt = np.array([2., 2., 2., 2.])
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    cand = sed_scatter(rng, Tt, Rt, 130)
+    mirror = []
+    for e in range(len(Tt)):
+        lanes = rng.permutation(130)
+        mirror.append((lanes[20:26], lanes[26:32]))
+        cand[e, lanes[:16], 0] = np.tile([0., -1., np.inf, np.nan], 4)
+        cand[e, lanes[12:20], 1] = np.tile([0., -2.], 4)     # (lanes 12-15: a zero-model T AND such an R)
+        cand[e, lanes[20:26], 1] = -cand[e, lanes[26:32], 1]  # the mirror images of six ordinary candidates
+        cand[e, lanes[20:26], 0] = cand[e, lanes[26:32], 0]
+        cand[e, lanes[20:26], 2] = cand[e, lanes[26:32], 2]
+    case = SedCase(names, y, dy, cand, z)
+    case.tabs, case.itab, case.mirror = tabs, itab, mirror   # (per epoch: lanes with -R, lanes with R)
+    return case
+
+
+def _case_many():
+    """14 unique filters in 6 epochs of mixed subsets, 70 candidates; truths below, inside and above the range."""
+    rng = np.random.default_rng(307)
+    z = 0.01
+    tabs, itab = sed_tables(SED14, z)
+    names = [SED14, SED14[::2], SED14[1::2], SED14[3:11], SED14[:5] + SED14[9:], SED14[5:]]
+    Tt = np.array([0.6, 3., 8., 20., 60., 800.])
+    Rt = _log_uniform(rng, 0.5, 20., len(Tt))
+    y, dy = sed_observe(rng, names, Tt, Rt, z)
+    case = SedCase(names, y, dy, sed_scatter(rng, Tt, Rt, 70), z)
+    case.tabs, case.itab, case.truth_T = tabs, itab, Tt
+    return case
+
+
+def _case_fuzz(seed):
+    """Random redshift, cut-off, filters, epochs and candidate count; truths log-uniform over 0.3-2000 kK."""
+    from lightcurve_fitting_amd import filters as F
+    rng = np.random.default_rng(3000 + seed)
+    z = float(rng.choice([0., 0.01, 0.3]))
+    cut = float(rng.choice([np.inf, 700.]))
+    pool = list(rng.choice([f.name for f in F.all_filters if f.filename], int(rng.integers(3, 10)), replace=False))
+    n_ep, n_c = int(rng.integers(1, 21)), int(rng.integers(1, 201))
+    names = [[str(n) for n in rng.choice(pool, int(rng.integers(1, 10)))] for _ in range(n_ep)]
+    Tt = _log_uniform(rng, 0.3, 2000., n_ep)
+    Rt = _log_uniform(rng, 0.5, 20., n_ep)
+    y, dy = sed_observe(rng, names, Tt, Rt, z, cut)
+    case = SedCase(names, y, dy, sed_scatter(rng, Tt, Rt, n_c, lo=0.3, hi=2000.), z, cut)
+    case.form = SED_FORMS[int(rng.integers(3))]
+    return case
+
+
+def sed_tolerances(case, form):
+    """Per-candidate tolerance of the device against ``case.expected(form)``, and the number it rests on.
+
+    Where the float64 oracle is within 1e-12 of the reference the project's bound SED_TOL = 1e-11 applies (the host
+    test asserts that premise).  Below :func:`sed_cold_edge` it is not: there the deviation ``d_cold`` of the oracle
+    from the reference is measured on these very candidates, and the device is allowed ``max(1e-11, 10 d_cold)`` -- its
+    table exponential carries the same (a / T) ulp error as NumPy's, and one decade covers the other summation order.
+    -> (tol[n_epochs, n_cand], d_cold)."""
+    cold = (case.cand[..., 0] < sed_cold_edge(case.z)) & case.live()
+    d_cold = 0.
+    if cold.any() and LD_OK:
+        ref = np.asarray(case.reference(form)[cold], dtype=np.float64)
+        orc = case.oracle(form, np.nonzero(cold.any(axis=1))[0])
+        d_cold = float(np.max(np.abs(orc[cold] - ref) / np.abs(ref)))
+    return np.where(cold, max(SED_TOL, 10. * d_cold), SED_TOL), d_cold
+
+
+def sed_worst(got, case, form):
+    """Largest |got - expected| / |expected| over the candidates, and the largest ratio of that to its tolerance."""
+    tol, _ = sed_tolerances(case, form)
+    want = np.asarray(case.expected(form), dtype=np.float64)
+    assert np.array_equal(np.isnan(got), np.isnan(want)) and got.shape == want.shape
+    ok = ~np.isnan(want)
+    err = np.zeros(want.shape)
+    err[ok] = np.abs(got[ok] - want[ok]) / np.maximum(np.abs(want[ok]), 1e-300)
+    return float(err.max(initial=0.)), float((err / tol).max(initial=0.))

@@ -77,7 +77,9 @@ def test_sed_grid_at_config4_width_against_oracle():
     ref = np.array([O.log_likelihood(m, None, bands, y, dy, cand[e].T) for e, (_, y, dy) in enumerate(epochs)])
     assert relerr(got, ref) < 1e-11
     assert relerr(like(cand, precision='f64-tables'), ref) < 1e-11
-    assert np.any(cand[..., 0] < 2.)          # (some candidates are colder than the interpolants' range: k_sed_rest)
+    # (U(1, 100) lies inside the interpolants' range, 0.94-256 kK: every candidate here is finished by k_sed_interp.
+    # The list of candidates outside it and k_sed_rest are tested in tests/test_gpu_sed_edges.py)
+    assert np.all(like.itab_tmin < cand[..., 0].min()) and cand[..., 0].max() < 256.
     # candidates with a fitted sigma, and an epoch count that is not a multiple of anything
     cand3 = np.concatenate([cand, rng.uniform(0., 2., (n_ep, n_c, 1))], axis=-1)[:37, :101]
     like37 = B.SpectrumLikelihood(epochs[:37], z=0.)
