@@ -402,6 +402,28 @@ lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64
                                          int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
                                          double* out, int64_t* n_valid);
 
+/* ---- thermal bands and validity: T, R_bb, L_bol of the blackbody behind the light curves, over ALL samples -------- */
+/* `grid` is an evaluation engine with one point per distinct time and any single filter (what temperature_radius is
+ * evaluated on); the model is any but LCF_MODEL_BLACKBODY.  Per (sample, time): T [kK] and R_bb [1000 Rsun] as
+ * lcf_temperature_radius returns them (for the companion-shocking models: of the shock component) and L_bol = 4 pi
+ * sigma_SB R_bb^2 T^4 [W] of that pair.  Per time, over the samples: the percentiles q[n_q] of each of the three
+ * (definition, workspace and reproducibility as for lcf_predict_quantiles; 3 * n_q <= 512), the number of non-NaN
+ * values of each, the number of samples with T < T_floor (T is exactly 0 before a sample's explosion time: that is
+ * cold), and the number with t_min(p) <= t <= t_max(p), the model's own validity window at opacity kappa = 1
+ * (models.py:276-298, 414-430, 499-504, 634-657, 830-845; a NaN bound: not inside; ShockCooling2 has no lower bound).
+ * All counts are exact integers.  Times are in the order the engine was given them.
+ * Over n host samples P[n][ld] (the first n_par columns are used): */
+lcf_status lcf_predict_thermal(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                               double T_floor, int64_t workspace_bytes,
+                               double* out /* [3][n_q][n_times]: T, R_bb, L_bol */,
+                               int64_t* n_valid /* [3][n_times] */, int64_t* n_cold /* [n_times] */,
+                               int64_t* n_inside /* [n_times] */);
+/* The same over rows discard, discard + thin, ... of the sampler's last stored run, read in place; status codes as
+ * for lcf_sampler_predict_quantiles. */
+lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, const double* q,
+                                       int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
+                                       int64_t* n_valid, int64_t* n_cold, int64_t* n_inside);
+
 #ifdef __cplusplus
 }
 #endif

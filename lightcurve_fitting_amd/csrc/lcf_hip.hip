@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <dlfcn.h>
+#include <functional>
 #include <cstring>
 #include <mutex>
 #include <numeric>
@@ -4214,9 +4215,9 @@ static lcf_status predict_impl(lcf_engine* grid, const PredictSamples& in, int32
     return predict_run(grid->device, dp, in, table.data(), component, q, n_q, workspace_bytes, out, n_valid);
 }
 
-lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t component,
-                                 const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
-    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+// n host samples P[n][ld] on the grid engine's device for as long as `run` takes.
+static lcf_status with_uploaded_samples(lcf_engine* grid, const double* P, int64_t n, int32_t ld,
+                                        const std::function<lcf_status(const PredictSamples&)>& run) {
     if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
     if (ld < 1 || ld < grid->dp.n_par) return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than the model's parameter count");
     if (n > (1LL << 40) / ld) return fail(LCF_ERR_INVALID_ARGUMENT, "too many samples");
@@ -4226,15 +4227,13 @@ lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, i
     lcf_status st = LCF_OK;
     if (hipMemcpy(dP, P, (size_t)n * ld * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         st = fail(LCF_ERR_HIP, "copying the samples to the device failed");
-    if (!st) st = predict_impl(grid, PredictSamples{dP, n, n, 0, ld}, component, q, n_q, workspace_bytes, out, n_valid);
+    if (!st) st = run(PredictSamples{dP, n, n, 0, ld});
     hipFree(dP);
     return st;
 }
 
-lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin,
-                                         int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
-                                         double* out, int64_t* n_valid) {
-    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+// Rows discard, discard + thin, ... of the sampler's last stored run as samples, where they lie.
+static lcf_status stored_samples(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, PredictSamples* in) {
     if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
     if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
     if (!s->ds.store_chain || s->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
@@ -4246,8 +4245,70 @@ lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64
     LCF_HIP(hipSetDevice(grid->device));
     const DevSampler& ds = s->ds;
     const int64_t row = (int64_t)ds.n_walkers * ds.n_dim, steps = (s->run_steps - discard + thin - 1) / thin;
-    const PredictSamples in{ds.chain + discard * row, steps * ds.n_walkers, ds.n_walkers, thin * row, ds.n_dim};
+    *in = PredictSamples{ds.chain + discard * row, steps * ds.n_walkers, ds.n_walkers, thin * row, ds.n_dim};
+    return LCF_OK;
+}
+
+lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t component,
+                                 const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
+    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+    return with_uploaded_samples(grid, P, n, ld, [&](const PredictSamples& in) {
+        return predict_impl(grid, in, component, q, n_q, workspace_bytes, out, n_valid);
+    });
+}
+
+lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin,
+                                         int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
+                                         double* out, int64_t* n_valid) {
+    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+    PredictSamples in;
+    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
     return predict_impl(grid, in, component, q, n_q, workspace_bytes, out, n_valid);
+}
+
+// What both thermal entry points check before the device is touched.
+static lcf_status thermal_check(const lcf_engine* grid, const double* q, int32_t n_q, const double* out,
+                                const int64_t* n_valid, const int64_t* n_cold, const int64_t* n_inside) {
+    if (!n_cold || !n_inside) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = predict_check(grid, 0, q, n_q, out, n_valid)) return st;
+    if (grid->dp.model == kBlackbody)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the blackbody model has no thermal evolution or validity window");
+    if (grid->dp.n_points != grid->dp.n_epochs)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine must hold one point per distinct time");
+    return LCF_OK;
+}
+
+// The grid engine's times in the caller's order and the run itself.
+static lcf_status thermal_impl(lcf_engine* grid, const PredictSamples& in, const double* q, int32_t n_q, double T_floor,
+                               int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_cold,
+                               int64_t* n_inside) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points;
+    std::vector<int> orig(N), epoch(N);
+    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int32_t> time_orig(N);
+    for (int i = 0; i < N; ++i) time_orig[epoch[i]] = orig[i];   // (N points on N distinct times: a bijection)
+    return predict_thermal_run(grid->device, dp, in, time_orig.data(), q, n_q, T_floor, workspace_bytes, out, n_valid,
+                               n_cold, n_inside);
+}
+
+lcf_status lcf_predict_thermal(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                               double T_floor, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_cold,
+                               int64_t* n_inside) {
+    if (lcf_status st = thermal_check(grid, q, n_q, out, n_valid, n_cold, n_inside)) return st;
+    return with_uploaded_samples(grid, P, n, ld, [&](const PredictSamples& in) {
+        return thermal_impl(grid, in, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
+    });
+}
+
+lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, const double* q,
+                                       int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
+                                       int64_t* n_valid, int64_t* n_cold, int64_t* n_inside) {
+    if (lcf_status st = thermal_check(grid, q, n_q, out, n_valid, n_cold, n_inside)) return st;
+    PredictSamples in;
+    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
+    return thermal_impl(grid, in, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
 }
 
 }  // extern "C"

@@ -133,5 +133,11 @@ struct PredictSamples {
 lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig,
                        int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
                        int64_t* n_valid);
+// Thermal form: quantiles of T, R_bb, L_bol and the validity counters on the distinct times of `dp`; time_orig
+// [n_epochs] (host): the time's index in the caller's order.  out[3][n_q][n_epochs], n_valid[3][n_epochs],
+// n_cold[n_epochs], n_inside[n_epochs] (host, caller's order).
+lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* time_orig,
+                               const double* q, int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
+                               int64_t* n_valid, int64_t* n_cold, int64_t* n_inside);
 
 }  // namespace lcf

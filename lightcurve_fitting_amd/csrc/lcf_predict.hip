@@ -18,6 +18,15 @@
 // that key).  All counts are integers and the collected keys are sorted, so no result depends on the order in which
 // workgroups arrive, on the sample chunks or on how the times are tiled over the workspace; there is no floating-point
 // atomic and no workgroup waits for another.  (DESIGN.md "Posterior-predictive quantiles".)
+//
+// The thermal form (DESIGN.md "Thermal bands and validity") runs the same searches on what the band sums are made from:
+//   k_th_sample   walker_coefficients and the validity window (t_min, t_max) of every sample, once, [8][n] and [2][n]
+//   k_th_pass     the geometry and modes of k_pq_pass with three "filters" per time -- T, R_bb = sqrt(R_bb^2) and
+//                 L_bol = 4 pi sigma_SB R_bb^2 T^4 of ONE linear-space thermal_state, the values of
+//                 lcf_temperature_radius -- and no band sum, filter descriptor or exp table.  In mode 0 it also counts,
+//                 per time, the samples with T < T_floor and those with t_min <= t <= t_max: wave ballot + popcount,
+//                 a sum per workgroup in LDS, one 64-bit integer atomic per workgroup and counter.
+// k_pq_pick and k_pq_finish serve both forms; the host driver (quantile_run) differs in the two launches only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -170,6 +179,93 @@ __device__ __forceinline__ const double* pq_row(const PqArgs& a, long long s) {
     return a.base + (s / a.n_w) * a.step_stride + (s % a.n_w) * a.ld;
 }
 
+// What both pass kernels do with the values of a point.  Per search in LDS: prefix, successor, prefix bits, collect
+// flag; behind them the histogram counters.
+struct PqLds {
+    unsigned long long *prefix, *succ;
+    int *pbits, *col;
+    unsigned int* hist;
+};
+
+// The searches' LDS at `at` (8-byte aligned): counters zeroed, the tile time's searches loaded (modes 1, 2).  The caller
+// synchronises.
+__device__ __forceinline__ PqLds pq_lds_setup(const PqArgs& a, void* at, const PqSearch* search, int ns, int n_hist,
+                                              int tid) {
+    PqLds s;
+    s.prefix = reinterpret_cast<unsigned long long*>(at);
+    s.succ = s.prefix + ns;
+    s.pbits = reinterpret_cast<int*>(s.succ + ns);
+    s.col = s.pbits + ns;
+    s.hist = reinterpret_cast<unsigned int*>(s.col + ns);
+    for (int k = tid; k < n_hist; k += kPqThreads) s.hist[k] = 0u;
+    if (a.mode != 0)
+        for (int k = tid; k < ns; k += kPqThreads) {
+            const PqSearch sr = search[k];
+            s.prefix[k] = sr.prefix;
+            s.succ[k] = kNoKey;
+            s.pbits[k] = (a.mode == 1 ? sr.active != 0 : sr.pbits > 0) ? sr.pbits : -1;
+            s.col[k] = sr.collect;
+        }
+    return s;
+}
+
+// The value v of (this lane's sample, series f of the workgroup's time) enters the histograms (modes 0, 1) or the
+// searches' buffers and successors (mode 2).
+__device__ __forceinline__ void pq_consume(const PqArgs& a, const PqLds& s, PqSearch* search, int ns, int f, double v,
+                                           int lane, unsigned int mask) {
+    const bool valid = v == v;
+    const unsigned long long key = pq_key(v);
+    if (a.mode == 0) {
+        // (the values of a point mostly share their exponent: lanes with the same bin add once, together)
+        const int bin = (int)(key >> a.shift);
+        unsigned long long m = __builtin_amdgcn_ballot_w64(valid);
+        while (m) {
+            const int leader = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m));
+            const int b0 = __builtin_amdgcn_readlane(bin, leader);
+            const unsigned long long peers = __builtin_amdgcn_ballot_w64(valid && bin == b0);
+            if (lane == leader) atomicAdd(&s.hist[(f << a.bits) + b0], (unsigned int)__popcll(peers));
+            m &= ~peers;
+        }
+    } else if (valid) {
+        for (int j = 0; j < a.n_q; ++j) {
+            const int k = f * a.n_q + j, pbits = s.pbits[k];
+            if (pbits < 0) continue;
+            const unsigned long long pre = s.prefix[k];
+            if (a.mode == 1) {   // (every active search has the same 64 - shift - bits prefix bits)
+                // One ds_add per lane.  (Measured and not kept: a round of the sharing above in front of it --
+                // the first refinement, whose keys still crowd into a few bins, 76 -> 66 ms, the second, whose
+                // keys are spread, 46 -> 60 ms at 2 048 000 samples x 6000 points.)
+                if ((key >> (a.shift + a.bits)) == pre)
+                    atomicAdd(&s.hist[(k << a.bits) + (int)((unsigned int)(key >> a.shift) & mask)], 1u);
+            } else {
+                const unsigned long long head = pbits >= 64 ? key : key >> (64 - pbits);
+                if (head == pre) {
+                    if (s.col[k]) {
+                        const unsigned int at = atomicAdd(&search[k].fill, 1u);
+                        if (at < (unsigned int)kPqCap) a.buf[((size_t)blockIdx.x * ns + k) * kPqCap + at] = key;
+                    }
+                } else if (head > pre && key < s.succ[k]) {
+                    atomicMin(&s.succ[k], key);
+                }
+            }
+        }
+    }
+}
+
+// After the workgroup's last value (and a barrier): its histogram, or its successors, join the tile time's.
+__device__ __forceinline__ void pq_merge(const PqArgs& a, const PqLds& s, PqSearch* search, int ns, int n_hist, int tid) {
+    if (a.mode == 2) {
+        for (int k = tid; k < ns; k += kPqThreads)
+            if (s.succ[k] != kNoKey) atomicMin(&search[k].succ, s.succ[k]);
+    } else {
+        unsigned int* g = a.hist + (size_t)blockIdx.x * n_hist;
+        for (int k = tid; k < n_hist; k += kPqThreads) {
+            const unsigned int v = s.hist[k];
+            if (v) atomicAdd(&g[k], v);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_pq_coef(const DevProblem pb, const PqArgs a, double* __restrict__ coef) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= a.n) return;
@@ -185,11 +281,6 @@ __global__ __launch_bounds__(kPqThreads) void k_pq_pass(const DevProblem pb, con
     extern __shared__ __align__(16) unsigned char smem[];
     const int nf = pb.n_filters, ns = nf * a.n_q;
     double* exptab = reinterpret_cast<double*>(smem);
-    unsigned long long* s_prefix = reinterpret_cast<unsigned long long*>(exptab + kExpTabSize);
-    unsigned long long* s_succ = s_prefix + ns;
-    int* s_pbits = reinterpret_cast<int*>(s_succ + ns);
-    int* s_col = s_pbits + ns;
-    unsigned int* s_hist = reinterpret_cast<unsigned int*>(s_col + ns);
 
     const int model = MODEL ? MODEL : pb.model;
     const bool companion = model >= kCompanion && model <= kCompanion3;
@@ -198,15 +289,7 @@ __global__ __launch_bounds__(kPqThreads) void k_pq_pass(const DevProblem pb, con
     const int n_hist = a.mode == 0 ? nf << a.bits : a.mode == 1 ? ns << a.bits : 0;
     PqSearch* search = a.search + (size_t)blockIdx.x * ns;
     for (int k = tid; k < kExpTabSize; k += kPqThreads) exptab[k] = pb.exp2tab[k];
-    for (int k = tid; k < n_hist; k += kPqThreads) s_hist[k] = 0u;
-    if (a.mode != 0)
-        for (int k = tid; k < ns; k += kPqThreads) {
-            const PqSearch sr = search[k];
-            s_prefix[k] = sr.prefix;
-            s_succ[k] = kNoKey;
-            s_pbits[k] = (a.mode == 1 ? sr.active != 0 : sr.pbits > 0) ? sr.pbits : -1;
-            s_col[k] = sr.collect;
-        }
+    const PqLds lds = pq_lds_setup(a, exptab + kExpTabSize, search, ns, n_hist, tid);
     __syncthreads();
 
     const ExpTab et{exptab};
@@ -235,57 +318,124 @@ __global__ __launch_bounds__(kPqThreads) void k_pq_pass(const DevProblem pb, con
         }
         for (int f = 0; f < nf; ++f) {
             if (orig[f] < 0) continue;
-            const double v = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, a.component);
-            const bool valid = v == v;
-            const unsigned long long key = pq_key(v);
-            if (a.mode == 0) {
-                // (the values of a point mostly share their exponent: lanes with the same bin add once, together)
-                const int bin = (int)(key >> a.shift);
-                unsigned long long m = __builtin_amdgcn_ballot_w64(valid);
-                while (m) {
-                    const int leader = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m));
-                    const int b0 = __builtin_amdgcn_readlane(bin, leader);
-                    const unsigned long long peers = __builtin_amdgcn_ballot_w64(valid && bin == b0);
-                    if (lane == leader) atomicAdd(&s_hist[(f << a.bits) + b0], (unsigned int)__popcll(peers));
-                    m &= ~peers;
-                }
-            } else if (valid) {
-                for (int j = 0; j < a.n_q; ++j) {
-                    const int k = f * a.n_q + j, pbits = s_pbits[k];
-                    if (pbits < 0) continue;
-                    const unsigned long long pre = s_prefix[k];
-                    if (a.mode == 1) {   // (every active search has the same 64 - shift - bits prefix bits)
-                        // One ds_add per lane.  (Measured and not kept: a round of the sharing above in front of it --
-                        // the first refinement, whose keys still crowd into a few bins, 76 -> 66 ms, the second, whose
-                        // keys are spread, 46 -> 60 ms at 2 048 000 samples x 6000 points.)
-                        if ((key >> (a.shift + a.bits)) == pre)
-                            atomicAdd(&s_hist[(k << a.bits) + (int)((unsigned int)(key >> a.shift) & mask)], 1u);
-                    } else {
-                        const unsigned long long head = pbits >= 64 ? key : key >> (64 - pbits);
-                        if (head == pre) {
-                            if (s_col[k]) {
-                                const unsigned int at = atomicAdd(&search[k].fill, 1u);
-                                if (at < (unsigned int)kPqCap)
-                                    a.buf[((size_t)blockIdx.x * ns + k) * kPqCap + at] = key;
-                            }
-                        } else if (head > pre && key < s_succ[k]) {
-                            atomicMin(&s_succ[k], key);
-                        }
-                    }
-                }
-            }
+            pq_consume(a, lds, search, ns, f, pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, a.component), lane, mask);
         }
     }
     __syncthreads();
-    if (a.mode == 2) {
-        for (int k = tid; k < ns; k += kPqThreads)
-            if (s_succ[k] != kNoKey) atomicMin(&search[k].succ, s_succ[k]);
-    } else {
-        unsigned int* g = a.hist + (size_t)blockIdx.x * n_hist;
-        for (int k = tid; k < n_hist; k += kPqThreads) {
-            const unsigned int v = s_hist[k];
-            if (v) atomicAdd(&g[k], v);
+    pq_merge(a, lds, search, ns, n_hist, tid);
+}
+
+// ---- the thermal form: T, R_bb, L_bol as the three series of a time, and the validity counters -----------------------
+constexpr int kThSeries = 3;
+constexpr double kThSigmaSB = 2.744452656619892e+28;   // W (1000 Rsun)^-2 kK^-4: kSigmaSB of lcf_bolo.hip
+constexpr double kThFourPi = 12.566370614359172;
+
+struct ThArgs {
+    double* win;                     // [2][n]: t_min, t_max of every sample
+    double T_floor;
+    unsigned long long* n_cold;      // [n_epochs] samples with T < T_floor
+    unsigned long long* n_inside;    // [n_epochs] samples with t_min <= t <= t_max
+};
+
+// max / min that keep a NaN, as np.maximum / np.minimum do (models.py:287, 657)
+__device__ __forceinline__ double th_max(double a, double b) { return a != a ? a : b != b ? b : fmax(a, b); }
+__device__ __forceinline__ double th_min(double a, double b) { return a != a ? a : b != b ? b : fmin(a, b); }
+
+// The times between which the model of parameter row p holds, kappa = 1: the t_min / t_max methods of the reference
+// (models.py:276-298, 414-430, 499-504, 634-657, 830-845).  c: the row's walker_coefficients.  A NaN means "never".
+__device__ inline void th_window(const DevProblem& pb, const double* __restrict__ p, const double* __restrict__ c,
+                                 double& t_lo, double& t_hi) {
+    const double* k = pb.consts;
+    const double t0 = c[0];
+    switch (pb.model) {
+        case kShockCooling:
+        case kShockCooling3: {
+            const double v = p[0], f = p[2], R = p[3];
+            t_lo = 0.2 * R / v * th_max(0.5, pow(R, 0.4) * pow(f, -0.2) * pow(v, -0.7)) + t0;
+            t_hi = 7.4 * pow(R, 0.55) + t0;
+            break;
         }
+        case kShockCooling2:   // (no lower bound; 8.12 kK = 0.7 eV; epsilon_T = 2 epsilon_1 - 0.5)
+            t_lo = -INFINITY;
+            t_hi = pow(8.12 / p[0], 1. / (2. * k[3] - 0.5)) + t0;
+            break;
+        case kShockCooling4: {   // (19.5 ** sqrt(...): the reference's, kept; k[6] = 19.5, k[1] = a)
+            const double v = p[0], M = p[1], f = p[2], R = p[3];
+            t_lo = 0.012 * R + t0;
+            t_hi = th_min(6.86 * pow(R, 0.56) * pow(v, 0.16) * pow(f, -0.06), pow(k[6], sqrt(M / v)) / k[1]) + t0;
+            break;
+        }
+        case kCompanion:
+        case kCompanion2:
+        case kCompanion3:   // the template's first and last epoch at the sample's stretch, about its t_peak
+            t_lo = c[3] + c[4] * pb.knot0;
+            t_hi = c[3] + c[4] * pb.knot_last;
+            break;
+        default:
+            t_lo = t_hi = qnan();
+            break;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_th_sample(const DevProblem pb, const PqArgs a, double* __restrict__ coef,
+                                                   double* __restrict__ win) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.n) return;
+    const double* p = pq_row(a, s);
+    double c[kNCoef], t_lo, t_hi;
+    walker_coefficients(pb, p, c);
+    th_window(pb, p, c, t_lo, t_hi);
+    for (int i = 0; i < kNCoef; ++i) coef[(long long)i * a.n + s] = c[i];
+    win[s] = t_lo;
+    win[a.n + s] = t_hi;
+}
+
+// blockIdx.x = time of the tile, blockIdx.y = chunk of samples.  Dynamic LDS: per search prefix, successor, prefix
+// bits, collect flag | histogram counters.
+template <int MODEL>
+__global__ __launch_bounds__(kPqThreads) void k_th_pass(const DevProblem pb, const PqArgs a, const ThArgs th) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ unsigned int s_count[2];
+    const int ns = kThSeries * a.n_q;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ep = a.ep0 + blockIdx.x;
+    const int n_hist = a.mode == 0 ? kThSeries << a.bits : a.mode == 1 ? ns << a.bits : 0;
+    PqSearch* search = a.search + (size_t)blockIdx.x * ns;
+    const PqLds lds = pq_lds_setup(a, smem, search, ns, n_hist, tid);
+    if (tid < 2) s_count[tid] = 0u;
+    __syncthreads();
+
+    const double t_in = pb.epoch_t[ep];
+    const unsigned int mask = (1u << a.bits) - 1u;
+    const long long s0 = (long long)blockIdx.y * a.chunk, s1 = min(a.n, s0 + a.chunk);
+    unsigned int cold = 0u, inside = 0u;   // of this wave's samples (wave-uniform)
+    for (long long sb = s0; sb < s1; sb += kPqThreads) {
+        const long long s = sb + tid;
+        if (s >= s1) continue;
+        double c[kNCoef];
+#pragma unroll
+        for (int i = 0; i < kNCoef; ++i) c[i] = a.coef[(long long)i * a.n + s];
+        double T, invT, pref;
+        thermal_state<MODEL>(pb, c, t_in, T, invT, pref);   // (what mode 2 of k_points evaluates)
+        const double R = sqrt(pref), T2 = T * T;
+        const double v[kThSeries] = {T, R, kThFourPi * (R * R) * kThSigmaSB * (T2 * T2)};
+        if (a.mode == 0) {
+            const double t_lo = th.win[s], t_hi = th.win[a.n + s];
+            cold += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(T < th.T_floor));
+            inside += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(t_lo <= t_in && t_in <= t_hi));
+        }
+#pragma unroll
+        for (int f = 0; f < kThSeries; ++f) pq_consume(a, lds, search, ns, f, v[f], lane, mask);
+    }
+    if (a.mode == 0 && lane == 0) {
+        atomicAdd(&s_count[0], cold);
+        atomicAdd(&s_count[1], inside);
+    }
+    __syncthreads();
+    pq_merge(a, lds, search, ns, n_hist, tid);
+    if (a.mode == 0 && tid == 0) {
+        atomicAdd(&th.n_cold[ep], (unsigned long long)s_count[0]);
+        atomicAdd(&th.n_inside[ep], (unsigned long long)s_count[1]);
     }
 }
 
@@ -430,36 +580,81 @@ int hist_bits(long long n_hist, int max_bits) {
     return b;
 }
 
-template <int MODEL>
-lcf_status launch_pass(const DevProblem& dp, const PqArgs& a, int n_ep, size_t lds) {
+// What the two forms do differently on the host: the launch that prepares the samples and the pass launch.
+struct PqForm {
+    int nf;                // series per time: the filters, or T / R_bb / L_bol
+    size_t sample_bytes;   // device memory per sample ...
+    size_t time_bytes;     // ... and per time of the whole grid, beyond what every form needs
+    size_t lds_head;       // dynamic LDS of a pass in front of the searches' words and the histograms
+    virtual lcf_status prepare(PqBuf& mem, PqArgs& a, double* d_coef) = 0;   // ... and whatever else the passes read
+    virtual lcf_status pass(const PqArgs& a, int n_ep, size_t lds) = 0;
+    virtual ~PqForm() {}
+};
+
+template <class Kernel, class... Extra>
+lcf_status launch_pass(Kernel kernel, const DevProblem& dp, const PqArgs& a, int n_ep, size_t lds, Extra... extra) {
     const unsigned chunks = (unsigned)((a.n + a.chunk - 1) / a.chunk);
-    hipLaunchKernelGGL(k_pq_pass<MODEL>, dim3((unsigned)n_ep, chunks), dim3(kPqThreads), lds, 0, dp, a);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_ep, chunks), dim3(kPqThreads), lds, 0, dp, a, extra...);
     LCF_HIP(hipGetLastError());
     return LCF_OK;
 }
 
-lcf_status run_pass(const DevProblem& dp, const PqArgs& a, int n_ep, size_t lds) {
-    if (dp.model == kShockCooling) return launch_pass<kShockCooling>(dp, a, n_ep, lds);
-    return launch_pass<0>(dp, a, n_ep, lds);
-}
+struct LightCurveForm : PqForm {
+    const DevProblem& dp;
+    explicit LightCurveForm(const DevProblem& d) : dp(d) {
+        nf = d.n_filters;
+        sample_bytes = kNCoef * sizeof(double);
+        time_bytes = 0;
+        lds_head = kExpTabSize * sizeof(double);
+    }
+    lcf_status prepare(PqBuf&, PqArgs& a, double* d_coef) override {
+        hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
+        LCF_HIP(hipGetLastError());
+        return LCF_OK;
+    }
+    lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
+        if (dp.model == kShockCooling) return launch_pass(k_pq_pass<kShockCooling>, dp, a, n_ep, lds);
+        return launch_pass(k_pq_pass<0>, dp, a, n_ep, lds);
+    }
+};
 
-}  // namespace
+struct ThermalForm : PqForm {
+    const DevProblem& dp;
+    ThArgs th{};
+    ThermalForm(const DevProblem& d, double T_floor) : dp(d) {
+        nf = kThSeries;
+        sample_bytes = (kNCoef + 2) * sizeof(double);   // + t_min, t_max
+        time_bytes = 2 * sizeof(unsigned long long);    // the two counters
+        lds_head = 0;
+        th.T_floor = T_floor;
+    }
+    lcf_status prepare(PqBuf& mem, PqArgs& a, double* d_coef) override {
+        lcf_status st;
+        if ((st = mem.alloc(&th.win, (size_t)a.n * 2)) || (st = mem.alloc(&th.n_cold, (size_t)dp.n_epochs * 2))) return st;
+        th.n_inside = th.n_cold + dp.n_epochs;
+        LCF_HIP(hipMemset(th.n_cold, 0, (size_t)dp.n_epochs * 2 * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(k_th_sample, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef, th.win);
+        LCF_HIP(hipGetLastError());
+        return LCF_OK;
+    }
+    lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
+        if (dp.model == kShockCooling) return launch_pass(k_th_pass<kShockCooling>, dp, a, n_ep, lds, th);
+        return launch_pass(k_th_pass<0>, dp, a, n_ep, lds, th);
+    }
+};
 
-namespace lcf {
-
-lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig_host,
-                       int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
-                       int64_t* n_valid) {
+// The searches of every point (time x series of `form`), the times in tiles that fit the workspace.  orig_host
+// [n_ep_all][nf]: where the point's results go, -1 = no such point.  out[n_q][n_points], n_valid[n_points] (host).
+lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_points, const PredictSamples& in,
+                        const int32_t* orig_host, int32_t component, const double* q, int32_t n_q,
+                        int64_t workspace_bytes, PqBuf& mem, double* out, int64_t* n_valid) {
     LCF_HIP(hipSetDevice(device));
-    const int nf = dp.n_filters, n_ep_all = dp.n_epochs, ns = nf * n_q;
-    const long long n_points = dp.n_points;
-    if (ns > kPqMaxSearch)
-        return fail(LCF_ERR_UNSUPPORTED, "filters x percentiles of one call must not exceed 512");
+    const int nf = form.nf, ns = nf * n_q;
     const int bits0 = hist_bits(nf, kPqMaxBits), bits1 = hist_bits(ns, kPqMaxBits);
-    const size_t lds_head = kExpTabSize * sizeof(double) + (size_t)ns * 24;
-    // device memory: per sample the coefficients, per point the results, per time of a tile the rest
-    const size_t fixed = (size_t)in.n * kNCoef * sizeof(double) + (size_t)n_points * (n_q + 1) * 8 +
-                         (size_t)n_ep_all * nf * 4 + 4096;
+    const size_t lds_head = form.lds_head + (size_t)ns * 24;
+    // device memory: per sample the coefficients (and window), per point the results, per time of a tile the rest
+    const size_t fixed = (size_t)in.n * form.sample_bytes + (size_t)n_points * (n_q + 1) * 8 +
+                         (size_t)n_ep_all * (nf * 4 + form.time_bytes) + 4096;
     const size_t hist_ep = std::max((size_t)nf << bits0, (size_t)ns << bits1) * 4;
     const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8);
     if (workspace_bytes < 0 || (size_t)workspace_bytes < fixed + per_ep)
@@ -467,7 +662,6 @@ lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSample
                                                   std::to_string(fixed + per_ep) + " bytes");
     const int tile = (int)std::min<size_t>(((size_t)workspace_bytes - fixed) / per_ep, (size_t)n_ep_all);
 
-    PqBuf mem;
     double *d_coef, *d_q, *d_out;
     long long* d_nv;
     int* d_orig;
@@ -500,8 +694,7 @@ lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSample
     a.hist = d_hist;
     a.search = d_search;
     a.buf = d_buf;
-    hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((in.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
-    LCF_HIP(hipGetLastError());
+    if ((st = form.prepare(mem, a, d_coef))) return st;
 
     for (int ep0 = 0; ep0 < n_ep_all; ep0 += tile) {
         const int n_ep = std::min(tile, n_ep_all - ep0);
@@ -519,7 +712,7 @@ lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSample
         a.shift = 64 - bits0;
         LCF_HIP(hipMemsetAsync(d_hist, 0, (size_t)n_ep * ((size_t)nf << bits0) * 4, 0));
         LCF_HIP(hipMemsetAsync(d_active, 0, 4, 0));
-        if ((st = run_pass(dp, a, n_ep, lds_head + ((size_t)nf << bits0) * 4))) return st;
+        if ((st = form.pass(a, n_ep, lds_head + ((size_t)nf << bits0) * 4))) return st;
         hipLaunchKernelGGL(k_pq_pick, dim3((unsigned)(n_ep * ns)), dim3(256), 0, 0, pk);
         LCF_HIP(hipGetLastError());
         // passes 1, 2, ...: the next bits of the keys under every search's prefix, while a search holds too many keys
@@ -533,7 +726,7 @@ lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSample
             a.shift = 64 - pbits - bits;
             LCF_HIP(hipMemsetAsync(d_hist, 0, (size_t)n_ep * ((size_t)ns << bits) * 4, 0));
             LCF_HIP(hipMemsetAsync(d_active, 0, 4, 0));
-            if ((st = run_pass(dp, a, n_ep, lds_head + ((size_t)ns << bits) * 4))) return st;
+            if ((st = form.pass(a, n_ep, lds_head + ((size_t)ns << bits) * 4))) return st;
             pk.bits = bits;
             pk.mode = 1;
             hipLaunchKernelGGL(k_pq_pick, dim3((unsigned)(n_ep * ns)), dim3(256), 0, 0, pk);
@@ -544,13 +737,57 @@ lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSample
         a.mode = 2;
         a.bits = 0;
         a.shift = 0;
-        if ((st = run_pass(dp, a, n_ep, lds_head))) return st;
+        if ((st = form.pass(a, n_ep, lds_head))) return st;
         hipLaunchKernelGGL(k_pq_finish, dim3((unsigned)(n_ep * ns)), dim3(256), 0, 0, d_search, d_buf,
                            d_orig + (size_t)ep0 * nf, n_q, n_points, d_out);
         LCF_HIP(hipGetLastError());
     }
     LCF_HIP(hipMemcpy(out, d_out, (size_t)n_points * n_q * sizeof(double), hipMemcpyDeviceToHost));
     LCF_HIP(hipMemcpy(n_valid, d_nv, (size_t)n_points * sizeof(long long), hipMemcpyDeviceToHost));
+    return LCF_OK;
+}
+
+}  // namespace
+
+namespace lcf {
+
+lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig_host,
+                       int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
+                       int64_t* n_valid) {
+    if (dp.n_filters * n_q > kPqMaxSearch)
+        return fail(LCF_ERR_UNSUPPORTED, "filters x percentiles of one call must not exceed 512");
+    LightCurveForm form(dp);
+    PqBuf mem;
+    return quantile_run(device, form, dp.n_epochs, dp.n_points, in, orig_host, component, q, n_q, workspace_bytes, mem,
+                        out, n_valid);
+}
+
+lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* time_orig,
+                               const double* q, int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
+                               int64_t* n_valid, int64_t* n_cold, int64_t* n_inside) {
+    if (kThSeries * n_q > kPqMaxSearch)
+        return fail(LCF_ERR_UNSUPPORTED, "3 x percentiles of one call must not exceed 512");
+    const int nt = dp.n_epochs;
+    // the three quantities take the place of a time's filters: point index = quantity * n_times + time
+    std::vector<int32_t> orig((size_t)nt * kThSeries);
+    for (int ep = 0; ep < nt; ++ep)
+        for (int f = 0; f < kThSeries; ++f) orig[(size_t)ep * kThSeries + f] = f * nt + time_orig[ep];
+    std::vector<double> by_q((size_t)n_q * kThSeries * nt);
+    ThermalForm form(dp, T_floor);
+    PqBuf mem;
+    if (lcf_status st = quantile_run(device, form, nt, (long long)kThSeries * nt, in, orig.data(), 0, q, n_q,
+                                     workspace_bytes, mem, by_q.data(), n_valid))
+        return st;
+    for (int f = 0; f < kThSeries; ++f)   // [n_q][3][n_times] -> [3][n_q][n_times]
+        for (int j = 0; j < n_q; ++j)
+            std::copy_n(&by_q[((size_t)j * kThSeries + f) * nt], nt, out + ((size_t)f * n_q + j) * nt);
+    // (the counters are per time of the engine's order: to the caller's)
+    std::vector<unsigned long long> cnt((size_t)nt * 2);
+    LCF_HIP(hipMemcpy(cnt.data(), form.th.n_cold, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int ep = 0; ep < nt; ++ep) {
+        n_cold[time_orig[ep]] = (int64_t)cnt[ep];
+        n_inside[time_orig[ep]] = (int64_t)cnt[nt + ep];
+    }
     return LCF_OK;
 }
 

@@ -142,6 +142,11 @@ SIGNATURES = [
                                         _dp, C.POINTER(C.c_int64)]),
     ('lcf_sampler_predict_quantiles', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp,
                                                 C.c_int32, C.c_int64, _dp, C.POINTER(C.c_int64)]),
+    ('lcf_predict_thermal', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, C.c_int64, _dp,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('lcf_sampler_predict_thermal', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double,
+                                              C.c_int64, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64)]),
 ]
 
 
@@ -750,3 +755,31 @@ def predict_quantiles(grid_engine, samples, percentiles, component=COMPONENT_MOD
             raise ValueError('samples must have shape (n, n_columns)')
         _check(lib.lcf_predict_quantiles(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
     return out, n_valid
+
+
+#: the series of a thermal call: T [kK], R_bb [1000 Rsun], L_bol [W]
+THERMAL_SERIES = 3
+
+
+def predict_thermal(grid_engine, samples, percentiles, T_floor=8.12, workspace_bytes=None, discard=0, thin=1):
+    """``lcf_predict_thermal`` / ``lcf_sampler_predict_thermal``: percentiles over all samples of T, R_bb and L_bol on
+    the times of ``grid_engine`` (an evaluation engine with one point per distinct time), with the validity counters.
+    ``samples`` as for :func:`predict_quantiles`; at most ``PREDICT_MAX_SEARCHES // 3`` percentiles.  Returns
+    ``(quantiles[3, n_q, n_t], n_valid[3, n_t], n_cold[n_t], n_inside[n_t])``."""
+    lib = load_library()
+    q = _f64(percentiles)
+    n_t = grid_engine.npoints
+    out = np.empty((THERMAL_SERIES, len(q), n_t))
+    n_valid = np.empty((THERMAL_SERIES, n_t), dtype=np.int64)
+    n_cold, n_inside = np.empty(n_t, dtype=np.int64), np.empty(n_t, dtype=np.int64)
+    ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    tail = (_ptr(q), len(q), float(T_floor), ws, _ptr(out)) + tuple(a.ctypes.data_as(C.POINTER(C.c_int64))
+                                                                   for a in (n_valid, n_cold, n_inside))
+    if isinstance(samples, NativeSampler):
+        _check(lib.lcf_sampler_predict_thermal(grid_engine.handle, samples._h, int(discard), int(thin), *tail))
+    else:
+        P = _f64(samples)
+        if P.ndim != 2:
+            raise ValueError('samples must have shape (n, n_columns)')
+        _check(lib.lcf_predict_thermal(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
+    return out, n_valid, n_cold, n_inside

@@ -6,13 +6,15 @@ figures only consume ``sampler.chain`` / ``sampler.flatchain``, which the return
 ``lightcurve_model_plot`` (fitting.py:337-360) are here: :func:`posterior_predictive` gives the percentile bands of
 the model light curves -- and, for the companion-shocking models, of the SiFTO term the reference draws dashed -- over
 every sample of the chain instead of 100 random draws, computed on the device without storing a value per (sample,
-grid point).
+grid point).  :func:`thermal_predictive` does the same for what those light curves are made from -- the blackbody
+temperature, radius and bolometric luminosity -- and counts, time by time, the samples that are colder than the models
+allow or outside their validity window: the check the reference's usage guide asks for after every shock-cooling fit.
 """
 import warnings
 
 import numpy as np
 
-from .models import BaseCompanionShocking, Model, UniformPrior, _column
+from .models import BaseCompanionShocking, Blackbody, Model, UniformPrior, _column
 from .filters import as_filter
 from .sampler import EnsembleSampler
 
@@ -226,6 +228,34 @@ def _predictive_samples(samples, discard, thin):
     return None, P, P.shape[0], P.shape[1]
 
 
+def _percentile_array(percentiles):
+    q = np.array(percentiles, dtype=np.float64).ravel()
+    if q.size == 0:
+        raise ValueError('percentiles must not be empty')
+    if not np.all((q >= 0.) & (q <= 100.)):
+        raise ValueError('percentiles must be in the range [0, 100]')
+    return q
+
+
+def _model_samples(model, samples, discard, thin, use_sigma):
+    """:func:`_predictive_samples` and the column count ``model`` wants: ``(sampler or None, host array or None,
+    n_samples)``."""
+    sampler, P, n_samples, n_col = _predictive_samples(samples, discard, thin)
+    want = model.n_model_params + int(bool(use_sigma))
+    if n_col != want:
+        raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
+                         + (' and one for sigma' if use_sigma else ''))
+    return sampler, P, n_samples
+
+
+def _sample_source(sampler, P, discard, thin):
+    """What the native call reads: the sampler's chain where it lies when its whole stored chain is the last run's, else
+    the host rows."""
+    if sampler is not None and not (len(sampler._chain_host) == 0 and sampler._chain_on_device > 0):
+        P, sampler = sampler.get_chain(discard=int(discard), thin=int(thin), flat=True), None
+    return sampler._native if sampler is not None else P
+
+
 def posterior_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=None, tmin=None, tmax=None,
                          num=1000, xscale='linear', filters_to_model=None, discard=0, thin=1, use_sigma=False,
                          component='model', workspace_bytes=None):
@@ -245,28 +275,18 @@ def posterior_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=
     samples stays below ``workspace_bytes`` (default 1 GiB), the times being worked through in tiles.  Results are
     bitwise reproducible and do not depend on ``workspace_bytes``.  Returns a :class:`PosteriorPredictive`."""
     from . import engine as _eng
-    q = np.array(percentiles, dtype=np.float64).ravel()
-    if q.size == 0:
-        raise ValueError('percentiles must not be empty')
-    if not np.all((q >= 0.) & (q <= 100.)):
-        raise ValueError('percentiles must be in the range [0, 100]')
+    q = _percentile_array(percentiles)
     if component not in ('model', 'sifto'):
         raise ValueError("component must be 'model' or 'sifto'")
     if component == 'sifto' and not isinstance(model, BaseCompanionShocking):
         raise ValueError("component='sifto' needs a companion-shocking model")
-    sampler, P, n_samples, n_col = _predictive_samples(samples, discard, thin)
-    want = model.n_model_params + int(bool(use_sigma))
-    if n_col != want:
-        raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
-                         + (' and one for sigma' if use_sigma else ''))
+    sampler, P, n_samples = _model_samples(model, samples, discard, thin, use_sigma)
     times, filters = predictive_grid(lc, t, tmin, tmax, num, xscale, filters_to_model)
     if len(filters) > _eng.PREDICT_MAX_SEARCHES:
         raise ValueError(f'at most {_eng.PREDICT_MAX_SEARCHES} filters')
 
     grid_engine, shape = Model._eval_engine(model, times, filters, False)   # the dense grid, filter-major
-    if sampler is not None and not (len(sampler._chain_host) == 0 and sampler._chain_on_device > 0):
-        P, sampler = sampler.get_chain(discard=int(discard), thin=int(thin), flat=True), None
-    source = sampler._native if sampler is not None else P
+    source = _sample_source(sampler, P, discard, thin)
     comp = _eng.COMPONENT_SIFTO if component == 'sifto' else _eng.COMPONENT_MODEL
     per_call = max(1, _eng.PREDICT_MAX_SEARCHES // len(filters))
     quantiles, n_valid = [], None
@@ -276,3 +296,80 @@ def posterior_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=
         quantiles.append(out)
     quantiles = np.concatenate(quantiles).reshape((len(q),) + shape)
     return PosteriorPredictive(times, filters, q, quantiles, n_valid.reshape(shape), n_samples)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# thermal bands and validity (temperature_radius over the whole chain; t_min / t_max, the 0.7 eV floor)
+# ---------------------------------------------------------------------------------------------------------------
+class ThermalPredictive:
+    """Result of :func:`thermal_predictive`: ``t`` (nt,), ``percentiles`` (nq,); ``temperature`` [kK], ``radius``
+    [1000 Rsun] and ``luminosity`` [W], each (nq, nt); ``n_valid`` (3, nt) -- the non-NaN values of the three, in that
+    order; ``n_cold`` (nt,) -- samples with a temperature below ``T_floor``; ``n_inside`` (nt,) -- samples whose validity
+    window holds the time; ``n_samples``."""
+    __slots__ = ('t', 'percentiles', 'temperature', 'radius', 'luminosity', 'n_valid', 'n_cold', 'n_inside', 'n_samples')
+
+    def __init__(self, t, percentiles, temperature, radius, luminosity, n_valid, n_cold, n_inside, n_samples):
+        self.t, self.percentiles = t, percentiles
+        self.temperature, self.radius, self.luminosity = temperature, radius, luminosity
+        self.n_valid, self.n_cold, self.n_inside = n_valid, n_cold, n_inside
+        self.n_samples = n_samples
+
+    @property
+    def frac_cold(self):
+        """Fraction of the samples with a temperature that are below the floor, per time (NaN where none has one)."""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self.n_cold / self.n_valid[0]
+
+    @property
+    def frac_inside(self):
+        """Fraction of all samples whose validity window holds the time, per time."""
+        return self.n_inside / self.n_samples
+
+    def __repr__(self):
+        return (f'<ThermalPredictive: {len(self.percentiles)} percentiles x {len(self.t)} times over '
+                f'{self.n_samples} samples>')
+
+
+def _thermal_filter(model):
+    """Any filter the model can build an engine for: the thermal state does not depend on it."""
+    f = model._any_filter()
+    if isinstance(model, BaseCompanionShocking) and f not in model.sifto:
+        f = next(iter(model.sifto))
+    return f
+
+
+def thermal_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=None, tmin=None, tmax=None,
+                       num=1000, xscale='linear', discard=0, thin=1, use_sigma=False, T_floor=8.12,
+                       workspace_bytes=None):
+    """Percentile bands of the blackbody temperature [kK], radius [1000 Rsun] and bolometric luminosity [W] behind the
+    model light curves over ALL samples of a chain, and how many samples the model is valid for, time by time.
+
+    ``samples``, ``discard``, ``thin``, ``use_sigma``, ``workspace_bytes`` and the time grid ``t`` ... ``xscale`` as in
+    :func:`posterior_predictive`.  ``model``: any of the seven reference models; for the companion-shocking models the
+    quantities are those of the shock component.  T and R are ``model.temperature_radius`` of every (sample, time)
+    pair, the luminosity ``bolometric.stefan_boltzmann(T, R)`` of that pair (not of the T and R percentiles); the
+    percentiles of each are ``np.nanpercentile(..., axis=samples)``, NaN where no sample has a value.
+
+    The models hold above ``T_floor`` (0.7 eV = 8.12 kK) and inside ``model.t_min(p) <= t <= model.t_max(p)`` (opacity
+    kappa = 1; ``ShockCooling2`` has no lower bound): ``n_cold[t]`` counts the samples with T < ``T_floor`` -- T is
+    exactly 0 before a sample's explosion time, which counts -- and ``n_inside[t]`` those whose window holds ``t``; a
+    NaN bound holds nothing.  Nothing is stored per (sample, time) and all counts are exact.  Returns a
+    :class:`ThermalPredictive`."""
+    from . import engine as _eng
+    if isinstance(model, Blackbody):
+        raise ValueError('the Blackbody model has no thermal evolution or validity window')
+    q = _percentile_array(percentiles)
+    sampler, P, n_samples = _model_samples(model, samples, discard, thin, use_sigma)
+    filt = _thermal_filter(model)
+    times, _ = predictive_grid(lc, t, tmin, tmax, num, xscale, [filt])
+    distinct, where = np.unique(times, return_inverse=True)     # the engine holds one point per distinct time
+
+    grid_engine, _ = Model._eval_engine(model, distinct, [filt] * len(distinct))
+    source = _sample_source(sampler, P, discard, thin)
+    per_call = _eng.PREDICT_MAX_SEARCHES // _eng.THERMAL_SERIES
+    parts = [_eng.predict_thermal(grid_engine, source, q[k:k + per_call], T_floor, workspace_bytes,
+                                  discard=int(discard), thin=int(thin)) for k in range(0, len(q), per_call)]
+    quantiles = np.concatenate([part[0] for part in parts], axis=1)[:, :, where]
+    _, n_valid, n_cold, n_inside = parts[0]
+    return ThermalPredictive(times, q, quantiles[0], quantiles[1], quantiles[2], n_valid[:, where], n_cold[where],
+                             n_inside[where], n_samples)
