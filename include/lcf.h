@@ -424,6 +424,35 @@ lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t
                                        int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
                                        int64_t* n_valid, int64_t* n_cold, int64_t* n_inside);
 
+/* ---- corner histograms: what corner.corner counts for lightcurve_corner (fitting.py:241-253), over ALL samples ---- */
+/* Two passes over the samples where they lie.  The range pass gives, per column, the minimum and the maximum of the
+ * non-NaN values (NaN, NaN when there is none) and the number of NaNs.  The histogram pass counts v = x[d] - shift[d]
+ * (one float64 subtraction) into `bins` bins per column whose bins + 1 edges the caller passes, ascending -- NumPy's
+ * np.linspace(lo, hi, bins + 1) for its np.histogram / np.histogram2d: bin i holds edges[i] <= v < edges[i + 1], the
+ * last bin also v == edges[bins]; a NaN, v < edges[0] or v > edges[bins] is in no bin (np.searchsorted(edges, v,
+ * 'right') - 1 with the last edge folded in).  hist1d[d][i]: column d.  hist2d[p][i][j] for the pair p = a (a - 1) / 2
+ * + b of columns b < a: the samples with column b in bin i AND column a in bin j -- H of np.histogram2d(x[:, b],
+ * x[:, a]), the panel in row a, column b of the figure; a sample enters only with both coordinates in a bin.  All
+ * counts are exact integers and do not depend on how the samples are split over workgroups.
+ * 1 <= n_dim <= 16, 1 <= bins <= 128; hist2d may be NULL when n_dim == 1.
+ * Over n host samples P[n][ld] (the first n_dim columns): */
+lcf_status lcf_chain_range(int32_t device, const double* P, int64_t n, int32_t ld, int32_t n_dim,
+                           double* lo /* [n_dim] */, double* hi /* [n_dim] */, int64_t* n_nan /* [n_dim] */);
+lcf_status lcf_chain_hist(int32_t device, const double* P, int64_t n, int32_t ld, int32_t n_dim,
+                          const double* shift /* [n_dim] */, const double* edges /* [n_dim][bins + 1] */, int32_t bins,
+                          int64_t* hist1d /* [n_dim][bins] */, int64_t* hist2d /* [n_pairs][bins][bins] */);
+/* The same over rows discard, discard + thin, ... of the last stored run of n_samplers samplers (one device), read in
+ * place, in one sequence of launches; every walker of a kept step is a sample and every column of the chain is
+ * counted.  Each sampler has its own n_dim, shift and edges; inputs and outputs of the samplers lie one after another
+ * (lo / hi / n_nan / shift: n_dim entries each, edges: n_dim (bins + 1), hist1d: n_dim bins, hist2d: n_dim (n_dim -
+ * 1) / 2 bins^2).  LCF_ERR_STATE when a sampler has no stored chain, LCF_ERR_INVALID_ARGUMENT for discard past the
+ * chain, LCF_ERR_UNSUPPORTED when the samplers are on different devices. */
+lcf_status lcf_samplers_chain_range(lcf_sampler** samplers, int32_t n_samplers, int64_t discard, int64_t thin,
+                                    double* lo, double* hi, int64_t* n_nan);
+lcf_status lcf_samplers_chain_hist(lcf_sampler** samplers, int32_t n_samplers, int64_t discard, int64_t thin,
+                                   const double* shift, const double* edges, int32_t bins, int64_t* hist1d,
+                                   int64_t* hist2d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,4 +140,16 @@ lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const Predi
                                const double* q, int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
                                int64_t* n_valid, int64_t* n_cold, int64_t* n_inside);
 
+// Corner histograms (lcf_corner.hip): per entry of `in`, n samples of n_dim columns in device memory, sample s being
+// the ld-strided row at base + (s / n_w) * step_stride + (s % n_w) * ld.  Inputs and outputs (host) hold the entries'
+// parts one after another, as lcf_samplers_chain_range / lcf_samplers_chain_hist describe them.
+struct CornerSamples {
+    const double* base;
+    int64_t n, n_w, step_stride;
+    int32_t ld, n_dim;
+};
+lcf_status corner_range_run(int32_t device, const CornerSamples* in, int32_t n, double* lo, double* hi, int64_t* n_nan);
+lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, const double* shift, const double* edges,
+                           int32_t bins, int64_t* hist1d, int64_t* hist2d);
+
 }  // namespace lcf

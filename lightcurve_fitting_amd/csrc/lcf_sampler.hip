@@ -920,6 +920,43 @@ lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discar
     return autocorr_run(s[0]->e->device, series.data(), n, c, tau, window);
 }
 
+// Rows discard, discard + thin, ... of every sampler's last stored run as the samples of a corner pass, where they lie.
+static lcf_status corner_samples(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin,
+                                 std::vector<CornerSamples>* in) {
+    if (!s || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
+    for (int32_t i = 0; i < n; ++i) {
+        if (!s[i]) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
+        if (!s[i]->ds.store_chain || s[i]->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
+        if (discard >= s[i]->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
+        if (s[i]->e->device != s[0]->e->device) return fail(LCF_ERR_UNSUPPORTED, "the samplers are on different devices");
+    }
+    in->resize(n);
+    for (int32_t i = 0; i < n; ++i) {
+        if (lcf_status st = settle(s[i])) return st;  // (the trailing commit writes the last chain row)
+        const DevSampler& ds = s[i]->ds;
+        const int64_t row = (int64_t)ds.n_walkers * ds.n_dim, steps = (s[i]->run_steps - discard + thin - 1) / thin;
+        (*in)[i] = CornerSamples{ds.chain + discard * row, steps * ds.n_walkers, ds.n_walkers, thin * row, ds.n_dim,
+                                 ds.n_dim};
+    }
+    return LCF_OK;
+}
+
+lcf_status lcf_samplers_chain_range(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double* lo, double* hi,
+                                    int64_t* n_nan) {
+    if (!lo || !hi || !n_nan) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<CornerSamples> in;
+    if (lcf_status st = corner_samples(s, n, discard, thin, &in)) return st;
+    return corner_range_run(s[0]->e->device, in.data(), n, lo, hi, n_nan);
+}
+
+lcf_status lcf_samplers_chain_hist(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, const double* shift,
+                                   const double* edges, int32_t bins, int64_t* hist1d, int64_t* hist2d) {
+    std::vector<CornerSamples> in;
+    if (lcf_status st = corner_samples(s, n, discard, thin, &in)) return st;
+    return corner_hist_run(s[0]->e->device, in.data(), n, shift, edges, bins, hist1d, hist2d);
+}
+
 lcf_status lcf_sampler_get_naccepted(lcf_sampler* s, int64_t* n_accepted) {
     if (!s || !n_accepted) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = settle(s)) return st;

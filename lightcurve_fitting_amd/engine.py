@@ -147,6 +147,13 @@ SIGNATURES = [
     ('lcf_sampler_predict_thermal', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double,
                                               C.c_int64, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                               C.POINTER(C.c_int64)]),
+    ('lcf_chain_range', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]),
+    ('lcf_chain_hist', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.c_int32,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('lcf_samplers_chain_range', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, _dp, _dp,
+                                           C.POINTER(C.c_int64)]),
+    ('lcf_samplers_chain_hist', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_int32,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]
 
 
@@ -783,3 +790,81 @@ def predict_thermal(grid_engine, samples, percentiles, T_floor=8.12, workspace_b
             raise ValueError('samples must have shape (n, n_columns)')
         _check(lib.lcf_predict_thermal(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
     return out, n_valid, n_cold, n_inside
+
+
+#: limits of the corner entry points (include/lcf.h)
+CORNER_MAX_DIM, CORNER_MAX_BINS = 16, 128
+
+
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _corner_sources(samples, device):
+    """``(native samplers or None, host array or None, column counts)`` of what a corner call reads: one host array
+    (n, n_columns), one :class:`NativeSampler` or a list of them."""
+    if isinstance(samples, NativeSampler):
+        samples = [samples]
+    if isinstance(samples, (list, tuple)) and samples and all(isinstance(s, NativeSampler) for s in samples):
+        return list(samples), None, [s.ndim for s in samples]
+    P = _f64(samples)
+    if P.ndim != 2:
+        raise ValueError('samples must have shape (n, n_columns)')
+    return None, P, [P.shape[1]]
+
+
+def chain_range(samples, discard=0, thin=1, device=0):
+    """``lcf_chain_range`` / ``lcf_samplers_chain_range``: per column the minimum and maximum of the non-NaN values
+    (NaN, NaN where there is none) and the number of NaNs.  ``samples``: a host array (n, n_columns), or one
+    :class:`NativeSampler` or a list of them (one device) whose last stored runs are read in place (rows
+    ``discard::thin``).  Returns ``(lo, hi, n_nan)``, or a list of such triples for a list of samplers."""
+    lib = load_library()
+    natives, P, dims = _corner_sources(samples, device)
+    total = sum(dims)
+    lo, hi, n_nan = np.empty(total), np.empty(total), np.empty(total, dtype=np.int64)
+    if natives is None:
+        _check(lib.lcf_chain_range(int(device), _ptr(P), P.shape[0], P.shape[1], P.shape[1], _ptr(lo), _ptr(hi),
+                                   _i64p(n_nan)))
+        return lo, hi, n_nan
+    arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
+    _check(lib.lcf_samplers_chain_range(arr, len(natives), int(discard), int(thin), _ptr(lo), _ptr(hi), _i64p(n_nan)))
+    at = np.concatenate([[0], np.cumsum(dims)])
+    out = [(lo[i:j].copy(), hi[i:j].copy(), n_nan[i:j].copy()) for i, j in zip(at[:-1], at[1:])]
+    return out if isinstance(samples, (list, tuple)) else out[0]
+
+
+def chain_hist(samples, shift, edges, discard=0, thin=1, device=0):
+    """``lcf_chain_hist`` / ``lcf_samplers_chain_hist``: the histogram of every column of ``x - shift`` and the joint
+    histogram of every pair of columns on the bin ``edges`` (n_columns, bins + 1) -- NumPy's bins for
+    ``np.linspace(lo, hi, bins + 1)``.  ``samples`` as for :func:`chain_range`; for a list of samplers ``shift`` and
+    ``edges`` are lists with one entry per sampler (the same ``bins`` in all).  Returns ``(hist1d[n_columns, bins],
+    hist2d[n_pairs, bins, bins])``, int64, the pair of columns ``b < a`` at index ``a (a - 1) / 2 + b`` with the bins
+    of ``b`` on the first axis -- ``np.histogram2d(x[:, b], x[:, a])[0]`` -- or a list of such tuples."""
+    lib = load_library()
+    natives, P, dims = _corner_sources(samples, device)
+    many = isinstance(samples, (list, tuple))
+    shifts = [_f64(v).ravel() for v in (shift if many else [shift])]
+    tables = [_f64(e) for e in (edges if many else [edges])]
+    if len(shifts) != len(dims) or len(tables) != len(dims):
+        raise ValueError('shift and edges need one entry per sampler')
+    bins = tables[0].shape[-1] - 1 if tables[0].ndim == 2 else -1
+    for n_dim, sh, e in zip(dims, shifts, tables):
+        if sh.shape != (n_dim,) or e.shape != (n_dim, bins + 1):
+            raise ValueError('shift must have shape (n_columns,) and edges (n_columns, bins + 1)')
+    pairs = [d * (d - 1) // 2 for d in dims]
+    sh, ed = np.concatenate(shifts), np.concatenate([e.ravel() for e in tables])
+    h1 = np.zeros(sum(dims) * bins, dtype=np.int64)
+    h2 = np.zeros(sum(pairs) * bins * bins, dtype=np.int64)
+    h2p = _i64p(h2) if h2.size else None
+    if natives is None:
+        _check(lib.lcf_chain_hist(int(device), _ptr(P), P.shape[0], P.shape[1], P.shape[1], _ptr(sh), _ptr(ed), bins,
+                                  _i64p(h1), h2p))
+    else:
+        arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
+        _check(lib.lcf_samplers_chain_hist(arr, len(natives), int(discard), int(thin), _ptr(sh), _ptr(ed), bins,
+                                           _i64p(h1), h2p))
+    out, i, j = [], 0, 0
+    for d, p in zip(dims, pairs):
+        out.append((h1[i:i + d * bins].reshape(d, bins).copy(), h2[j:j + p * bins * bins].reshape(p, bins, bins).copy()))
+        i, j = i + d * bins, j + p * bins * bins
+    return out if many else out[0]

@@ -9,6 +9,9 @@ every sample of the chain instead of 100 random draws, computed on the device wi
 grid point).  :func:`thermal_predictive` does the same for what those light curves are made from -- the blackbody
 temperature, radius and bolometric luminosity -- and counts, time by time, the samples that are colder than the models
 allow or outside their validity window: the check the reference's usage guide asks for after every shock-cooling fit.
+The numbers behind ``lightcurve_corner`` (fitting.py:241-253) are :func:`posterior_corner`: the marginal histogram of
+every parameter, the joint histogram of every pair and the counts of the contour levels, with the reference's ``t_0``
+offset, counted on the device over every sample.
 """
 import warnings
 
@@ -373,3 +376,191 @@ def thermal_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=No
     _, n_valid, n_cold, n_inside = parts[0]
     return ThermalPredictive(times, q, quantiles[0], quantiles[1], quantiles[2], n_valid[:, where], n_cold[where],
                              n_inside[where], n_samples)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# corner histograms (what corner.corner counts for lightcurve_corner, fitting.py:241-253, over the whole chain)
+# ---------------------------------------------------------------------------------------------------------------
+#: corner.hist2d's default contour levels: the mass inside 0.5, 1, 1.5 and 2 sigma of a two-dimensional Gaussian
+CORNER_LEVELS = tuple(1. - np.exp(-0.5 * np.arange(0.5, 2.1, 0.5) ** 2))
+#: the columns lightcurve_corner shifts by ``t0_offset`` (fitting.py:243)
+CORNER_TIME_NAMES = ('t_0', 't_\\mathrm{max}')
+
+
+class CornerData:
+    """Result of :func:`posterior_corner` for P columns: ``names`` and ``labels`` (P strings each), ``offsets`` (P,) --
+    what was subtracted from each column -- ``range`` (P, 2) and ``edges`` (P, bins + 1) in shifted coordinates,
+    ``hist1d`` (P, bins) and ``hist2d`` (P, P, bins, bins), int64 -- ``hist2d[a, b]`` for ``b < a`` is
+    ``np.histogram2d(x[:, b], x[:, a])[0]``, the panel in row ``a``, column ``b`` of the figure, zero elsewhere --
+    ``levels`` (n_levels,), ``contour_levels`` (P, P, n_levels) -- the counts at which the contours of that panel are
+    drawn, NaN where there is no panel or no sample in it -- ``n_samples`` and ``n_nan`` (P,)."""
+    __slots__ = ('names', 'labels', 'offsets', 'range', 'edges', 'hist1d', 'hist2d', 'levels', 'contour_levels',
+                 'n_samples', 'n_nan')
+
+    def __init__(self, names, labels, offsets, range, edges, hist1d, hist2d, levels, contour_levels, n_samples, n_nan):
+        self.names, self.labels, self.offsets, self.range, self.edges = names, labels, offsets, range, edges
+        self.hist1d, self.hist2d, self.levels, self.contour_levels = hist1d, hist2d, levels, contour_levels
+        self.n_samples, self.n_nan = n_samples, n_nan
+
+    def pair(self, a, b):
+        """``(H, x_edges, y_edges, V)`` of the panel with column ``b`` on the horizontal and column ``a`` on the vertical
+        axis, ``a != b`` in either order: ``H[i, j]`` counts the samples with column ``b`` in bin ``i`` and column ``a``
+        in bin ``j`` (``np.histogram2d(x[:, b], x[:, a])``), ``V`` the counts of the contour levels."""
+        n = len(self.names)
+        a, b = int(a), int(b)
+        if not (0 <= a < n and 0 <= b < n) or a == b:
+            raise IndexError(f'pair({a}, {b}): need two different columns below {n}')
+        if b < a:
+            return self.hist2d[a, b], self.edges[b], self.edges[a], self.contour_levels[a, b]
+        return self.hist2d[b, a].T, self.edges[b], self.edges[a], self.contour_levels[b, a]
+
+    def __repr__(self):
+        return (f'<CornerData: {len(self.names)} columns x {self.hist1d.shape[1]} bins over {self.n_samples} samples>')
+
+
+def corner_contour_levels(H, levels=CORNER_LEVELS):
+    """The counts at which ``corner.hist2d`` draws the contours that enclose the fractions ``levels`` of the samples
+    of a two-dimensional histogram ``H``: flatten ``H`` and sort it descending, take the cumulative sum normalised to 1,
+    and let ``V[i]`` be the last sorted count whose cumulative share is ``<= levels[i]`` -- the largest count if none
+    is; sort ``V``, multiply the first of two equal neighbours by ``1 - 1e-4`` for as long as there are any, and sort
+    again.  NaN for every level when ``H`` is empty."""
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    Hflat = np.sort(np.asarray(H, dtype=np.float64).ravel())[::-1]
+    total = Hflat.sum()
+    if not total > 0.:
+        return np.full(len(levels), np.nan)
+    sm = np.cumsum(Hflat) / total
+    V = np.empty(len(levels))
+    for i, v0 in enumerate(levels):
+        inside = Hflat[sm <= v0]
+        V[i] = inside[-1] if len(inside) else Hflat[0]
+    V.sort()
+    m = np.diff(V) == 0
+    while np.any(m):
+        V[np.where(m)[0][0]] *= 1. - 1e-4
+        m = np.diff(V) == 0
+    V.sort()
+    return V
+
+
+class _CornerPlan:
+    """What :func:`posterior_corner` settles before the device is touched: names, labels, bins, levels, the time columns
+    and the caller's ranges; then, from the columns' extremes, the offsets, ranges and edges."""
+
+    def __init__(self, model, n_col, bins, range, levels, t0_offset, use_sigma):
+        from . import engine as _eng
+        if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= _eng.CORNER_MAX_BINS:
+            raise ValueError(f'bins must be an integer from 1 to {_eng.CORNER_MAX_BINS}')
+        self.bins = int(bins)
+        if model is None:
+            self.names = [f'p{i}' for i in np.arange(n_col)]
+            self.labels = list(self.names)
+            if t0_offset is not None:
+                raise ValueError('t0_offset needs a model: without one no column is known to be a time')
+        else:
+            want = model.n_model_params + int(bool(use_sigma))
+            if n_col != want:
+                raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
+                                 + (' and one for sigma' if use_sigma else ''))
+            self.names = list(type(model).input_names) + (['\\sigma'] if use_sigma else [])
+            units = list(type(model).units) + ([''] if use_sigma else [])
+            self.labels = ['${}$ ({})'.format(var, unit) if unit else '${}$'.format(var)
+                           for var, unit in zip(self.names, units)]
+        if not 1 <= n_col <= _eng.CORNER_MAX_DIM:
+            raise ValueError(f'the samples must have from 1 to {_eng.CORNER_MAX_DIM} columns')
+        self.time_columns = [self.names.index(var) for var in CORNER_TIME_NAMES if var in self.names] \
+            if model is not None else []
+        if t0_offset is not None and not np.isfinite(t0_offset):
+            raise ValueError('t0_offset must be finite')
+        self.t0_offset = None if t0_offset is None else float(t0_offset)
+        self.levels = np.array(CORNER_LEVELS if levels is None else levels, dtype=np.float64).ravel()
+        if self.levels.size == 0 or not np.all((self.levels > 0.) & (self.levels <= 1.)):
+            raise ValueError('levels must be fractions in (0, 1]')
+        self.user_range = [None] * n_col
+        if range is not None:
+            if len(range) != n_col:
+                raise ValueError(f'range needs one entry per column: {n_col}, got {len(range)}')
+            for d, r in enumerate(range):
+                if r is None:
+                    continue
+                lo, hi = (float(v) for v in r)
+                if not (np.isfinite(lo) and np.isfinite(hi)) or hi < lo:
+                    raise ValueError(f'range of column {d} ({self.names[d]}): need finite lo <= hi')
+                self._refuse_degenerate(d, lo, hi)
+                self.user_range[d] = (lo, hi)
+
+    def _refuse_degenerate(self, d, lo, hi):
+        if lo == hi:   # corner: "It looks like the parameter(s) in column(s) ... have no dynamic range."
+            raise ValueError(f'column {d} ({self.names[d]}) has no dynamic range: its range is ({lo}, {hi})')
+
+    def settle(self, lo, hi):
+        """``(offsets, range, edges, labels)`` from the columns' smallest and largest non-NaN values ``lo``, ``hi``
+        (unshifted).  The offset is the reference's: for each time column in turn, the floor of the first one's
+        minimum unless the caller gave it; subtracted, and written into the label, where it is not zero."""
+        n_col = len(self.names)
+        offsets, labels, t0 = np.zeros(n_col), list(self.labels), self.t0_offset
+        for var, i in zip([v for v in CORNER_TIME_NAMES if v in self.names], self.time_columns):
+            if t0 is None:
+                t0 = np.floor(lo[i])
+                if not np.isfinite(t0):
+                    raise ValueError(f'column {i} ({var}) has no finite minimum to take t0_offset from')
+            if t0 != 0.:
+                offsets[i] = t0
+                formatted = '{:f}'.format(t0).rstrip('0').rstrip('.')
+                labels[i] = f'${var} - {formatted}$ (d)'
+        rng = np.empty((n_col, 2))
+        for d in np.arange(n_col):
+            if self.user_range[d] is not None:
+                rng[d] = self.user_range[d]
+                continue
+            rng[d] = lo[d] - offsets[d], hi[d] - offsets[d]   # (rounding is monotone: the extremes of x - offset)
+            if not np.all(np.isfinite(rng[d])):
+                raise ValueError(f'column {d} ({self.names[d]}) has no finite range: ({rng[d, 0]}, {rng[d, 1]})')
+            self._refuse_degenerate(d, rng[d, 0], rng[d, 1])
+        edges = np.array([np.linspace(r[0], r[1], self.bins + 1) for r in rng])
+        return offsets, rng, edges, labels
+
+    def data(self, offsets, rng, edges, labels, hist1d, pairs, n_samples, n_nan):
+        n_col, n_lev = len(self.names), len(self.levels)
+        hist2d = np.zeros((n_col, n_col, self.bins, self.bins), dtype=np.int64)
+        contours = np.full((n_col, n_col, n_lev), np.nan)
+        for a in np.arange(1, n_col):
+            for b in np.arange(a):
+                hist2d[a, b] = pairs[a * (a - 1) // 2 + b]
+                contours[a, b] = corner_contour_levels(hist2d[a, b], self.levels)
+        return CornerData(self.names, labels, offsets, rng, edges, hist1d, hist2d, self.levels, contours, n_samples,
+                          n_nan)
+
+
+def posterior_corner(model, samples, bins=20, range=None, levels=None, t0_offset=None, discard=0, thin=1,
+                     use_sigma=False):
+    """Every histogram of the corner plot of ``lightcurve_corner`` (fitting.py:241-253) over ALL samples of a chain:
+    the marginal histogram of every column, the joint histogram of every pair of columns and the counts at which the
+    contours of each pair are drawn.  Drawing them is left to the caller.
+
+    ``samples``, ``discard``, ``thin`` as in :func:`posterior_predictive`: a sampler's chain is read where it lies in
+    device memory when the whole stored chain is the last run's, else uploaded from ``get_chain``; or a host array
+    ``(n_samples, n_columns)``.  ``model``: the fitted model -- its parameter names and axis labels, with
+    ``'\\sigma'`` for the last column if ``use_sigma`` -- or ``None``: columns ``p0, p1, ...``, no offset.
+
+    ``t0_offset`` (fitting.py:241-251): the columns named ``t_0`` and ``t_\\mathrm{max}`` are counted as
+    ``x - t0_offset``, by default the floor of the minimum of the first of them; where it is not zero the axis label
+    becomes ``$t_0 - <offset>$ (d)``.  ``range``: per column ``None`` -- the smallest and largest non-NaN shifted
+    value, corner's default -- or ``(lo, hi)`` in shifted coordinates; a column without dynamic range raises
+    ``ValueError``, as corner refuses it.  The bins are NumPy's for ``np.linspace(lo, hi, bins + 1)``: bin ``i`` holds
+    ``edges[i] <= v < edges[i + 1]``, the last also ``v == hi``; NaNs (``n_nan`` per column) and values outside the
+    range are in no bin, and a sample enters a pair's histogram only with both coordinates in a bin.  Every count
+    equals ``np.histogram`` / ``np.histogram2d`` on the same samples.
+
+    ``levels``: the fractions of the samples the contours enclose, default ``1 - exp(-0.5 [0.5, 1, 1.5, 2]^2)``; their
+    counts per pair follow ``corner.hist2d`` (:func:`corner_contour_levels`).  No smoothing, no weights.  Returns a
+    :class:`CornerData`."""
+    from . import engine as _eng
+    sampler, P, n_samples, n_col = _predictive_samples(samples, discard, thin)
+    plan = _CornerPlan(model, n_col, bins, range, levels, t0_offset, use_sigma)
+    source = _sample_source(sampler, P, discard, thin)
+    kw = dict(discard=int(discard), thin=int(thin), device=0 if model is None else model.device)
+    lo, hi, n_nan = _eng.chain_range(source, **kw)
+    offsets, rng, edges, labels = plan.settle(lo, hi)
+    hist1d, pairs = _eng.chain_hist(source, offsets, edges, **kw)
+    return plan.data(offsets, rng, edges, labels, hist1d, pairs, n_samples, n_nan)

@@ -274,6 +274,48 @@ class PopulationSampler:
             raise AutocorrError(raw, '\n'.join(msgs))
         return taus
 
+    def corner(self, models=None, bins=20, range=None, levels=None, t0_offset=None, discard=0, thin=1, use_sigma=None):
+        """``{index: CornerData}`` of this rank's transients, each as :func:`~lightcurve_fitting_amd.fitting.
+        posterior_corner` gives it; the chains still on the device go through one native call per pass together.
+        ``models``: index -> the transient's model (mapping or sequence), or None (columns ``p0, p1, ...``).  ``range``,
+        ``t0_offset`` and ``use_sigma`` hold for every transient, or are dicts index -> value; ``use_sigma=None``: a
+        chain with one column more than its model has parameters carries sigma."""
+        from .engine import chain_hist, chain_range
+        from .fitting import _CornerPlan, posterior_corner
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+
+        def pick(value, k):
+            return value.get(k) if isinstance(value, dict) else value
+        plans, n_samples = {}, {}
+        for k, s in self.samplers.items():
+            model = None if models is None else models[k]
+            sigma = pick(use_sigma, k)
+            if sigma is None:
+                sigma = model is not None and s.ndim == model.n_model_params + 1
+            plans[k] = (model, sigma, _CornerPlan(model, s.ndim, bins, pick(range, k), levels, pick(t0_offset, k), sigma))
+            if s.iteration == 0:
+                raise ValueError(f'no chain is stored (transient {k}): run the sampler with store=True first')
+            if discard >= s.iteration:
+                raise ValueError(f'discard={discard} leaves no steps of the {s.iteration} stored (transient {k})')
+            n_samples[k] = (s.iteration - discard + thin - 1) // thin * s.nwalkers
+        resident = [k for k, s in self.samplers.items() if len(s._chain_host) == 0 and s._chain_on_device > 0]
+        out = {}
+        for k, s in self.samplers.items():
+            if k not in resident:
+                model, sigma, _ = plans[k]
+                out[k] = posterior_corner(model, s, bins=bins, range=pick(range, k), levels=levels,
+                                          t0_offset=pick(t0_offset, k), discard=discard, thin=thin, use_sigma=sigma)
+        if resident:
+            natives = [self.samplers[k]._native for k in resident]
+            extremes = chain_range(natives, discard, thin)
+            settled = [plans[k][2].settle(lo, hi) for k, (lo, hi, _) in zip(resident, extremes)]
+            counts = chain_hist(natives, [st[0] for st in settled], [st[2] for st in settled], discard, thin)
+            for k, st, (_, _, n_nan), (hist1d, pairs) in zip(resident, settled, extremes, counts):
+                out[k] = plans[k][2].data(*st, hist1d, pairs, n_samples[k], n_nan)
+        return {k: out[k] for k in self.samplers}
+
     def __getitem__(self, k):
         return self.samplers[k]
 
