@@ -453,6 +453,46 @@ lcf_status lcf_samplers_chain_hist(lcf_sampler** samplers, int32_t n_samplers, i
                                    const double* shift, const double* edges, int32_t bins, int64_t* hist1d,
                                    int64_t* hist2d);
 
+/* ---- chain history: the numbers of the chain plots of lightcurve_mcmc(show=True) (fitting.py:135-158) -------------- */
+/* From a stored chain[n_t][n_w][n_dim] and its log-probabilities log_prob[n_t][n_w].  The kept steps are k = 0 ..
+ * n_keep - 1 at stored step t_k = discard + k thin, n_keep = ceil((n_t - discard) / thin).
+ * Ensemble bands: for every kept step and every column c -- c < n_dim a column of the chain, c == n_dim the
+ * log-probability -- the values of the n_w walkers are ordered (-inf < ... < -0 < +0 < ... < +inf, infinities being
+ * ordinary values; NaNs last, n_valid[k][c] values are none).  For each percentile q[i] in [0, 100]: h = (n_valid - 1)
+ * (q[i] / 100), lo = floor(h), hi = min(lo + 1, n_valid - 1); stat_lo[i][k][c] and stat_hi[i][k][c] are the order
+ * statistics of rank lo and hi, copies of input values.  The percentile is the caller's to interpolate, stat_lo +
+ * (h - lo) (stat_hi - stat_lo) evaluated as NumPy evaluates it (np.nanpercentile, default method); the library does
+ * not, because its arithmetic is contracted and would round differently.  n_valid == 0: both are NaN.  A NULL log_prob:
+ * column n_dim has n_valid 0 and NaNs.
+ * Moves: n_moved[k] is the number of walkers whose row at stored step t_k differs from their row at stored step t_k - 1
+ * -- the step before in the STORED chain, not the kept step before -- two rows differing when the 64-bit pattern of
+ * any column does (-0 and +0 differ; a NaN equals itself); -1 for t_k == 0, whose predecessor is not in the chain.  It
+ * is the number of proposals accepted in that step.
+ * Trace density: counts[d][i][j] is the number of (kept step k, walker) pairs with (k t_bins) / n_keep == i (integer
+ * division) whose value in column d is in bin j of the v_bins bins between the ascending edges[d][0 .. v_bins]; bin
+ * membership is that of lcf_chain_hist (edges[j] <= v < edges[j + 1], the last bin closed; a NaN and a value outside
+ * are in no bin); no shift is applied.  Columns of the chain only.
+ * All results are exact, bitwise reproducible and independent of how the work is split.
+ * 1 <= n_dim <= 16, 1 <= n_q <= 16, 1 <= v_bins <= 256, 1 <= t_bins <= min(n_keep, 4096); n_w > 16384 is
+ * LCF_ERR_UNSUPPORTED.  Over a host chain (uploaded whole, so that the first kept step has its predecessor, and freed): */
+lcf_status lcf_chain_history(int32_t device, const double* chain, const double* log_prob /* or NULL */, int64_t n_t,
+                             int32_t n_w, int32_t n_dim, int64_t discard, int64_t thin, const double* q, int32_t n_q,
+                             double* stat_lo, double* stat_hi /* [n_q][n_keep][n_dim + 1] */,
+                             int64_t* n_valid /* [n_keep][n_dim + 1] */, int64_t* n_moved /* [n_keep] */);
+lcf_status lcf_chain_raster(int32_t device, const double* chain, int64_t n_t, int32_t n_w, int32_t n_dim,
+                            int64_t discard, int64_t thin, int32_t t_bins,
+                            const double* edges /* [n_dim][v_bins + 1] */, int32_t v_bins,
+                            int64_t* counts /* [n_dim][t_bins][v_bins] */);
+/* The same over the last stored run of n_samplers samplers (one device), chain and log-probabilities read in place, in
+ * one sequence of launches.  Each sampler has its own n_dim, n_keep and edges; inputs and outputs of the samplers lie
+ * one after another (stat_lo / stat_hi: n_q n_keep (n_dim + 1) entries each, n_valid: n_keep (n_dim + 1), n_moved:
+ * n_keep, edges: n_dim (v_bins + 1), counts: n_dim t_bins v_bins).  Status codes as for lcf_samplers_chain_range. */
+lcf_status lcf_samplers_chain_history(lcf_sampler** samplers, int32_t n_samplers, int64_t discard, int64_t thin,
+                                      const double* q, int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
+                                      int64_t* n_moved);
+lcf_status lcf_samplers_chain_raster(lcf_sampler** samplers, int32_t n_samplers, int64_t discard, int64_t thin,
+                                     int32_t t_bins, const double* edges, int32_t v_bins, int64_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

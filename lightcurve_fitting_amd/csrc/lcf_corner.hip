@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "lcf.h"
+#include "lcf_corner.h"
 #include "lcf_host.h"
 
 using namespace lcf;
@@ -52,17 +53,6 @@ struct CornerSeg {
     unsigned long long *h1, *h2;               // [n_dim][bins], [n_pairs][bins][bins]
     int bins, n_pairs, group_pairs;
 };
-
-// doubles ordered as unsigned integers (-inf < ... < -0 < +0 < ... < +inf)
-__host__ __device__ __forceinline__ unsigned long long corner_key(unsigned long long b) {
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-inline double corner_value(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    std::memcpy(&v, &b, sizeof v);
-    return v;
-}
 
 __device__ __forceinline__ const double* corner_row(const CornerSeg& sg, long long s) {
     if (sg.n_w == sg.n) return sg.base + s * sg.ld;   // (one block of rows: a host array, or a chain with thin = 1)
@@ -114,19 +104,6 @@ __global__ __launch_bounds__(kCornerThreads) void k_corner_range(const CornerSeg
     }
 }
 
-// The bin of v among the ascending edges e[0 .. bins]: the largest i with e[i] <= v, the last edge belonging to the last
-// bin -- np.searchsorted(e, v, 'right') - 1 with e[bins] folded in; kNoBin for a NaN and outside [e[0], e[bins]].  The
-// guess is np.histogram's (multiply and truncate); the edge table decides.
-__device__ __forceinline__ unsigned int corner_bin(const double* __restrict__ e, int bins, double v) {
-    const double lo = e[0], hi = e[bins];
-    if (!(v >= lo && v <= hi)) return kNoBin;
-    const double g = (v - lo) * ((double)bins / (hi - lo));
-    int i = g >= 0. && g < (double)bins ? (int)g : g >= (double)bins ? bins - 1 : 0;
-    while (i > 0 && v < e[i]) --i;
-    while (i < bins - 1 && v >= e[i + 1]) ++i;
-    return (unsigned int)i;
-}
-
 // byte d of the packed bin numbers (d is wave-uniform)
 __device__ __forceinline__ unsigned int corner_byte(unsigned long long lo, unsigned long long hi, int d) {
     return (unsigned int)((d < 8 ? lo >> (8 * d) : hi >> (8 * (d - 8))) & 0xffull);
@@ -154,7 +131,7 @@ __global__ __launch_bounds__(kCornerThreads) void k_corner_hist(const CornerSeg*
         const double* row = corner_row(sg, s);
         unsigned long long lo = 0ull, hi = 0ull;   // the row's bin numbers, a byte per column
         for (int d = 0; d < nd; ++d) {
-            const unsigned int bin = corner_bin(sg.edges + (size_t)d * (bins + 1), bins, row[d] - sg.shift[d]);
+            const unsigned int bin = corner_bin<kNoBin>(sg.edges + (size_t)d * (bins + 1), bins, row[d] - sg.shift[d]);
             if (group == 0 && bin < (unsigned int)bins) atomicAdd(&cnt[d * bins + (int)bin], 1u);
             if (d < 8)
                 lo |= (unsigned long long)bin << (8 * d);

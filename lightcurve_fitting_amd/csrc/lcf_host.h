@@ -152,4 +152,18 @@ lcf_status corner_range_run(int32_t device, const CornerSamples* in, int32_t n, 
 lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, const double* shift, const double* edges,
                            int32_t bins, int64_t* hist1d, int64_t* hist2d);
 
+// Chain history (lcf_history.hip): per entry of `in`, a whole stored chain [n_t][n_w][n_dim] and its log-probabilities
+// [n_t][n_w] (or nullptr) in device memory; the kept steps are discard, discard + thin, ...  Inputs and outputs (host)
+// hold the entries' parts one after another, as lcf_samplers_chain_history / lcf_samplers_chain_raster describe them.
+struct HistoryChain {
+    const double *chain, *log_prob;
+    int64_t n_t;
+    int32_t n_w, n_dim;
+};
+lcf_status history_steps_run(int32_t device, const HistoryChain* in, int32_t n, int64_t discard, int64_t thin,
+                             const double* q, int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
+                             int64_t* n_moved);
+lcf_status history_raster_run(int32_t device, const HistoryChain* in, int32_t n, int64_t discard, int64_t thin,
+                              int32_t t_bins, const double* edges, int32_t v_bins, int64_t* counts);
+
 }  // namespace lcf

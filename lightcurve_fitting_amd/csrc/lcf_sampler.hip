@@ -957,6 +957,34 @@ lcf_status lcf_samplers_chain_hist(lcf_sampler** s, int32_t n, int64_t discard, 
     return corner_hist_run(s[0]->e->device, in.data(), n, shift, edges, bins, hist1d, hist2d);
 }
 
+// Every sampler's last stored run, whole, as the chains of a history pass, where they lie.
+static lcf_status history_chains(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin,
+                                 std::vector<HistoryChain>* in) {
+    std::vector<CornerSamples> rows;   // (the checks, the status codes and the settling of corner_samples)
+    if (lcf_status st = corner_samples(s, n, discard, thin, &rows)) return st;
+    in->resize(n);
+    for (int32_t i = 0; i < n; ++i) {
+        const DevSampler& ds = s[i]->ds;
+        (*in)[i] = HistoryChain{ds.chain, ds.chain_lp, s[i]->run_steps, ds.n_walkers, ds.n_dim};
+    }
+    return LCF_OK;
+}
+
+lcf_status lcf_samplers_chain_history(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, const double* q,
+                                      int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
+                                      int64_t* n_moved) {
+    std::vector<HistoryChain> in;
+    if (lcf_status st = history_chains(s, n, discard, thin, &in)) return st;
+    return history_steps_run(s[0]->e->device, in.data(), n, discard, thin, q, n_q, stat_lo, stat_hi, n_valid, n_moved);
+}
+
+lcf_status lcf_samplers_chain_raster(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, int32_t t_bins,
+                                     const double* edges, int32_t v_bins, int64_t* counts) {
+    std::vector<HistoryChain> in;
+    if (lcf_status st = history_chains(s, n, discard, thin, &in)) return st;
+    return history_raster_run(s[0]->e->device, in.data(), n, discard, thin, t_bins, edges, v_bins, counts);
+}
+
 lcf_status lcf_sampler_get_naccepted(lcf_sampler* s, int64_t* n_accepted) {
     if (!s || !n_accepted) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = settle(s)) return st;

@@ -154,6 +154,14 @@ SIGNATURES = [
                                            C.POINTER(C.c_int64)]),
     ('lcf_samplers_chain_hist', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_int32,
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('lcf_chain_history', C.c_int, [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _dp,
+                                    C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('lcf_chain_raster', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp,
+                                   C.c_int32, C.POINTER(C.c_int64)]),
+    ('lcf_samplers_chain_history', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int32, _dp,
+                                             _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('lcf_samplers_chain_raster', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp,
+                                            C.c_int32, C.POINTER(C.c_int64)]),
 ]
 
 
@@ -867,4 +875,100 @@ def chain_hist(samples, shift, edges, discard=0, thin=1, device=0):
     for d, p in zip(dims, pairs):
         out.append((h1[i:i + d * bins].reshape(d, bins).copy(), h2[j:j + p * bins * bins].reshape(p, bins, bins).copy()))
         i, j = i + d * bins, j + p * bins * bins
+    return out if many else out[0]
+
+
+#: limits of the chain-history entry points (include/lcf.h)
+HISTORY_MAX_WALKERS, HISTORY_MAX_PERCENTILES, HISTORY_MAX_VBINS, HISTORY_MAX_TBINS = 16384, 16, 256, 4096
+
+
+def _history_sources(samples, discard, thin):
+    """``(native samplers or None, host chain or None, [(n_keep, n_dim)])`` of what a history call reads: one host
+    chain (n_t, n_w, n_dim), one :class:`NativeSampler` or a list of them.  ``n_keep`` is 0 where the native call will
+    refuse (no stored run, ``discard`` past it)."""
+    if isinstance(samples, NativeSampler):
+        samples = [samples]
+    if isinstance(samples, (list, tuple)) and samples and all(isinstance(s, NativeSampler) for s in samples):
+        steps = [s._last[0] if getattr(s, '_last', (0, False))[1] else 0 for s in samples]
+        return list(samples), None, [(len(range(int(discard), n_t, int(thin))) if thin >= 1 and discard >= 0 else 0,
+                                      s.ndim) for n_t, s in zip(steps, samples)]
+    x = _f64(samples)
+    if x.ndim != 3:
+        raise ValueError('chain must have shape (n_t, n_w, n_dim)')
+    n_keep = len(range(int(discard), x.shape[0], int(thin))) if thin >= 1 and discard >= 0 else 0
+    return None, x, [(n_keep, x.shape[2])]
+
+
+def chain_history(samples, percentiles, log_prob=None, discard=0, thin=1, device=0):
+    """``lcf_chain_history`` / ``lcf_samplers_chain_history``: for every kept step (stored steps ``discard::thin``) and
+    every column -- the log-probability being column ``n_dim`` -- the two order statistics of the walkers' values around
+    each percentile (ranks ``lo``, ``hi`` of :func:`~lightcurve_fitting_amd.fitting.quantile_ranks`) and the number of
+    non-NaN values, and per kept step the number of walkers whose row differs from the stored step before (-1 for
+    stored step 0).  ``samples``: a host chain (n_t, n_w, n_dim) with an optional ``log_prob`` (n_t, n_w), or one
+    :class:`NativeSampler` or a list of them (one device) whose last stored runs are read in place.  Returns
+    ``(stat_lo[n_q, n_keep, n_dim + 1], stat_hi, n_valid[n_keep, n_dim + 1], n_moved[n_keep])``, or a list of such
+    tuples for a list of samplers."""
+    lib = load_library()
+    natives, x, shapes = _history_sources(samples, discard, thin)
+    q = _f64(percentiles).ravel()
+    n_q = len(q)
+    cells = [n_keep * (n_dim + 1) for n_keep, n_dim in shapes]
+    lo, hi = np.empty(max(1, n_q * sum(cells))), np.empty(max(1, n_q * sum(cells)))
+    n_valid = np.empty(max(1, sum(cells)), dtype=np.int64)
+    n_moved = np.empty(max(1, sum(n_keep for n_keep, _ in shapes)), dtype=np.int64)
+    if natives is None:
+        lp = None
+        if log_prob is not None:
+            lp = _f64(log_prob)
+            if lp.shape != x.shape[:2]:
+                raise ValueError(f'log_prob must have shape {x.shape[:2]}, got {lp.shape}')
+        _check(lib.lcf_chain_history(int(device), _ptr(x), None if lp is None else _ptr(lp), x.shape[0], x.shape[1],
+                                     x.shape[2], int(discard), int(thin), _ptr(q), n_q, _ptr(lo), _ptr(hi),
+                                     _i64p(n_valid), _i64p(n_moved)))
+    else:
+        if log_prob is not None:
+            raise ValueError('log_prob goes with a host chain; a sampler brings its own')
+        arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
+        _check(lib.lcf_samplers_chain_history(arr, len(natives), int(discard), int(thin), _ptr(q), n_q, _ptr(lo),
+                                              _ptr(hi), _i64p(n_valid), _i64p(n_moved)))
+    out, c, k = [], 0, 0
+    for (n_keep, n_dim), n_cell in zip(shapes, cells):
+        shape = (n_q, n_keep, n_dim + 1)
+        out.append((lo[n_q * c:n_q * (c + n_cell)].reshape(shape).copy(),
+                    hi[n_q * c:n_q * (c + n_cell)].reshape(shape).copy(),
+                    n_valid[c:c + n_cell].reshape(n_keep, n_dim + 1).copy(), n_moved[k:k + n_keep].copy()))
+        c, k = c + n_cell, k + n_keep
+    return out if isinstance(samples, (list, tuple)) else out[0]
+
+
+def chain_raster(samples, t_bins, edges, discard=0, thin=1, device=0):
+    """``lcf_chain_raster`` / ``lcf_samplers_chain_raster``: ``counts[n_dim, t_bins, v_bins]``, int64 -- the (kept step,
+    walker) pairs with step bin ``(k * t_bins) // n_keep`` and the column's value in the bin of ``edges`` (n_dim,
+    v_bins + 1) that :func:`chain_hist` would count it in.  ``samples`` as for :func:`chain_history`; for a list of
+    samplers ``edges`` is a list with one table per sampler (the same ``v_bins`` in all) and a list is returned."""
+    lib = load_library()
+    natives, x, shapes = _history_sources(samples, discard, thin)
+    many = isinstance(samples, (list, tuple))
+    tables = [_f64(e) for e in (edges if many else [edges])]
+    if len(tables) != len(shapes):
+        raise ValueError('edges needs one entry per sampler')
+    v_bins = tables[0].shape[-1] - 1 if tables[0].ndim == 2 else -1
+    for (_, n_dim), e in zip(shapes, tables):
+        if e.shape != (n_dim, v_bins + 1):
+            raise ValueError('edges must have shape (n_columns, v_bins + 1)')
+    t_bins = int(t_bins)
+    ed = np.concatenate([e.ravel() for e in tables])
+    sizes = [n_dim * max(t_bins, 0) * max(v_bins, 0) for _, n_dim in shapes]
+    counts = np.zeros(max(1, sum(sizes)), dtype=np.int64)
+    if natives is None:
+        _check(lib.lcf_chain_raster(int(device), _ptr(x), x.shape[0], x.shape[1], x.shape[2], int(discard), int(thin),
+                                    t_bins, _ptr(ed), v_bins, _i64p(counts)))
+    else:
+        arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
+        _check(lib.lcf_samplers_chain_raster(arr, len(natives), int(discard), int(thin), t_bins, _ptr(ed), v_bins,
+                                             _i64p(counts)))
+    out, i = [], 0
+    for (_, n_dim), size in zip(shapes, sizes):
+        out.append(counts[i:i + size].reshape(n_dim, t_bins, v_bins).copy())
+        i += size
     return out if many else out[0]

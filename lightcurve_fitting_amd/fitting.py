@@ -11,7 +11,10 @@ temperature, radius and bolometric luminosity -- and counts, time by time, the s
 allow or outside their validity window: the check the reference's usage guide asks for after every shock-cooling fit.
 The numbers behind ``lightcurve_corner`` (fitting.py:241-253) are :func:`posterior_corner`: the marginal histogram of
 every parameter, the joint histogram of every pair and the counts of the contour levels, with the reference's ``t_0``
-offset, counted on the device over every sample.
+offset, counted on the device over every sample.  The numbers behind the chain plots of ``lightcurve_mcmc(show=True)``
+(fitting.py:135-158) are :func:`chain_history`: per step the percentile bands of the walker ensemble and the number of
+walkers that moved, and the (step, value) raster of every walker's trace; with ``show`` or ``save_plot_as`` the
+burn-in's is kept as ``sampler.burnin_history`` before the burn-in chain is dropped.
 """
 import warnings
 
@@ -126,6 +129,11 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks.append(('burn_in', time.perf_counter()))
     if show or save_plot_as:
         warnings.warn('chain plots are not produced by the MI355X engine; plot sampler.chain with the reference tools')
+        # the left column of the reference's figure (fitting.py:135-158): the burn-in chain is gone after reset()
+        # (no burn-in, or more walkers than chain_history takes: the call goes on as it always has, without it)
+        from . import engine as _eng
+        if sampler.iteration > 0 and nwalkers <= _eng.HISTORY_MAX_WALKERS:
+            sampler.burnin_history = chain_history(model, sampler, use_sigma=bool(use_sigma))
     sampler.reset()                                                    # keep only the post-burn-in chain
     sampler.run_mcmc(burned_in.coords, nsteps, skip_initial_state_check=True)
     marks.append(('run', time.perf_counter()))
@@ -443,6 +451,27 @@ def corner_contour_levels(H, levels=CORNER_LEVELS):
     return V
 
 
+def _column_names(model, n_col, use_sigma):
+    """``(names, labels)`` of the ``n_col`` columns of a chain: the model's parameter names and axis labels, with
+    ``'\\sigma'`` for the last column if ``use_sigma`` -- the model itself is left as it is --, or ``p0, p1, ...``
+    without a model.  ``ValueError`` when the model takes another number of columns, or for more than 16."""
+    from . import engine as _eng
+    if model is None:
+        names = [f'p{i}' for i in np.arange(n_col)]
+        labels = list(names)
+    else:
+        want = model.n_model_params + int(bool(use_sigma))
+        if n_col != want:
+            raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
+                             + (' and one for sigma' if use_sigma else ''))
+        names = list(type(model).input_names) + (['\\sigma'] if use_sigma else [])
+        units = list(type(model).units) + ([''] if use_sigma else [])
+        labels = ['${}$ ({})'.format(var, unit) if unit else '${}$'.format(var) for var, unit in zip(names, units)]
+    if not 1 <= n_col <= _eng.CORNER_MAX_DIM:
+        raise ValueError(f'the samples must have from 1 to {_eng.CORNER_MAX_DIM} columns')
+    return names, labels
+
+
 class _CornerPlan:
     """What :func:`posterior_corner` settles before the device is touched: names, labels, bins, levels, the time columns
     and the caller's ranges; then, from the columns' extremes, the offsets, ranges and edges."""
@@ -452,22 +481,9 @@ class _CornerPlan:
         if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= _eng.CORNER_MAX_BINS:
             raise ValueError(f'bins must be an integer from 1 to {_eng.CORNER_MAX_BINS}')
         self.bins = int(bins)
-        if model is None:
-            self.names = [f'p{i}' for i in np.arange(n_col)]
-            self.labels = list(self.names)
-            if t0_offset is not None:
-                raise ValueError('t0_offset needs a model: without one no column is known to be a time')
-        else:
-            want = model.n_model_params + int(bool(use_sigma))
-            if n_col != want:
-                raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
-                                 + (' and one for sigma' if use_sigma else ''))
-            self.names = list(type(model).input_names) + (['\\sigma'] if use_sigma else [])
-            units = list(type(model).units) + ([''] if use_sigma else [])
-            self.labels = ['${}$ ({})'.format(var, unit) if unit else '${}$'.format(var)
-                           for var, unit in zip(self.names, units)]
-        if not 1 <= n_col <= _eng.CORNER_MAX_DIM:
-            raise ValueError(f'the samples must have from 1 to {_eng.CORNER_MAX_DIM} columns')
+        if model is None and t0_offset is not None:
+            raise ValueError('t0_offset needs a model: without one no column is known to be a time')
+        self.names, self.labels = _column_names(model, n_col, use_sigma)
         self.time_columns = [self.names.index(var) for var in CORNER_TIME_NAMES if var in self.names] \
             if model is not None else []
         if t0_offset is not None and not np.isfinite(t0_offset):
@@ -564,3 +580,179 @@ def posterior_corner(model, samples, bins=20, range=None, levels=None, t0_offset
     offsets, rng, edges, labels = plan.settle(lo, hi)
     hist1d, pairs = _eng.chain_hist(source, offsets, edges, **kw)
     return plan.data(offsets, rng, edges, labels, hist1d, pairs, n_samples, n_nan)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# chain history (the numbers of the chain plots of lightcurve_mcmc(show=True), reference fitting.py:135-158)
+# ---------------------------------------------------------------------------------------------------------------
+#: the default bands of :func:`chain_history`: the extremes, the median and the central 68 %
+HISTORY_PERCENTILES = (0., 15.87, 50., 84.14, 100.)
+#: step bins of the trace raster unless the caller says otherwise (or the chain has fewer kept steps)
+HISTORY_T_BINS = 512
+
+
+class ChainHistory:
+    """Result of :func:`chain_history` for ``n_keep`` kept steps of ``n_walkers`` walkers and P columns: ``steps``
+    (n_keep,) -- the stored step ``t_k`` of every kept step -- ``percentiles`` (nq,), ``quantiles`` (nq, n_keep, P) and
+    ``log_prob_quantiles`` (nq, n_keep) -- the percentiles across the walkers, NaN where no walker has a value --
+    ``n_valid`` (n_keep, P + 1) -- the non-NaN values per step and column, the log-probability last -- ``n_moved``
+    (n_keep,) -- the walkers whose row differs from the stored step before, -1 for stored step 0 -- ``frac_moved``
+    (that over ``n_walkers``, NaN where ``n_moved`` is -1), ``counts`` (P, t_bins, v_bins), int64 -- the (kept step,
+    walker) pairs per step bin and value bin -- ``step_edges`` (t_bins + 1,) -- step bin ``i`` holds the kept steps
+    ``step_edges[i] <= k < step_edges[i + 1]`` -- ``edges`` (P, v_bins + 1), ``range`` (P, 2), ``names`` and
+    ``labels`` (P strings each)."""
+    __slots__ = ('steps', 'percentiles', 'quantiles', 'log_prob_quantiles', 'n_valid', 'n_moved', 'frac_moved',
+                 'counts', 'step_edges', 'edges', 'range', 'names', 'labels', 'n_walkers')
+
+    def __init__(self, steps, percentiles, quantiles, log_prob_quantiles, n_valid, n_moved, counts, step_edges, edges,
+                 range, names, labels, n_walkers):
+        self.steps, self.percentiles = steps, percentiles
+        self.quantiles, self.log_prob_quantiles, self.n_valid, self.n_moved = quantiles, log_prob_quantiles, n_valid, n_moved
+        self.frac_moved = np.where(n_moved < 0, np.nan, n_moved / n_walkers)
+        self.counts, self.step_edges, self.edges, self.range = counts, step_edges, edges, range
+        self.names, self.labels, self.n_walkers = names, labels, n_walkers
+
+    def __repr__(self):
+        return (f'<ChainHistory: {len(self.percentiles)} percentiles x {len(self.steps)} steps x {len(self.names)} '
+                f'columns of {self.n_walkers} walkers; raster {self.counts.shape[1]} x {self.counts.shape[2]}>')
+
+
+def _bin_count(value, name, most):
+    if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= most:
+        raise ValueError(f'{name} must be an integer from 1 to {most}')
+    return int(value)
+
+
+class _HistoryPlan:
+    """What :func:`chain_history` settles before the device is touched -- names, labels, percentiles, the kept steps,
+    both bin counts and the caller's ranges -- and what it makes of the device's answers."""
+
+    def __init__(self, model, n_t, n_w, n_col, percentiles, t_bins, v_bins, range, discard, thin, use_sigma):
+        from . import engine as _eng
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        if n_t < 1 or n_w < 1:
+            raise ValueError('the chain needs at least one step and one walker')
+        self.steps = np.arange(discard, n_t, thin, dtype=np.int64)
+        if len(self.steps) == 0:
+            raise ValueError(f'discard={discard} leaves no steps of the {n_t} stored')
+        if n_w > _eng.HISTORY_MAX_WALKERS:
+            raise ValueError(f'at most {_eng.HISTORY_MAX_WALKERS} walkers, got {n_w}')
+        if use_sigma is None:   # a chain with one column more than its model has parameters carries sigma
+            use_sigma = model is not None and n_col == model.n_model_params + 1
+        self.names, self.labels = _column_names(model, n_col, use_sigma)
+        self.n_walkers, self.discard, self.thin = int(n_w), discard, thin
+        self.percentiles = _percentile_array(percentiles)
+        if len(self.percentiles) > _eng.HISTORY_MAX_PERCENTILES:
+            raise ValueError(f'at most {_eng.HISTORY_MAX_PERCENTILES} percentiles')
+        n_keep = len(self.steps)
+        self.v_bins = _bin_count(v_bins, 'v_bins', _eng.HISTORY_MAX_VBINS)
+        self.t_bins = min(n_keep, HISTORY_T_BINS) if t_bins is None else \
+            _bin_count(t_bins, 't_bins', min(n_keep, _eng.HISTORY_MAX_TBINS))
+        #: step bin i holds the kept steps k with (k * t_bins) // n_keep == i
+        self.step_edges = -(-(np.arange(self.t_bins + 1, dtype=np.int64) * n_keep) // self.t_bins)
+        self.user_range = [None] * n_col
+        if range is not None:
+            if len(range) != n_col:
+                raise ValueError(f'range needs one entry per column: {n_col}, got {len(range)}')
+            for d, r in enumerate(range):
+                if r is None:
+                    continue
+                lo, hi = (float(v) for v in r)
+                if not (np.isfinite(lo) and np.isfinite(hi)) or not lo < hi:
+                    raise ValueError(f'range of column {d} ({self.names[d]}) has no extent: need finite lo < hi, got '
+                                     f'({lo}, {hi})')
+                self.user_range[d] = (lo, hi)
+
+    @property
+    def needs_extremes(self):
+        return any(r is None for r in self.user_range)
+
+    def settle(self, lo=None, hi=None):
+        """``(range, edges)``: the caller's range, else the column's smallest and largest non-NaN value ``lo``, ``hi`` over
+        the kept rows -- widened by one half either way when they are equal, as ``np.histogram`` widens it."""
+        n_col = len(self.names)
+        rng = np.empty((n_col, 2))
+        for d in np.arange(n_col):
+            if self.user_range[d] is not None:
+                rng[d] = self.user_range[d]
+                continue
+            rng[d] = lo[d], hi[d]
+            if not np.all(np.isfinite(rng[d])):
+                raise ValueError(f'column {d} ({self.names[d]}) has no finite range: ({rng[d, 0]}, {rng[d, 1]})')
+            if rng[d, 0] == rng[d, 1]:
+                rng[d] = rng[d, 0] - 0.5, rng[d, 1] + 0.5
+        return rng, np.array([np.linspace(r[0], r[1], self.v_bins + 1) for r in rng])
+
+    def data(self, stat_lo, stat_hi, n_valid, n_moved, counts, rng, edges):
+        """The order statistics ``stat_lo``, ``stat_hi`` (nq, n_keep, P + 1) interpolated as NumPy interpolates them."""
+        _, _, gamma = quantile_ranks(np.maximum(n_valid, 1)[None], self.percentiles[:, None, None])
+        quantiles = np.where(n_valid[None] > 0, quantile_lerp(stat_lo, stat_hi, gamma), np.nan)
+        return ChainHistory(self.steps, self.percentiles, quantiles[:, :, :-1], quantiles[:, :, -1], n_valid, n_moved,
+                            counts, self.step_edges, edges, rng, self.names, self.labels, self.n_walkers)
+
+
+def chain_history(model, samples, percentiles=HISTORY_PERCENTILES, t_bins=None, v_bins=64, range=None, log_prob=None,
+                  discard=0, thin=1, use_sigma=None):
+    """The numbers of the chain plots of ``lightcurve_mcmc(..., show=True)`` (fitting.py:135-158), which draw every
+    walker's trace, one panel per parameter: whether burn-in was long enough and whether walkers are stuck.  Drawing
+    them is left to the caller.
+
+    ``samples``: a sampler -- its stored chain and log-probabilities, read where they lie in device memory when the
+    whole stored chain is the last run's, else uploaded from ``get_chain`` / ``get_log_prob`` -- or a host chain
+    ``(n_t, n_w, n_dim)`` with an optional ``log_prob`` ``(n_t, n_w)``.  The kept steps are ``k = 0 .. n_keep - 1`` at
+    stored step ``t_k = discard + k * thin``.  ``model``, ``use_sigma``: names and labels as in
+    :func:`posterior_corner` (``use_sigma=None``: a chain with one column more than the model has parameters carries
+    sigma); the ``t_0`` column and its label are left as they are, as the reference's chain plot leaves them.
+
+    Ensemble bands: ``quantiles[:, k, d]`` is ``np.nanpercentile(chain[t_k, :, d], percentiles)`` across the walkers,
+    NumPy's default method, bit for bit (the device sorts and selects, the interpolation is NumPy's own arithmetic);
+    ``log_prob_quantiles`` the same for the log-probability.  NaN where ``n_valid`` is 0; infinities are ordinary
+    values.  At most 16 percentiles, at most 16384 walkers.
+
+    Moves: ``n_moved[k]`` is the number of walkers whose row at stored step ``t_k`` differs, in any bit, from their
+    row at stored step ``t_k - 1`` -- the predecessor in the stored chain, not the kept step before: the number of
+    proposals accepted in that step.  -1 for ``t_k == 0``.
+
+    Trace density: ``counts[d, i, j]`` is the number of (kept step, walker) pairs with step bin ``i = (k * t_bins) //
+    n_keep`` (``t_bins`` defaults to ``min(n_keep, 512)``, at most 4096) and the value of column ``d`` in bin ``j`` of
+    ``np.linspace(lo, hi, v_bins + 1)`` (``v_bins`` at most 256) -- ``np.histogram``'s bins, the last closed; NaNs and
+    values outside are in no bin.  ``range``: per column ``None`` -- the extremes of the kept rows -- or ``(lo, hi)``.
+
+    Results are exact and bitwise reproducible.  Returns a :class:`ChainHistory`."""
+    from . import engine as _eng
+    is_sampler = isinstance(samples, EnsembleSampler) or (hasattr(samples, '_native') and hasattr(samples, 'get_chain'))
+    if is_sampler:
+        if log_prob is not None:
+            raise ValueError('log_prob goes with a host chain; a sampler brings its own')
+        if samples.iteration == 0:
+            raise ValueError('no chain is stored: run the sampler with store=True first')
+        n_t, n_w, n_col = samples.iteration, samples.nwalkers, samples.ndim
+        device = samples.engine.device
+    else:
+        x = np.ascontiguousarray(samples, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError('samples must be a sampler or a chain of shape (n_t, n_w, n_dim)')
+        n_t, n_w, n_col = x.shape
+        if log_prob is not None:
+            log_prob = np.ascontiguousarray(log_prob, dtype=np.float64)
+            if log_prob.shape != (n_t, n_w):
+                raise ValueError(f'log_prob must have shape {(n_t, n_w)}, got {log_prob.shape}')
+        device = 0 if model is None else model.device
+    plan = _HistoryPlan(model, n_t, n_w, n_col, percentiles, t_bins, v_bins, range, discard, thin, use_sigma)
+    kw = dict(discard=plan.discard, thin=plan.thin, device=device)
+    if is_sampler and len(samples._chain_host) == 0 and samples._chain_on_device > 0:
+        source = rows = samples._native
+        stats = _eng.chain_history(source, plan.percentiles, **kw)
+    else:
+        if is_sampler:
+            x, log_prob = samples.get_chain(), samples.get_log_prob()
+        source, rows = x, x[plan.discard::plan.thin].reshape(-1, n_col)
+        stats = _eng.chain_history(source, plan.percentiles, log_prob=log_prob, **kw)
+    lo = hi = None
+    if plan.needs_extremes:
+        lo, hi, _ = _eng.chain_range(rows, **(kw if rows is source else dict(device=device)))
+    rng, edges = plan.settle(lo, hi)
+    counts = _eng.chain_raster(source, plan.t_bins, edges, **kw)
+    return plan.data(*stats, counts, rng, edges)

@@ -316,6 +316,52 @@ class PopulationSampler:
                 out[k] = plans[k][2].data(*st, hist1d, pairs, n_samples[k], n_nan)
         return {k: out[k] for k in self.samplers}
 
+    def history(self, models=None, percentiles=None, t_bins=None, v_bins=64, range=None, discard=0, thin=1,
+                use_sigma=None):
+        """``{index: ChainHistory}`` of this rank's transients, each as :func:`~lightcurve_fitting_amd.fitting.
+        chain_history` gives it; the chains still on the device go through one native call per pass together.
+        ``models``: index -> the transient's model (mapping or sequence), or None (columns ``p0, p1, ...``).  ``range``
+        and ``use_sigma`` hold for every transient, or are dicts index -> value; ``t_bins=None``: ``min(n_keep, 512)``
+        per transient, and the transients with the same number of step bins share a native call."""
+        from .engine import chain_history as native_history, chain_range, chain_raster
+        from .fitting import HISTORY_PERCENTILES, _HistoryPlan, chain_history
+        percentiles = HISTORY_PERCENTILES if percentiles is None else percentiles
+
+        def pick(value, k):
+            return value.get(k) if isinstance(value, dict) else value
+        plans = {}
+        for k, s in self.samplers.items():
+            if s.iteration == 0:
+                raise ValueError(f'no chain is stored (transient {k}): run the sampler with store=True first')
+            try:
+                plans[k] = _HistoryPlan(None if models is None else models[k], s.iteration, s.nwalkers, s.ndim,
+                                        percentiles, t_bins, v_bins, pick(range, k), discard, thin, pick(use_sigma, k))
+            except ValueError as exc:
+                raise ValueError(f'{exc} (transient {k})') from None
+        resident = [k for k, s in self.samplers.items() if len(s._chain_host) == 0 and s._chain_on_device > 0]
+        out = {}
+        for k, s in self.samplers.items():
+            if k not in resident:
+                out[k] = chain_history(None if models is None else models[k], s, percentiles=percentiles, t_bins=t_bins,
+                                       v_bins=v_bins, range=pick(range, k), discard=discard, thin=thin,
+                                       use_sigma=pick(use_sigma, k))
+        if resident:
+            discard, thin = int(discard), int(thin)
+            natives = [self.samplers[k]._native for k in resident]
+            stats = native_history(natives, plans[resident[0]].percentiles, discard=discard, thin=thin)
+            if any(plans[k].needs_extremes for k in resident):
+                extremes = chain_range(natives, discard, thin)
+            else:
+                extremes = [(None, None, None)] * len(resident)
+            settled = {k: plans[k].settle(lo, hi) for k, (lo, hi, _) in zip(resident, extremes)}
+            for nb in sorted({plans[k].t_bins for k in resident}):
+                group = [k for k in resident if plans[k].t_bins == nb]
+                counts = chain_raster([self.samplers[k]._native for k in group], nb, [settled[k][1] for k in group],
+                                      discard, thin)
+                for k, c in zip(group, counts):
+                    out[k] = plans[k].data(*stats[resident.index(k)], c, *settled[k])
+        return {k: out[k] for k in self.samplers}
+
     def __getitem__(self, k):
         return self.samplers[k]
 
