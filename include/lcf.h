@@ -493,6 +493,42 @@ lcf_status lcf_samplers_chain_history(lcf_sampler** samplers, int32_t n_samplers
 lcf_status lcf_samplers_chain_raster(lcf_sampler** samplers, int32_t n_samplers, int64_t discard, int64_t thin,
                                      int32_t t_bins, const double* edges, int32_t v_bins, int64_t* counts);
 
+/* ---- parallel-tempered ensembles: degenerate posteriors and the log-evidence (emcee 2's PTSampler) ------------------ */
+/* n_temps rungs k of inverse temperature betas[0] = 1 >= betas[1] >= ... >= betas[n_temps - 1] >= 0 (a ladder descends
+ * strictly; between equal neighbours every swap is accepted, which the library allows and tests use), each an ensemble of
+ * n_walkers walkers of its own; per walker the state keeps x, ln L(x) (likelihood only) and ln prior(x).  Rung k draws
+ * from the sampler's generators (LCF_SPLIT_RANDOM colouring, z, partner, ln u) under seed + k 0x9E3779B97F4A7C15 (mod
+ * 2^64), keyed by the absolute step.  Step s: for each half and all rungs at once, q = partner - (partner - x) z, ONE
+ * likelihood call for the n_temps ceil(n_walkers / 2) proposals, accept iff ln prior(q) is finite, ln L(q) > -inf and
+ * (n_dim - 1) ln z + betas[k] (ln L(q) - ln L(x)) + (ln prior(q) - ln prior(x)) > ln u (betas[k] = 0: no product is
+ * formed); a NaN ln L(q) inside the prior ends the run with LCF_ERR_NAN_LOGPROB, outside it is ignored.  Then the pairs
+ * (k, k + 1) with k = s (mod 2) swap slot by slot: ln u = log(u01(r0, r1)), (r0, r1, ., .) = Philox(counter (slot, s, 3,
+ * k), key seed); accept iff (betas[k] - betas[k + 1]) (ln L[k + 1][i] - ln L[k][i]) > ln u; x, ln L and ln prior change
+ * places, the move counts stay with the slot.
+ * 1 <= n_temps <= 64 and 2 n_dim <= n_walkers <= 16384 (beyond: LCF_ERR_UNSUPPORTED).  The engine's priors decide what a
+ * rung at beta = 0 samples: the caller makes sure they are proper. */
+typedef struct lcf_tempered lcf_tempered;
+lcf_status lcf_tempered_create(lcf_engine* e, int32_t n_temps, const double* betas, int32_t n_walkers, uint64_t seed,
+                               double a, lcf_tempered** out);
+void lcf_tempered_destroy(lcf_tempered* t);
+/* coords[n_temps][n_walkers][n_dim] host.  A start row outside the prior is LCF_ERR_STATE, one whose likelihood is NaN
+ * LCF_ERR_NAN_LOGPROB.  Clears the counts. */
+lcf_status lcf_tempered_set_state(lcf_tempered* t, const double* coords);
+/* coords[n_temps][n_walkers][n_dim], lnL / lnpr[n_temps][n_walkers] (any may be NULL) */
+lcf_status lcf_tempered_get_state(lcf_tempered* t, double* coords, double* lnL, double* lnpr);
+/* n_steps steps numbered from first_step.  store: 0 = nothing is stored (the stored chain stays), 1 = the run's steps
+ * replace the stored chain, 2 = they are appended to it.  LCF_ERR_OUT_OF_MEMORY, before anything is allocated, when the
+ * chain does not fit the device's free memory. */
+lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store);
+/* The stored chain: chain[n_stored][n_temps][n_walkers][n_dim], lnL[n_stored][n_temps][n_walkers] (either may be NULL). */
+lcf_status lcf_tempered_get_chain(lcf_tempered* t, double* chain, double* lnL);
+/* Since the last set_state: accepted moves per slot [n_temps][n_walkers], accepted and proposed swaps per pair (k, k + 1)
+ * [n_temps - 1] (any may be NULL). */
+lcf_status lcf_tempered_get_counts(lcf_tempered* t, int64_t* n_accepted, int64_t* swaps_accepted, int64_t* swaps_proposed);
+/* out[k] = mean of ln L over the stored steps discard .. and all walkers of rung k, reduced on the device in a fixed
+ * order (what thermodynamic integration needs of the chain). */
+lcf_status lcf_tempered_mean_loglike(lcf_tempered* t, int64_t discard, double* out /* [n_temps] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
-// What lcf_hip.hip (kernels, engine, launches, runs over ranks and populations) and lcf_sampler.hip (the bookkeeping of
-// runs) share: what the sampler's kernels and the host exchange, the engine and the sampler behind the C ABI's opaque
-// pointers, and the host functions that cross the two files.
+// What lcf_hip.hip (kernels, engine, launches, runs over ranks and populations), lcf_sampler.hip (the bookkeeping of
+// runs) and lcf_tempered.hip (the tempered driver beside the sampler) share: what the sampler's kernels and the host
+// exchange, the engine and the sampler behind the C ABI's opaque pointers, and the host functions that cross the files.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -378,6 +378,8 @@ lcf_status dalloc(T** p, size_t n, std::vector<void*>& owned) {
 }
 
 // lcf_sampler.hip
+lcf_status generate_multi(const void* gen, int n_items, int n_walkers, int n_half, long long first_step, long long n_steps,
+                          int buf, long long front_row, hipStream_t st);
 lcf_status generate_block(lcf_sampler* const* ss, int n, int64_t b, hipStream_t consumer, const void* gen = nullptr);
 lcf_status enter_half_step(lcf_sampler* const* ss, int n, long long rel, hipStream_t st, const void* gen = nullptr);
 lcf_status leave_half_step(lcf_sampler* const* ss, int n, hipStream_t st, const void* gen = nullptr);

@@ -295,6 +295,27 @@ static lcf_status generate_steps(lcf_sampler* s, int buf, int64_t step0, int64_t
     return LCF_OK;
 }
 
+// The launcher of the batched generation kernels: `n_steps` steps from absolute step `first_step` for the `n_items`
+// GenItems at `gen_items` (device memory; equal walker counts), permutations and draw records into their buffers `buf`,
+// one launch of each kernel.  An item without a slot table gets records without slot bookkeeping.  `front_row`: as
+// k_make_perm_multi takes it.  (A population's samplers, and the rungs of a tempered ensemble: lcf_tempered.hip.)
+lcf_status generate_multi(const void* gen_items, int n_items, int n_walkers, int n_half, long long first_step,
+                          long long n_steps, int buf, long long front_row, hipStream_t st) {
+    const GenItem* gen = static_cast<const GenItem*>(gen_items);
+    const auto [n_pad, threads] = perm_shape(n_walkers);
+    LCF_HIP(prepare_kernel(k_make_perm_multi, (size_t)n_pad * 8));
+    hipLaunchKernelGGL(k_make_perm_multi, dim3((unsigned)n_steps, (unsigned)n_items), dim3(threads), (size_t)n_pad * 8, st, gen,
+                       n_walkers, n_pad, first_step, buf, n_half, front_row);
+    DevSampler sm{};   // (the kernel reads the common shape from it; key, dimension and stretch scale come from the item)
+    sm.n_walkers = n_walkers;
+    sm.n_half = n_half;
+    const long long recs = n_steps * 2 * n_half;
+    hipLaunchKernelGGL(k_draws_multi, dim3((unsigned)((recs + 255) / 256), (unsigned)n_items), dim3(256), 0, st, gen, sm, buf,
+                       first_step, n_steps);
+    LCF_HIP(hipGetLastError());
+    return LCF_OK;
+}
+
 // Block b of the current run (block b lives in buffer b & 1) for a GROUP of samplers ss[0, n) that share their block
 // geometry -- a population's transients, or one sampler on its own; so do enter_half_step and leave_half_step.  `gen`:
 // the group's GenItems in device memory, the block of all of them from one launch of each batched generation kernel;
@@ -306,15 +327,9 @@ lcf_status generate_block(lcf_sampler* const* ss, int n, int64_t b, hipStream_t 
         const lcf_sampler* s0 = ss[0];
         const DevSampler& d0 = s0->ds;
         const int64_t k0 = s0->block_start(b), len = s0->block_len(b);
-        const auto [n_pad, threads] = perm_shape(d0.n_walkers);
         const long long front_row = b > 0 ? 2 * (long long)s0->block_len(b - 1) : -1;
-        LCF_HIP(prepare_kernel(k_make_perm_multi, (size_t)n_pad * 8));
-        hipLaunchKernelGGL(k_make_perm_multi, dim3((unsigned)len, (unsigned)n), dim3(threads), (size_t)n_pad * 8, consumer, gen,
-                           d0.n_walkers, n_pad, (long long)(s0->run_first + k0), buf, d0.n_half, front_row);
-        const long long recs = (long long)len * 2 * d0.n_half;
-        hipLaunchKernelGGL(k_draws_multi, dim3((unsigned)((recs + 255) / 256), (unsigned)n), dim3(256), 0, consumer, gen, d0,
-                           buf, (long long)(s0->run_first + k0), (long long)len);
-        LCF_HIP(hipGetLastError());
+        if (lcf_status r = generate_multi(gen, n, d0.n_walkers, d0.n_half, s0->run_first + k0, len, buf, front_row, consumer))
+            return r;
     }
     for (int t = 0; t < n; ++t) {
         lcf_sampler* s = ss[t];

@@ -162,6 +162,16 @@ SIGNATURES = [
                                              _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ('lcf_samplers_chain_raster', C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp,
                                             C.c_int32, C.POINTER(C.c_int64)]),
+    ('lcf_tempered_create', C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_uint64, C.c_double,
+                                      C.POINTER(C.c_void_p)]),
+    ('lcf_tempered_destroy', None, [C.c_void_p]),
+    ('lcf_tempered_set_state', C.c_int, [C.c_void_p, _dp]),
+    ('lcf_tempered_get_state', C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    ('lcf_tempered_run', C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
+    ('lcf_tempered_get_chain', C.c_int, [C.c_void_p, _dp, _dp]),
+    ('lcf_tempered_get_counts', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64)]),
+    ('lcf_tempered_mean_loglike', C.c_int, [C.c_void_p, C.c_int64, _dp]),
 ]
 
 
@@ -282,6 +292,8 @@ class Engine:
         _check(lib.lcf_engine_create(C.byref(pr), int(device), C.byref(self._h)))
         self.ndim = n_dim
         self.npoints = pr.n_points
+        #: the prior descriptors the engine was created with (None: none)
+        self.priors = None if priors is None else [tuple(p) for p in priors]
         self.device = int(device)
         self.samples_per_eval = lib.lcf_engine_samples_per_eval(self._h)
 
@@ -550,6 +562,66 @@ class NativeSampler:
 
     def last_run_ms(self):
         return float(self._lib.lcf_sampler_last_run_ms(self._h))
+
+
+class NativeTempered:
+    """Thin handle on ``lcf_tempered`` (parallel-tempered ensembles): ``ntemps`` rungs of ``nwalkers`` walkers."""
+
+    STORE = {False: 0, True: 1, 'append': 2}
+
+    def __init__(self, engine, betas, nwalkers, seed=0, a=2.0):
+        self._lib = engine._lib
+        self.engine = engine
+        betas = _f64(betas)
+        self.ntemps, self.nwalkers, self.ndim = len(betas), int(nwalkers), engine.ndim
+        self._h = C.c_void_p()
+        _check(self._lib.lcf_tempered_create(engine.handle, self.ntemps, _ptr(betas), self.nwalkers,
+                                             C.c_uint64(int(seed) & (2 ** 64 - 1)), float(a), C.byref(self._h)))
+
+    def close(self):
+        h = getattr(self, '_h', None)
+        if h is not None and h.value:
+            self._h = None   # (no module global is touched here: this also runs at interpreter shutdown)
+            self._lib.lcf_tempered_destroy(h)
+
+    __del__ = close
+
+    def set_state(self, coords):
+        coords = _f64(coords)
+        if coords.shape != (self.ntemps, self.nwalkers, self.ndim):
+            raise ValueError(f'coords must have shape ({self.ntemps}, {self.nwalkers}, {self.ndim})')
+        _check(self._lib.lcf_tempered_set_state(self._h, _ptr(coords)))
+
+    def get_state(self):
+        """``(x (K, W, D), lnL (K, W), lnpr (K, W))``"""
+        x = np.empty((self.ntemps, self.nwalkers, self.ndim))
+        ll, lpr = np.empty(x.shape[:2]), np.empty(x.shape[:2])
+        _check(self._lib.lcf_tempered_get_state(self._h, _ptr(x), _ptr(ll), _ptr(lpr)))
+        return x, ll, lpr
+
+    def run(self, first_step, nsteps, store=True):
+        """``store``: False, True (the run replaces the stored chain) or 'append'."""
+        _check(self._lib.lcf_tempered_run(self._h, int(first_step), int(nsteps), self.STORE[store]))
+
+    def get_chain(self, nstored):
+        """``(chain (nstored, K, W, D), lnL (nstored, K, W))`` of the ``nstored`` steps the device holds."""
+        chain = np.empty((int(nstored), self.ntemps, self.nwalkers, self.ndim))
+        ll = np.empty(chain.shape[:3])
+        if nstored:
+            _check(self._lib.lcf_tempered_get_chain(self._h, _ptr(chain), _ptr(ll)))
+        return chain, ll
+
+    def counts(self):
+        """``(n_accepted (K, W), swaps_accepted (K-1,), swaps_proposed (K-1,))`` since the last ``set_state``."""
+        acc = np.zeros((self.ntemps, self.nwalkers), dtype=np.int64)
+        sa, sp = np.zeros(self.ntemps - 1, dtype=np.int64), np.zeros(self.ntemps - 1, dtype=np.int64)
+        _check(self._lib.lcf_tempered_get_counts(self._h, _i64p(acc), _i64p(sa), _i64p(sp)))
+        return acc, sa, sp
+
+    def mean_loglike(self, discard=0):
+        out = np.empty(self.ntemps)
+        _check(self._lib.lcf_tempered_mean_loglike(self._h, int(discard), _ptr(out)))
+        return out
 
 
 def population_run(native_samplers, first_step, nsteps, split='random', store=True):

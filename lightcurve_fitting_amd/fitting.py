@@ -87,12 +87,17 @@ def _check_start_box(names, priors, p_lo, p_up):
 def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p_up=None,
                     nwalkers=100, nsteps=1000, nsteps_burnin=1000, model_kwargs=None,
                     show=False, save_plot_as='', save_sampler_as='', use_sigma=False, sigma_type='relative',
-                    seed=None):
+                    seed=None, ntemps=None, betas=None, Tmax=None):
     """Fit an analytical model to observed photometry with an affine-invariant ensemble sampler on the GPU.
 
     Arguments as in the reference (fitting.py:16-58).  ``seed`` (extension) keys the counter-based RNG; by default
     it is drawn from NumPy's global generator, which also provides the starting guesses (fitting.py:132), so
     ``np.random.seed`` makes a run reproducible exactly as it does for the reference.
+
+    ``ntemps`` / ``betas`` / ``Tmax`` (extension; all None: the call is what it always was): fit with a
+    parallel-tempered ensemble, :class:`~lightcurve_fitting_amd.sampler.TemperedSampler`, of ``nwalkers`` walkers per
+    rung -- for degenerate or multi-modal posteriors, and for the log-evidence (``sampler.log_evidence()``).  Every
+    rung starts uniform in the starting box; ``chain`` / ``flatchain`` of the returned sampler are the cold rung's.
 
     Returns the sampler (``.chain`` (nwalkers, nsteps, ndim), ``.flatchain``, ``.run_mcmc``, ``.reset``).
     """
@@ -121,6 +126,18 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks.append(('engine', time.perf_counter()))
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
+    if ntemps is not None or betas is not None or Tmax is not None:
+        from .sampler import TemperedSampler
+        sampler = TemperedSampler(nwalkers, ndim, engine, ntemps=ntemps, betas=betas, Tmax=Tmax, seed=seed,
+                                  names=model.input_names)
+        start = p_lo + (p_up - p_lo) * np.random.rand(sampler.ntemps, nwalkers, ndim)
+        marks.append(('sampler', time.perf_counter()))
+        sampler.run_mcmc(start, nsteps_burnin, store=False)
+        marks.append(('burn_in', time.perf_counter()))
+        if show or save_plot_as:
+            warnings.warn('chain plots are not produced by the MI355X engine; plot sampler.chain with the reference tools')
+        sampler.run_mcmc(None, nsteps)
+        return _finish_mcmc(sampler, engine, marks, save_sampler_as)
     sampler = EnsembleSampler(nwalkers, ndim, engine, seed=seed)
 
     start = p_lo + (p_up - p_lo) * np.random.rand(nwalkers, ndim)      # uniform in the starting box
@@ -136,6 +153,12 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
             sampler.burnin_history = chain_history(model, sampler, use_sigma=bool(use_sigma))
     sampler.reset()                                                    # keep only the post-burn-in chain
     sampler.run_mcmc(burned_in.coords, nsteps, skip_initial_state_check=True)
+    return _finish_mcmc(sampler, engine, marks, save_sampler_as)
+
+
+def _finish_mcmc(sampler, engine, marks, save_sampler_as):
+    """The end of ``lightcurve_mcmc`` for either sampler: the call's timings, and the flatchain saved if asked."""
+    import time
     marks.append(('run', time.perf_counter()))
     #: seconds of this call, phase by phase, up to the chain complete in HBM (it crosses PCIe when it is first read):
     #: argument checks and photometry; the engine (band tables packed on the host + device engine created; ~0 when the

@@ -815,3 +815,265 @@ class EnsembleSampler:
     @property
     def last_run_ms(self):
         return self._native.last_run_ms()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# parallel-tempered ensembles (what emcee 2 had as PTSampler): degenerate posteriors and the log-evidence
+# ---------------------------------------------------------------------------------------------------------------
+MAX_TEMPS = 64   # rungs the native driver takes (include/lcf.h)
+
+
+def default_betas(ndim, ntemps, Tmax=None):
+    """The ladder of inverse temperatures, ``betas[0] = 1`` descending.  ``Tmax=None``: ``betas[k] = c**-k`` with
+    ``c = 1 + 2 sqrt(ln 4) / sqrt(ndim)`` (neighbouring rungs of a Gaussian posterior then swap about every fourth
+    time); a finite ``Tmax``: ``betas[k] = Tmax**(-k / (ntemps - 1))``; ``Tmax=inf``: ``c**-k`` below a last rung at
+    ``beta = 0``, which samples the prior."""
+    ndim, ntemps = int(ndim), int(ntemps)
+    if ndim < 1 or ntemps < 1:
+        raise ValueError('need ndim >= 1 and ntemps >= 1')
+    k = np.arange(ntemps, dtype=np.float64)
+    c = 1. + 2. * np.sqrt(np.log(4.)) / np.sqrt(ndim)
+    if Tmax is None:
+        return c ** -k
+    if np.isinf(Tmax):
+        betas = c ** -k
+        if ntemps > 1:
+            betas[-1] = 0.
+        return betas
+    if not Tmax > 1.:
+        raise ValueError('Tmax must be greater than 1')
+    return np.ones(1) if ntemps == 1 else Tmax ** (-k / (ntemps - 1))
+
+
+def check_betas(betas):
+    """``betas`` as a float64 vector, or ``ValueError``: it starts at 1, descends strictly and stays ``>= 0``."""
+    betas = np.array(betas, dtype=np.float64)
+    if betas.ndim != 1 or not 1 <= len(betas) <= MAX_TEMPS:
+        raise ValueError(f'betas must be a vector of 1 to {MAX_TEMPS} inverse temperatures')
+    if betas[0] != 1.:
+        raise ValueError('betas must start at 1 (the posterior itself)')
+    if not np.all(betas >= 0.) or not np.all(np.diff(betas) < 0.):    # (a NaN fails both)
+        raise ValueError('betas must descend strictly and stay >= 0')
+    return betas
+
+
+def check_proper_priors(priors, names=None):
+    """A rung at ``beta = 0`` samples the prior itself, so every prior must be proper: Uniform needs finite bounds,
+    LogUniform finite bounds with ``p_min > 0``, Gaussian always is.  ``priors``: descriptors ``(kind, p_min, p_max,
+    mean, stddev)`` (``Prior.descriptor()``) or None (no priors: improper).  ``ValueError`` names the parameter."""
+    from .engine import PRIOR_GAUSSIAN, PRIOR_LOG_UNIFORM
+    if priors is None:
+        raise ValueError('a rung at beta = 0 samples the prior, and the engine has no priors: they are improper')
+    for i, (kind, lo, hi, *_) in enumerate(priors):
+        name = names[i] if names is not None and i < len(names) else f'p{i}'
+        if kind == PRIOR_GAUSSIAN:
+            continue
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError(f'a rung at beta = 0 samples the prior, and the prior of {name} is improper: its bounds '
+                             f'({lo}, {hi}) are not finite')
+        if kind == PRIOR_LOG_UNIFORM and not lo > 0.:
+            raise ValueError(f'a rung at beta = 0 samples the prior, and the log-uniform prior of {name} is improper: '
+                             f'p_min = {lo} is not positive')
+
+
+class LogEvidence(tuple):
+    """``(lnZ, dlnZ)`` of :func:`thermodynamic_integration`; ``reaches_prior`` says whether the ladder ended at
+    ``beta = 0`` (otherwise the integrand was continued flat from the last rung, as emcee 2 did)."""
+
+    def __new__(cls, lnZ, dlnZ, reaches_prior):
+        self = super().__new__(cls, (float(lnZ), float(dlnZ)))
+        self.reaches_prior = bool(reaches_prior)
+        return self
+
+    lnZ = property(lambda self: self[0])
+    dlnZ = property(lambda self: self[1])
+
+
+def _trapezoid(betas, mean):
+    return float(np.sum(0.5 * (mean[:-1] + mean[1:]) * (betas[:-1] - betas[1:])))
+
+
+def thermodynamic_integration(betas, mean_lnL):
+    """``ln Z = integral over beta in [0, 1] of <ln L>_beta`` by the trapezoid rule over the ladder:
+    ``lnZ = sum_k (m_k + m_{k+1}) / 2 * (betas[k] - betas[k+1])``.  A ladder that stops at ``betas[-1] > 0`` is first
+    continued by the pair ``(0, m_{K-1})`` (emcee 2's convention; the result then has ``reaches_prior = False`` and
+    is an upper bound in spirit only: ``<ln L>`` falls towards the prior).  ``dlnZ = |lnZ - lnZ_coarse|``, the
+    coarse ladder being the rungs 0, 2, 4, ... plus the last one if it was skipped.
+
+    ``dlnZ`` measures the discretisation only, and a coarse ladder near ``beta = 0`` dominates it: ``<ln L>`` there
+    changes by orders of magnitude between neighbouring rungs (on the small test problem of this repository the
+    prior rung's mean ``ln L`` is about -1e7 against -2.7e3 at ``beta = 1/16``), so the last trapezoid carries
+    nearly all of the error.  Returns a :class:`LogEvidence`."""
+    betas = np.array(betas, dtype=np.float64)
+    mean = np.array(mean_lnL, dtype=np.float64)
+    if betas.ndim != 1 or betas.shape != mean.shape or len(betas) < 1:
+        raise ValueError('betas and mean_lnL must be vectors of one length')
+    reaches = bool(betas[-1] == 0.)
+    if not reaches:
+        betas, mean = np.append(betas, 0.), np.append(mean, mean[-1])
+    lnZ = _trapezoid(betas, mean)
+    keep = np.arange(0, len(betas), 2)
+    if keep[-1] != len(betas) - 1:
+        keep = np.append(keep, len(betas) - 1)
+    return LogEvidence(lnZ, abs(lnZ - _trapezoid(betas[keep], mean[keep])), reaches)
+
+
+class TemperedSampler:
+    """A parallel-tempered ensemble on one engine: ``ntemps`` rungs of inverse temperature ``betas`` (1 first), each
+    an ensemble of ``nwalkers`` walkers that makes the stretch move on ``prior * L**beta``; after every step
+    neighbouring rungs offer each other their walkers slot by slot.  The cold rung (``temp=0``) samples the posterior
+    and is what ``chain`` / ``flatchain`` give, in the shapes of :class:`EnsembleSampler`; the hot rungs cross between
+    modes and along degeneracies and hand what they find down the ladder, and the rungs' mean log-likelihoods
+    integrate to the log-evidence (:meth:`log_evidence`).
+
+    ``betas`` wins over ``ntemps`` / ``Tmax`` (:func:`default_betas`; ``ntemps=None`` with ``Tmax`` given is not
+    guessed).  A rung at ``beta = 0`` needs proper priors (:func:`check_proper_priors`).  Rung ``k`` draws under
+    ``seed + k * 0x9E3779B97F4A7C15``, so rung 0 of a sampler is the :class:`EnsembleSampler` of the same seed until
+    the first accepted swap.  ``names``: the parameters' names, for the message that refuses an improper prior
+    (default ``p0, p1, ...``)."""
+
+    def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, Tmax=None, seed=0, a=2.0, names=None):
+        from .engine import NativeTempered
+        if nwalkers < 2 * ndim:
+            raise ValueError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of '
+                             'dimensions.')
+        if ndim != engine.ndim:
+            raise ValueError(f'ndim = {ndim} but the engine has {engine.ndim} parameters')
+        if betas is None:
+            if ntemps is None:
+                raise ValueError('give ntemps or betas')
+            betas = default_betas(ndim, ntemps, Tmax)
+        self.betas = check_betas(betas)
+        if self.betas[-1] == 0.:
+            check_proper_priors(getattr(engine, 'priors', None), names)
+        self.ntemps, self.nwalkers, self.ndim = len(self.betas), int(nwalkers), int(ndim)
+        self.engine = engine
+        self.seed = int(seed)
+        self._tempered = NativeTempered(engine, self.betas, nwalkers, seed, a)
+        self._steps_done = 0      # RNG step counter: never reset
+        self._stored = 0          # steps of the stored chain (on the device)
+        self._host = None         # (chain, lnL) once read, until the next stored run
+        self._nacc = np.zeros((self.ntemps, self.nwalkers), dtype=np.int64)
+        self._swaps = np.zeros((2, self.ntemps - 1), dtype=np.int64)   # accepted, proposed
+        self._nsteps_counted = 0
+        self._state = None
+
+    def close(self):
+        self._tempered.close()
+
+    def reset(self):
+        """Forget the stored chain and the counts (not the RNG position)."""
+        self._stored, self._host = 0, None
+        self._nacc[:] = 0
+        self._swaps[:] = 0
+        self._nsteps_counted = 0
+
+    def run_mcmc(self, initial_state, nsteps, store=True, **kwargs):
+        """``initial_state``: (ntemps, nwalkers, ndim) coordinates (or a state tuple whose first entry they are), or
+        None to continue.  Returns ``State(coords, lnL, None)`` of all rungs."""
+        nt = self._tempered
+        if initial_state is not None:
+            coords = np.array(initial_state[0] if isinstance(initial_state, tuple) else initial_state, dtype=np.float64)
+            if coords.shape != (self.ntemps, self.nwalkers, self.ndim):
+                raise ValueError('incompatible input dimensions')
+            if not np.all(np.isfinite(coords)):
+                raise ValueError('At least one parameter value was infinite or NaN')
+            try:
+                nt.set_state(coords)
+            except Exception as exc:
+                if getattr(exc, 'status', None) == 6:
+                    raise ValueError('Probability function returned NaN') from None
+                if getattr(exc, 'status', None) == 7:
+                    raise ValueError(f'Initial state outside the prior: {exc}') from None
+                raise
+            before = (0, 0, 0)
+        elif self._state is None:
+            raise ValueError('Cannot have `initial_state=None` if run_mcmc has never been called.')
+        else:
+            before = nt.counts()
+        try:
+            nt.run(self._steps_done, nsteps, ('append' if self._stored else True) if store else False)
+        except Exception as exc:
+            if store and not self._stored:   # (a run that replaces the chain and fails leaves none; an appending one, the old)
+                self._host = None
+            if getattr(exc, 'status', None) == 6:
+                raise ValueError('Probability function returned NaN') from None
+            raise
+        self._steps_done += nsteps
+        if store and nsteps:
+            self._stored += nsteps
+            self._host = None
+        acc, sa, sp = nt.counts()
+        self._nacc += acc - before[0]
+        self._swaps += np.stack([sa - before[1], sp - before[2]])
+        self._nsteps_counted += nsteps
+        x, ll, _ = nt.get_state()
+        self._state = State(x, ll, None)
+        return self._state
+
+    def _collect(self):
+        if self._host is None:
+            self._host = self._tempered.get_chain(self._stored)
+        return self._host
+
+    @property
+    def iteration(self):
+        return self._stored
+
+    def get_chain(self, temp=0, flat=False, thin=1, discard=0):
+        """(nsteps, nwalkers, ndim) of rung ``temp``; ``temp=None``: (nsteps, ntemps, nwalkers, ndim)."""
+        c = self._collect()[0][discard::thin]
+        if temp is None:
+            return c.reshape(-1, self.ndim) if flat else c
+        c = c[:, temp]
+        return c.reshape(-1, self.ndim) if flat else c
+
+    def get_log_like(self, temp=None, flat=False, thin=1, discard=0):
+        """Log-LIKELIHOODS (no prior): (nsteps, ntemps, nwalkers), or (nsteps, nwalkers) of rung ``temp``."""
+        ll = self._collect()[1][discard::thin]
+        if temp is not None:
+            ll = ll[:, temp]
+        return ll.reshape(-1) if flat else ll
+
+    @property
+    def chain(self):
+        """The cold rung, (nwalkers, nsteps, ndim) as ``EnsembleSampler.chain``."""
+        return np.swapaxes(self.get_chain(0), 0, 1)
+
+    @property
+    def flatchain(self):
+        """The cold rung, (nwalkers * nsteps, ndim), walker-major as ``EnsembleSampler.flatchain``."""
+        c = self.chain
+        return c.reshape(c.shape[0] * c.shape[1], c.shape[2])
+
+    @property
+    def acceptance_fraction(self):
+        """(ntemps, nwalkers): accepted moves per slot and step since the last reset."""
+        return self._nacc / max(1, self._nsteps_counted)
+
+    @property
+    def swap_acceptance_fraction(self):
+        """(ntemps - 1,): accepted / proposed swaps of the pairs (k, k + 1) since the last reset (NaN: none proposed)."""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(self._swaps[1] > 0, self._swaps[0] / self._swaps[1], np.nan)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+        """``thin * integrated_time`` of the cold chain (``lightcurve_fitting_amd.autocorr``)."""
+        from .autocorr import integrated_time
+        if self._stored == 0:
+            raise ValueError('no chain is stored: run the sampler with store=True first')
+        return thin * integrated_time(self.get_chain(0, discard=discard, thin=thin), c=c, tol=tol, quiet=quiet,
+                                      device=self.engine.device)
+
+    def mean_log_like(self, discard=0):
+        """(ntemps,): every rung's mean log-likelihood over the stored steps ``discard:`` and all walkers, reduced on
+        the device in a fixed order."""
+        if self._stored == 0:
+            raise ValueError('no chain is stored: run the sampler with store=True first')
+        if not 0 <= int(discard) < self._stored:
+            raise ValueError(f'discard={discard} leaves no steps of the {self._stored} stored')
+        return self._tempered.mean_loglike(discard)
+
+    def log_evidence(self, discard=0):
+        """``(lnZ, dlnZ)`` by :func:`thermodynamic_integration` over the ladder, with ``reaches_prior``."""
+        return thermodynamic_integration(self.betas, self.mean_log_like(discard))
