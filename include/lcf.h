@@ -529,6 +529,29 @@ lcf_status lcf_tempered_get_counts(lcf_tempered* t, int64_t* n_accepted, int64_t
  * order (what thermodynamic integration needs of the chain). */
 lcf_status lcf_tempered_mean_loglike(lcf_tempered* t, int64_t discard, double* out /* [n_temps] */);
 
+/* An adaptive ladder (Vousden, Farr & Mandel 2016): lcf_tempered_run with the rungs moving on the device, in stream order,
+ * until neighbouring pairs swap equally often.  Needs n_temps >= 3 and betas[n_temps - 1] == 0, finite lag > 0 and
+ * time > 0 (otherwise LCF_ERR_INVALID_ARGUMENT, before any launch).  After the swaps of every odd step s, if every pair
+ * was offered since the last adaptation (the window): A_k = accepted / offered swaps of pair k in the window,
+ * kappa = lag / (t + lag) / time with t = t0 + (s - first_step) + 1, dT_k = (1 / beta_{k+1} - 1 / beta_k) exp(kappa (A_k -
+ * A_{k+1})) for k = 0 .. n_temps - 3, then in this order T_0 = 1, T_{k+1} = T_k + dT_k, beta_{k+1} = 1 / T_{k+1}; the
+ * window closes.  beta_0 = 1 and the last beta = 0 never move.  t0: the adapting steps this handle has made before (the
+ * caller counts them).  An adapting run that follows an adapting run goes on in its window, so a run cut in two gives
+ * the same ladders and chains; after lcf_tempered_run or lcf_tempered_set_state the window starts empty.  Gaps that round
+ * away leave equal neighbours, which the driver takes. */
+lcf_status lcf_tempered_run_adaptive(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store, double lag,
+                                     double time, int64_t t0);
+/* The ladder now: betas[n_temps]. */
+lcf_status lcf_tempered_get_betas(lcf_tempered* t, double* betas);
+/* betas[n_stored][n_temps]: the ladder every stored step was sampled under (before the adaptation that follows it). */
+lcf_status lcf_tempered_get_beta_history(lcf_tempered* t, double* betas);
+/* Stepping stones (Xie et al. 2011), per pair k and batch b of the stored steps discard + (b n) / n_batches .. (n the
+ * steps kept): over ln L of rung k + 1, all walkers, max = the maximum m, sum = sum exp((beta_k - beta_{k+1}) (ln L - m))
+ * (0 when m = -inf), count = the number of terms; each [n_temps - 1][n_batches], reduced on the device in a fixed order.
+ * The ladder is the one step `discard` was sampled under.  1 <= n_batches <= n. */
+lcf_status lcf_tempered_stepping_stones(lcf_tempered* t, int64_t discard, int32_t n_batches, double* max, double* sum,
+                                        double* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,9 @@
 // seed + k * 0x9E3779B97F4A7C15), the likelihood of a half-step's K * ceil(W / 2) proposals from ONE call of
 // lcf_log_likelihood_dev on the engine's stream.  Per half-step: k_t_propose, the likelihood's launches, k_t_accept;
 // per step one k_t_swap more, which also stores the step.  One stream, stream order is all the synchronisation.
+// An adapting run (lcf_tempered_run_adaptive) launches k_t_adapt behind the k_t_swap of every odd step: the ladder moves
+// on the device, from the swap counts since the last adaptation, and the host reads nothing until the run has ended.
+// k_t_stone reduces the stored ln L to the stepping-stone partials of every (pair, batch).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -81,11 +84,13 @@ __global__ void k_t_accept(const DevTempered tp, const DrawRec* __restrict__ dra
 
 // After both halves of step `step`: the pairs (k, k + 1) with k = step (mod 2) swap slot by slot, then the step is
 // stored (chain != null: row `row` of chain[.][n_temps][n_walkers][n_dim] and chain_ll[.][n_temps][n_walkers]).  One
-// thread per (rung, slot); the thread of a pair's lower rung does the pair, the upper rung's does nothing.
+// thread per (rung, slot); the thread of a pair's lower rung does the pair, the upper rung's does nothing.  Row `row` of
+// chain_betas[.][n_temps] gets the ladder the step was sampled under (an adaptation comes behind this launch).
 __global__ void k_t_swap(const DevTempered tp, long long step, double* __restrict__ chain, double* __restrict__ chain_ll,
-                         long long row) {
+                         double* __restrict__ chain_betas, long long row) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= tp.n_temps * tp.n_walkers) return;
+    if (chain && idx < tp.n_temps) chain_betas[(size_t)row * tp.n_temps + idx] = tp.betas[idx];
     const int k = idx / tp.n_walkers, i = idx - k * tp.n_walkers;
     const int parity = (int)(step & 1);
     if (k >= 1 && ((k - 1) & 1) == parity) return;            // the upper rung of a pair
@@ -145,6 +150,94 @@ __global__ __launch_bounds__(256) void k_t_mean(const double* __restrict__ chain
     if (t == 0) out[k] = part[0] / (double)n;
 }
 
+// The ladder after the swaps of an odd step (one workgroup of 64 threads; n_temps <= 64).  Nothing happens unless every
+// pair was offered since the last adaptation.  A_k: the fraction of pair k's swaps accepted since then;
+// kappa = lag / (t + lag) / time; dT_k = (1 / beta_{k+1} - 1 / beta_k) exp(kappa (A_k - A_{k+1})) for k = 0 .. K - 3, by
+// the lanes; then ONE lane, left to right: T_0 = 1, T_{k+1} = T_k + dT_k, beta_{k+1} = 1 / T_{k+1}.  beta_0 and
+// beta_{K-1} (= 0: the last gap is no free variable) are never written.  Then seen := the counts.
+__global__ __launch_bounds__(64) void k_t_adapt(int n_temps, double* __restrict__ betas,
+                                                const unsigned long long* __restrict__ swap_acc,
+                                                const unsigned long long* __restrict__ swap_prop,
+                                                unsigned long long* __restrict__ seen_acc,
+                                                unsigned long long* __restrict__ seen_prop, double lag, double time,
+                                                long long t_adapt) {
+    __shared__ double A[64], dT[64];
+    __shared__ int closed;
+    const int t = threadIdx.x, pairs = n_temps - 1;
+    if (t == 0) closed = 0;
+    __syncthreads();
+    unsigned long long acc = 0, prop = 0;
+    if (t < pairs) {
+        acc = swap_acc[t];
+        prop = swap_prop[t];
+        const unsigned long long dp = prop - seen_prop[t];
+        if (dp == 0)
+            closed = 1;   // (every writer writes the same value)
+        else
+            A[t] = (double)(acc - seen_acc[t]) / (double)dp;
+    }
+    __syncthreads();
+    if (closed) return;   // (uniform: read behind the barrier)
+    const double kappa = lag / ((double)t_adapt + lag) / time;
+    if (t < pairs - 1) dT[t] = (1. / betas[t + 1] - 1. / betas[t]) * exp(kappa * (A[t] - A[t + 1]));
+    __syncthreads();
+    if (t == 0) {
+        double T = 1.;
+        for (int k = 0; k < pairs - 1; ++k) {
+            T += dT[k];
+            betas[k + 1] = 1. / T;
+        }
+    }
+    if (t < pairs) {
+        seen_acc[t] = acc;
+        seen_prop[t] = prop;
+    }
+}
+
+// Stepping stones: one workgroup per (pair k, batch b) over ln L of rung k + 1, the stored steps s0 + (b n) / B ..
+// s0 + ((b + 1) n) / B - 1 (n = n_steps - s0) and all walkers, in the fixed order of k_t_mean: thread t takes the
+// elements t, t + 256, ..., then a tree.  Two passes: the maximum m, then sum exp((beta_k - beta_{k+1}) (ln L - m)).
+// Idle threads hold the identities (-inf, 0); a batch whose maximum is -inf has sum 0.  The ladder is row s0 of
+// chain_betas.  out: max, sum, count, each [n_temps - 1][n_batches].
+__global__ __launch_bounds__(256) void k_t_stone(const double* __restrict__ chain_ll, const double* __restrict__ chain_betas,
+                                                 long long n_steps, int n_temps, int n_walkers, long long s0, int n_batches,
+                                                 double* __restrict__ out) {
+    __shared__ double part[256];
+    const int k = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const long long nk = n_steps - s0;
+    const long long lo = s0 + ((long long)b * nk) / n_batches, hi = s0 + ((long long)(b + 1) * nk) / n_batches;
+    const long long n = (hi - lo) * n_walkers;
+    const double db = chain_betas[(size_t)s0 * n_temps + k] - chain_betas[(size_t)s0 * n_temps + k + 1];
+    const auto at = [&](long long e) {
+        return chain_ll[((size_t)(lo + e / n_walkers) * n_temps + (k + 1)) * n_walkers + (size_t)(e % n_walkers)];
+    };
+    double m = -INFINITY;
+    for (long long e = t; e < n; e += 256) m = fmax(m, at(e));
+    part[t] = m;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) part[t] = fmax(part[t], part[t + h]);
+        __syncthreads();
+    }
+    m = part[0];
+    __syncthreads();
+    double s = 0.;
+    if (m > -INFINITY)
+        for (long long e = t; e < n; e += 256) s += exp(db * (at(e) - m));
+    part[t] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) part[t] += part[t + h];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const size_t o = (size_t)k * n_batches + b, plane = (size_t)(n_temps - 1) * n_batches;
+        out[o] = m;
+        out[plane + o] = part[0];
+        out[2 * plane + o] = (double)n;
+    }
+}
+
 }  // namespace
 
 struct lcf_tempered {
@@ -161,14 +254,24 @@ struct lcf_tempered {
     GenItem* d_items = nullptr;     // [n_temps]
     double* d_mean = nullptr;       // [n_temps]
     double *chain = nullptr, *chain_ll = nullptr;
+    double* chain_betas = nullptr;  // [chain_cap][n_temps]: the ladder every stored step was sampled under
     int64_t chain_cap = 0, chain_steps = 0;
     bool has_state = false;
+    // adaptation (k_t_adapt): the ladder dt.betas points to, writable, and the swap counts at the last adaptation
+    double* d_betas = nullptr;                                       // [n_temps]
+    unsigned long long *seen_acc = nullptr, *seen_prop = nullptr;    // [n_temps - 1] used
+    bool ends_at_prior = false;     // betas[n_temps - 1] == 0 (never written after create)
+    bool window_open = false;       // the last run adapted: the next adapting run goes on in its window
+    double* d_stone = nullptr;      // [3][n_temps - 1][stone_cap] of k_t_stone
+    int64_t stone_cap = 0;
 
     ~lcf_tempered() {
         hipSetDevice(device);
         for (void* p : owned) hipFree(p);
         if (chain) hipFree(chain);
         if (chain_ll) hipFree(chain_ll);
+        if (chain_betas) hipFree(chain_betas);
+        if (d_stone) hipFree(d_stone);
     }
     size_t rows() const { return (size_t)dt.n_temps * dt.n_walkers; }
 };
@@ -182,37 +285,44 @@ unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 lcf_status reserve_chain(lcf_tempered* t, int64_t steps, int64_t keep) {
     if (steps <= t->chain_cap) return LCF_OK;
     const size_t per_step = t->rows();
-    const size_t nd = t->dt.n_dim;
+    const size_t nd = t->dt.n_dim, K = t->dt.n_temps;
     if ((double)steps * (double)per_step * (double)(nd + 1) * 8. > 9e18)
         return fail(LCF_ERR_OUT_OF_MEMORY, "the chain of the run does not fit in an address space");
     int64_t cap = steps;
     size_t free_b = 0, total_b = 0;
     LCF_HIP(hipStreamSynchronize(t->e->stream));
     LCF_HIP(hipMemGetInfo(&free_b, &total_b));
-    const auto bytes = [&](int64_t s) { return (size_t)s * per_step * (nd + 1) * sizeof(double); };
+    const auto bytes = [&](int64_t s) { return (size_t)s * (per_step * (nd + 1) + K) * sizeof(double); };
     if (keep > 0 && bytes(std::max(steps, 2 * t->chain_cap)) <= free_b / 2) cap = std::max(steps, 2 * t->chain_cap);
     if (bytes(cap) > free_b)
         return fail(LCF_ERR_OUT_OF_MEMORY, "the chain of the run needs " + std::to_string(bytes(cap)) + " bytes of device memory, " +
                                                std::to_string(free_b) + " are free");
-    double *c = nullptr, *l = nullptr;
+    double *c = nullptr, *l = nullptr, *b = nullptr;
     LCF_HIP(hipMalloc((void**)&c, (size_t)cap * per_step * nd * sizeof(double)));
-    if (hipError_t err = hipMalloc((void**)&l, (size_t)cap * per_step * sizeof(double))) {
+    hipError_t err = hipMalloc((void**)&l, (size_t)cap * per_step * sizeof(double));
+    if (!err) err = hipMalloc((void**)&b, (size_t)cap * K * sizeof(double));
+    if (err) {
         hipFree(c);
+        if (l) hipFree(l);
         return fail(err == hipErrorOutOfMemory ? LCF_ERR_OUT_OF_MEMORY : LCF_ERR_HIP, hipGetErrorString(err));
     }
     if (keep > 0) {
-        hipError_t err = hipMemcpy(c, t->chain, (size_t)keep * per_step * nd * sizeof(double), hipMemcpyDeviceToDevice);
+        err = hipMemcpy(c, t->chain, (size_t)keep * per_step * nd * sizeof(double), hipMemcpyDeviceToDevice);
         if (!err) err = hipMemcpy(l, t->chain_ll, (size_t)keep * per_step * sizeof(double), hipMemcpyDeviceToDevice);
+        if (!err) err = hipMemcpy(b, t->chain_betas, (size_t)keep * K * sizeof(double), hipMemcpyDeviceToDevice);
         if (err) {
             hipFree(c);
             hipFree(l);
+            hipFree(b);
             return fail(LCF_ERR_HIP, hipGetErrorString(err));
         }
     }
     if (t->chain) hipFree(t->chain);
     if (t->chain_ll) hipFree(t->chain_ll);
+    if (t->chain_betas) hipFree(t->chain_betas);
     t->chain = c;
     t->chain_ll = l;
+    t->chain_betas = b;
     t->chain_cap = cap;
     return LCF_OK;
 }
@@ -251,14 +361,16 @@ lcf_status lcf_tempered_create(lcf_engine* e, int32_t n_temps, const double* bet
     // about 2^19 draw records (28 MiB) per block of steps
     t->blk_cap = std::max<int64_t>(1, std::min<int64_t>(256, (int64_t)(1 << 19) / (int64_t)nw));
     lcf_status st;
-    double* d_betas = nullptr;
+    double*& d_betas = t->d_betas;
 #define AL(p, n) if ((st = dalloc(&p, n, t->owned)) != LCF_OK) { delete t; return st; }
     AL(d_betas, K); AL(dt.X, nw * nd); AL(dt.LL, nw); AL(dt.LPR, nw); AL(dt.nacc, nw);
     AL(dt.Q, nh * nd); AL(dt.QLL, nh); AL(dt.QPR, nh);
     AL(dt.swap_acc, K); AL(dt.swap_prop, K); AL(dt.err, 1);
     AL(t->d_perm, nw * t->blk_cap); AL(t->d_draws, 2 * nh * t->blk_cap); AL(t->d_items, K); AL(t->d_mean, K);
+    AL(t->seen_acc, K); AL(t->seen_prop, K);
 #undef AL
     dt.betas = d_betas;
+    t->ends_at_prior = betas[n_temps - 1] == 0.;
     std::vector<GenItem> items(K);
     for (size_t k = 0; k < K; ++k) {
         const uint64_t sk = seed + (uint64_t)k * 0x9E3779B97F4A7C15ull;   // (mod 2^64)
@@ -276,6 +388,8 @@ lcf_status lcf_tempered_create(lcf_engine* e, int32_t n_temps, const double* bet
     if (!err) err = hipMemset(dt.nacc, 0, nw * sizeof(long long));
     if (!err) err = hipMemset(dt.swap_acc, 0, K * sizeof(unsigned long long));
     if (!err) err = hipMemset(dt.swap_prop, 0, K * sizeof(unsigned long long));
+    if (!err) err = hipMemset(t->seen_acc, 0, K * sizeof(unsigned long long));
+    if (!err) err = hipMemset(t->seen_prop, 0, K * sizeof(unsigned long long));
     if (!err) err = hipMemset(dt.err, 0, sizeof(int));
     if (err) {
         delete t;
@@ -307,6 +421,8 @@ lcf_status lcf_tempered_set_state(lcf_tempered* t, const double* coords) {
     LCF_HIP(hipMemsetAsync(dt.nacc, 0, nw * sizeof(long long), e->stream));
     LCF_HIP(hipMemsetAsync(dt.swap_acc, 0, dt.n_temps * sizeof(unsigned long long), e->stream));
     LCF_HIP(hipMemsetAsync(dt.swap_prop, 0, dt.n_temps * sizeof(unsigned long long), e->stream));
+    LCF_HIP(hipMemsetAsync(t->seen_acc, 0, dt.n_temps * sizeof(unsigned long long), e->stream));   // (the window too)
+    LCF_HIP(hipMemsetAsync(t->seen_prop, 0, dt.n_temps * sizeof(unsigned long long), e->stream));
     LCF_HIP(hipMemsetAsync(dt.err, 0, sizeof(int), e->stream));
     std::vector<double> ll(nw), lpr(nw);
     LCF_HIP(hipMemcpyAsync(ll.data(), dt.LL, nw * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -337,13 +453,25 @@ lcf_status lcf_tempered_get_state(lcf_tempered* t, double* coords, double* lnL, 
     return LCF_OK;
 }
 
-lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store) {
+}  // extern "C"
+
+namespace {
+
+// The run of lcf_tempered_run (adapt = false) and of lcf_tempered_run_adaptive.
+lcf_status run_steps(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store, bool adapt, double lag,
+                     double time, int64_t t0) {
     if (!t || n_steps < 0 || first_step < 0 || store < 0 || store > 2) return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument");
     // (the step is a 32-bit counter word of the generators; far below anything that could overflow the sums below)
     if (first_step > (1LL << 40) || n_steps > (1LL << 40)) return fail(LCF_ERR_INVALID_ARGUMENT, "step numbers beyond 2^40");
+    const DevTempered& dt = t->dt;
+    if (adapt) {
+        if (dt.n_temps < 3 || !t->ends_at_prior)
+            return fail(LCF_ERR_INVALID_ARGUMENT, "an adaptive ladder needs at least 3 rungs and a last rung at beta = 0");
+        if (!(lag > 0.) || !(time > 0.) || !std::isfinite(lag) || !std::isfinite(time) || t0 < 0 || t0 > (1LL << 40))
+            return fail(LCF_ERR_INVALID_ARGUMENT, "adaptation needs finite lag > 0 and time > 0, and 0 <= t0 <= 2^40");
+    }
     if (!t->has_state) return fail(LCF_ERR_STATE, "lcf_tempered_set_state must be called first");
     lcf_engine* e = t->e;
-    const DevTempered& dt = t->dt;
     LCF_HIP(hipSetDevice(e->device));
     int64_t row0 = 0;
     if (store) {
@@ -352,6 +480,12 @@ lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps
         t->chain_steps = row0;
     }
     hipStream_t st = e->stream;
+    if (adapt && !t->window_open) {   // after a frozen run (or none): the window starts here
+        const size_t pb = (size_t)(dt.n_temps - 1) * sizeof(unsigned long long);
+        LCF_HIP(hipMemcpyAsync(t->seen_acc, dt.swap_acc, pb, hipMemcpyDeviceToDevice, st));
+        LCF_HIP(hipMemcpyAsync(t->seen_prop, dt.swap_prop, pb, hipMemcpyDeviceToDevice, st));
+    }
+    t->window_open = adapt;
     const size_t n_prop = (size_t)dt.n_temps * dt.n_half;
     const long long rung_stride = (long long)t->blk_cap * 2 * dt.n_half;
     for (int64_t k0 = 0; k0 < n_steps; k0 += t->blk_cap) {
@@ -365,8 +499,13 @@ lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps
                 if (lcf_status r = lcf_log_likelihood_dev(e, (int64_t)n_prop, dt.Q, dt.QLL, st)) return r;
                 hipLaunchKernelGGL(k_t_accept, dim3(blocks_for(n_prop)), dim3(256), 0, st, dt, draws, rung_stride);
             }
-            hipLaunchKernelGGL(k_t_swap, dim3(blocks_for(t->rows())), dim3(256), 0, st, dt, (long long)(first_step + k0 + j),
-                               store ? t->chain : nullptr, store ? t->chain_ll : nullptr, (long long)(row0 + k0 + j));
+            const int64_t step = first_step + k0 + j;
+            hipLaunchKernelGGL(k_t_swap, dim3(blocks_for(t->rows())), dim3(256), 0, st, dt, (long long)step,
+                               store ? t->chain : nullptr, store ? t->chain_ll : nullptr, store ? t->chain_betas : nullptr,
+                               (long long)(row0 + k0 + j));
+            if (adapt && (step & 1))
+                hipLaunchKernelGGL(k_t_adapt, dim3(1), dim3(64), 0, st, dt.n_temps, t->d_betas, dt.swap_acc, dt.swap_prop,
+                                   t->seen_acc, t->seen_prop, lag, time, (long long)(t0 + k0 + j + 1));
         }
         LCF_HIP(hipGetLastError());
     }
@@ -376,6 +515,68 @@ lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps
     // (a run that met a NaN stores nothing: the chain stays what it was before the run, or empty when it was replaced)
     if (err) return fail(LCF_ERR_NAN_LOGPROB, "a proposal inside the prior had a NaN likelihood");
     if (store) t->chain_steps = row0 + n_steps;
+    return LCF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store) {
+    return run_steps(t, first_step, n_steps, store, false, 0., 0., 0);
+}
+
+lcf_status lcf_tempered_run_adaptive(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store, double lag,
+                                     double time, int64_t t0) {
+    return run_steps(t, first_step, n_steps, store, true, lag, time, t0);
+}
+
+lcf_status lcf_tempered_get_betas(lcf_tempered* t, double* betas) {
+    if (!t || !betas) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    LCF_HIP(hipSetDevice(t->device));
+    LCF_HIP(hipStreamSynchronize(t->e->stream));
+    LCF_HIP(hipMemcpy(betas, t->d_betas, (size_t)t->dt.n_temps * sizeof(double), hipMemcpyDeviceToHost));
+    return LCF_OK;
+}
+
+lcf_status lcf_tempered_get_beta_history(lcf_tempered* t, double* betas) {
+    if (!t || !betas) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (t->chain_steps == 0) return fail(LCF_ERR_STATE, "no chain is stored");
+    LCF_HIP(hipSetDevice(t->device));
+    LCF_HIP(hipStreamSynchronize(t->e->stream));
+    LCF_HIP(hipMemcpy(betas, t->chain_betas, (size_t)t->chain_steps * t->dt.n_temps * sizeof(double), hipMemcpyDeviceToHost));
+    return LCF_OK;
+}
+
+lcf_status lcf_tempered_stepping_stones(lcf_tempered* t, int64_t discard, int32_t n_batches, double* max, double* sum,
+                                        double* count) {
+    if (!t || !max || !sum || !count) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (t->dt.n_temps < 2) return fail(LCF_ERR_INVALID_ARGUMENT, "stepping stones need at least 2 rungs");
+    if (t->chain_steps == 0) return fail(LCF_ERR_STATE, "no chain is stored");
+    if (discard < 0 || discard >= t->chain_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no stored step");
+    if (n_batches < 1 || n_batches > t->chain_steps - discard)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "n_batches must be from 1 to the number of stored steps kept");
+    if (n_batches > 65535) return fail(LCF_ERR_UNSUPPORTED, "at most 65535 batches");
+    const DevTempered& dt = t->dt;
+    const size_t plane = (size_t)(dt.n_temps - 1) * n_batches;
+    hipStream_t st = t->e->stream;
+    LCF_HIP(hipSetDevice(t->device));
+    if (n_batches > t->stone_cap) {
+        LCF_HIP(hipStreamSynchronize(st));
+        if (t->d_stone) hipFree(t->d_stone);
+        t->d_stone = nullptr;
+        t->stone_cap = 0;
+        LCF_HIP(hipMalloc((void**)&t->d_stone, 3 * plane * sizeof(double)));
+        t->stone_cap = n_batches;
+    }
+    hipLaunchKernelGGL(k_t_stone, dim3((unsigned)(dt.n_temps - 1), (unsigned)n_batches), dim3(256), 0, st, t->chain_ll,
+                       t->chain_betas, (long long)t->chain_steps, dt.n_temps, dt.n_walkers, (long long)discard,
+                       (int)n_batches, t->d_stone);
+    LCF_HIP(hipGetLastError());
+    LCF_HIP(hipMemcpyAsync(max, t->d_stone, plane * sizeof(double), hipMemcpyDeviceToHost, st));
+    LCF_HIP(hipMemcpyAsync(sum, t->d_stone + plane, plane * sizeof(double), hipMemcpyDeviceToHost, st));
+    LCF_HIP(hipMemcpyAsync(count, t->d_stone + 2 * plane, plane * sizeof(double), hipMemcpyDeviceToHost, st));
+    LCF_HIP(hipStreamSynchronize(st));
     return LCF_OK;
 }
 

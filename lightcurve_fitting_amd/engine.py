@@ -172,6 +172,11 @@ SIGNATURES = [
     ('lcf_tempered_get_counts', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64)]),
     ('lcf_tempered_mean_loglike', C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    ('lcf_tempered_run_adaptive', C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                            C.c_int64]),
+    ('lcf_tempered_get_betas', C.c_int, [C.c_void_p, _dp]),
+    ('lcf_tempered_get_beta_history', C.c_int, [C.c_void_p, _dp]),
+    ('lcf_tempered_stepping_stones', C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp]),
 ]
 
 
@@ -622,6 +627,30 @@ class NativeTempered:
         out = np.empty(self.ntemps)
         _check(self._lib.lcf_tempered_mean_loglike(self._h, int(discard), _ptr(out)))
         return out
+
+    def run_adaptive(self, first_step, nsteps, store, lag, time, t0):
+        """``run`` with the ladder adapting on the device; ``t0``: the adapting steps made before this run."""
+        _check(self._lib.lcf_tempered_run_adaptive(self._h, int(first_step), int(nsteps), self.STORE[store], float(lag),
+                                                   float(time), int(t0)))
+
+    def get_betas(self):
+        """The ladder now, (K,)."""
+        out = np.empty(self.ntemps)
+        _check(self._lib.lcf_tempered_get_betas(self._h, _ptr(out)))
+        return out
+
+    def get_beta_history(self, nstored):
+        """(nstored, K): the ladder every stored step was sampled under."""
+        out = np.empty((int(nstored), self.ntemps))
+        if nstored:
+            _check(self._lib.lcf_tempered_get_beta_history(self._h, _ptr(out)))
+        return out
+
+    def stepping_stones(self, discard, batches):
+        """``(max, sum, count)``, each (K - 1, batches): the stepping-stone partials of every pair and batch."""
+        m, s, n = (np.empty((self.ntemps - 1, int(batches))) for _ in range(3))
+        _check(self._lib.lcf_tempered_stepping_stones(self._h, int(discard), int(batches), _ptr(m), _ptr(s), _ptr(n)))
+        return m, s, n
 
 
 def population_run(native_samplers, first_step, nsteps, split='random', store=True):

@@ -87,7 +87,7 @@ def _check_start_box(names, priors, p_lo, p_up):
 def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p_up=None,
                     nwalkers=100, nsteps=1000, nsteps_burnin=1000, model_kwargs=None,
                     show=False, save_plot_as='', save_sampler_as='', use_sigma=False, sigma_type='relative',
-                    seed=None, ntemps=None, betas=None, Tmax=None):
+                    seed=None, ntemps=None, betas=None, Tmax=None, adapt=False):
     """Fit an analytical model to observed photometry with an affine-invariant ensemble sampler on the GPU.
 
     Arguments as in the reference (fitting.py:16-58).  ``seed`` (extension) keys the counter-based RNG; by default
@@ -98,6 +98,9 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     parallel-tempered ensemble, :class:`~lightcurve_fitting_amd.sampler.TemperedSampler`, of ``nwalkers`` walkers per
     rung -- for degenerate or multi-modal posteriors, and for the log-evidence (``sampler.log_evidence()``).  Every
     rung starts uniform in the starting box; ``chain`` / ``flatchain`` of the returned sampler are the cold rung's.
+    ``adapt=True`` (tempered fits only, ``ValueError`` otherwise; needs ``ntemps >= 3`` and ``Tmax=inf``): the ladder
+    adapts during the burn-in until neighbouring rungs swap equally often, and is frozen for the stored run, so that
+    ``sampler.log_evidence(method='stepping_stone')`` is over one ladder.
 
     Returns the sampler (``.chain`` (nwalkers, nsteps, ndim), ``.flatchain``, ``.run_mcmc``, ``.reset``).
     """
@@ -105,6 +108,8 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks = [('call', time.perf_counter())]
     if model_kwargs is not None:
         raise Exception(MODEL_KWARGS_WARNING)
+    if adapt and ntemps is None and betas is None and Tmax is None:
+        raise ValueError('adapt=True adapts a temperature ladder: give ntemps, betas or Tmax')
     _prepare_photometry(lc, model)
     if use_sigma and model.input_names[-1] != '\\sigma':   # the intrinsic-scatter parameter joins the model's own
         model.input_names.append('\\sigma')
@@ -132,7 +137,7 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
                                   names=model.input_names)
         start = p_lo + (p_up - p_lo) * np.random.rand(sampler.ntemps, nwalkers, ndim)
         marks.append(('sampler', time.perf_counter()))
-        sampler.run_mcmc(start, nsteps_burnin, store=False)
+        sampler.run_mcmc(start, nsteps_burnin, store=False, adapt=bool(adapt))
         marks.append(('burn_in', time.perf_counter()))
         if show or save_plot_as:
             warnings.warn('chain plots are not produced by the MI355X engine; plot sampler.chain with the reference tools')

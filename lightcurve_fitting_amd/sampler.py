@@ -877,8 +877,9 @@ def check_proper_priors(priors, names=None):
 
 
 class LogEvidence(tuple):
-    """``(lnZ, dlnZ)`` of :func:`thermodynamic_integration`; ``reaches_prior`` says whether the ladder ended at
-    ``beta = 0`` (otherwise the integrand was continued flat from the last rung, as emcee 2 did)."""
+    """``(lnZ, dlnZ)`` of :func:`thermodynamic_integration` or :func:`stepping_stone`; ``reaches_prior`` says whether
+    the ladder ended at ``beta = 0`` (otherwise thermodynamic integration continued the integrand flat from the last
+    rung, as emcee 2 did, and the stepping stones stop at the last rung)."""
 
     def __new__(cls, lnZ, dlnZ, reaches_prior):
         self = super().__new__(cls, (float(lnZ), float(dlnZ)))
@@ -918,6 +919,51 @@ def thermodynamic_integration(betas, mean_lnL):
     return LogEvidence(lnZ, abs(lnZ - _trapezoid(betas[keep], mean[keep])), reaches)
 
 
+def stepping_stone(betas, partials):
+    """``ln Z`` by the stepping-stone estimator (Xie et al. 2011): ``Z = prod_k r_k`` with
+    ``r_k = Z(betas[k]) / Z(betas[k+1]) = < L**(betas[k] - betas[k+1]) >`` over the samples of rung ``k + 1``.
+
+    ``partials = (max, sum, count)``, each (K - 1, B): per pair ``k`` and batch ``b`` of the stored steps the maximum
+    ``m`` of rung ``k + 1``'s ``ln L``, ``sum exp((betas[k] - betas[k+1]) (ln L - m))`` and the number of terms
+    (``TemperedSampler.log_evidence`` gets them from the device).  ``ln r_kb = dbeta_k m + ln(sum / count)``;
+    ``ln r_k`` combines the batches' partials by log-sum-exp (the average over all samples, not the mean of the
+    batches' logarithms); ``lnZ = sum_k ln r_k``; ``dlnZ = sqrt(sum_k var_b(ln r_kb, ddof=1) / B)``, the batch-means
+    standard error.  ``reaches_prior = (betas[-1] == 0)``: otherwise the sum is ``ln(Z / Z(betas[-1]))``, the
+    evidence relative to the hottest rung's, not the evidence.
+
+    What ``dlnZ`` cannot see: a stone whose average is carried by samples its hot rung never drew.  ``L**dbeta`` is
+    then dominated by a tail no batch has visited, every batch agrees on too small a value, and the estimate is biased
+    low with a small ``dlnZ``.  Close rungs near ``beta = 0`` (an adapted ladder) are the remedy, not more steps.
+    Batches are taken as independent; steps correlated over more than a batch make ``dlnZ`` too small as well."""
+    betas = np.array(betas, dtype=np.float64)
+    if betas.ndim != 1 or len(betas) < 2:
+        raise ValueError('betas must be a vector of at least 2 inverse temperatures')
+    try:
+        m, total, count = (np.array(p, dtype=np.float64) for p in partials)
+    except (TypeError, ValueError):
+        raise ValueError('partials must be (max, sum, count)') from None
+    if not (m.shape == total.shape == count.shape and m.ndim == 2 and m.shape[0] == len(betas) - 1):
+        raise ValueError('max, sum and count must each have shape (len(betas) - 1, batches)')
+    B = m.shape[1]
+    if B < 2:
+        raise ValueError('the batch-means error needs batches >= 2')
+    dbeta = (betas[:-1] - betas[1:])[:, None]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ln_rkb = dbeta * m + np.log(total / count)
+        top = np.max(m, axis=1, keepdims=True)
+        scaled = np.where(total > 0., total * np.exp(dbeta * (m - top)), 0.)
+        ln_rk = dbeta[:, 0] * top[:, 0] + np.log(np.sum(scaled, axis=1) / np.sum(count, axis=1))
+        dlnZ = np.sqrt(np.sum(np.var(ln_rkb, axis=1, ddof=1)) / B)
+    return LogEvidence(np.sum(ln_rk), dlnZ, betas[-1] == 0.)
+
+
+def check_adaptive(betas):
+    """``ValueError`` unless the ladder can adapt: at least 3 rungs, the last one at ``beta = 0`` (with a finite
+    hottest rung the last gap is no free variable, and the rungs could cross)."""
+    if len(betas) < 3 or betas[-1] != 0.:
+        raise ValueError('an adaptive ladder needs at least 3 rungs and a last rung at beta = 0 (Tmax=inf)')
+
+
 class TemperedSampler:
     """A parallel-tempered ensemble on one engine: ``ntemps`` rungs of inverse temperature ``betas`` (1 first), each
     an ensemble of ``nwalkers`` walkers that makes the stretch move on ``prior * L**beta``; after every step
@@ -930,9 +976,17 @@ class TemperedSampler:
     guessed).  A rung at ``beta = 0`` needs proper priors (:func:`check_proper_priors`).  Rung ``k`` draws under
     ``seed + k * 0x9E3779B97F4A7C15``, so rung 0 of a sampler is the :class:`EnsembleSampler` of the same seed until
     the first accepted swap.  ``names``: the parameters' names, for the message that refuses an improper prior
-    (default ``p0, p1, ...``)."""
+    (default ``p0, p1, ...``).
 
-    def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, Tmax=None, seed=0, a=2.0, names=None):
+    ``run_mcmc(..., adapt=True)`` moves the rungs while it runs, on the device, until neighbouring pairs swap equally
+    often (Vousden, Farr & Mandel 2016, as ``ptemcee``; ``adaptation_lag`` and ``adaptation_time`` are its names and
+    defaults): after every second step, from the swaps since the last adaptation, the gaps ``1 / beta_{k+1} -
+    1 / beta_k`` are scaled by ``exp(kappa (A_k - A_{k+1}))`` with ``kappa = lag / (t + lag) / time`` and ``t`` the
+    adapting steps made so far (``adaptation_steps``, never reset).  Needs ``ntemps >= 3`` and a last rung at
+    ``beta = 0``.  A moving ladder samples no fixed distribution: adapt during burn-in, then run frozen."""
+
+    def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, Tmax=None, seed=0, a=2.0, names=None,
+                 adaptation_lag=10000, adaptation_time=100):
         from .engine import NativeTempered
         if nwalkers < 2 * ndim:
             raise ValueError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of '
@@ -943,9 +997,13 @@ class TemperedSampler:
             if ntemps is None:
                 raise ValueError('give ntemps or betas')
             betas = default_betas(ndim, ntemps, Tmax)
-        self.betas = check_betas(betas)
+        self.betas = check_betas(betas)        # the ladder now: read back after every run
         if self.betas[-1] == 0.:
             check_proper_priors(getattr(engine, 'priors', None), names)
+        if not (0. < adaptation_lag < np.inf and 0. < adaptation_time < np.inf):
+            raise ValueError('adaptation_lag and adaptation_time must be positive and finite')
+        self.adaptation_lag, self.adaptation_time = float(adaptation_lag), float(adaptation_time)
+        self.adaptation_steps = 0   # adapting steps made: never reset
         self.ntemps, self.nwalkers, self.ndim = len(self.betas), int(nwalkers), int(ndim)
         self.engine = engine
         self.seed = int(seed)
@@ -953,6 +1011,7 @@ class TemperedSampler:
         self._steps_done = 0      # RNG step counter: never reset
         self._stored = 0          # steps of the stored chain (on the device)
         self._host = None         # (chain, lnL) once read, until the next stored run
+        self._host_betas = None   # (stored, K) ladder per stored step, likewise
         self._nacc = np.zeros((self.ntemps, self.nwalkers), dtype=np.int64)
         self._swaps = np.zeros((2, self.ntemps - 1), dtype=np.int64)   # accepted, proposed
         self._nsteps_counted = 0
@@ -963,15 +1022,18 @@ class TemperedSampler:
 
     def reset(self):
         """Forget the stored chain and the counts (not the RNG position)."""
-        self._stored, self._host = 0, None
+        self._stored, self._host, self._host_betas = 0, None, None
         self._nacc[:] = 0
         self._swaps[:] = 0
         self._nsteps_counted = 0
 
-    def run_mcmc(self, initial_state, nsteps, store=True, **kwargs):
+    def run_mcmc(self, initial_state, nsteps, store=True, adapt=False, **kwargs):
         """``initial_state``: (ntemps, nwalkers, ndim) coordinates (or a state tuple whose first entry they are), or
-        None to continue.  Returns ``State(coords, lnL, None)`` of all rungs."""
+        None to continue.  ``adapt``: the ladder moves during this run (see the class).  Returns
+        ``State(coords, lnL, None)`` of all rungs."""
         nt = self._tempered
+        if adapt:
+            check_adaptive(self.betas)
         if initial_state is not None:
             coords = np.array(initial_state[0] if isinstance(initial_state, tuple) else initial_state, dtype=np.float64)
             if coords.shape != (self.ntemps, self.nwalkers, self.ndim):
@@ -991,18 +1053,26 @@ class TemperedSampler:
             raise ValueError('Cannot have `initial_state=None` if run_mcmc has never been called.')
         else:
             before = nt.counts()
+        mode = ('append' if self._stored else True) if store else False
         try:
-            nt.run(self._steps_done, nsteps, ('append' if self._stored else True) if store else False)
+            if adapt:
+                nt.run_adaptive(self._steps_done, nsteps, mode, self.adaptation_lag, self.adaptation_time,
+                                self.adaptation_steps)
+            else:
+                nt.run(self._steps_done, nsteps, mode)
         except Exception as exc:
             if store and not self._stored:   # (a run that replaces the chain and fails leaves none; an appending one, the old)
-                self._host = None
+                self._host = self._host_betas = None
             if getattr(exc, 'status', None) == 6:
                 raise ValueError('Probability function returned NaN') from None
             raise
         self._steps_done += nsteps
+        if adapt:
+            self.adaptation_steps += nsteps
+        self.betas = nt.get_betas()
         if store and nsteps:
             self._stored += nsteps
-            self._host = None
+            self._host = self._host_betas = None
         acc, sa, sp = nt.counts()
         self._nacc += acc - before[0]
         self._swaps += np.stack([sa - before[1], sp - before[2]])
@@ -1034,6 +1104,13 @@ class TemperedSampler:
         if temp is not None:
             ll = ll[:, temp]
         return ll.reshape(-1) if flat else ll
+
+    def get_betas(self, discard=0, thin=1):
+        """(nsteps, ntemps): the ladder every stored step was sampled under (before any adaptation that follows the
+        step).  All rows are equal unless the chain was stored while adapting."""
+        if self._host_betas is None:
+            self._host_betas = self._tempered.get_beta_history(self._stored)
+        return self._host_betas[discard::thin]
 
     @property
     def chain(self):
@@ -1074,6 +1151,30 @@ class TemperedSampler:
             raise ValueError(f'discard={discard} leaves no steps of the {self._stored} stored')
         return self._tempered.mean_loglike(discard)
 
-    def log_evidence(self, discard=0):
-        """``(lnZ, dlnZ)`` by :func:`thermodynamic_integration` over the ladder, with ``reaches_prior``."""
-        return thermodynamic_integration(self.betas, self.mean_log_like(discard))
+    def log_evidence(self, discard=0, method='thermodynamic', batches=8):
+        """``(lnZ, dlnZ)`` with ``reaches_prior``, from the stored steps ``discard:``.  ``method='thermodynamic'``:
+        :func:`thermodynamic_integration` of the rungs' mean log-likelihoods, only as good as the ladder is fine where
+        ``<ln L>`` is steep.  ``method='stepping_stone'``: :func:`stepping_stone` over ``batches`` contiguous batches
+        of the steps, reduced on the device; right to a few tenths on ladders where the trapezoids are off by
+        thousands.  Both need a chain sampled under ONE ladder (``ValueError`` otherwise): adapt during burn-in, store
+        the frozen run."""
+        if method not in ('thermodynamic', 'stepping_stone'):
+            raise ValueError(f"method must be 'thermodynamic' or 'stepping_stone', not {method!r}")
+        if method == 'stepping_stone' and (batches != int(batches) or int(batches) < 2):
+            raise ValueError('the batch-means error needs an integer batches >= 2')
+        if self._stored == 0:
+            raise ValueError('no chain is stored: run the sampler with store=True first')
+        if not 0 <= int(discard) < self._stored:
+            raise ValueError(f'discard={discard} leaves no steps of the {self._stored} stored')
+        if method == 'stepping_stone':
+            if self.ntemps < 2:
+                raise ValueError('stepping stones need at least 2 rungs')
+            if int(batches) > self._stored - int(discard):
+                raise ValueError(f'batches={batches} is more than the {self._stored - int(discard)} stored steps kept')
+        ladder = self.get_betas(discard=int(discard))
+        if np.any(ladder != ladder[0]):
+            raise ValueError('the ladder moved while these steps were stored (they were sampled with adapt=True): '
+                             'adapt during burn-in, then store a frozen run, or discard the adapting steps')
+        if method == 'stepping_stone':
+            return stepping_stone(ladder[0], self._tempered.stepping_stones(int(discard), int(batches)))
+        return thermodynamic_integration(ladder[0], self.mean_log_like(discard))

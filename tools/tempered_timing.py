@@ -12,7 +12,14 @@ The split of the device time between the new kernels (``k_t_*``) and the existin
 separate ``rocprofv3 --kernel-trace --stats`` run of this script (nothing else collected); ``--kernel-stats CSV``
 reads that run's kernel statistics and adds the split to the report.
 
-Usage:  python tools/tempered_timing.py [--steps 300] [--json profiles/tempered_timing.json] [--kernel-stats CSV]"""
+``--adapt`` measures the adaptive ladder and the stepping stones instead (default ``--json
+profiles/tempered_adaptive.json``): the same configuration frozen and adapting, interleaved ``--repeats`` times; what
+``log_evidence(method='stepping_stone')`` costs on the stored chain (one ``k_t_stone`` launch and its copies, host
+clock); and, at 8 and 16 rungs, the swap fractions and the log-evidence by both methods on the fixed ladder and on the
+ladder adapted during ``--burn`` steps.
+
+Usage:  python tools/tempered_timing.py [--steps 300] [--json profiles/tempered_timing.json] [--kernel-stats CSV]
+        python tools/tempered_timing.py --adapt [--repeats 5] [--burn 1000]"""
 import argparse
 import csv
 import json
@@ -93,8 +100,66 @@ def run(walkers, ntemps, steps, warmup, compare=True):
     return res
 
 
+def evidence_case(eng, walkers, ntemps, burn, steps, adapt, lag, time_):
+    """Burn in (adapting or not), store ``steps`` frozen steps: the ladder, swap fractions and both log-evidences."""
+    rng = np.random.default_rng(1)
+    start = default_betas(eng.ndim, ntemps, Tmax=np.inf)
+    s = TemperedSampler(walkers, eng.ndim, eng, betas=start, seed=1, adaptation_lag=lag, adaptation_time=time_)
+    s.run_mcmc(LO + (HI - LO) * rng.random((ntemps, walkers, eng.ndim)), burn, store=False, adapt=adapt)
+    burn_swaps = s.swap_acceptance_fraction
+    s.reset()
+    s.run_mcmc(None, steps)
+    ti, ss = s.log_evidence(), s.log_evidence(method='stepping_stone')
+    res = {'ntemps': ntemps, 'adapted': bool(adapt), 'betas': [float(b) for b in s.betas],
+           'swap_acceptance_burn_in': [float(a) for a in burn_swaps],
+           'swap_acceptance_stored': [float(a) for a in s.swap_acceptance_fraction],
+           'mean_log_like': [float(m) for m in s.mean_log_like()],
+           'lnZ_thermodynamic': list(ti), 'lnZ_stepping_stone': list(ss)}
+    s.close()
+    return res
+
+
+def run_adaptive(walkers, ntemps, steps, warmup, repeats, burn, lag, time_):
+    lc, model = lc_case(), M.ShockCooling(redshift=0.)
+    eng = model.engine_for(lc, priors=PRIORS)
+    rng = np.random.default_rng(1)
+    betas = default_betas(eng.ndim, ntemps, Tmax=np.inf)
+    x0 = LO + (HI - LO) * rng.random((ntemps, walkers, eng.ndim))
+    samplers = {}
+    for mode in ('frozen', 'adapting'):
+        s = TemperedSampler(walkers, eng.ndim, eng, betas=betas, seed=1, adaptation_lag=lag, adaptation_time=time_)
+        s.run_mcmc(x0, warmup, store=False, adapt=mode == 'adapting')
+        samplers[mode] = s
+    ms = {'frozen': [], 'adapting': []}
+    for _ in range(repeats):          # interleaved: both modes see the same drift of the machine
+        for mode, s in samplers.items():
+            s.reset()
+            ms[mode].append(1e3 * timed(lambda: s.run_mcmc(None, steps, adapt=mode == 'adapting')) / steps)
+    res = {'walkers': walkers, 'ntemps': ntemps, 'steps': steps, 'warmup': warmup, 'repeats': repeats,
+           'n_points': int(eng.npoints), 'adaptation_lag': lag, 'adaptation_time': time_,
+           'launches_per_step': {'frozen': 11, 'adapting': 11.5},
+           'ms_per_step': {m: {'median': float(np.median(v)), 'min': float(min(v)), 'max': float(max(v)), 'runs': v}
+                           for m, v in ms.items()}}
+    f = samplers['frozen']
+    f.log_evidence(method='stepping_stone')           # (allocates the partials once)
+    stone = [1e3 * timed(lambda: f.log_evidence(method='stepping_stone')) for _ in range(repeats)]
+    mean = [1e3 * timed(lambda: f.log_evidence()) for _ in range(repeats)]
+    res['log_evidence_ms'] = {'stored_steps': steps, 'batches': 8, 'stepping_stone': float(np.median(stone)),
+                              'thermodynamic': float(np.median(mean))}
+    for s in samplers.values():
+        s.close()
+    res['evidence'] = [evidence_case(eng, walkers, k, burn, steps, adapt, lag, time_)
+                       for k in (8, 16) for adapt in (False, True)]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--adapt', action='store_true', help='measure the adaptive ladder and the stepping stones')
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--burn', type=int, default=1000, help='--adapt: burn-in steps of the evidence cases')
+    ap.add_argument('--lag', type=float, default=1000.)
+    ap.add_argument('--time', type=float, default=10.)
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--warmup', type=int, default=30)
     ap.add_argument('--walkers', type=int, default=1024)
@@ -103,7 +168,11 @@ def main():
     ap.add_argument('--kernel-stats', default=None, help='kernel statistics (CSV) of a rocprofv3 --kernel-trace --stats run')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
-    res = run(a.walkers, a.ntemps, a.steps, a.warmup, compare=not a.no_compare)
+    if a.adapt:
+        res = run_adaptive(a.walkers, a.ntemps, a.steps, a.warmup, a.repeats, a.burn, a.lag, a.time)
+        a.json = a.json or os.path.join(ROOT, 'profiles', 'tempered_adaptive.json')
+    else:
+        res = run(a.walkers, a.ntemps, a.steps, a.warmup, compare=not a.no_compare)
     if a.kernel_stats:
         res['device_time'] = kernel_split(a.kernel_stats)
     print(json.dumps(res))
