@@ -294,8 +294,9 @@ __device__ inline double band_sum_fast(TabPtr tab, int cnt, double invT, const E
 // amplitudes c[1], c[2] -- one exponential each -- are then not needed and are left NaN.
 // MODEL > 0: the model is a compile-time constant (kernels specialised for one model: the other models' code is not
 // even in the instruction stream); 0: pb.model decides at run time.
-template <int MODEL = 0>
-__device__ inline void walker_coefficients(const DevProblem& pb, const double* __restrict__ p,
+// PB: DevProblem, or anything else with its `consts` and `model` (a resident launch's copy of them in LDS).
+template <int MODEL = 0, class PB = DevProblem>
+__device__ inline void walker_coefficients(const PB& pb, const double* __restrict__ p,
                                            const double* __restrict__ lq, double* __restrict__ c,
                                            bool log_only = false) {
     const double* k = pb.consts;
@@ -595,7 +596,9 @@ __device__ inline void encode_linear(double invT, double pref, double& x, double
 // Log-space state of a power-law model (ShockCooling, ShockCooling2) at a POSITIVE phase t: u = ln T_K and lp = ln R_bb^2
 // from one logarithm and at most one exponential; lL = ln(c3^2 L), NaN where L < 0 or NaN (and everything is NaN for
 // t <= 0: the callers decide on the phase themselves).  c3, c6, c7 = the walker's coefficients c[3], c[6], c[7].
-__device__ __forceinline__ void powerlaw_log_state(const DevProblem& pb, double c3, double c6, double c7, double t,
+// (PB: DevProblem, or anything else with its `consts`)
+template <class PB>
+__device__ __forceinline__ void powerlaw_log_state(const PB& pb, double c3, double c6, double c7, double t,
                                                    const ExpTab et, double& u, double& lp, double& lL) {
     const double* k = pb.consts;
     const double eps1 = k[3], eps2 = k[4], alpha = k[2];

@@ -315,8 +315,9 @@ __device__ unsigned int g_progress[64 * 16];
 // (A compile-time choice: with both in one function the two sets of loads share registers, and the LDS reads then wait
 // for every outstanding global load -- the column's own photometry included.)
 // `lnr2k` = ln R_bb^2 x 256 / ln 2: y_fit = 2^((ln S + ln R_bb^2) 256 / ln 2 / 256), the scaling folded into one FMA.
-template <int M, bool IN_LDS>
-__device__ __forceinline__ void interp_columns(const DevProblem& pb, int lds_at, int f0, int row, double s, double lnr2k,
+// (PB: DevProblem, or anything else with its `itab_m` and `itab`)
+template <int M, bool IN_LDS, class PB>
+__device__ __forceinline__ void interp_columns(const PB& pb, int lds_at, int f0, int row, double s, double lnr2k,
                                                const ExpTab et, double (&yfit)[M]) {
     extern __shared__ __align__(16) unsigned char smem[];
     double2 q[M][4];
@@ -420,8 +421,8 @@ __device__ __forceinline__ void fetch_column(const DevProblem& pb, int part, int
 
 // The interpolated points of one dense column (the lane's): sum of squared scaled residuals.
 // ... of kPreK filters whose photometry is in registers already (fetch_column): two groups of three, all operands at hand
-template <bool IN_LDS>
-__device__ __forceinline__ double fast_column_fetched(const DevProblem& pb, int itab_at, int row, double s, double lnr2k,
+template <bool IN_LDS, class PB>
+__device__ __forceinline__ double fast_column_fetched(const PB& pb, int itab_at, int row, double s, double lnr2k,
                                                       const ExpTab et, const double2 (&o)[kPreK]) {
     static_assert(kPreK == 6, "two groups of three");
     double acc = 0.;
@@ -546,8 +547,9 @@ __device__ __attribute__((noinline)) double cold_column_with_state(const DevProb
 // coefficients the state needs as vector registers (no scalar copies, nothing hoisted).  The arithmetic is epochs_loop's
 // fast branch, operation for operation.  Returns false (wave-uniform) where a state of the wave is outside the
 // interpolants: the caller then takes the general path for the column.
-template <int MODEL>
-__device__ __forceinline__ bool lean_column(const DevProblem& pb, const double* __restrict__ sc, const ColumnOperands& first,
+// PB: DevProblem, or what a resident launch holds of it in LDS (ColumnView: consts, itab_u0, itab_inv_h, itab_m, itab).
+template <int MODEL, class PB>
+__device__ __forceinline__ bool lean_column(const PB& pb, const double* __restrict__ sc, const ColumnOperands& first,
                                             const ExpTab et, int itab_at, double& acc) {
     const double t = first.t - sc[0];
     double u, lp, lL;
@@ -561,6 +563,17 @@ __device__ __forceinline__ bool lean_column(const DevProblem& pb, const double* 
     acc = fast_column_fetched<true>(pb, itab_at, row, s, lp * kInvLn2N, et, first.o);
     return true;
 }
+// The fields lean_column and the head's coefficients read, as a resident launch holds them (copies out of RunUniforms).
+struct ColumnView {
+    const double* consts;
+    double itab_u0, itab_inv_h;
+    int itab_m;
+    const double* itab;   // (the interpolants in memory: not read by the staged path)
+};
+struct ConstsView {
+    const double* consts;
+    int model;
+};
 
 // chi^2 share of virtual thread `vtid` (0 .. kBlock-1) of part `part` for one walker: parameters p, coefficients c.
 // Virtual wave v = vtid / 64 owns the columns part_col0 + 64 v + lane + 256 m, m = 0, 1, ...: whichever kernel walks a
@@ -1241,6 +1254,23 @@ __device__ inline unsigned long long* board_entry(unsigned long long* board, con
                                                   int col) {
     return board + 2 * ((((size_t)(tag & (unsigned int)(sm.ring - 1)) * sm.n_walkers) + wid) * board_row_entries(sm.n_dim) + col);
 }
+#ifndef LCF_EARLY_POST
+#define LCF_EARLY_POST 0
+#endif
+// A value the loop optimiser must not compute ahead of the loop over the half-steps: what it hoists there lives across
+// the whole launch and comes back from scratch memory on the path every other workgroup waits for.
+__device__ __forceinline__ int not_hoisted(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// ... from a resident launch's block of invariants (RunUniforms): the same address, multiplied out once per launch
+__device__ __forceinline__ size_t board_entry_bytes(const RunUniforms& u, unsigned int tag, int wid, int col) {
+    return (tag & u.ring_mask) * u.ver_bytes + ((size_t)(unsigned int)wid * u.row_bytes + 16u * (unsigned int)col);
+}
+__device__ __forceinline__ unsigned long long* board_entry(unsigned long long* board, const RunUniforms& u, unsigned int tag,
+                                                           int wid, int col) {
+    return reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(board) + board_entry_bytes(u, tag, wid, col));
+}
 __device__ inline unsigned int* board_progress(unsigned long long* board, const DevSampler& sm) {
     return reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned char*>(board) +
                                            board_rows_bytes(sm.ring, sm.n_walkers, sm.n_dim));
@@ -1250,6 +1280,7 @@ __device__ inline unsigned int* board_progress(unsigned long long* board, const 
 // the language has no 16-byte atomic: the hardware moves an aligned 16-byte lane access as one piece, and the tags make
 // even 8-byte pieces safe.
 typedef unsigned int lcf_u32x4 __attribute__((ext_vector_type(4)));
+typedef int lcf_i32x4 __attribute__((ext_vector_type(4)));
 // AGENT: the board of a one-launch run lives in this GPU's ordinary memory and is shared by its own workgroups only.
 // Its 16-byte accesses are nevertheless issued at system scope (sc0 sc1), like those of the inter-rank boards: with sc1
 // alone (device scope) the same run takes TWICE as long (0.70 against 0.37 ms per launch of 64 half-steps at configs[1]
@@ -1267,15 +1298,22 @@ __device__ __forceinline__ void load16_past_caches(const unsigned long long* p, 
     hi = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
 }
 template <bool AGENT = false>
-__device__ inline void board_post(unsigned long long* board, const DevSampler& sm, unsigned int tag, int wid, int col, double v) {
+__device__ inline void board_post_at(unsigned long long* entry, unsigned int tag, double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v), t = (unsigned long long)tag << 32;
-    store16_past_caches<AGENT>(board_entry(board, sm, tag, wid, col), (b & 0xffffffffull) | t, (b >> 32) | t);
+    store16_past_caches<AGENT>(entry, (b & 0xffffffffull) | t, (b >> 32) | t);
+}
+template <bool AGENT = false>
+__device__ inline void board_post(unsigned long long* board, const DevSampler& sm, unsigned int tag, int wid, int col, double v) {
+    board_post_at<AGENT>(board_entry(board, sm, tag, wid, col), tag, v);
+}
+template <bool AGENT = false>
+__device__ inline bool board_aborted_at(const unsigned int* flag) {
+    return (AGENT ? __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                  : __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != 0u;
 }
 template <bool AGENT = false>
 __device__ inline bool board_aborted(const DevSampler& sm) {
-    const unsigned int* flag = board_progress(sm.board, sm) + kMaxPeers;
-    return (AGENT ? __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                  : __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != 0u;
+    return board_aborted_at<AGENT>(board_progress(sm.board, sm) + kMaxPeers);
 }
 __device__ inline unsigned int* board_arrivals(const DevSampler& sm) { return board_progress(sm.board, sm) + kMaxPeers + 5; }
 // (what: 1 = a row, a = tag, b = walker, c = column; 2 = the progress words, a = half-step, b = rank that is behind;
@@ -1303,9 +1341,10 @@ __device__ inline void board_abort(const DevSampler& sm, unsigned int what, unsi
 // bound of a head computed AHEAD of the partner's commit -- a second wave computes it from stale rows while the first one
 // polls, wrong chain, timing only: 5.13 against 5.31 us; with the two candidate heads, the second post and the second
 // poll a real version needs, nothing would be left of the 0.19.)
+// `p`: the entry (board_entry of this rank's board).
 template <bool AGENT = false>
-__device__ inline double board_take(const DevSampler& sm, unsigned int tag, int wid, int col, unsigned int arrive_goal = 0u) {
-    const unsigned long long* p = board_entry(sm.board, sm, tag, wid, col);
+__device__ inline double board_take_at(const DevSampler& sm, const unsigned long long* p, unsigned int tag, int wid, int col,
+                                       unsigned int arrive_goal = 0u) {
     const unsigned long long t0 = wall_clock64();
     bool resident = arrive_goal == 0u;
     for (int spin = 0;; ++spin) {
@@ -1338,6 +1377,10 @@ __device__ inline double board_take(const DevSampler& sm, unsigned int tag, int 
         }
         __builtin_amdgcn_s_sleep(1);
     }
+}
+template <bool AGENT = false>
+__device__ inline double board_take(const DevSampler& sm, unsigned int tag, int wid, int col, unsigned int arrive_goal = 0u) {
+    return board_take_at<AGENT>(sm, board_entry(sm.board, sm, tag, wid, col), tag, wid, col, arrive_goal);
 }
 // Version of a row a half-step G asks for: the walker's last move was `age` half-steps ago; rows nobody has moved in
 // this run carry the run's start tag.
@@ -1404,11 +1447,14 @@ struct HeadRows {
     PriorDev prior;         // lane d: the prior of parameter d
 };
 
-template <int ND, int BOARD = 0>
+// RES (the resident k_solo_run): what does not change within a launch comes from the launch's block in LDS, `ru`
+// (RunUniforms), not through scalar loads from `pb` / `sm`.
+template <int ND, int BOARD = 0, bool RES = false>
 __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSampler& sm, const DrawRec& dr, int lane,
-                                           HeadRows<ND>& h, long long G = 0, long long g_run0 = 0, unsigned int arrive_goal = 0u) {
+                                           HeadRows<ND>& h, long long G = 0, long long g_run0 = 0, unsigned int arrive_goal = 0u,
+                                           const RunUniforms* ru = nullptr) {
     constexpr int kD = ND > 0 ? ND : kMaxDim;
-    const int nd = ND > 0 ? ND : sm.n_dim;
+    const int nd = ND > 0 ? ND : RES ? __builtin_amdgcn_readfirstlane(ru->nd) : sm.n_dim;
     const double* xs = sm.X + (size_t)dr.wid * nd;
     const double* cs_ = sm.X + (size_t)dr.pid * nd;
     h.got = 0.;
@@ -1416,7 +1462,12 @@ __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSample
         const bool own = lane >= 16;
         const int col = own ? lane - 16 : lane;
         if (own ? col <= nd + 1 : col < nd) {
-            h.got = board_take<BOARD == 2>(sm, board_tag(G, own ? dr.wage : dr.page, g_run0), own ? dr.wid : dr.pid, col, arrive_goal);
+            const unsigned int tag = board_tag(G, own ? dr.wage : dr.page, g_run0);
+            const int who = own ? dr.wid : dr.pid;
+            if constexpr (RES)
+                h.got = board_take_at<BOARD == 2>(sm, board_entry(ru->board, *ru, tag, who, col), tag, who, col, arrive_goal);
+            else
+                h.got = board_take<BOARD == 2>(sm, tag, who, col, arrive_goal);
         }
     }
     h.lp_i = BOARD ? lane_value(h.got, 16 + nd) : sm.LP[dr.wid];
@@ -1427,16 +1478,25 @@ __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSample
     }
     // (measured: requesting the prior in FRONT of the poll instead changes nothing -- 5.45 against 5.43 us; its way from L2
     // is hidden behind the logarithms either way)
-    h.prior = PriorDev{0, 0, 0., 0., 0., 1.};
-    if (lane < pb.n_dim && pb.has_priors) h.prior = pb.priors[lane];
+    if constexpr (RES) {
+        // (the block holds a flat prior where the problem has none; lanes >= kMaxDim read the entry of lane - 16, 32, 48
+        // and never use it: proposal_head takes a prior's term from lanes below n_dim only)
+        h.prior = ru->priors[not_hoisted(lane) & (kMaxDim - 1)];
+    } else {
+        h.prior = PriorDev{0, 0, 0., 0., 0., 1.};
+        if (lane < pb.n_dim && pb.has_priors) h.prior = pb.priors[lane];
+    }
 }
 
-template <int ND, int BOARD = 0, int MODEL = 0>
+template <int ND, int BOARD = 0, int MODEL = 0, bool RES = false>
 __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSampler& sm, const DrawRec& dr, int lane,
                                               double* __restrict__ sc, double* __restrict__ sq, double* __restrict__ sx,
-                                              const HeadRows<ND>& h) {
+                                              const HeadRows<ND>& h, const RunUniforms* ru = nullptr) {
     constexpr int kD = ND > 0 ? ND : kMaxDim;
-    const int nd = ND > 0 ? ND : sm.n_dim;
+    const int nd = ND > 0 ? ND : RES ? __builtin_amdgcn_readfirstlane(ru->nd) : sm.n_dim;
+    // (RES: the head's share of the block, requested together; has_priors as a scalar, for the branch)
+    int n_par_r = 0, n_dim_r = 0, has_priors_r = 0;
+    if constexpr (RES) n_par_r = ru->n_par, n_dim_r = ru->n_dim, has_priors_r = __builtin_amdgcn_readfirstlane(ru->has_priors);
     const PriorDev my_prior = h.prior;
     double x[kD], q[kMaxDim], lq[kMaxDim];
 #pragma unroll
@@ -1449,7 +1509,7 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
         x[d] = h.x[d];
         const double cj = h.cj[d];
         q[d] = d < nd ? cj - (cj - x[d]) * dr.z : 0.;   // emcee: c_j - (c_j - x_i) z
-        if (lane == d && d < pb.n_par) arg = q[d];
+        if (lane == d && d < (RES ? n_par_r : pb.n_par)) arg = q[d];
     }
 #ifdef LCF_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1460,15 +1520,18 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
     for (int d = 0; d < kD; ++d) lq[d] = lane_value(lg, d);
     LCF_STAMP(0, 3);
     double c[kNCoef];
-    walker_coefficients<MODEL>(pb, q, lq, c, MODEL ? true : pb.use_itab != 0);
+    if constexpr (RES)
+        walker_coefficients<MODEL>(ConstsView{ru->consts, MODEL ? MODEL : ru->model}, q, lq, c, MODEL ? true : pb.use_itab != 0);
+    else
+        walker_coefficients<MODEL>(pb, q, lq, c, MODEL ? true : pb.use_itab != 0);
     LCF_STAMP(0, 4);
     double lpr = 0.;
-    if (pb.has_priors) {
+    if (RES ? has_priors_r : pb.has_priors) {
         double qv = 0.;
 #pragma unroll
         for (int d = 0; d < kD; ++d)
             if (lane == d) qv = q[d];
-        const double mine = lane < pb.n_dim ? prior_term(my_prior, qv) : 0.;
+        const double mine = lane < (RES ? n_dim_r : pb.n_dim) ? prior_term(my_prior, qv) : 0.;
 #pragma unroll
         for (int d = 0; d < kD; ++d)
             if (d < nd) lpr += lane_value(mine, d);   // the same ordered sum as walker_log_prior
@@ -1527,22 +1590,29 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                                                const DrawRec* __restrict__ draws, const DrawRec* draws_next, long long G,
                                                long long g_run0, int i, unsigned char* smem, ColumnOperands& first_col,
                                                bool first, bool write_state, const int tid, const int run_flags = 0,
-                                               const unsigned int arrive_goal = 0u) {
+                                               const unsigned int arrive_goal = 0u, const RunUniforms* ru = nullptr) {
+    // RES (k_solo_run): the launch's invariants come from its block in LDS, `ru` (RunUniforms, right behind the words
+    // below), wherever the half-step would otherwise load a field of `pb` / `sm`; the cold paths keep `pb`.
+    constexpr bool RES = BOARD >= 2;
     double* exptab = reinterpret_cast<double*>(smem);
     double* red = exptab + kExpTabSize;                                     // 4 wave sums per part (32 reserved)
     double2* ltab = reinterpret_cast<double2*>(smem + kLdsHead * sizeof(double));
-    const FiltDesc* fdesc = reinterpret_cast<const FiltDesc*>(ltab + pb.n_lds_tab);
-    const int itab_at = pb.n_itab_lds > 0
-                            ? (int)(kLdsHead * sizeof(double) + (pb.n_lds_tab + kFdD2 * pb.n_filters) * sizeof(double2)) : -1;
-    double* sc = reinterpret_cast<double*>(ltab + pb.stage_d2);  // coefficients, then log-prior
+    const FiltDesc* fdesc = RES ? nullptr : reinterpret_cast<const FiltDesc*>(ltab + pb.n_lds_tab);   // (RES: where needed)
+    int itab_at = -1;
+    if constexpr (!RES)
+        itab_at = pb.n_itab_lds > 0
+                      ? (int)(kLdsHead * sizeof(double) + (pb.n_lds_tab + kFdD2 * pb.n_filters) * sizeof(double2)) : -1;
+    double* sc = RES ? reinterpret_cast<double*>(const_cast<RunUniforms*>(ru)) - (kSoloScratch + 4)
+                     : reinterpret_cast<double*>(ltab + pb.stage_d2);  // coefficients, then log-prior
     double* sq = sc + kNCoef + 2;                                           // the proposal
     double* sx = sq + kMaxDim + (kMaxDim & 1);                              // the walker's current position, lp, draw
-    int* sctl = reinterpret_cast<int*>(sc + kSoloScratch + 2);              // BOARD: [0] = 1: the launch is aborted
+    // BOARD: [0] = 1: the launch is aborted (RES: the word beside the log-prior, so that one LDS read brings both)
+    int* sctl = reinterpret_cast<int*>(sc + (RES ? kNCoef + 1 : kSoloScratch + 2));
     constexpr int kGroups = NPARTS == 8 ? 4 : 2;     // groups of 256 threads, each walks one part at a time
     constexpr int kThreads = kBlock * kGroups;
     constexpr int kD = ND > 0 ? ND : kMaxDim;
-    const int nd = ND > 0 ? ND : sm.n_dim;
-    const bool reddened = !MODEL && pb.model == kShockCooling3;
+    const int nd = ND > 0 ? ND : RES ? __builtin_amdgcn_readfirstlane(ru->nd) : sm.n_dim;
+    const bool reddened = !MODEL && (RES ? __builtin_amdgcn_readfirstlane(ru->model) : pb.model) == kShockCooling3;
     LCF_STAMP(0, 0);
 #ifdef LCF_STAMPS
     if (tid == 0 && blockIdx.x < 1024) g_wall[((G & 1) * 1024 + blockIdx.x) * 2] = wall_clock64();
@@ -1568,9 +1638,9 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         // 8.06 against 7.71 us)
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);
         HeadRows<ND> rows;
-        head_fetch<ND, BOARD>(pb, sm, dr, tid, rows, G, g_run0, arrive_goal);
+        head_fetch<ND, BOARD, RES>(pb, sm, dr, tid, rows, G, g_run0, arrive_goal, ru);
         if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
-        proposal_head<ND, BOARD, MODEL>(pb, sm, dr, tid, sc, sq, sx, rows);
+        proposal_head<ND, BOARD, MODEL, RES>(pb, sm, dr, tid, sc, sq, sx, rows, ru);
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(0);
     } else {
         if (LCF_HEAD_START > 0) __builtin_amdgcn_s_sleep(LCF_HEAD_START);
@@ -1596,7 +1666,8 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         }
         if (!reddened && first) stage_tables<VARIANT, true>(pb, exptab, ltab, 0., tid - 64, kThreads - 64);
         LCF_STAMP(1, 11);
-        if (BOARD >= 2 && tid == 64) sctl[0] = board_aborted<BOARD == 2>(sm) ? 1 : 0;   // (in the shadow of the head)
+        if constexpr (RES)
+            if (tid == 64) sctl[0] = board_aborted_at<BOARD == 2>(ru->abort_word) ? 1 : 0;   // (in the shadow of the head)
         if (BOARD == 1 && tid < 128) {
             // In the shadow of the head: has every rank finished half-step G - 2 (lane = rank)?  has this rank given up?
             const int lane = tid - 64;
@@ -1623,8 +1694,28 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
     }
     __syncthreads();
     LCF_STAMP(0, 6);
-    if (BOARD && sctl[0] != 0) return true;   // (uniform: everybody reads the same word)
-    const double lpr = sc[kNCoef];
+    double lpr;
+    // (RES, lean columns: the group's record, the interpolants' grid and the state's constants)
+    lcf_i32x4 col_group = {0, 0, 0, 0}, col_itab = {0, 0, 0, 0};
+    double2 col_grid = make_double2(0., 0.);
+    double col_consts[5] = {0., 0., 0., 0., 0.};
+    if constexpr (RES) {
+        // log-prior and abort word in one read; and with it everything of the block that the columns read
+        const double2 la = *reinterpret_cast<const double2*>(sc + kNCoef);
+        if constexpr (MODEL != 0 && NPARTS <= 2) {
+            const int group = __builtin_amdgcn_readfirstlane(not_hoisted(tid) / kBlock);
+            col_group = *reinterpret_cast<const lcf_i32x4*>(&ru->group[group]);
+            col_grid = *reinterpret_cast<const double2*>(&ru->itab_u0);
+            col_itab = *reinterpret_cast<const lcf_i32x4*>(&ru->itab_m);
+            const double2 k23 = *reinterpret_cast<const double2*>(&ru->consts[2]);
+            col_consts[2] = k23.x, col_consts[3] = k23.y, col_consts[4] = ru->consts[4];
+        }
+        lpr = la.x;
+        if (__builtin_amdgcn_readfirstlane(__double2loint(la.y)) != 0) return true;
+    } else {
+        if (BOARD && sctl[0] != 0) return true;   // (uniform: everybody reads the same word)
+        lpr = sc[kNCoef];
+    }
     double term = 0.;
     const bool excluded = lpr == -INFINITY;  // prior excludes the proposal: likelihood skipped (fitting.py:125)
     // The benchmark shape in a MODEL-specialised kernel: every lane has ONE column, fetched ahead of the head
@@ -1632,28 +1723,47 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
     // a state outside the interpolants -- goes through epochs_loop / the cold path, same numbers.
     bool lean = false;
     if (MODEL != 0 && NPARTS <= 2 && !excluded) {
-        const int part = __builtin_amdgcn_readfirstlane(tid / kBlock), ltid = tid % kBlock;
-        const int c0 = part_entry(pb.part_col0, part), c1 = part_entry(pb.part_col0, part + 1);
-        lean = first_col.have_o && itab_at >= 0 && c1 - c0 <= kBlock && part < pb.n_parts;   // (wave-uniform)
+        const int tid_c = RES ? not_hoisted(tid) : tid;
+        const int part = __builtin_amdgcn_readfirstlane(tid_c / kBlock), ltid = tid_c % kBlock;
+        int c0, c1;
+        if constexpr (RES) {
+            c0 = __builtin_amdgcn_readfirstlane(col_group.x);
+            c1 = __builtin_amdgcn_readfirstlane(col_group.y);
+            lean = first_col.have_o && __builtin_amdgcn_readfirstlane(col_group.z) != 0;
+        } else {
+            c0 = part_entry(pb.part_col0, part);
+            c1 = part_entry(pb.part_col0, part + 1);
+            lean = first_col.have_o && itab_at >= 0 && c1 - c0 <= kBlock && part < pb.n_parts;   // (wave-uniform)
+        }
         if (lean) {
             LCF_STAMP(0, 7);
             double acc = 0.;
             if (c0 + (ltid & ~63) < c1) {   // (a virtual wave without columns adds nothing)
                 const bool live = c0 + ltid < c1;
-                if (!lean_column<MODEL>(pb, sc, first_col, ExpTab{exptab}, itab_at, acc))
+                bool in_grid;
+                if constexpr (RES)
+                    in_grid = lean_column<MODEL>(ColumnView{col_consts, col_grid.x, col_grid.y, col_itab.x, nullptr}, sc, first_col,
+                                                 ExpTab{exptab}, col_itab.y, acc);
+                else
+                    in_grid = lean_column<MODEL>(pb, sc, first_col, ExpTab{exptab}, itab_at, acc);
+                if (!in_grid)
                     acc = cold_column_with_state<VARIANT, MODEL>(pbp, sc, sq, first_col.t, min(c0 + ltid, c1 - 1), live);
                 term = live ? acc : 0.;     // (lanes beyond the part repeated its last column)
             }
             LCF_STAMP(0, 8);
             LCF_STAMP(1, 12);
             const double ws = wave_sum(term);
-            if ((tid & 63) == 0) red[tid >> 6] = ws;
+            if ((tid & 63) == 0) red[tid_c >> 6] = ws;
         }
     }
     if (!excluded && !lean) {
         double cs[kNCoef];
 #pragma unroll
         for (int k = 0; k < kNCoef; ++k) cs[k] = uniform_f64(sc[k]);
+        if constexpr (RES) {   // (the general path: not where the time goes)
+            fdesc = reinterpret_cast<const FiltDesc*>(ltab + pb.n_lds_tab);
+            itab_at = __builtin_amdgcn_readfirstlane(ru->itab_at);
+        }
         if (reddened) stage_tables<VARIANT, true>(pb, exptab, ltab, cs[6], tid, kThreads);
         // threads [256 j, 256 j + 256) are the virtual threads of part j (NPARTS = 4: then of part j + 2, ...): each lane
         // computes the thermal state of its column and walks the column's points (epochs_loop)
@@ -1678,6 +1788,11 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             if ((tid & 63) == 0) red[tid >> 6] = ws;
         }
     }
+    // (LCF_EARLY_POST, measurement only: wave 0 multiplies the row's address out in front of barrier 2, in the shadow of the
+    // columns, and carries it across -- two more vector registers there; DESIGN section 5 has the A/B)
+    size_t entry_early = 0;
+    if constexpr (RES && LCF_EARLY_POST != 0)
+        if (tid < 64) entry_early = board_entry_bytes(*ru, (unsigned int)(G + 1), dr.wid, not_hoisted(tid));
     __syncthreads();
     LCF_STAMP(0, 9);
     if (BOARD) {
@@ -1686,6 +1801,77 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         // the run ends, and the chain is written from the board)
         if (tid >= 64) return false;
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);   // (the row's readers wait for this)
+        if constexpr (RES) {
+            // Every LDS read between here and the post is requested NOW -- the wave sums, the walker's log-posterior and
+            // count, this lane's number of the proposal and of the position, the block's words for the sum and for the
+            // row's address -- and waited for once; the sum keeps its order, (w0 + w1) + (w2 + w3) per part, parts in order.
+            const double2* red2 = reinterpret_cast<const double2*>(red);
+            const double2 lc = *reinterpret_cast<const double2*>(sx + kMaxDim);   // log-posterior | acceptance count
+            const int col = not_hoisted(tid);
+            const int mine = col < nd ? col : 0;
+            const double q_mine = sq[mine], x_mine = sx[mine];
+            const double sum0 = ru->sum0;
+            const unsigned int tag = (unsigned int)(G + 1);
+            const size_t entry = LCF_EARLY_POST != 0 ? entry_early : board_entry_bytes(*ru, tag, dr.wid, col);   // (the same on every rank's board)
+            unsigned char* const own_board = reinterpret_cast<unsigned char*>(ru->board);
+            double sum = sum0;
+            if (NPARTS <= 2) {
+                const int n_parts = ru->n_parts;
+                const double2 a0 = red2[0], a1 = red2[1], b0 = red2[2], b1 = red2[3];
+                const double s1 = sum + ((a0.x + a0.y) + (a1.x + a1.y));
+                sum = n_parts > 0 ? s1 : sum;
+                const double s2 = sum + ((b0.x + b0.y) + (b1.x + b1.y));
+                sum = n_parts > 1 ? s2 : sum;
+            } else {
+                const int n_parts = __builtin_amdgcn_readfirstlane(ru->n_parts);
+                for (int k = 0; k < n_parts; ++k) sum += (red2[2 * k].x + red2[2 * k].y) + (red2[2 * k + 1].x + red2[2 * k + 1].y);
+            }
+            const double scored = lpr - 0.5 * sum;
+            const double nlp = excluded ? -INFINITY : scored;
+            const double lp_i = lc.x;
+            const bool ok = (dr.zl + nlp - lp_i) > dr.lnu;
+            const double count = lc.y + (ok ? 1. : 0.);
+            if (tid <= nd + 1) {
+                const double v = tid < nd ? (ok ? q_mine : x_mine) : tid == nd ? (ok ? nlp : lp_i) : count;
+                // the row first: its readers wait for it; state, snapshot and chain follow
+                if (BOARD == 2) {
+                    board_post_at<true>(reinterpret_cast<unsigned long long*>(own_board + entry), tag, v);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < kMaxPeers; ++r)
+                        if (r < sm.n_board_ranks)
+                            board_post_at(reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(sm.peer_board[r]) + entry),
+                                          tag, v);
+                }
+                if (BOARD == 2 && write_state) {   // (the set of state buffers the run did NOT start from: chosen by the fill)
+                    if (tid < nd)
+                        ru->X[(size_t)dr.wid * nd + tid] = v;
+                    else if (tid == nd)
+                        ru->LP[dr.wid] = v;
+                    else
+                        ru->nacc[dr.wid] = (long long)v;
+                    unsigned long long* const snap = ru->snap_out;
+                    if (snap) {   // ... and the host's copy of it
+                        const size_t nw = ru->n_walkers;
+                        if (tid < nd) snap[1 + (size_t)dr.wid * nd + tid] = (unsigned long long)__double_as_longlong(v);
+                        else if (tid == nd) snap[1 + nw * nd + dr.wid] = (unsigned long long)__double_as_longlong(v);
+                        else snap[1 + nw * nd + nw + dr.wid] = (unsigned long long)(long long)v;
+                    }
+                }
+                if (BOARD == 2 && (run_flags & kRunStoreChain)) {   // (one GPU: every walker's row is decided here)
+                    const size_t at = (size_t)row * ru->n_walkers + dr.wid;
+                    if (tid < nd) ru->chain[at * nd + tid] = v;
+                    else if (tid == nd) ru->chain_lp[at] = v;
+                }
+            }
+            if (tid == 0 && nlp != nlp) {
+                atomicOr(sm.err, 1);
+                if (BOARD == 2 && sm.snap_flags) sm.snap_flags[blockIdx.x & (kSnapFlags - 1)] = 1u;
+            }
+            __builtin_amdgcn_s_setprio(0);
+            LCF_STAMP(0, 10);
+            return false;
+        }
         double nlp = -INFINITY;
         if (!excluded) {
             double sum = pb.use_sigma ? 0. : pb.log_norm_const;
@@ -1802,6 +1988,64 @@ void k_solo(const DevProblem* __restrict__ pbp, const DevSampler sm, long long r
 // reached `need_progress` (the first half-step of the launch before the previous one; 0: nothing to wait for).  With
 // at most kRunSpan half-steps per launch, anything a rank still reads is then less than kRing versions behind
 // anything another rank writes.
+// The launch's block of invariants (RunUniforms), written by ONE wave (lane = 0 .. 63) in front of the loop over the
+// half-steps: the first half-step's head reads it like every other one.  `ranks`: no state is written by the launch.
+__device__ __forceinline__ void fill_run_uniforms(const DevProblem& pb, const DevSampler& sm, RunUniforms* ru, int run_flags,
+                                                  bool ranks, int lane) {
+    if (lane == 0) {
+        const int entries = board_row_entries(sm.n_dim);
+        ru->board = sm.board;
+        ru->ring_mask = (unsigned int)(sm.ring - 1);
+        ru->row_bytes = 16u * (unsigned int)entries;
+        ru->ver_bytes = (unsigned long long)sm.n_walkers * (unsigned long long)entries * 16ull;
+        ru->abort_word = board_progress(sm.board, sm) + kMaxPeers;
+        ru->sum0 = pb.use_sigma ? 0. : pb.log_norm_const;
+        ru->n_parts = pb.n_parts;
+        ru->n_walkers = sm.n_walkers;
+        ru->n_dim = pb.n_dim;
+        ru->n_par = pb.n_par;
+        ru->has_priors = pb.has_priors;
+        ru->model = pb.model;
+        // (one-launch runs write the state into the set of buffers the run did NOT start from -- kRunFlip says which)
+        const bool to_out = !(run_flags & kRunFlip);
+        ru->X = ranks ? nullptr : to_out ? sm.X_out : sm.X;
+        ru->LP = ranks ? nullptr : to_out ? sm.LP_out : sm.LP;
+        ru->nacc = ranks ? nullptr : to_out ? sm.nacc_out : sm.nacc;
+        ru->snap_out = sm.snap_out;
+        ru->chain = sm.chain;
+        ru->chain_lp = sm.chain_lp;
+        ru->itab_u0 = pb.itab_u0;
+        ru->itab_inv_h = pb.itab_inv_h;
+        ru->itab_m = pb.itab_m;
+        ru->nd = sm.n_dim;
+        ru->pad1 = 0;
+    }
+    // where the interpolants are staged (solo_half_step's layout)
+    const int itab_at = pb.n_itab_lds > 0
+                            ? (int)(kLdsHead * sizeof(double) + (pb.n_lds_tab + kFdD2 * pb.n_filters) * sizeof(double2)) : -1;
+    if (lane == 1) ru->itab_at = itab_at;
+    if (lane >= 2 && lane < 4) {   // per group of 256 threads: its first part
+        const int g = lane - 2;
+        const int c0 = part_entry(pb.part_col0, g), c1 = part_entry(pb.part_col0, g + 1);
+        ru->group[g].c0 = c0;
+        ru->group[g].c1 = c1;
+        ru->group[g].lean = itab_at >= 0 && c1 - c0 <= kBlock && g < pb.n_parts ? 1 : 0;
+        ru->group[g].pad = 0;
+    }
+    if (lane >= 16 && lane < 28) ru->consts[lane - 16] = pb.consts[lane - 16];
+    if (lane >= 32 && lane < 32 + kMaxDim) {
+        const int d = lane - 32;
+        const bool has = d < pb.n_dim && pb.has_priors;   // (field by field: a struct selected as a whole goes through scratch memory)
+        const PriorDev* pr = pb.priors + (has ? d : 0);
+        ru->priors[d].kind = has ? pr->kind : 0;
+        ru->priors[d].pad = 0;
+        ru->priors[d].p_min = has ? pr->p_min : 0.;
+        ru->priors[d].p_max = has ? pr->p_max : 0.;
+        ru->priors[d].mean = has ? pr->mean : 0.;
+        ru->priors[d].stddev = has ? pr->stddev : 1.;
+    }
+}
+
 template <int ND, int VARIANT, bool THERM, int NPARTS, int MODEL, bool RANKS = false>
 __global__ __launch_bounds__(kBlock * (NPARTS == 8 ? 4 : 2), LCF_WAVES)
 void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict__ smp, long long rel0,
@@ -1822,6 +2066,14 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
     const DevSampler& sm = *(const DevSampler*)(SamplerPtr)smp;
     constexpr int kBoard = RANKS ? 3 : 2;
     bool first = true;
+    // What no half-step of the launch changes: into LDS, once (RunUniforms), behind the half-step's scratch words.
+    // Filled HERE, not by the launch's first executed half-step (`first` below): that half-step's head reads the block
+    // in front of its first barrier like every other one.  So the block does not depend on `first`, nor on whether a
+    // workgroup's first slot is an empty one; what `first` still guards is the staging of the tables and the first columns.
+    RunUniforms* const ru = reinterpret_cast<RunUniforms*>(smem + kLdsHead * sizeof(double) + (size_t)pb.stage_d2 * sizeof(double2) +
+                                                           (kSoloScratch + 4) * sizeof(double));
+    if (threadIdx.x >= 64 && threadIdx.x < 128) fill_run_uniforms(pb, sm, ru, run_flags, RANKS, threadIdx.x - 64);
+    if (!RANKS) __syncthreads();   // (RANKS: the barrier below)
     // "this workgroup has started": what a workgroup that waits unusually long for a row looks at (board_take)
     if (threadIdx.x == 0) __hip_atomic_fetch_add(board_arrivals(sm), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (RANKS) {
@@ -1874,23 +2126,24 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
             }
     }
     const int slot_end = slot_lo + n_slots;
+    const int n_half = sm.n_half;   // (one scalar register across the loop instead of a load per half-step)
     // (Measured and dropped: the draw record of the NEXT half-step requested one half-step ahead -- by a wave beside the head
     // into LDS, or as a scalar load carried in registers across the half-step -- instead of the touch that only brings
     // it into this XCD's L2: 5.80 / 5.94 against 5.51 us per half-step.  The record's two round trips are hidden
     // already; what the extra live registers cost is not.)
 #pragma unroll 1
     for (int h = 0; h < n_hs; ++h) {
-        const DrawRec* draws = draws0 + (size_t)h * sm.n_half;
+        const DrawRec* draws = draws0 + (size_t)h * n_half;
 #pragma unroll 1
         for (int i = slot_lo + blockIdx.x; i < slot_end; i += n_wg) {
             if (draws[i].wid < 0) continue;   // (uniform) an odd ensemble's smaller colour leaves its last slot empty
             // the record this workgroup needs next: its next slot of this half-step, else its first of the next one
             const bool more = i + n_wg < slot_end;
-            const DrawRec* hint = more ? draws + n_wg : h + 1 < n_hs ? draws + sm.n_half + (slot_lo + (int)blockIdx.x - i) : nullptr;
+            const DrawRec* hint = more ? draws + n_wg : h + 1 < n_hs ? draws + n_half + (slot_lo + (int)blockIdx.x - i) : nullptr;
             const int tid = threadIdx.x;
             if (solo_half_step<ND, VARIANT, THERM, NPARTS, kBoard, MODEL>(pb, pbp, sm, (rel0 + h) >> 1, draws, hint,
                                                                           g_run0 + rel0 + h, g_run0, i, smem, first_col, first,
-                                                                          rel0 + h >= state_from, tid, run_flags, arrive_goal))
+                                                                          rel0 + h >= state_from, tid, run_flags, arrive_goal, ru))
                 return;
             first = false;
         }
@@ -3135,6 +3388,9 @@ static size_t solo_lds_bytes(const lcf_engine* e) {
            (kSoloScratch + 4) * sizeof(double);
 }
 
+// ... of a resident launch (k_solo_run): the block of launch invariants behind it (RunUniforms)
+static size_t run_lds_bytes(const lcf_engine* e) { return solo_lds_bytes(e) + sizeof(RunUniforms); }
+
 bool solo_eligible(const lcf_sampler* s) {
     static const bool disabled = std::getenv("LCF_NO_SOLO") != nullptr;
     const lcf_engine* e = s->e;
@@ -3233,8 +3489,8 @@ static bool resident_size(const lcf_sampler* s, int width, int slots) {
 bool run_eligible(const lcf_sampler* s) {
     static const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr;
     static const bool any_size = std::getenv("LCF_RUN_ANY_SIZE") != nullptr;   // (tests: several slots per workgroup)
-    return !disabled && !s->run_off && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) && s->ds.n_peers == 0 &&
-           (resident_size(s, s->ds.n_half, kRunSlots) || any_size);
+    return !disabled && !s->run_off && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) &&
+           run_lds_bytes(s->e) <= kLdsPerCU && s->ds.n_peers == 0 && (resident_size(s, s->ds.n_half, kRunSlots) || any_size);
 }
 
 struct RunBusy { hipEvent_t ev = nullptr; hipStream_t stream = nullptr; bool used = false; bool enqueuing = false; };
@@ -3383,7 +3639,7 @@ lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, b
         hi = s->ds.n_half;
     }
     const DrawRec* draws = dry ? nullptr : s->rows(rel);
-    const size_t lds = solo_lds_bytes(e);
+    const size_t lds = run_lds_bytes(e);
     const long long g_run0 = s->g_run0;
     const long long state_from = 2 * (s->run_steps - 1);   // X / LP / counts: written by the run's last step
     // (test of the recovery from a launch whose workgroups are not all resident: the last one is not launched at all)
@@ -3716,7 +3972,7 @@ namespace {
 bool rows_resident_eligible(const lcf_sampler* s, int width) {
     const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr || std::getenv("LCF_ROWS_PER_HALF_STEP") != nullptr;
     const bool any_size = std::getenv("LCF_RUN_ANY_SIZE") != nullptr;
-    return !disabled && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) &&
+    return !disabled && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) && run_lds_bytes(s->e) <= kLdsPerCU &&
            (resident_size(s, width, 2 * kRunSlots) || any_size);
 }
 

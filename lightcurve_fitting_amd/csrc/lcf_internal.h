@@ -143,6 +143,44 @@ __host__ __device__ inline size_t board_rows_bytes(int ring, int n_walkers, int 
     return (size_t)ring * n_walkers * board_row_entries(n_dim) * 16;
 }
 
+// ---- what a resident launch reads in EVERY half-step and no half-step changes -----------------------------------------
+// k_solo_run reads problem and sampler through constant-address-space pointers: a scalar load, and a wait for the scalar
+// cache, wherever a field is used -- 26 loads and 18 serialised waits per half-step on the one wave everybody else waits
+// for, plus the 64-bit multiplications of a row's address and the select chains of part_col0[part], all for values that
+// are the same in every half-step of a launch.  The launch therefore writes them ONCE, already multiplied out, into
+// this block of its dynamic LDS (behind the half-step's scratch words; k_solo_run fills it in front of its loop), and
+// the half-step reads a phase's share of it with 16-byte LDS reads issued together with the phase's other LDS reads.
+// Every group below is 16 bytes or a multiple, at a 16-byte offset.  Resident kernels only (BOARD >= 2 in
+// solo_half_step): a launch of one half-step would pay the fill for nothing.
+struct alignas(16) RunUniforms {
+    // rows: entry (tag, wid, col) = board + (tag & ring_mask) * ver_bytes + wid * row_bytes + 16 col
+    unsigned long long* board;
+    unsigned int ring_mask, row_bytes;
+    unsigned long long ver_bytes;       // one version of every walker's row
+    unsigned int* abort_word;           // the board's abort word (board_aborted)
+    // accept
+    double sum0;                        // what the chi^2 sum starts from: 0 with a fitted sigma, else log_norm_const
+    int n_parts, n_walkers;
+    // head
+    int n_dim, n_par, has_priors, model;
+    // the state, the host's snapshot and the chain as this launch writes them (the set of state buffers chosen)
+    double* X;
+    double* LP;
+    long long* nacc;
+    unsigned long long* snap_out;
+    double* chain;
+    double* chain_lp;
+    // columns: the interpolants' grid, where they are staged (byte offset in the dynamic LDS, -1: not staged), and per
+    // group of 256 threads (of the 512-thread kernels) the columns [c0, c1) of its first part and whether lean_column may
+    // take them
+    double itab_u0, itab_inv_h;
+    int itab_m, itab_at, nd, pad1;      // (nd: the sampler's n_dim, what a row holds)
+    struct Group { int c0, c1, lean, pad; } group[2];
+    double consts[12];                  // DevProblem::consts
+    PriorDev priors[kMaxDim];           // the parameters' priors (flat where the problem has none)
+};
+static_assert(sizeof(RunUniforms) % 16 == 0 && sizeof(RunUniforms) <= 1024, "a small block of 16-byte groups");
+
 }  // namespace
 
 struct lcf_engine {
