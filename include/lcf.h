@@ -44,7 +44,8 @@ typedef enum lcf_model {
     LCF_MODEL_COMPANION_SHOCKING = 5, /* CompanionShocking     models.py:848-918  p = t_0,a,Mv7,t_max,s,r_r,r_i,r_U   */
     LCF_MODEL_COMPANION_SHOCKING2 = 6,/* CompanionShocking2    models.py:921-980  p = t_0,a,Mv7,t_max,s,dt_U,dt_i     */
     LCF_MODEL_COMPANION_SHOCKING3 = 7,/* CompanionShocking3    models.py:983-1045 p = t_0,a,theta,t_max,s,dt_U,dt_i   */
-    LCF_MODEL_BLACKBODY = 8           /* direct (T, R) blackbody, bolometric.py:154-164                              */
+    LCF_MODEL_BLACKBODY = 8,          /* direct (T, R) blackbody, bolometric.py:154-164                              */
+    LCF_MODEL_CUSTOM = 9              /* T(t), R(t) from a program compiled at run time: "custom models" below       */
 } lcf_model;
 
 /* Priors (reference models.py:1048-1098).  Bounds are strict: p_min < p < p_max, else log-prior = -inf. */
@@ -66,8 +67,9 @@ enum { LCF_N_CONSTS = 12 };
  * consts[] by model:
  *   SHOCK_COOLING, SHOCK_COOLING2: A, a, alpha, epsilon_1, epsilon_2, L_0, T_0, Tph_to_Tcol  (models.py:192-226)
  *   SHOCK_COOLING4:                A, a, alpha, L_br_0, T_col_br_0, t_br_0, t_tr_0           (models.py:567-577)
+ *   CUSTOM:                        all 12 are the caller's: what the state function receives as `consts`
  *   others:                        unused
- *   (consts[8..11] are scratch for the engine: whatever the caller puts there is overwritten)
+ *   (consts[8..11] are scratch for the engine: whatever the caller puts there is overwritten -- not for CUSTOM)
  *
  * Band tables: filter i owns samples tab_off[i] .. tab_off[i+1]-1 of (tab_a, tab_w) with
  *   a_k = c1 nu_k (1+z)  [kK],   W_k = c2 nu'_k^3 min(1, nu_cut/nu'_k) tw_k Tnorm_k,
@@ -81,7 +83,7 @@ enum { LCF_N_CONSTS = 12 };
 typedef struct lcf_problem {
     int32_t abi_version; /* LCF_ABI_VERSION */
     int32_t model;       /* lcf_model */
-    int32_t n_par;       /* model parameters (without the optional intrinsic-scatter parameter) */
+    int32_t n_par;       /* model parameters (without the optional intrinsic-scatter parameter); CUSTOM: the caller's */
     int32_t use_sigma;   /* 1: the last of n_dim = n_par + 1 parameters is sigma (models.py:128-130) */
     int32_t sigma_type;  /* LCF_SIGMA_RELATIVE | LCF_SIGMA_ABSOLUTE (models.py:121-126) */
     int32_t n_filters;
@@ -551,6 +553,50 @@ lcf_status lcf_tempered_get_beta_history(lcf_tempered* t, double* betas);
  * The ladder is the one step `discard` was sampled under.  1 <= n_batches <= n. */
 lcf_status lcf_tempered_stepping_stones(lcf_tempered* t, int64_t discard, int32_t n_batches, double* max, double* sum,
                                         double* count);
+
+/* ---- custom models: a user-written photosphere T(t), R(t), compiled at run time for the GPU ----------------------- */
+/* What the reference's `Model` subclasses are to lightcurve_mcmc (models.py: temperature_radius, then
+ * blackbody_to_filters), for the models the library has no kernel of its own for.  `source` is HIP device code that
+ * defines, at global scope, the __device__ function lcf_user_state, returning void, of exactly the parameters
+ *     (double t_in, const double* p, const double* consts, double z, double& T_kK, double& R_1000Rsun)
+ * t_in: the observation time as the engine was given it (the function subtracts its explosion time and applies 1 + z as
+ * its model requires); p: the n_par model parameters of the row (no fitted sigma); consts: lcf_problem.consts, all 12;
+ * z: the engine's redshift for custom models (below).  Units are those of lcf_temperature_radius and
+ * lcf_blackbody_to_filters.  Everything in csrc/lcf_device.h is visible, so lcf::pw -- the reference's power: base > 0 ?
+ * base ** e : 0 -- makes "zero before the explosion" one call.  The model light curve is lcf_blackbody_to_filters of the
+ * state at every point: T <= 0 or T >= 1e15 kK gives 0; a NaN T or R gives a NaN likelihood (LCF_ERR_NAN_LOGPROB at the
+ * end of a run when inside the prior's support).  The function must return, and write nowhere but its two outputs.
+ *
+ * lcf_custom_compile: the program text is csrc/lcf_device.h, `#line 1 "user_model"`, the source, then the library's
+ * kernel (csrc/lcf_custom_kernel.h), compiled by hiprtc with the library's own code-generation flags for `arch`
+ * ("gfx950"; NULL or "": the base name of the architecture of `device` -- with a name no device is needed).  hiprtc is
+ * bound at run time: LCF_HIPRTC_LIB, <ROCM_PATH | HIP_PATH | /opt/rocm>/lib/libhiprtc.so, the directory the process's HIP
+ * runtime was loaded from (PyTorch's lib), the loader's path; LCF_ERR_UNSUPPORTED with the paths tried when none loads.
+ * A source that does not compile is LCF_ERR_INVALID_ARGUMENT, lcf_last_error carrying the compiler's log, in which the
+ * source's lines are user_model:<line>.  Programs are cached per process by (source, arch): compiling the same pair
+ * again returns the same handle.  The cache owns the programs; lcf_custom_destroy is the call that ends a caller's use
+ * of a handle and frees nothing.
+ * lcf_custom_log: the compiler's log of a successful compile (warnings; "" if none).
+ * lcf_custom_code: the code object (*n_bytes long; n_bytes may be NULL), owned by the program. */
+typedef struct lcf_custom lcf_custom;
+lcf_status lcf_custom_compile(const char* source, const char* arch, int32_t device, lcf_custom** out);
+const char* lcf_custom_log(const lcf_custom* c);
+const void* lcf_custom_code(const lcf_custom* c, int64_t* n_bytes);
+void lcf_custom_destroy(lcf_custom* c);
+/* Attach a program to an engine created with LCF_MODEL_CUSTOM (any n_par with n_par + use_sigma <= 16; consts, band
+ * tables, priors and sigma mode as for every model).  The program must have been compiled for the engine's device
+ * architecture (LCF_ERR_INVALID_ARGUMENT otherwise); its module is loaded once per device.  The engine then serves
+ * lcf_log_likelihood / lcf_log_posterior and their _dev forms, lcf_model_evaluate, lcf_temperature_radius (T and R as
+ * the state function returned them) and, through lcf_log_likelihood_dev, lcf_tempered_*: one workgroup per (row, part of
+ * the light curve), one lane per data point, the band sum chosen per point as lcf_blackbody_to_filters chooses it, sums
+ * in a fixed order -- a row's value does not depend on the rows evaluated with it.  Before a program is attached these
+ * calls return LCF_ERR_STATE.  What is compiled per model -- lcf_sampler_create and with it every lcf_sampler_* and
+ * population run, lcf_predict_*, lcf_sampler_predict_*, lcf_profile_loglike_kernel -- returns LCF_ERR_UNSUPPORTED for
+ * such an engine, naming this route, and launches nothing. */
+lcf_status lcf_engine_set_custom(lcf_engine* e, lcf_custom* c);
+/* The z handed to the state function (0 until set): the band tables carry 1 + z already, as for every model; the time
+ * axis is the state function's own business. */
+lcf_status lcf_engine_set_custom_redshift(lcf_engine* e, double z);
 
 #ifdef __cplusplus
 }

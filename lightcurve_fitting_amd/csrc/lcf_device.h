@@ -4,8 +4,20 @@
 // organised for a 64-lane wavefront: one lane = one (walker, data point) pair, the walker's derived coefficients are
 // wave-uniform (scalar registers), the per-filter band tables sit in LDS as interleaved (a_k, W_k) pairs.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#else
+// Compiled at run time behind a custom model's source (lcf_custom.hip): hiprtc has no headers to include, keeps the
+// fixed-width integers in a namespace of its own and has no INFINITY.
+typedef __hip_internal::int32_t int32_t;
+typedef __hip_internal::uint32_t uint32_t;
+typedef __hip_internal::int64_t int64_t;
+typedef __hip_internal::uint64_t uint64_t;
+#ifndef INFINITY
+#define INFINITY __builtin_huge_valf()
+#endif
+#endif
 
 namespace lcf {
 
@@ -672,6 +684,33 @@ __device__ inline void thermal_state_log(const DevProblem& pb, const double* __r
     } else if (u > -50.) {  // outside the interpolants' range: the sample tables, in linear space
         encode_linear(exp(-u), exp(lp), x, p);
     }
+}
+
+// ln S_f(e^u) from the filter's interpolant: interval of u, then Horner's rule on 8 coefficients (four 16-byte reads).
+// `lds_at` >= 0: the interpolants are staged in LDS at that byte offset of the workgroup's dynamic LDS (the address is
+// formed from the LDS symbol itself, so that the reads are ds_read_b128 and not generic-pointer loads); < 0: global.
+// r = the temperature's interval coordinate (thermal_state_log): interval (int)r, position 2 frac(r) - 1 in [-1, 1).
+// (Measured and not kept: a row of padding behind every filter's rows in the staged copy, against bank conflicts between
+// lanes that hold different filters -- no change for photometry without shared epochs, 26.1 against 25.7 us.)
+__device__ __forceinline__ double interp_log_band_sum(const DevProblem& pb, int lds_at, int filt, double r) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int j = (int)r;
+    const double s = fma(__builtin_amdgcn_fract(r), 2., -1.);
+    double2 q0, q1, q2, q3;
+    if (lds_at >= 0) {
+        const double2* q = reinterpret_cast<const double2*>(smem + lds_at) + (filt * pb.itab_m * 8 + 8 * j) / 2;
+        q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    } else {
+        const double2* q = reinterpret_cast<const double2*>(pb.itab + filt * pb.itab_m * 8 + 8 * j);
+        q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    }
+    double g = fma(q0.x, s, q0.y);
+    g = fma(g, s, q1.x);
+    g = fma(g, s, q1.y);
+    g = fma(g, s, q2.x);
+    g = fma(g, s, q2.y);
+    g = fma(g, s, q3.x);
+    return fma(g, s, q3.y);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -133,32 +133,7 @@ __device__ __forceinline__ double band_sum_at(const TabSel<TabPtr>& ts, bool use
     return VARIANT == 0 ? band_sum_ref(tab, cnt, invT) : band_sum_fast(tab, cnt, invT, et);
 }
 
-// ln S_f(e^u) from the filter's interpolant: interval of u, then Horner's rule on 8 coefficients (four 16-byte reads).
-// `lds_at` >= 0: the interpolants are staged in LDS at that byte offset of the workgroup's dynamic LDS (the address is
-// formed from the LDS symbol itself, so that the reads are ds_read_b128 and not generic-pointer loads); < 0: global.
-// r = the temperature's interval coordinate (thermal_state_log): interval (int)r, position 2 frac(r) - 1 in [-1, 1).
-// (Measured and not kept: a row of padding behind every filter's rows in the staged copy, against bank conflicts between
-// lanes that hold different filters -- no change for photometry without shared epochs, 26.1 against 25.7 us.)
-__device__ __forceinline__ double interp_log_band_sum(const DevProblem& pb, int lds_at, int filt, double r) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int j = (int)r;
-    const double s = fma(__builtin_amdgcn_fract(r), 2., -1.);
-    double2 q0, q1, q2, q3;
-    if (lds_at >= 0) {
-        const double2* q = reinterpret_cast<const double2*>(smem + lds_at) + (filt * pb.itab_m * 8 + 8 * j) / 2;
-        q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-    } else {
-        const double2* q = reinterpret_cast<const double2*>(pb.itab + filt * pb.itab_m * 8 + 8 * j);
-        q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-    }
-    double g = fma(q0.x, s, q0.y);
-    g = fma(g, s, q1.x);
-    g = fma(g, s, q1.y);
-    g = fma(g, s, q2.x);
-    g = fma(g, s, q2.y);
-    g = fma(g, s, q3.x);
-    return fma(g, s, q3.y);
-}
+// (interp_log_band_sum, the interpolants' lookup, is in lcf_device.h: the run-time-compiled kernel of custom models takes it too)
 
 // Everything one lane does for its data point after the thermal state (1/T, R_bb^2): band sum(s) -> template term.
 // STAGED: the band tables (or their compressed levels) are in LDS; the on-the-fly reddening fall-back exists only in
@@ -2610,10 +2585,17 @@ namespace lcf {
 // log-likelihood / log-posterior of n walkers, device pointers, enqueue only.
 lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout, hipStream_t st, int with_prior) {
     if (n == 0) return LCF_OK;
+    const bool custom = e->dp.model == LCF_MODEL_CUSTOM;   // the attached program's kernel between the same two launches
+    if (custom)
+        if (lcf_status s = custom_ready(e)) return s;
     const int bs = 128;
     hipLaunchKernelGGL(k_prepare, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, dP, e->wcoef,
                        e->wlprior, with_prior);
-    launch_points<0>(e, 0, (int)n, dP, e->wcoef, e->wlprior, e->wtherm, e->wpart, nullptr, st);
+    if (custom) {
+        if (lcf_status s = custom_launch(e, 0, 0, (int)n, dP, e->wlprior, e->wpart, nullptr, st)) return s;
+    } else {
+        launch_points<0>(e, 0, (int)n, dP, e->wcoef, e->wlprior, e->wtherm, e->wpart, nullptr, st);
+    }
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, e->wpart,
                        e->wlprior, dout);
     LCF_HIP(hipGetLastError());
@@ -2659,12 +2641,15 @@ lcf_status lcf_engine_create(const lcf_problem* pr, int32_t device, lcf_engine**
         case LCF_MODEL_SHOCK_COOLING4:
         case LCF_MODEL_COMPANION_SHOCKING: case LCF_MODEL_COMPANION_SHOCKING2: case LCF_MODEL_COMPANION_SHOCKING3:
         case LCF_MODEL_BLACKBODY:
+        case LCF_MODEL_CUSTOM:
             break;
         default:
             return fail(LCF_ERR_UNSUPPORTED, "unknown or unsupported model id");
     }
     static const int kNPar[9] = {0, 5, 4, 7, 5, 8, 7, 7, 2};
-    if (pr->n_par != kNPar[pr->model]) return fail(LCF_ERR_INVALID_ARGUMENT, "n_par does not match the model");
+    // (a custom model has as many parameters as its state function reads: the caller says how many)
+    if (pr->model == LCF_MODEL_CUSTOM ? pr->n_par < 0 : pr->n_par != kNPar[pr->model])
+        return fail(LCF_ERR_INVALID_ARGUMENT, "n_par does not match the model");
     const int n_dim = pr->n_par + (pr->use_sigma ? 1 : 0);
     if (n_dim > kMaxDim) return fail(LCF_ERR_INVALID_ARGUMENT, "too many parameters");
     if (pr->n_points < 0 || pr->n_points > (1 << 26) || pr->n_filters <= 0)
@@ -3192,6 +3177,9 @@ lcf_status lcf_log_posterior_dev(lcf_engine* e, int64_t n, const double* dP, dou
 static lcf_status evaluate_impl(lcf_engine* e, int64_t n, const double* P, double* o0, double* o1, int mode) {
     if (!e || n < 0 || (n > 0 && (!P || !o0 || (mode == 2 && !o1)))) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0 || e->dp.n_points == 0) return LCF_OK;
+    const bool custom = e->dp.model == LCF_MODEL_CUSTOM;
+    if (custom)
+        if (lcf_status st = custom_ready(e)) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (lcf_status st = e->reserve(n)) return st;
     const size_t N = e->dp.n_points;
@@ -3206,7 +3194,10 @@ static lcf_status evaluate_impl(lcf_engine* e, int64_t n, const double* P, doubl
         const int64_t m = std::min(per, n - lo);
         double* b0 = e->wbig;
         double* b1 = e->wbig + per * N;
-        if (mode == 1)
+        if (custom) {
+            if (lcf_status st = custom_launch(e, mode, (int)lo, (int)m, e->wP, e->wlprior, b0, mode == 2 ? b1 : nullptr, e->stream))
+                return st;
+        } else if (mode == 1)
             launch_points<1>(e, (int)lo, (int)m, e->wP, e->wcoef, e->wlprior, e->wtherm, b0, nullptr, e->stream);
         else
             launch_points<2>(e, (int)lo, (int)m, e->wP, e->wcoef, e->wlprior, e->wtherm, b0, b1, e->stream);
@@ -3259,6 +3250,7 @@ lcf_status lcf_blackbody_to_filters(lcf_engine* e, int64_t m, const int32_t* fil
 extern "C" lcf_status lcf_profile_loglike_kernel(lcf_engine* e, int64_t n, const double* P, int32_t reps,
                                                  double* avg_ms) {
     if (!e || n <= 0 || !P || reps <= 0 || !avg_ms) return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument");
+    if (lcf_status st = custom_refuse(e, "lcf_profile_loglike_kernel")) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (lcf_status st = e->reserve(n)) return st;
     LCF_HIP(hipMemcpyAsync(e->wP, P, n * e->dp.n_dim * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -4443,6 +4435,7 @@ lcf_status lcf_population_run(lcf_sampler** ss, int32_t n, int64_t first_step, i
 static lcf_status predict_check(const lcf_engine* grid, int32_t component, const double* q, int32_t n_q,
                                 const double* out, const int64_t* n_valid) {
     if (!grid || !q || !out || !n_valid) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = custom_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
     if (n_q < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one percentile");
     for (int32_t j = 0; j < n_q; ++j)
         if (!(q[j] >= 0. && q[j] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");

@@ -196,6 +196,10 @@ struct lcf_engine {
     bool have_ctab = false, have_itab = false;
     int n_cus = 256;             // compute units of the device (launch shapes depend on it)
     DevProblem* d_dp = nullptr;  // `dp` in device memory, for the kernels that read it through a pointer
+    // LCF_MODEL_CUSTOM: the likelihood / evaluation kernel of the attached program on this device (lcf_engine_set_custom;
+    // null: none yet) and the redshift its state function is handed
+    hipFunction_t custom_points = nullptr;
+    double custom_z = 0.;
     lcf_status sync_dp();        // after every change of `dp`
     // workspace for n walkers
     int64_t cap = 0;
@@ -252,6 +256,12 @@ namespace lcf {
 // polled_alloc: `bytes` of it on the current device, cleared (complete on return).
 void polled_give(int dev, bool uncached, size_t bytes, void* p);
 lcf_status polled_alloc(int dev, bool uncached, size_t bytes, void** out);
+// lcf_custom.hip: engines of LCF_MODEL_CUSTOM.  custom_refuse: LCF_ERR_UNSUPPORTED, naming the supported route, for what is
+// compiled per model (`what` names the caller); LCF_OK for every other engine.
+lcf_status custom_refuse(const lcf_engine* e, const char* what);
+lcf_status custom_launch(lcf_engine* e, int mode, int w_lo, int n, const double* dP, const double* lprior, double* out0,
+                         double* out1, hipStream_t st);
+lcf_status custom_ready(const lcf_engine* e);
 }  // namespace lcf
 
 struct lcf_sampler {

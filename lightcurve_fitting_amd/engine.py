@@ -22,6 +22,7 @@ MODEL_COMPANION_SHOCKING = 5
 MODEL_COMPANION_SHOCKING2 = 6
 MODEL_COMPANION_SHOCKING3 = 7
 MODEL_BLACKBODY = 8
+MODEL_CUSTOM = 9
 
 PRIOR_UNIFORM, PRIOR_LOG_UNIFORM, PRIOR_GAUSSIAN = 0, 1, 2
 SIGMA_RELATIVE, SIGMA_ABSOLUTE = 0, 1
@@ -177,6 +178,12 @@ SIGNATURES = [
     ('lcf_tempered_get_betas', C.c_int, [C.c_void_p, _dp]),
     ('lcf_tempered_get_beta_history', C.c_int, [C.c_void_p, _dp]),
     ('lcf_tempered_stepping_stones', C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp]),
+    ('lcf_custom_compile', C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    ('lcf_custom_log', C.c_char_p, [C.c_void_p]),
+    ('lcf_custom_code', C.c_void_p, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ('lcf_custom_destroy', None, [C.c_void_p]),
+    ('lcf_engine_set_custom', C.c_int, [C.c_void_p, C.c_void_p]),
+    ('lcf_engine_set_custom_redshift', C.c_int, [C.c_void_p, C.c_double]),
 ]
 
 
@@ -317,6 +324,13 @@ class Engine:
     def set_variant(self, variant):
         _check(self._lib.lcf_engine_set_variant(self._h, int(variant)))
 
+    def set_custom(self, program, redshift=0.):
+        """Attach a :class:`CustomProgram` (engines created with ``MODEL_CUSTOM``) and the redshift its state function
+        is handed."""
+        _check(self._lib.lcf_engine_set_custom(self._h, program.handle))
+        _check(self._lib.lcf_engine_set_custom_redshift(self._h, float(redshift)))
+        self.program = program   # (kept alive with the engine)
+
     def _block(self, P):
         P = _f64(P)
         if P.ndim == 1:
@@ -369,6 +383,32 @@ class Engine:
         out = np.empty(len(f))
         _check(self._lib.lcf_blackbody_to_filters(self._h, len(f), _ptr(f, _ip), _ptr(T), _ptr(R), _ptr(out)))
         return out
+
+
+class CustomProgram:
+    """A custom model's source compiled for one GPU architecture (``lcf_custom_compile``): ``arch`` such as
+    ``'gfx950'``, or None for the architecture of ``device``.  A source that does not compile raises
+    :class:`LcfError` carrying the compiler's log, in which the source's own lines are ``user_model:<line>``.  The
+    library caches programs per process by (source, architecture): the same pair gives the same ``handle.value``."""
+
+    def __init__(self, source, arch=None, device=0):
+        self._lib = load_library()
+        self.handle = C.c_void_p()
+        self.source, self.arch = str(source), arch
+        _check(self._lib.lcf_custom_compile(self.source.encode(), arch.encode() if arch else None, int(device),
+                                            C.byref(self.handle)))
+
+    @property
+    def log(self):
+        """The compiler's log (warnings; '' if none)."""
+        return self._lib.lcf_custom_log(self.handle).decode()
+
+    @property
+    def code(self):
+        """The code object, as bytes."""
+        n = C.c_int64()
+        ptr = self._lib.lcf_custom_code(self.handle, C.byref(n))
+        return C.string_at(ptr, n.value) if ptr else b''
 
 
 #: `lcf_sampler_last_run_kernel` values (include/lcf.h: LCF_KERNEL_*) -> the names `last_run_kernel()` returns

@@ -20,7 +20,7 @@ import warnings
 
 import numpy as np
 
-from .models import BaseCompanionShocking, Blackbody, Model, UniformPrior, _column
+from .models import BaseCompanionShocking, Blackbody, CustomModel, Model, UniformPrior, _column
 from .filters import as_filter
 from .sampler import EnsembleSampler
 
@@ -102,6 +102,11 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     adapts during the burn-in until neighbouring rungs swap equally often, and is frozen for the stored run, so that
     ``sampler.log_evidence(method='stepping_stone')`` is over one ladder.
 
+    A :class:`~lightcurve_fitting_amd.models.CustomModel` is always fitted by that sampler -- without the tempering
+    arguments on one rung at ``beta = 1``, which makes the ensemble sampler's moves -- because the resident sampler's
+    kernels are compiled per built-in model; ``chain``, ``flatchain``, ``get_autocorr_time`` are the same,
+    ``acceptance_fraction`` has a leading axis of length one.
+
     Returns the sampler (``.chain`` (nwalkers, nsteps, ndim), ``.flatchain``, ``.run_mcmc``, ``.reset``).
     """
     import time
@@ -131,6 +136,8 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks.append(('engine', time.perf_counter()))
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
+    if isinstance(model, CustomModel) and ntemps is None and betas is None and Tmax is None:
+        betas = [1.]   # the resident sampler's kernels are compiled per built-in model: one rung is the same ensemble
     if ntemps is not None or betas is not None or Tmax is not None:
         from .sampler import TemperedSampler
         sampler = TemperedSampler(nwalkers, ndim, engine, ntemps=ntemps, betas=betas, Tmax=Tmax, seed=seed,
@@ -276,6 +283,15 @@ def _percentile_array(percentiles):
     return q
 
 
+def _refuse_custom(model, what):
+    """The predictive kernels are compiled per built-in model: a ``CustomModel`` is refused before anything is built."""
+    if isinstance(model, CustomModel):
+        from .engine import LcfError
+        raise LcfError(5, f'{what} is compiled per built-in model and does not take a CustomModel; its fit (the '
+                          'tempered route, TemperedSampler) gives the chain, and model(t, filters, *p) evaluates '
+                          'any of its rows')
+
+
 def _model_samples(model, samples, discard, thin, use_sigma):
     """:func:`_predictive_samples` and the column count ``model`` wants: ``(sampler or None, host array or None,
     n_samples)``."""
@@ -314,6 +330,7 @@ def posterior_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=
     samples stays below ``workspace_bytes`` (default 1 GiB), the times being worked through in tiles.  Results are
     bitwise reproducible and do not depend on ``workspace_bytes``.  Returns a :class:`PosteriorPredictive`."""
     from . import engine as _eng
+    _refuse_custom(model, 'posterior_predictive')
     q = _percentile_array(percentiles)
     if component not in ('model', 'sifto'):
         raise ValueError("component must be 'model' or 'sifto'")
@@ -395,6 +412,7 @@ def thermal_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=No
     NaN bound holds nothing.  Nothing is stored per (sample, time) and all counts are exact.  Returns a
     :class:`ThermalPredictive`."""
     from . import engine as _eng
+    _refuse_custom(model, 'thermal_predictive')
     if isinstance(model, Blackbody):
         raise ValueError('the Blackbody model has no thermal evolution or validity window')
     q = _percentile_array(percentiles)
@@ -492,8 +510,9 @@ def _column_names(model, n_col, use_sigma):
         if n_col != want:
             raise ValueError(f'the samples have {n_col} columns, the model takes {model.n_model_params}'
                              + (' and one for sigma' if use_sigma else ''))
-        names = list(type(model).input_names) + (['\\sigma'] if use_sigma else [])
-        units = list(type(model).units) + ([''] if use_sigma else [])
+        # (the model's own parameters: the first n_model_params of the instance's lists -- a CustomModel has no others)
+        names = list(model.input_names[:model.n_model_params]) + (['\\sigma'] if use_sigma else [])
+        units = list(model.units[:model.n_model_params]) + ([''] if use_sigma else [])
         labels = ['${}$ ({})'.format(var, unit) if unit else '${}$'.format(var) for var, unit in zip(names, units)]
     if not 1 <= n_col <= _eng.CORNER_MAX_DIM:
         raise ValueError(f'the samples must have from 1 to {_eng.CORNER_MAX_DIM} columns')

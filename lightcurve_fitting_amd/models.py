@@ -542,6 +542,67 @@ class Blackbody(Model):
         return super()._eval_engine(t_in, f, True)
 
 
+class CustomModel(Model):
+    """A model the user writes: a photosphere ``T(t, p)``, ``R(t, p)`` in HIP device code, followed by
+    ``blackbody_to_filters(f, T, R, z)`` -- the two steps of every shock-cooling class of the reference -- compiled at
+    run time for the GPU and fitted like the built-in models.
+
+    ``source`` defines exactly this function (see ``include/lcf.h``, "custom models")::
+
+        __device__ void lcf_user_state(double t_in, const double* p, const double* consts, double z,
+                                       double& T_kK, double& R_1000Rsun);
+
+    ``t_in``: the observation time as stored in the light curve (subtract the explosion time and apply ``1 + z`` as the
+    model requires); ``p``: the ``len(input_names)`` parameters, without a fitted sigma; ``consts``: up to 12 numbers
+    given here; units as ``temperature_radius`` returns them.  ``lcf::pw`` is the reference's ``power()``.
+    ``T <= 0`` or ``T >= 1e15`` gives a zero light curve, a NaN state a NaN likelihood.
+
+    ``log_likelihood``, ``evaluate`` / ``__call__``, ``temperature_radius``, ``make_log_posterior`` and
+    ``lightcurve_mcmc`` work as for every model; the fit runs through :class:`~lightcurve_fitting_amd.sampler.
+    TemperedSampler` (one rung at ``beta = 1`` unless a ladder is asked for), since the resident sampler's kernels,
+    ``posterior_predictive`` and ``thermal_predictive`` are compiled per built-in model and raise ``LcfError`` here.
+    The source is compiled on first use (:meth:`compile`); an error in it raises ``LcfError`` with the compiler's log,
+    which names the source's own lines as ``user_model:<line>``."""
+    model_id = _eng.MODEL_CUSTOM
+
+    def __init__(self, source, input_names, units=None, consts=(), lc=None, redshift=0., output_quantity='lum'):
+        super().__init__(lc, redshift=redshift)
+        self.source = str(source)
+        self.input_names = list(input_names)
+        self.units = [''] * len(self.input_names) if units is None else list(units)
+        if len(self.units) != len(self.input_names):
+            raise ValueError('units must have one entry per parameter')
+        self._n_par = len(self.input_names)
+        if not 1 <= self._n_par <= 15:
+            raise ValueError('a custom model has 1 to 15 parameters')
+        self._custom_consts = [float(c) for c in consts]
+        if len(self._custom_consts) > _eng.N_CONSTS:
+            raise ValueError(f'at most {_eng.N_CONSTS} consts')
+        self.output_quantity = output_quantity
+        self._programs = {}
+
+    @property
+    def n_model_params(self):
+        return self._n_par
+
+    def _consts(self):
+        return self._custom_consts
+
+    def compile(self, arch=None, device=None):
+        """The :class:`~lightcurve_fitting_amd.engine.CustomProgram` of the source for ``arch`` (e.g. ``'gfx950'``:
+        no GPU needed) or, by default, for the architecture of ``device`` (the model's)."""
+        device = self.device if device is None else device
+        key = arch or ('device', device)
+        if key not in self._programs:
+            self._programs[key] = _eng.CustomProgram(self.source, arch, device)
+        return self._programs[key]
+
+    def make_engine(self, t, filts, y, dy, use_sigma=False, sigma_type='relative', priors=None, device=None):
+        eng = super().make_engine(t, filts, y, dy, use_sigma, sigma_type, priors, device)
+        eng.set_custom(self.compile(device=eng.device), self.z)
+        return eng
+
+
 def blackbody_to_filters(filters, T, R, z=0., cutoff_freq=np.inf, ebv=0., variant=None):
     """Band-averaged L_nu of blackbodies through filters (models.py:1131-1165).
 
