@@ -2588,11 +2588,14 @@ lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout,
     const bool custom = e->dp.model == LCF_MODEL_CUSTOM;   // the attached program's kernel between the same two launches
     if (custom)
         if (lcf_status s = custom_ready(e)) return s;
+    const bool central = is_central(e->dp.model);           // k_central_points (lcf_central.hip), likewise
     const int bs = 128;
     hipLaunchKernelGGL(k_prepare, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, dP, e->wcoef,
                        e->wlprior, with_prior);
     if (custom) {
         if (lcf_status s = custom_launch(e, 0, 0, (int)n, dP, e->wlprior, e->wpart, nullptr, st)) return s;
+    } else if (central) {
+        if (lcf_status s = central_launch(e, 0, 0, (int)n, dP, e->wlprior, e->wpart, st)) return s;
     } else {
         launch_points<0>(e, 0, (int)n, dP, e->wcoef, e->wlprior, e->wtherm, e->wpart, nullptr, st);
     }
@@ -2636,6 +2639,7 @@ lcf_status lcf_engine_create(const lcf_problem* pr, int32_t device, lcf_engine**
     if (!pr || !out) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     if (pr->abi_version != LCF_ABI_VERSION) return fail(LCF_ERR_INVALID_ARGUMENT, "abi_version mismatch");
+    if (is_central(pr->model)) return central_engine_create(pr, device, out);   // (no filters: an engine of its own making)
     switch (pr->model) {
         case LCF_MODEL_SHOCK_COOLING: case LCF_MODEL_SHOCK_COOLING2: case LCF_MODEL_SHOCK_COOLING3:
         case LCF_MODEL_SHOCK_COOLING4:
@@ -3180,6 +3184,9 @@ static lcf_status evaluate_impl(lcf_engine* e, int64_t n, const double* P, doubl
     const bool custom = e->dp.model == LCF_MODEL_CUSTOM;
     if (custom)
         if (lcf_status st = custom_ready(e)) return st;
+    const bool central = is_central(e->dp.model);
+    if (central && mode == 2)
+        if (lcf_status st = central_refuse(e, "lcf_temperature_radius")) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (lcf_status st = e->reserve(n)) return st;
     const size_t N = e->dp.n_points;
@@ -3197,6 +3204,8 @@ static lcf_status evaluate_impl(lcf_engine* e, int64_t n, const double* P, doubl
         if (custom) {
             if (lcf_status st = custom_launch(e, mode, (int)lo, (int)m, e->wP, e->wlprior, b0, mode == 2 ? b1 : nullptr, e->stream))
                 return st;
+        } else if (central) {
+            if (lcf_status st = central_launch(e, 1, (int)lo, (int)m, e->wP, e->wlprior, b0, e->stream)) return st;
         } else if (mode == 1)
             launch_points<1>(e, (int)lo, (int)m, e->wP, e->wcoef, e->wlprior, e->wtherm, b0, nullptr, e->stream);
         else
@@ -3251,6 +3260,7 @@ extern "C" lcf_status lcf_profile_loglike_kernel(lcf_engine* e, int64_t n, const
                                                  double* avg_ms) {
     if (!e || n <= 0 || !P || reps <= 0 || !avg_ms) return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument");
     if (lcf_status st = custom_refuse(e, "lcf_profile_loglike_kernel")) return st;
+    if (lcf_status st = central_refuse(e, "lcf_profile_loglike_kernel")) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (lcf_status st = e->reserve(n)) return st;
     LCF_HIP(hipMemcpyAsync(e->wP, P, n * e->dp.n_dim * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -4436,6 +4446,7 @@ static lcf_status predict_check(const lcf_engine* grid, int32_t component, const
                                 const double* out, const int64_t* n_valid) {
     if (!grid || !q || !out || !n_valid) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = custom_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
+    if (lcf_status st = central_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
     if (n_q < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one percentile");
     for (int32_t j = 0; j < n_q; ++j)
         if (!(q[j] >= 0. && q[j] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");

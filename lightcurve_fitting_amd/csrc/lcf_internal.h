@@ -262,6 +262,15 @@ lcf_status custom_refuse(const lcf_engine* e, const char* what);
 lcf_status custom_launch(lcf_engine* e, int mode, int w_lo, int n, const double* dP, const double* lprior, double* out0,
                          double* out1, hipStream_t st);
 lcf_status custom_ready(const lcf_engine* e);
+// lcf_central.hip: engines of LCF_MODEL_ARNETT / LCF_MODEL_MAGNETAR (a bolometric light curve, no filters).
+// central_engine_create: what lcf_engine_create does for these two ids; central_refuse: as custom_refuse;
+// central_launch: rows [w_lo, w_lo + n) of P through k_central_points on st -- mode 0: chi^2 partial sums -> out0 (the
+// engine's part buffer; rows with lprior == -inf skipped), 1: L(t) -> out0[row][point], the caller's order.
+inline bool is_central(int model) { return model == LCF_MODEL_ARNETT || model == LCF_MODEL_MAGNETAR; }
+lcf_status central_engine_create(const lcf_problem* pr, int32_t device, lcf_engine** out);
+lcf_status central_refuse(const lcf_engine* e, const char* what);
+lcf_status central_launch(lcf_engine* e, int mode, int w_lo, int n, const double* dP, const double* lprior, double* out0,
+                          hipStream_t st);
 }  // namespace lcf
 
 struct lcf_sampler {

@@ -23,6 +23,8 @@ MODEL_COMPANION_SHOCKING2 = 6
 MODEL_COMPANION_SHOCKING3 = 7
 MODEL_BLACKBODY = 8
 MODEL_CUSTOM = 9
+MODEL_ARNETT = 10
+MODEL_MAGNETAR = 11
 
 PRIOR_UNIFORM, PRIOR_LOG_UNIFORM, PRIOR_GAUSSIAN = 0, 1, 2
 SIGMA_RELATIVE, SIGMA_ABSOLUTE = 0, 1
@@ -234,7 +236,8 @@ class Engine:
     """One light curve + one model instance resident on one MI355X.
 
     Parameters are the fields of ``lcf_problem`` (see ``include/lcf.h``): ``priors`` is a sequence of
-    ``(kind, p_min, p_max, mean, stddev)`` or ``None``."""
+    ``(kind, p_min, p_max, mean, stddev)`` or ``None``.  ``filt_idx`` and ``tab_off`` None: the filter-less problem of
+    the central-engine models (``n_filters = 0``, the table pointers NULL)."""
 
     def __init__(self, model_id, n_par, consts, t, y, dy, filt_idx, tab_off, tab_a, tab_w, use_sigma=False,
                  sigma_type=SIGMA_RELATIVE, priors=None, companion=None, device=0, ctab=None, tab_ext=None,
@@ -242,6 +245,9 @@ class Engine:
         lib = load_library()
         self._lib = lib
         self._h = C.c_void_p()
+        no_filters = tab_off is None
+        if no_filters:
+            filt_idx, tab_off, tab_a, tab_w = np.zeros(len(_f64(t)), dtype=np.int32), [0], [], []
         keep = [_f64(t), _f64(y), _f64(dy), _i32(filt_idx), _i32(tab_off), _f64(tab_a), _f64(tab_w)]
         pr = LcfProblem()
         pr.abi_version = LCF_ABI_VERSION
@@ -256,8 +262,9 @@ class Engine:
         cs = list(consts) + [0.] * (N_CONSTS - len(consts))
         pr.consts = (C.c_double * N_CONSTS)(*cs)
         pr.t, pr.y, pr.dy = _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2])
-        pr.filt_idx, pr.tab_off = _ptr(keep[3], _ip), _ptr(keep[4], _ip)
-        pr.tab_a, pr.tab_w = _ptr(keep[5]), _ptr(keep[6])
+        if not no_filters:
+            pr.filt_idx, pr.tab_off = _ptr(keep[3], _ip), _ptr(keep[4], _ip)
+            pr.tab_a, pr.tab_w = _ptr(keep[5]), _ptr(keep[6])
         if tab_ext is not None:  # A_lambda / E(B-V) per table sample (ShockCooling3)
             ext = _f64(tab_ext)
             if len(ext) != len(keep[5]):

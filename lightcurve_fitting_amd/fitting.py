@@ -20,7 +20,7 @@ import warnings
 
 import numpy as np
 
-from .models import BaseCompanionShocking, Blackbody, CustomModel, Model, UniformPrior, _column
+from .models import BaseCentralEngine, BaseCompanionShocking, Blackbody, CustomModel, Model, UniformPrior, _column
 from .filters import as_filter
 from .sampler import EnsembleSampler
 
@@ -105,7 +105,9 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     A :class:`~lightcurve_fitting_amd.models.CustomModel` is always fitted by that sampler -- without the tempering
     arguments on one rung at ``beta = 1``, which makes the ensemble sampler's moves -- because the resident sampler's
     kernels are compiled per built-in model; ``chain``, ``flatchain``, ``get_autocorr_time`` are the same,
-    ``acceptance_fraction`` has a leading axis of length one.
+    ``acceptance_fraction`` has a leading axis of length one.  So are the central-engine models
+    (:class:`~lightcurve_fitting_amd.models.Arnett`, :class:`~lightcurve_fitting_amd.models.Magnetar`), whose ``lc`` is a
+    bolometric light curve (``MJD``, ``L_bol``, ``dL_bol``; no magnitudes are converted).
 
     Returns the sampler (``.chain`` (nwalkers, nsteps, ndim), ``.flatchain``, ``.run_mcmc``, ``.reset``).
     """
@@ -136,8 +138,8 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks.append(('engine', time.perf_counter()))
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
-    if isinstance(model, CustomModel) and ntemps is None and betas is None and Tmax is None:
-        betas = [1.]   # the resident sampler's kernels are compiled per built-in model: one rung is the same ensemble
+    if isinstance(model, (CustomModel, BaseCentralEngine)) and ntemps is None and betas is None and Tmax is None:
+        betas = [1.]   # the resident sampler's kernels are compiled per photometric model: one rung is the same ensemble
     if ntemps is not None or betas is not None or Tmax is not None:
         from .sampler import TemperedSampler
         sampler = TemperedSampler(nwalkers, ndim, engine, ntemps=ntemps, betas=betas, Tmax=Tmax, seed=seed,
@@ -284,12 +286,18 @@ def _percentile_array(percentiles):
 
 
 def _refuse_custom(model, what):
-    """The predictive kernels are compiled per built-in model: a ``CustomModel`` is refused before anything is built."""
+    """The predictive kernels are compiled per built-in photometric model: a ``CustomModel`` and the central-engine
+    models (``Arnett``, ``Magnetar``) are refused before anything is built."""
     if isinstance(model, CustomModel):
         from .engine import LcfError
         raise LcfError(5, f'{what} is compiled per built-in model and does not take a CustomModel; its fit (the '
                           'tempered route, TemperedSampler) gives the chain, and model(t, filters, *p) evaluates '
                           'any of its rows')
+    if isinstance(model, BaseCentralEngine):
+        from .engine import LcfError
+        raise LcfError(5, f'{what} is compiled per photometric model and does not take a central-engine model (Arnett, '
+                          'Magnetar); its fit (the tempered route, TemperedSampler) gives the chain, and model(t, *p) '
+                          'evaluates any of its rows')
 
 
 def _model_samples(model, samples, discard, thin, use_sigma):

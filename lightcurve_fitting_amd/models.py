@@ -603,6 +603,146 @@ class CustomModel(Model):
         return eng
 
 
+class BaseCentralEngine(Model):
+    """A bolometric light curve ``L(t)`` [W] -- one number per epoch, no filters -- from a power source ``P(s)`` at the
+    centre of the ejecta, diffusing out as in Arnett (1982); fitted to what ``calculate_bolometric`` produces.
+
+    With ``t = (MJD - t_0) / (1 + z)`` in days, ``L = 0`` for ``t <= 0`` and otherwise::
+
+        L(t) = leak(t) * int_0^t P(s) (2 s / tau_m^2) exp(-(t - s)(t + s) / tau_m^2) ds
+        leak(t) = 1,  or  1 - exp(-(t_gamma / t)^2)  with gamma_leakage=True
+
+    The integral is one fixed 64-node quadrature that is part of the model's definition (``include/lcf.h``, "central-
+    engine models"): within 1e-6 of the exact integral (measured: 4e-12) for ``2 <= tau_m <= 60`` d,
+    ``0.01 <= t <= 400`` d and a magnetar spin-down time ``1 <= t_p <= 100`` d.  Below ``t_p = 1`` d the accuracy
+    degrades (5e-6 at 0.1 d), so a prior should keep ``t_p`` above it.  A non-finite parameter, ``tau_m <= 0``,
+    ``t_p <= 0`` or ``t_gamma <= 0`` gives NaN: the priors have to exclude them.
+
+    ``lc`` needs the columns ``MJD``, ``ycol`` (default ``'L_bol'``) and ``dycol`` (default ``'d' + ycol``), in watts, and
+    no ``filter`` column; rows with a non-finite or non-positive uncertainty raise ``ValueError`` (``calculate_bolometric``
+    leaves NaN where a fit failed: drop those rows).  ``model(t, *p)`` evaluates ``L``; ``log_likelihood``,
+    ``make_log_posterior`` and ``lightcurve_mcmc`` work as for every model, the fit running through
+    :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` (one rung at ``beta = 1`` unless a ladder is asked for).
+    The resident sampler, ``posterior_predictive``, ``thermal_predictive`` and ``temperature_radius`` are compiled per
+    photometric model and raise ``LcfError`` here."""
+    #: parameters of the source, in front of tau_m
+    _source_names = []
+    _source_units = []
+
+    def __init__(self, lc=None, redshift=0., gamma_leakage=False, ycol='L_bol', dycol=None):
+        super().__init__(lc, redshift=redshift)
+        self.gamma_leakage = bool(gamma_leakage)
+        self.output_quantity = ycol
+        self.dycol = 'd' + ycol if dycol is None else dycol
+        self.input_names = list(self._source_names) + ['\\tau_m'] + (['t_\\gamma'] if self.gamma_leakage else []) + ['t_0']
+        self.units = list(self._source_units) + ['d'] + (['d'] if self.gamma_leakage else []) + ['d']
+        self._n_par = len(self.input_names)
+
+    def __repr__(self):
+        return f'<{self.__class__.__name__}: z={self.z:.3f}, gamma_leakage={self.gamma_leakage}>'
+
+    @property
+    def n_model_params(self):
+        return self._n_par
+
+    def _consts(self):
+        return [float(self.z), 1. if self.gamma_leakage else 0.]
+
+    def make_engine(self, t, y, dy, use_sigma=False, sigma_type='relative', priors=None, device=None):
+        """Build a device engine for an explicit bolometric light curve: epochs ``t`` (MJD), ``y`` and ``dy`` in W."""
+        if sigma_type == 'relative':
+            st = _eng.SIGMA_RELATIVE
+        elif sigma_type == 'absolute':
+            st = _eng.SIGMA_ABSOLUTE
+        else:
+            raise Exception('sigma_type must either be "relative" or "absolute"')
+        dy = np.asarray(dy, dtype=np.float64)
+        bad = np.nonzero(~(np.isfinite(dy) & (dy > 0.)))[0]
+        if len(bad):
+            raise ValueError(f'rows {bad.tolist()} of the light curve have a non-finite or non-positive {self.dycol}: '
+                             'drop them (calculate_bolometric leaves NaN where a fit failed)')
+        pri = None if priors is None else [p.descriptor() for p in priors]
+        return _eng.Engine(self.model_id, self.n_model_params, self._consts(), t, y, dy, None, None, None, None,
+                           use_sigma=use_sigma, sigma_type=st, priors=pri,
+                           device=self.device if device is None else device)
+
+    def engine_for(self, lc, use_sigma=False, sigma_type='relative', priors=None):
+        """Engine bound to the columns ``MJD``, ``ycol`` and ``dycol`` as ``lc`` holds them NOW (cached by content, as
+        :meth:`Model.engine_for`)."""
+        if sigma_type not in ('relative', 'absolute'):
+            raise Exception('sigma_type must either be "relative" or "absolute"')
+        t = np.asarray(_column(lc, 'MJD'), dtype=np.float64)
+        y = np.asarray(_column(lc, self.output_quantity), dtype=np.float64)
+        dy = np.asarray(_column(lc, self.dycol), dtype=np.float64)
+        none = np.empty(0, dtype=object)
+        mode = (bool(use_sigma), sigma_type, None if priors is None else tuple(p.descriptor() for p in priors))
+        for k, bound in enumerate(self._bound):
+            if bound.mode == mode and bound.holds(t, none, y, dy):
+                if k:  # most recently used first
+                    self._bound.insert(0, self._bound.pop(k))
+                return bound.engine
+        eng = self.make_engine(t, y, dy, use_sigma, sigma_type, priors)
+        self._bound.insert(0, _BoundEngine(eng, mode, t, none, y, dy))
+        del self._bound[self.max_bound_engines:]
+        return eng
+
+    def evaluate(self, t_in, *params):
+        """``L(t)`` [W] at the times ``t_in`` (MJD).  Scalar parameters -> (ntimes,); array parameters of length n ->
+        (ntimes, n)."""
+        if len(params) != self.n_model_params:
+            raise TypeError(f'{type(self).__name__} takes {self.n_model_params} parameters, got {len(params)}')
+        t_in = np.atleast_1d(np.asarray(t_in, dtype=np.float64)).ravel()
+        cols = np.broadcast_arrays(*[np.asarray(x, dtype=np.float64) for x in params])
+        scalar = cols[0].ndim == 0
+        key = ('eval', t_in.tobytes())
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = self.make_engine(t_in, np.zeros(len(t_in)), np.ones(len(t_in)))
+            self._engines = {key: eng}  # one evaluation grid at a time
+        y = eng.evaluate(np.column_stack([np.atleast_1d(c).ravel() for c in cols]))  # (n, ntimes)
+        return y[0] if scalar else y.T
+
+    def temperature_radius(self, t_in, *params):
+        """Not for this family: the model is a luminosity, it has no photosphere.  Raises ``LcfError`` (status 5)."""
+        raise _eng.LcfError(5, 'temperature_radius is compiled per photometric model: a central-engine model (Arnett, '
+                               'Magnetar) is a bolometric luminosity without a photosphere; model(t, *p) evaluates it, '
+                               'and its fit runs through the tempered route (TemperedSampler)')
+
+    @staticmethod
+    def ejecta_mass(tau_m, v_ej, kappa=0.07, beta=13.8):
+        """Ejecta mass [Msun] from the diffusion time: ``tau_m^2 beta c v_ej / (2 kappa)`` with ``tau_m`` [d], ``v_ej``
+        [1000 km/s] and the opacity ``kappa`` [cm^2/g] (Arnett 1982; ``beta = 13.8``).  Vectorised."""
+        tau = np.asarray(tau_m, dtype=np.float64) * 86400.
+        v = np.asarray(v_ej, dtype=np.float64) * 1e8
+        return tau ** 2 * beta * 2.99792458e10 * v / (2. * kappa) / 1.988409870698051e33
+
+    @staticmethod
+    def kinetic_energy(M_ej, v_ej):
+        """Kinetic energy [1e51 erg] of homogeneous ejecta: ``0.3 M_ej v_ej^2`` with ``M_ej`` [Msun] and ``v_ej``
+        [1000 km/s].  Vectorised."""
+        v = np.asarray(v_ej, dtype=np.float64) * 1e8
+        return 0.3 * np.asarray(M_ej, dtype=np.float64) * 1.988409870698051e33 * v ** 2 / 1e51
+
+
+class Arnett(BaseCentralEngine):
+    """Radioactive heating by 56Ni -> 56Co -> 56Fe (Arnett 1982; Valenti et al. 2008): parameters ``M_Ni`` [Msun],
+    ``tau_m`` [d], (``t_gamma`` [d] with ``gamma_leakage=True``,) ``t_0`` [d];
+    ``P(s) = M_Ni Msun [(e_Ni - e_Co) exp(-s / 8.8 d) + e_Co exp(-s / 111.3 d)]`` with ``e_Ni = 3.9e10`` and
+    ``e_Co = 6.78e9`` erg/s/g."""
+    model_id = _eng.MODEL_ARNETT
+    _source_names = ['M_\\mathrm{Ni}']
+    _source_units = ['Msun']
+
+
+class Magnetar(BaseCentralEngine):
+    """Magnetar spin-down (Kasen & Bildsten 2010): parameters ``E_p`` [1e51 erg], ``t_p`` [d], ``tau_m`` [d], (``t_gamma``
+    [d] with ``gamma_leakage=True``,) ``t_0`` [d]; ``P(s) = E_p / t_p / (1 + s / t_p)^2``.  The quadrature holds its
+    accuracy for ``t_p >= 1`` d."""
+    model_id = _eng.MODEL_MAGNETAR
+    _source_names = ['E_p', 't_p']
+    _source_units = ['10^51 erg', 'd']
+
+
 def blackbody_to_filters(filters, T, R, z=0., cutoff_freq=np.inf, ebv=0., variant=None):
     """Band-averaged L_nu of blackbodies through filters (models.py:1131-1165).
 
