@@ -622,10 +622,29 @@ lcf_status lcf_engine_set_custom_redshift(lcf_engine* e, double z);
  * 1e-6 of the exact integral (measured: 4e-12) for 2 <= tau_m <= 60 d, 0.01 <= t <= 400 d, 1 <= t_p <= 100 d.
  * A non-finite parameter, tau_m <= 0, t_p <= 0 or t_gamma <= 0 gives NaN at every epoch.
  * Such an engine serves lcf_log_likelihood / lcf_log_posterior and their _dev forms, lcf_model_evaluate (L per epoch, in
- * the caller's order) and, through lcf_log_likelihood_dev, lcf_tempered_*; a row's value does not depend on the rows
- * evaluated with it.  What is compiled per photometric model -- lcf_sampler_create and with it every lcf_sampler_* and
- * population run, lcf_predict_*, lcf_sampler_predict_*, lcf_temperature_radius, lcf_profile_loglike_kernel -- returns
+ * the caller's order), through lcf_log_likelihood_dev, lcf_tempered_*, and lcf_predict_luminosity (below: the bands
+ * and peaks of L(t) over a whole chain); a row's value does not depend on the rows evaluated with it.  What is compiled
+ * per photometric model -- lcf_sampler_create and with it every lcf_sampler_* and population run, lcf_predict_quantiles,
+ * lcf_predict_thermal, lcf_sampler_predict_*, lcf_temperature_radius, lcf_profile_loglike_kernel -- returns
  * LCF_ERR_UNSUPPORTED, naming this route, and launches nothing; lcf_blackbody_to_filters has no filter to index. */
+
+/* ---- luminosity bands and peaks: L(t) of a central-engine model over ALL samples ---------------------------------- */
+/* `grid` is a central-engine engine whose epochs are the grid times (dummy y / dy, no sigma, no priors).  Per (sample,
+ * time): L [W], bit for bit what lcf_model_evaluate returns.  Per time, over the n host samples P[n][ld] (ld >= n_par;
+ * the first n_par columns are used): the percentiles q[n_q] of L (NaNs dropped; NumPy's nanpercentile, default method;
+ * NaN where no sample has a value; 1 <= n_q <= 512), n_valid = the samples whose L is not NaN, and n_dark = those
+ * whose L is exactly +0: the sample has not exploded yet at that time.  All three in the order of the engine's epochs.
+ * Per sample, when L_peak and i_peak are given (both or neither): L_peak = its largest non-NaN L over the epochs and
+ * i_peak = the LOWEST epoch index at which it is attained; NaN and -1 for a sample that is NaN at every epoch.
+ * Every (sample, time) pair is evaluated ONCE -- a value is a 64-node quadrature -- and kept as an 8-byte key while the
+ * percentiles of its time are searched: device memory beyond the samples is at most workspace_bytes, the times being
+ * worked through in tiles of as many times as fit, 8 n bytes each besides the searches' own (LCF_ERR_INVALID_ARGUMENT,
+ * with the amount needed, if not even one time fits).  Results, the peaks included, do not depend on the tiling and
+ * are bitwise reproducible.  An engine of another model: LCF_ERR_UNSUPPORTED, naming lcf_predict_quantiles. */
+lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                                  int64_t workspace_bytes, double* out /* [n_q][n_times] */,
+                                  int64_t* n_valid /* [n_times] */, int64_t* n_dark /* [n_times] */,
+                                  double* L_peak /* [n] or NULL */, int32_t* i_peak /* [n] or NULL */);
 
 #ifdef __cplusplus
 }

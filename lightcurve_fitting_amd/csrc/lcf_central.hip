@@ -15,11 +15,16 @@
 // are evaluated together and there are no atomics: a row's value is the same bits alone and among any others.
 // The engine's own k_prepare (log-prior, lcf_hip.hip) runs in front of the kernel and k_finalize behind it, as for every
 // model; rows the prior excludes are skipped.
+//
+// k_lq_eval is the same evaluation for the luminosity bands (lcf_predict_luminosity; the selection over its keys is in
+// lcf_predict.hip): wave = one sample of a chain at a time, its CentralRow built once and kept across the times of a
+// tile, lane = one node; the grid is sized to the device and the waves stride over the samples.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "lcf_internal.h"
+#include "lcf_keys.h"
 
 namespace {
 
@@ -165,6 +170,37 @@ __global__ __launch_bounds__(kBlock) void k_central_points(const DevProblem pb, 
     if (tid == 0) out0[(size_t)w * part_stride(pb) + part] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// What k_lq_eval reads: sample s is the row at base + (s / n_w) * step_stride + (s % n_w) * ld.
+struct LqEval {
+    const double* base;
+    long long n, n_w, step_stride;
+    int ld, ep0, n_ep;
+    unsigned long long* keys;   // [n_ep][n]
+};
+
+// keys[i][s] = the key of L(t) of sample s at epoch ep0 + i: central_row / central_luminosity in the arithmetic of
+// k_central_points mode 1, so the bits are lcf_model_evaluate's.  The wave index goes through readfirstlane: the row's
+// address, and with it everything of CentralRow, is then uniform to the compiler as well.
+__global__ __launch_bounds__(kBlock) void k_lq_eval(const DevProblem pb, const LqEval a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long n_waves = (long long)gridDim.x * (kBlock / 64);
+    const int model = pb.model;
+    const bool leak = pb.consts[1] != 0.;
+    const double one_plus_z = 1. + pb.consts[0];
+    const double x = kGaussLegendre[lane & (kCentralNodes - 1)];
+    const double wgt = kGaussLegendre[kCentralNodes + (lane & (kCentralNodes - 1))];
+    const bool first = lane < kCentralNodes;
+    for (long long s = (long long)blockIdx.x * (kBlock / 64) + wave; s < a.n; s += n_waves) {
+        const CentralRow r = central_row(model, leak, a.base + (s / a.n_w) * a.step_stride + (s % a.n_w) * a.ld);
+        for (int i = 0; i < a.n_ep; ++i) {
+            const double t = (pb.t[a.ep0 + i] - r.t_0) / one_plus_z;
+            const double L = central_luminosity(model, leak, r, t, x, wgt, first);
+            if (lane == 0) a.keys[(size_t)i * a.n + s] = pq_key(L);
+        }
+    }
+}
+
 const char kRoute[] = "a central-engine model (LCF_MODEL_ARNETT, LCF_MODEL_MAGNETAR) is evaluated by lcf_log_likelihood / "
                       "lcf_log_posterior (and _dev) and lcf_model_evaluate, and sampled through lcf_tempered_* "
                       "(TemperedSampler; one rung at beta = 1 is the ensemble sampler)";
@@ -183,6 +219,17 @@ lcf_status central_launch(lcf_engine* e, int mode, int w_lo, int n, const double
     if (n <= 0 || (mode != 0 && e->dp.n_points == 0)) return LCF_OK;   // (mode 0 without epochs: the parts' zeros)
     hipLaunchKernelGGL(k_central_points, dim3((unsigned)((size_t)n * e->dp.n_parts)), dim3(kBlock), 0, st, e->dp, mode,
                        w_lo, n, dP, lprior, out0);
+    LCF_HIP(hipGetLastError());
+    return LCF_OK;
+}
+
+lcf_status central_keys_launch(const DevProblem& dp, const PredictSamples& in, int ep0, int n_ep,
+                               unsigned long long* keys, int n_cus) {
+    if (in.n <= 0 || n_ep <= 0) return LCF_OK;
+    // eight workgroups of four waves per CU is what the registers allow resident; never more waves than samples
+    const long long blocks = std::min<long long>((long long)std::max(n_cus, 1) * 8, (in.n + kBlock / 64 - 1) / (kBlock / 64));
+    const LqEval a{in.base, in.n, in.n_w, in.step_stride, in.ld, ep0, n_ep, keys};
+    hipLaunchKernelGGL(k_lq_eval, dim3((unsigned)blocks), dim3(kBlock), 0, 0, dp, a);
     LCF_HIP(hipGetLastError());
     return LCF_OK;
 }

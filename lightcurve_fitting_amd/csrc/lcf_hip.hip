@@ -37,6 +37,7 @@
 #include "lcf_device.h"
 #include "lcf_host.h"
 #include "lcf_internal.h"
+#include "lcf_keys.h"
 
 // Tuning knobs of the likelihood loop (measured on the 1024-walker, 3000-point fit: 2-6 chunks of prefetch and 4-6
 // waves per SIMD are within 1 % of each other; 8 waves per SIMD spill and lose 40 %).
@@ -4569,6 +4570,26 @@ lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t
     PredictSamples in;
     if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
     return thermal_impl(grid, in, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
+}
+
+lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                                  int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
+                                  double* L_peak, int32_t* i_peak) {
+    if (!grid || !q || !out || !n_valid || !n_dark) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if ((L_peak == nullptr) != (i_peak == nullptr))
+        return fail(LCF_ERR_INVALID_ARGUMENT, "L_peak and i_peak are given together or not at all");
+    if (!is_central(grid->dp.model))
+        return fail(LCF_ERR_UNSUPPORTED, "lcf_predict_luminosity takes a central-engine engine (LCF_MODEL_ARNETT, "
+                                         "LCF_MODEL_MAGNETAR); the bands of a photometric model are lcf_predict_quantiles "
+                                         "and lcf_predict_thermal");
+    if (n_q < 1 || n_q > 512) return fail(LCF_ERR_INVALID_ARGUMENT, "need between 1 and 512 percentiles");
+    for (int32_t j = 0; j < n_q; ++j)
+        if (!(q[j] >= 0. && q[j] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no epochs");
+    return with_uploaded_samples(grid, P, n, ld, [&](const PredictSamples& in) {
+        return predict_luminosity_run(grid->device, grid->dp, in, q, n_q, workspace_bytes, out, n_valid, n_dark, L_peak,
+                                      i_peak);
+    });
 }
 
 }  // extern "C"

@@ -26,7 +26,17 @@
 //                 lcf_temperature_radius -- and no band sum, filter descriptor or exp table.  In mode 0 it also counts,
 //                 per time, the samples with T < T_floor and those with t_min <= t <= t_max: wave ballot + popcount,
 //                 a sum per workgroup in LDS, one 64-bit integer atomic per workgroup and counter.
-// k_pq_pick and k_pq_finish serve both forms; the host driver (quantile_run) differs in the two launches only.
+//
+// The luminosity form (DESIGN.md "Luminosity bands and peaks") is for the central-engine models, whose value is a
+// 64-node quadrature -- a wavefront -- and too dear to recompute in every pass: every (sample, time) pair of a tile is
+// evaluated ONCE into its key, keys[tile time][n] (k_lq_eval, lcf_central.hip, beside the quadrature), and
+//   k_kq_pass     the geometry and modes of k_pq_pass with one series per time, over the stored keys: lanes = samples,
+//                 coalesced 8-byte reads, NaN keys dropped.  In mode 0 it also counts, per time, the samples whose L
+//                 is exactly +0 (not exploded yet), as k_th_pass counts its two.
+//   k_lq_peak     lane = sample: walks the tile's times in ascending order and keeps the sample's largest non-NaN L
+//                 and the first time it is attained (strict >).  Tiles follow each other on one stream, so the first
+//                 occurrence wins whatever the tiling.
+// k_pq_pick and k_pq_finish serve all forms; the host driver (quantile_run) differs in the launches only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -35,6 +45,7 @@
 #include "lcf.h"
 #include "lcf_device.h"
 #include "lcf_host.h"
+#include "lcf_keys.h"
 
 using namespace lcf;
 
@@ -73,14 +84,7 @@ struct PqArgs {
     unsigned long long* buf;     // [search][kPqCap]
 };
 
-// doubles ordered as unsigned integers (-inf < ... < -0 < +0 < ... < +inf)
-__device__ __forceinline__ unsigned long long pq_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double pq_value(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
+// (pq_key / pq_value -- doubles ordered as unsigned integers -- are in lcf_keys.h: k_lq_eval writes them too)
 
 // ln S_f(e^u) from the filter's interpolant in device memory (the form of the likelihood kernels: interval of the
 // coordinate r, Horner's rule on 8 coefficients)
@@ -439,6 +443,68 @@ __global__ __launch_bounds__(kPqThreads) void k_th_pass(const DevProblem pb, con
     }
 }
 
+// ---- the luminosity form: one series per time, its keys evaluated once and stored -------------------------------------
+constexpr unsigned long long kKeyPlusZero = 0x8000000000000000ull;   // pq_key(+0.)
+
+struct KqArgs {
+    const unsigned long long* keys;   // [tile time][n]
+    unsigned long long* n_dark;       // [n_epochs] samples whose L is exactly +0
+};
+
+// blockIdx.x = time of the tile, blockIdx.y = chunk of samples.  Dynamic LDS: per search prefix, successor, prefix
+// bits, collect flag | histogram counters.
+__global__ __launch_bounds__(kPqThreads) void k_kq_pass(const PqArgs a, const KqArgs kq) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ unsigned int s_dark;
+    const int ns = a.n_q;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n_hist = a.mode == 0 ? 1 << a.bits : a.mode == 1 ? ns << a.bits : 0;
+    PqSearch* search = a.search + (size_t)blockIdx.x * ns;
+    const PqLds lds = pq_lds_setup(a, smem, search, ns, n_hist, tid);
+    if (tid == 0) s_dark = 0u;
+    __syncthreads();
+
+    const unsigned long long* keys = kq.keys + (size_t)blockIdx.x * a.n;
+    const unsigned int mask = (1u << a.bits) - 1u;
+    const long long s0 = (long long)blockIdx.y * a.chunk, s1 = min(a.n, s0 + a.chunk);
+    unsigned int dark = 0u;   // of this wave's samples (wave-uniform)
+    for (long long sb = s0; sb < s1; sb += kPqThreads) {
+        const long long s = sb + tid;
+        if (s >= s1) continue;
+        const unsigned long long key = keys[s];
+        if (a.mode == 0) dark += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(key == kKeyPlusZero));
+        pq_consume(a, lds, search, ns, 0, pq_value(key), lane, mask);   // (a NaN is dropped there)
+    }
+    if (a.mode == 0 && lane == 0) atomicAdd(&s_dark, dark);
+    __syncthreads();
+    pq_merge(a, lds, search, ns, n_hist, tid);
+    if (a.mode == 0 && tid == 0) atomicAdd(&kq.n_dark[a.ep0 + blockIdx.x], (unsigned long long)s_dark);
+}
+
+struct LqPeak {
+    const unsigned long long* keys;   // [tile time][n]
+    long long n;
+    int ep0, n_ep;
+    double* best;                     // [n] largest non-NaN L so far (meaningless while at is -1)
+    int* at;                          // [n] the first epoch it was attained at, -1: none yet
+};
+
+__global__ __launch_bounds__(256) void k_lq_peak(const LqPeak a) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= a.n) return;
+    double best = a.best[s];
+    int at = a.at[s];
+    for (int i = 0; i < a.n_ep; ++i) {
+        const double v = pq_value(a.keys[(size_t)i * a.n + s]);
+        if (v == v && (at < 0 || v > best)) {   // (as values, not keys: -0 does not lose to a later +0, np.nanargmax)
+            best = v;
+            at = a.ep0 + i;
+        }
+    }
+    a.best[s] = best;
+    a.at[s] = at;
+}
+
 struct PqPick {
     const unsigned int* hist;
     PqSearch* search;
@@ -582,10 +648,13 @@ int hist_bits(long long n_hist, int max_bits) {
 
 // What the two forms do differently on the host: the launch that prepares the samples and the pass launch.
 struct PqForm {
-    int nf;                // series per time: the filters, or T / R_bb / L_bol
+    int nf;                // series per time: the filters, T / R_bb / L_bol, or L
     size_t sample_bytes;   // device memory per sample ...
     size_t time_bytes;     // ... and per time of the whole grid, beyond what every form needs
+    size_t tile_bytes = 0; // ... and per time of a TILE, beyond the searches' (the luminosity form's stored keys)
     size_t lds_head;       // dynamic LDS of a pass in front of the searches' words and the histograms
+    bool coef = true;      // the samples' walker_coefficients are wanted ([kNCoef][n], part of sample_bytes)
+    int tile = 0;          // times per tile, set by quantile_run in front of prepare
     virtual lcf_status prepare(PqBuf& mem, PqArgs& a, double* d_coef) = 0;   // ... and whatever else the passes read
     virtual lcf_status pass(const PqArgs& a, int n_ep, size_t lds) = 0;
     virtual ~PqForm() {}
@@ -643,6 +712,55 @@ struct ThermalForm : PqForm {
     }
 };
 
+// Every (sample, time) value is evaluated once per tile, in front of the tile's first pass; the passes read the keys.
+struct LuminosityForm : PqForm {
+    const DevProblem& dp;
+    const PredictSamples& in;
+    const bool peak;
+    int n_cus = 1;
+    unsigned long long* keys = nullptr;
+    KqArgs kq{};
+    LqPeak pk{};
+    LuminosityForm(const DevProblem& d, const PredictSamples& s, bool want_peak, int cus)
+        : dp(d), in(s), peak(want_peak), n_cus(cus) {
+        nf = 1;
+        sample_bytes = want_peak ? sizeof(double) + sizeof(int) : 0;   // the largest L so far and where
+        time_bytes = sizeof(unsigned long long);                      // the dark counter
+        tile_bytes = (size_t)s.n * sizeof(unsigned long long);         // the keys
+        lds_head = 0;
+        coef = false;
+    }
+    lcf_status prepare(PqBuf& mem, PqArgs& a, double*) override {
+        lcf_status st;
+        if ((st = mem.alloc(&keys, (size_t)tile * a.n)) || (st = mem.alloc(&kq.n_dark, (size_t)dp.n_points))) return st;
+        kq.keys = keys;
+        LCF_HIP(hipMemset(kq.n_dark, 0, (size_t)dp.n_points * sizeof(unsigned long long)));
+        if (peak) {
+            if ((st = mem.alloc(&pk.best, (size_t)a.n)) || (st = mem.alloc(&pk.at, (size_t)a.n))) return st;
+            LCF_HIP(hipMemset(pk.best, 0, (size_t)a.n * sizeof(double)));
+            LCF_HIP(hipMemset(pk.at, 0xff, (size_t)a.n * sizeof(int)));   // -1
+            pk.keys = keys;
+            pk.n = a.n;
+        }
+        return LCF_OK;
+    }
+    lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
+        if (a.mode == 0) {   // the tile's first pass: its keys, then the peaks so far (all on the null stream, in order)
+            if (lcf_status st = central_keys_launch(dp, in, a.ep0, n_ep, keys, n_cus)) return st;
+            if (peak) {
+                pk.ep0 = a.ep0;
+                pk.n_ep = n_ep;
+                hipLaunchKernelGGL(k_lq_peak, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, 0, pk);
+                LCF_HIP(hipGetLastError());
+            }
+        }
+        const unsigned chunks = (unsigned)((a.n + a.chunk - 1) / a.chunk);
+        hipLaunchKernelGGL(k_kq_pass, dim3((unsigned)n_ep, chunks), dim3(kPqThreads), lds, 0, a, kq);
+        LCF_HIP(hipGetLastError());
+        return LCF_OK;
+    }
+};
+
 // The searches of every point (time x series of `form`), the times in tiles that fit the workspace.  orig_host
 // [n_ep_all][nf]: where the point's results go, -1 = no such point.  out[n_q][n_points], n_valid[n_points] (host).
 lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_points, const PredictSamples& in,
@@ -656,7 +774,7 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
     const size_t fixed = (size_t)in.n * form.sample_bytes + (size_t)n_points * (n_q + 1) * 8 +
                          (size_t)n_ep_all * (nf * 4 + form.time_bytes) + 4096;
     const size_t hist_ep = std::max((size_t)nf << bits0, (size_t)ns << bits1) * 4;
-    const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8);
+    const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8) + form.tile_bytes;
     if (workspace_bytes < 0 || (size_t)workspace_bytes < fixed + per_ep)
         return fail(LCF_ERR_INVALID_ARGUMENT, "workspace_bytes too small: this call needs at least " +
                                                   std::to_string(fixed + per_ep) + " bytes");
@@ -669,7 +787,8 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
     PqSearch* d_search;
     unsigned long long* d_buf;
     lcf_status st;
-    if ((st = mem.alloc(&d_coef, (size_t)in.n * kNCoef)) || (st = mem.alloc(&d_q, n_q)) ||
+    form.tile = tile;
+    if ((st = mem.alloc(&d_coef, form.coef ? (size_t)in.n * kNCoef : 0)) || (st = mem.alloc(&d_q, n_q)) ||
         (st = mem.alloc(&d_out, (size_t)n_points * n_q)) || (st = mem.alloc(&d_nv, n_points)) ||
         (st = mem.alloc(&d_orig, (size_t)n_ep_all * nf)) || (st = mem.alloc(&d_hist, (size_t)tile * hist_ep / 4)) ||
         (st = mem.alloc(&d_active, 1)) || (st = mem.alloc(&d_search, (size_t)tile * ns)) ||
@@ -787,6 +906,31 @@ lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const Predi
     for (int ep = 0; ep < nt; ++ep) {
         n_cold[time_orig[ep]] = (int64_t)cnt[ep];
         n_inside[time_orig[ep]] = (int64_t)cnt[nt + ep];
+    }
+    return LCF_OK;
+}
+
+lcf_status predict_luminosity_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const double* q,
+                                  int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
+                                  double* L_peak, int32_t* i_peak) {
+    if (n_q > kPqMaxSearch) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles of one call must not exceed 512");
+    const int nt = dp.n_points;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 64;
+    std::vector<int32_t> orig(nt);   // one series per epoch, in the engine's own order
+    for (int ep = 0; ep < nt; ++ep) orig[ep] = ep;
+    LuminosityForm form(dp, in, L_peak != nullptr, cus);
+    PqBuf mem;
+    if (lcf_status st = quantile_run(device, form, nt, nt, in, orig.data(), 0, q, n_q, workspace_bytes, mem, out, n_valid))
+        return st;
+    std::vector<unsigned long long> dark(nt);
+    LCF_HIP(hipMemcpy(dark.data(), form.kq.n_dark, (size_t)nt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int ep = 0; ep < nt; ++ep) n_dark[ep] = (int64_t)dark[ep];
+    if (L_peak) {
+        LCF_HIP(hipMemcpy(L_peak, form.pk.best, (size_t)in.n * sizeof(double), hipMemcpyDeviceToHost));
+        LCF_HIP(hipMemcpy(i_peak, form.pk.at, (size_t)in.n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t s = 0; s < in.n; ++s)
+            if (i_peak[s] < 0) L_peak[s] = std::nan("");
     }
     return LCF_OK;
 }

@@ -150,6 +150,8 @@ SIGNATURES = [
     ('lcf_sampler_predict_thermal', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double,
                                               C.c_int64, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                               C.POINTER(C.c_int64)]),
+    ('lcf_predict_luminosity', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_int64, _dp,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _ip]),
     ('lcf_chain_range', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]),
     ('lcf_chain_hist', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.c_int32,
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -946,6 +948,45 @@ def predict_thermal(grid_engine, samples, percentiles, T_floor=8.12, workspace_b
             raise ValueError('samples must have shape (n, n_columns)')
         _check(lib.lcf_predict_thermal(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
     return out, n_valid, n_cold, n_inside
+
+
+def luminosity_workspace(n_samples, n_times, n_q, tile=1, peak=True):
+    """Device memory [bytes] beyond the samples that :func:`predict_luminosity` needs to work through ``tile`` times at
+    once -- the least ``workspace_bytes`` for that tile (DESIGN.md, "Luminosity bands and peaks")::
+
+        fixed    = (12 if peak else 0) n_samples + 8 (n_q + 1) n_times + 12 n_times + 4096
+        per time = 8 n_samples + n_q (56 + 8 * 2048) + 4 max(2048, n_q 2^b)
+
+    with ``b`` the largest of 4 ... 11 for which ``n_q 2^b`` four-byte counters fit 48 KiB of LDS."""
+    b = 4
+    while b < 11 and (n_q << (b + 1)) * 4 <= 48 * 1024:
+        b += 1
+    fixed = (12 if peak else 0) * n_samples + 8 * (n_q + 1) * n_times + 12 * n_times + 4096
+    return fixed + tile * (8 * n_samples + n_q * (56 + 8 * 2048) + 4 * max(2048, n_q << b))
+
+
+def predict_luminosity(grid_engine, samples, percentiles, workspace_bytes=None, peak=True):
+    """``lcf_predict_luminosity``: percentiles over all samples of ``L(t)`` of a central-engine model on the epochs of
+    ``grid_engine`` (an evaluation engine of ``Arnett`` / ``Magnetar``), the valid and dark counts per epoch and, with
+    ``peak``, every sample's largest ``L`` and the first epoch it is attained at.  ``samples``: a host array (n, ld);
+    at most ``PREDICT_MAX_SEARCHES`` percentiles.  Every value is evaluated once and kept as a key: see
+    :func:`luminosity_workspace` for the memory.  Returns ``(quantiles[n_q, n_t], n_valid[n_t], n_dark[n_t], L_peak[n]
+    or None, i_peak[n] or None)``."""
+    lib = load_library()
+    q = _f64(percentiles)
+    P = _f64(samples)
+    if P.ndim != 2:
+        raise ValueError('samples must have shape (n, n_columns)')
+    n_t = grid_engine.npoints
+    out = np.empty((len(q), n_t))
+    n_valid, n_dark = np.empty(n_t, dtype=np.int64), np.empty(n_t, dtype=np.int64)
+    L_peak = np.empty(P.shape[0]) if peak else None
+    i_peak = np.empty(P.shape[0], dtype=np.int32) if peak else None
+    ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    _check(lib.lcf_predict_luminosity(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], _ptr(q), len(q), ws, _ptr(out),
+                                      _i64p(n_valid), _i64p(n_dark), _ptr(L_peak) if peak else None,
+                                      _ptr(i_peak, _ip) if peak else None))
+    return out, n_valid, n_dark, L_peak, i_peak
 
 
 #: limits of the corner entry points (include/lcf.h)

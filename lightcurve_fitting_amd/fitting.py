@@ -213,11 +213,8 @@ def quantile_lerp(a, b, gamma):
     return np.where(gamma == 0., a, out)
 
 
-def predictive_grid(lc, t=None, tmin=None, tmax=None, num=1000, xscale='linear', filters_to_model=None):
-    """The ``filters x times`` grid of ``lightcurve_model_plot`` (fitting.py:340-348): ``t`` if given, else ``num``
-    points from ``tmin`` to ``tmax`` (default: the range of ``lc['MJD']``), equally spaced (``xscale='linear'``) or
-    geometrically (``'log'``); the filters of ``filters_to_model``, else the distinct filters of ``lc``, sorted.
-    Returns ``(times, filters)``."""
+def _predictive_times(lc, t, tmin, tmax, num, xscale):
+    """The times of :func:`predictive_grid`."""
     if t is not None:
         times = np.array(t, dtype=np.float64).ravel()
     else:
@@ -230,6 +227,15 @@ def predictive_grid(lc, t=None, tmin=None, tmax=None, num=1000, xscale='linear',
         times = np.geomspace(tmin, tmax, int(num)) if xscale == 'log' else np.linspace(tmin, tmax, int(num))
     if len(times) == 0 or not np.all(np.isfinite(times)):
         raise ValueError('the grid needs at least one time, all finite')
+    return times
+
+
+def predictive_grid(lc, t=None, tmin=None, tmax=None, num=1000, xscale='linear', filters_to_model=None):
+    """The ``filters x times`` grid of ``lightcurve_model_plot`` (fitting.py:340-348): ``t`` if given, else ``num``
+    points from ``tmin`` to ``tmax`` (default: the range of ``lc['MJD']``), equally spaced (``xscale='linear'``) or
+    geometrically (``'log'``); the filters of ``filters_to_model``, else the distinct filters of ``lc``, sorted.
+    Returns ``(times, filters)``."""
+    times = _predictive_times(lc, t, tmin, tmax, num, xscale)
     if filters_to_model is None:
         filters = sorted(set(as_filter(f) for f in _column(lc, 'filter')))
     else:
@@ -296,8 +302,8 @@ def _refuse_custom(model, what):
     if isinstance(model, BaseCentralEngine):
         from .engine import LcfError
         raise LcfError(5, f'{what} is compiled per photometric model and does not take a central-engine model (Arnett, '
-                          'Magnetar); its fit (the tempered route, TemperedSampler) gives the chain, and model(t, *p) '
-                          'evaluates any of its rows')
+                          'Magnetar); its fit (the tempered route, TemperedSampler) gives the chain, model(t, *p) '
+                          'evaluates any of its rows, and luminosity_predictive gives the bands of L(t)')
 
 
 def _model_samples(model, samples, discard, thin, use_sigma):
@@ -438,6 +444,99 @@ def thermal_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=No
     _, n_valid, n_cold, n_inside = parts[0]
     return ThermalPredictive(times, q, quantiles[0], quantiles[1], quantiles[2], n_valid[:, where], n_cold[where],
                              n_inside[where], n_samples)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# luminosity bands and peaks (the central-engine models: does the fit go through the data, L_peak, t_rise)
+# ---------------------------------------------------------------------------------------------------------------
+class LuminosityPredictive:
+    """Result of :func:`luminosity_predictive`: ``t`` (nt,), ``percentiles`` (nq,), ``luminosity`` [W] (nq, nt);
+    ``n_valid`` (nt,) -- the samples whose ``L`` at the time is not NaN; ``n_dark`` (nt,) -- those whose ``L`` is exactly
+    ``+0.0``: not exploded yet; ``n_samples``.  With ``peak=True``, per sample over the distinct times in ascending
+    order: ``peak_index`` (int32, into ``np.unique(t)``; -1: NaN everywhere), ``L_peak`` [W], ``t_peak`` [MJD],
+    ``t_rise`` [d, rest frame], and the counts ``n_peak_first`` / ``n_peak_last`` of samples that peak at an edge of
+    the grid (their true peak may lie outside it); else all ``None``."""
+    __slots__ = ('t', 'percentiles', 'luminosity', 'n_valid', 'n_dark', 'n_samples', 'peak_index', 'L_peak', 't_peak',
+                 't_rise', 'n_peak_first', 'n_peak_last')
+
+    def __init__(self, t, percentiles, luminosity, n_valid, n_dark, n_samples, peak_index=None, L_peak=None,
+                 t_peak=None, t_rise=None, n_peak_first=None, n_peak_last=None):
+        self.t, self.percentiles, self.luminosity = t, percentiles, luminosity
+        self.n_valid, self.n_dark, self.n_samples = n_valid, n_dark, n_samples
+        self.peak_index, self.L_peak, self.t_peak, self.t_rise = peak_index, L_peak, t_peak, t_rise
+        self.n_peak_first, self.n_peak_last = n_peak_first, n_peak_last
+
+    @property
+    def frac_dark(self):
+        """Fraction of the samples with a value that have not exploded yet, per time (NaN where none has one)."""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self.n_dark / self.n_valid
+
+    def peak_summary(self, percentiles=None):
+        """``{'L_peak': ..., 't_peak': ..., 't_rise': ...}``: ``np.nanpercentile`` of the per-sample arrays at
+        ``percentiles`` (default: those of the bands)."""
+        if self.peak_index is None:
+            raise ValueError('the peaks were not computed: call luminosity_predictive with peak=True')
+        q = self.percentiles if percentiles is None else _percentile_array(percentiles)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)   # (every sample NaN: NaN)
+            return {name: np.nanpercentile(getattr(self, name), q) for name in ('L_peak', 't_peak', 't_rise')}
+
+    def __repr__(self):
+        return (f'<LuminosityPredictive: {len(self.percentiles)} percentiles x {len(self.t)} times over '
+                f'{self.n_samples} samples' + ('' if self.peak_index is None else ', with peaks') + '>')
+
+
+def luminosity_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=None, tmin=None, tmax=None, num=1000,
+                          xscale='linear', discard=0, thin=1, use_sigma=False, peak=True, workspace_bytes=None):
+    """Percentile bands of the bolometric light curve ``L(t)`` [W] of a central-engine model (``Arnett``,
+    ``Magnetar``) over ALL samples of a chain, and every sample's peak: what :func:`posterior_predictive` is for the
+    photometric models, plus the two numbers quoted from such a fit.
+
+    ``samples``: a host array ``(n_samples, n_columns)`` (``discard`` / ``thin`` do not apply), or the
+    :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` that ``lightcurve_mcmc`` returned -- any object with its
+    ``get_chain`` --: rows ``discard::thin`` of its cold rung, uploaded.  ``use_sigma``: the last column is the scatter
+    and does not enter the model.  The time grid ``t`` ... ``xscale`` as in :func:`predictive_grid`, without filters.
+
+    ``luminosity`` is ``np.nanpercentile(L, percentiles, axis=samples)`` of ``L[s, t] = model(t, *p_s)``, bit for bit
+    those values, NaN where no sample has one.  With ``peak=True`` the largest non-NaN ``L`` of every sample over the
+    distinct grid times, the first time it is attained (``np.nanargmax``), and ``t_rise = (t_peak - t_0) / (1 + z)``.
+    Every (sample, time) value is evaluated once on the device and kept there as an 8-byte key while the percentiles of
+    its time are searched; the times are worked through in tiles that keep device memory beyond the samples below
+    ``workspace_bytes`` (default 1 GiB; ``engine.luminosity_workspace``).  Results are bitwise reproducible and do not
+    depend on ``workspace_bytes``.  Returns a :class:`LuminosityPredictive`."""
+    from . import engine as _eng
+    if not isinstance(model, BaseCentralEngine):
+        raise _eng.LcfError(5, 'luminosity_predictive takes a central-engine model (Arnett, Magnetar); the bands of a '
+                               'photometric model are posterior_predictive and thermal_predictive')
+    q = _percentile_array(percentiles)
+    if not isinstance(samples, np.ndarray) and hasattr(samples, 'get_chain'):
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        samples = samples.get_chain(discard=discard, thin=thin, flat=True)
+        if len(samples) == 0:
+            raise ValueError(f'discard={discard} leaves no steps of the stored chain')
+        discard, thin = 0, 1
+    _, P, n_samples = _model_samples(model, samples, discard, thin, use_sigma)
+    times = _predictive_times(lc, t, tmin, tmax, num, xscale)
+    distinct, where = np.unique(times, return_inverse=True)     # ascending: "first" below is the earliest time
+
+    grid_engine = model._grid_engine(distinct)
+    per_call = _eng.PREDICT_MAX_SEARCHES
+    parts = [_eng.predict_luminosity(grid_engine, P, q[k:k + per_call], workspace_bytes, peak=bool(peak) and k == 0)
+             for k in range(0, len(q), per_call)]
+    bands = np.concatenate([part[0] for part in parts])[:, where]
+    _, n_valid, n_dark, L_peak, i_peak = parts[0]
+    res = LuminosityPredictive(times, q, bands, n_valid[where], n_dark[where], n_samples)
+    if peak:
+        none = i_peak < 0
+        res.peak_index, res.L_peak = i_peak, L_peak
+        res.t_peak = np.where(none, np.nan, distinct[np.maximum(i_peak, 0)])
+        res.t_rise = (res.t_peak - P[:, model.n_model_params - 1]) / (1. + model.z)
+        res.n_peak_first = int(np.sum(i_peak == 0))
+        res.n_peak_last = int(np.sum(i_peak == len(distinct) - 1))
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------

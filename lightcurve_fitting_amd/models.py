@@ -623,8 +623,9 @@ class BaseCentralEngine(Model):
     leaves NaN where a fit failed: drop those rows).  ``model(t, *p)`` evaluates ``L``; ``log_likelihood``,
     ``make_log_posterior`` and ``lightcurve_mcmc`` work as for every model, the fit running through
     :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` (one rung at ``beta = 1`` unless a ladder is asked for).
-    The resident sampler, ``posterior_predictive``, ``thermal_predictive`` and ``temperature_radius`` are compiled per
-    photometric model and raise ``LcfError`` here."""
+    :func:`~lightcurve_fitting_amd.fitting.luminosity_predictive` gives the percentile bands of ``L(t)`` over a whole
+    chain, and every sample's peak luminosity and rise time.  The resident sampler, ``posterior_predictive``,
+    ``thermal_predictive`` and ``temperature_radius`` are compiled per photometric model and raise ``LcfError`` here."""
     #: parameters of the source, in front of tau_m
     _source_names = []
     _source_units = []
@@ -686,6 +687,15 @@ class BaseCentralEngine(Model):
         del self._bound[self.max_bound_engines:]
         return eng
 
+    def _grid_engine(self, t_in):
+        """The evaluation engine on the times ``t_in`` (1-D float64): dummy data, no sigma, no priors."""
+        key = ('eval', t_in.tobytes())
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = self.make_engine(t_in, np.zeros(len(t_in)), np.ones(len(t_in)))
+            self._engines = {key: eng}  # one evaluation grid at a time
+        return eng
+
     def evaluate(self, t_in, *params):
         """``L(t)`` [W] at the times ``t_in`` (MJD).  Scalar parameters -> (ntimes,); array parameters of length n ->
         (ntimes, n)."""
@@ -694,11 +704,7 @@ class BaseCentralEngine(Model):
         t_in = np.atleast_1d(np.asarray(t_in, dtype=np.float64)).ravel()
         cols = np.broadcast_arrays(*[np.asarray(x, dtype=np.float64) for x in params])
         scalar = cols[0].ndim == 0
-        key = ('eval', t_in.tobytes())
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = self.make_engine(t_in, np.zeros(len(t_in)), np.ones(len(t_in)))
-            self._engines = {key: eng}  # one evaluation grid at a time
+        eng = self._grid_engine(t_in)
         y = eng.evaluate(np.column_stack([np.atleast_1d(c).ravel() for c in cols]))  # (n, ntimes)
         return y[0] if scalar else y.T
 
