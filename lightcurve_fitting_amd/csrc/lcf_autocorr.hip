@@ -151,20 +151,6 @@ __global__ __launch_bounds__(kTile) void k_acf_reduce(const AcfSeg* __restrict__
     f[(long long)blockIdx.y * width + (tau - lo)] = sum / (double)sg.n_w;
 }
 
-struct DevBuf {
-    std::vector<void*> p;
-    ~DevBuf() {
-        for (void* q : p) hipFree(q);
-    }
-    template <class T>
-    lcf_status alloc(T** d, size_t n) {
-        *d = nullptr;
-        LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
-        p.push_back(*d);
-        return LCF_OK;
-    }
-};
-
 // A device buffer that grows with the slab width (reallocated, contents not kept).
 struct Grow {
     double* p = nullptr;
@@ -213,13 +199,11 @@ struct Window {
     }
 };
 
-}  // namespace
-
-namespace lcf {
-
-lcf_status autocorr_run(int32_t device, const AutocorrSeries* in, int32_t n, double c, double* tau,
-                        int64_t* window) {
-    LCF_HIP(hipSetDevice(device));
+// One series per walker and parameter of every view's kept steps, where they lie in device memory.  tau / window
+// receive n_dim entries per view, in order.
+lcf_status autocorr_run(int32_t device, const ChainView* in, int32_t n, int64_t discard, int64_t thin, double c,
+                        double* tau, int64_t* window) {
+    if (lcf_status st = use_device(device)) return st;
     std::vector<AcfSeg> segs(n);
     std::vector<int> tile_seg;   // segment of every tile of 64 series
     std::vector<Window> win;     // one per (segment, parameter) row
@@ -227,11 +211,12 @@ lcf_status autocorr_run(int32_t device, const AutocorrSeries* in, int32_t n, dou
     long long max_t = 0;
     for (int g = 0; g < n; ++g) {
         AcfSeg& a = segs[g];
-        a.base = in[g].chain;
-        a.stride = in[g].row_stride;
-        a.n_t = in[g].n_t;
-        a.n_w = in[g].n_w;
-        a.n_d = in[g].n_d;
+        const KeptSteps k = kept_steps(in[g], discard, thin);
+        a.base = k.base;
+        a.stride = k.stride;
+        a.n_t = k.n;
+        a.n_w = (int)in[g].n_w;
+        a.n_d = in[g].n_dim;
         a.n_ser = a.n_w * a.n_d;
         a.ser0 = ser;
         a.row0 = rows;
@@ -316,7 +301,7 @@ lcf_status autocorr_run(int32_t device, const AutocorrSeries* in, int32_t n, dou
     return LCF_OK;
 }
 
-}  // namespace lcf
+}  // namespace
 
 extern "C" {
 
@@ -326,18 +311,20 @@ lcf_status lcf_autocorr_time(int32_t device, const double* chain, int64_t n_t, i
     if (n_t < 1 || n_w < 1 || n_d < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need n_t, n_w, n_d >= 1");
     if ((int64_t)n_w * n_d > (1 << 30)) return fail(LCF_ERR_INVALID_ARGUMENT, "n_w * n_d too large");
     if (!std::isfinite(c)) return fail(LCF_ERR_INVALID_ARGUMENT, "c must be finite");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
-    const size_t elems = (size_t)n_t * n_w * n_d;
-    DevBuf b;
-    double* dchain;
-    if (lcf_status st = b.alloc(&dchain, elems)) return st;
-    LCF_HIP(hipMemcpy(dchain, chain, elems * sizeof(double), hipMemcpyHostToDevice));
-    const AutocorrSeries s{dchain, n_t, (int64_t)n_w * n_d, n_w, n_d};
-    return autocorr_run(device, &s, 1, c, tau, window);
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = upload_chain(device, ChainView{chain, nullptr, n_t, n_w, n_d, n_d}, mem, &in)) return st;
+    return autocorr_run(device, &in, 1, 0, 1, c, tau, window);
+}
+
+lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double c,
+                                      double* tau, int64_t* window) {
+    if (!tau || !window) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (!std::isfinite(c)) return fail(LCF_ERR_INVALID_ARGUMENT, "c must be finite");
+    std::vector<ChainView> in;
+    int32_t device = 0;
+    if (lcf_status st = stored_chains(s, n, discard, thin, &in, &device)) return st;
+    return autocorr_run(device, in.data(), n, discard, thin, c, tau, window);
 }
 
 }  // extern "C"

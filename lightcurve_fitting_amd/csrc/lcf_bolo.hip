@@ -240,30 +240,6 @@ __global__ __launch_bounds__(kLumBlock) void k_bb_lum(long long n, const double2
     }
 }
 
-struct DevBuf {
-    std::vector<void*> p;
-    ~DevBuf() {
-        for (void* q : p) hipFree(q);
-    }
-};
-
-template <class T>
-lcf_status dev_alloc(DevBuf& b, T** d, size_t n) {
-    *d = nullptr;
-    LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
-    b.p.push_back(*d);
-    return LCF_OK;
-}
-
-lcf_status check_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
-    return LCF_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -291,15 +267,15 @@ lcf_status lcf_bb_lstsq(int32_t device, int64_t n_epochs, const int32_t* ep_off,
             box[6 * e + 2 + d] = l;
             box[6 * e + 4 + d] = h;
         }
-    lcf_status st = check_device(device);
+    lcf_status st = use_device(device);
     if (st != LCF_OK) return st;
     if (n_epochs == 0) return LCF_OK;
     DevBuf b;
     int *doff, *dst;
     double *dfreq, *dlum, *dbox, *dout;
-    if ((st = dev_alloc(b, &doff, n_epochs + 1)) || (st = dev_alloc(b, &dfreq, n_pts)) || (st = dev_alloc(b, &dlum, n_pts)) ||
-        (st = dev_alloc(b, &dbox, 6 * n_epochs)) || (st = dev_alloc(b, &dout, 8 * n_epochs)) ||
-        (st = dev_alloc(b, &dst, n_epochs)))
+    if ((st = b.alloc(&doff, n_epochs + 1)) || (st = b.alloc(&dfreq, n_pts)) || (st = b.alloc(&dlum, n_pts)) ||
+        (st = b.alloc(&dbox, 6 * n_epochs)) || (st = b.alloc(&dout, 8 * n_epochs)) ||
+        (st = b.alloc(&dst, n_epochs)))
         return st;
     LCF_HIP(hipMemcpy(doff, ep_off, (n_epochs + 1) * sizeof(int), hipMemcpyHostToDevice));
     if (n_pts) {
@@ -322,14 +298,14 @@ lcf_status lcf_bb_luminosity(int32_t device, int64_t n, const double* T, const d
     if (!(z > -1.) || !std::isfinite(z)) return fail(LCF_ERR_INVALID_ARGUMENT, "z must be finite and > -1");
     if (!std::isfinite(freq0) || n_grid < 0) return fail(LCF_ERR_INVALID_ARGUMENT, "need a finite freq0 and n_grid >= 0");
     if (!(cutoff_freq > 0.)) return fail(LCF_ERR_INVALID_ARGUMENT, "cutoff_freq must be > 0");
-    lcf_status st = check_device(device);
+    lcf_status st = use_device(device);
     if (st != LCF_OK) return st;
     if (n == 0) return LCF_OK;
     std::vector<double2> tr(n);
     for (int64_t k = 0; k < n; ++k) tr[k] = make_double2(T[k], R[k]);
     DevBuf b;
     double2 *din, *dout;
-    if ((st = dev_alloc(b, &din, n)) || (st = dev_alloc(b, &dout, n))) return st;
+    if ((st = b.alloc(&din, n)) || (st = b.alloc(&dout, n))) return st;
     LCF_HIP(hipMemcpy(din, tr.data(), n * sizeof(double2), hipMemcpyHostToDevice));
     const unsigned grid = (unsigned)std::min<int64_t>((n + kLumBlock - 1) / kLumBlock, 256 * 32);
     hipLaunchKernelGGL(k_bb_lum, dim3(grid), dim3(kLumBlock), 0, 0, (long long)n, din, 1. + z, freq0, (int)n_grid,

@@ -223,12 +223,14 @@ lcf_status central_launch(lcf_engine* e, int mode, int w_lo, int n, const double
     return LCF_OK;
 }
 
-lcf_status central_keys_launch(const DevProblem& dp, const PredictSamples& in, int ep0, int n_ep,
+lcf_status central_keys_launch(const DevProblem& dp, const ChainView& in, int64_t discard, int64_t thin, int ep0, int n_ep,
                                unsigned long long* keys, int n_cus) {
-    if (in.n <= 0 || n_ep <= 0) return LCF_OK;
+    const KeptSteps k = kept_steps(in, discard, thin);
+    if (k.samples <= 0 || n_ep <= 0) return LCF_OK;
     // eight workgroups of four waves per CU is what the registers allow resident; never more waves than samples
-    const long long blocks = std::min<long long>((long long)std::max(n_cus, 1) * 8, (in.n + kBlock / 64 - 1) / (kBlock / 64));
-    const LqEval a{in.base, in.n, in.n_w, in.step_stride, in.ld, ep0, n_ep, keys};
+    const long long blocks =
+        std::min<long long>((long long)std::max(n_cus, 1) * 8, (k.samples + kBlock / 64 - 1) / (kBlock / 64));
+    const LqEval a{k.base, k.samples, in.n_w, k.step_stride, in.ld, ep0, n_ep, keys};
     hipLaunchKernelGGL(k_lq_eval, dim3((unsigned)blocks), dim3(kBlock), 0, 0, dp, a);
     LCF_HIP(hipGetLastError());
     return LCF_OK;
@@ -252,11 +254,7 @@ lcf_status central_engine_create(const lcf_problem* pr, int32_t device, lcf_engi
         for (int i = 0; i < n_dim; ++i)
             if (pr->priors[i].kind < 0 || pr->priors[i].kind > 2) return fail(LCF_ERR_INVALID_ARGUMENT, "bad prior kind");
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
+    if (lcf_status st = use_device(device)) return st;
 
     auto* e = new lcf_engine();
     e->device = device;

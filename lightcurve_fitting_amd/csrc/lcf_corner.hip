@@ -159,32 +159,13 @@ __global__ __launch_bounds__(kCornerThreads) void k_corner_hist(const CornerSeg*
     }
 }
 
-struct CornerBuf {
-    std::vector<void*> p;
-    ~CornerBuf() {
-        for (void* q : p) hipFree(q);
-    }
-    template <class T>
-    lcf_status alloc(T** d, size_t n) {
-        *d = nullptr;
-        LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
-        p.push_back(*d);
-        return LCF_OK;
-    }
-    template <class T>
-    lcf_status put(T** d, const T* h, size_t n) {
-        if (lcf_status st = alloc(d, n)) return st;
-        if (n) LCF_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
-        return LCF_OK;
-    }
-};
-
-lcf_status check_samples(const CornerSamples* in, int32_t n) {
+// What needs no device: the limits of both passes.
+lcf_status check_samples(const ChainView* in, int32_t n) {
     if (!in || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     for (int32_t g = 0; g < n; ++g) {
         if (in[g].n_dim < 1 || in[g].n_dim > kMaxDim)
             return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= n_dim <= 16 columns");
-        if (!in[g].base || in[g].n < 1 || in[g].n_w < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
+        if (!in[g].chain || in[g].n_t < 1 || in[g].n_w < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
         if (in[g].ld < in[g].n_dim) return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than n_dim");
     }
     return LCF_OK;
@@ -197,15 +178,16 @@ long long corner_chunk(long long n, long long per_seg) {
     return std::min(std::max(chunk, unit), kMaxChunk);
 }
 
-// What both passes need of every entry.
-std::vector<CornerSeg> corner_segments(const CornerSamples* in, int32_t n) {
+// What both passes need of every entry: the walkers of its kept steps as samples.
+std::vector<CornerSeg> corner_segments(const ChainView* in, int32_t n, int64_t discard, int64_t thin) {
     std::vector<CornerSeg> segs(n, CornerSeg{});
     for (int32_t g = 0; g < n; ++g) {
+        const KeptSteps k = kept_steps(in[g], discard, thin);
         CornerSeg& a = segs[g];
-        a.base = in[g].base;
-        a.n = in[g].n;
+        a.base = k.base;
+        a.n = k.samples;
         a.n_w = in[g].n_w;
-        a.step_stride = in[g].step_stride;
+        a.step_stride = k.step_stride;
         if (a.n_w >= a.n || a.step_stride == a.n_w * in[g].ld) a.n_w = a.n;   // one block of rows
         a.ld = in[g].ld;
         a.n_dim = in[g].n_dim;
@@ -213,30 +195,21 @@ std::vector<CornerSeg> corner_segments(const CornerSamples* in, int32_t n) {
     return segs;
 }
 
-lcf_status device_cus(int32_t device, int* n_cu) {
-    LCF_HIP(hipSetDevice(device));
-    LCF_HIP(hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, device));
-    if (*n_cu < 1) *n_cu = 1;
-    return LCF_OK;
-}
-
-}  // namespace
-
-namespace lcf {
-
-lcf_status corner_range_run(int32_t device, const CornerSamples* in, int32_t n, double* lo, double* hi,
-                            int64_t* n_nan) {
+// Both runs: per entry of `in` the walkers of its kept steps, in device memory.  Inputs and outputs (host) hold the
+// entries' parts one after another, as lcf_samplers_chain_range / lcf_samplers_chain_hist describe them.
+lcf_status corner_range_run(int32_t device, const ChainView* in, int32_t n, int64_t discard, int64_t thin, double* lo,
+                            double* hi, int64_t* n_nan) {
     if (!lo || !hi || !n_nan) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = check_samples(in, n)) return st;
     int n_cu = 1;
-    if (lcf_status st = device_cus(device, &n_cu)) return st;
-    std::vector<CornerSeg> segs = corner_segments(in, n);
+    if (lcf_status st = use_device(device, &n_cu)) return st;
+    std::vector<CornerSeg> segs = corner_segments(in, n, discard, thin);
     size_t cols = 0;
     for (const CornerSeg& a : segs) cols += a.n_dim;
     // per column: minimum key, maximum key, NaN count
     std::vector<unsigned long long> res(3 * cols, 0ull);
     std::fill(res.begin(), res.begin() + cols, kNoKey);
-    CornerBuf mem;
+    DevBuf mem;
     unsigned long long* d_res;
     lcf_status st;
     if ((st = mem.put(&d_res, res.data(), res.size()))) return st;
@@ -269,8 +242,8 @@ lcf_status corner_range_run(int32_t device, const CornerSamples* in, int32_t n, 
     return LCF_OK;
 }
 
-lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, const double* shift, const double* edges,
-                           int32_t bins, int64_t* hist1d, int64_t* hist2d) {
+lcf_status corner_hist_run(int32_t device, const ChainView* in, int32_t n, int64_t discard, int64_t thin,
+                           const double* shift, const double* edges, int32_t bins, int64_t* hist1d, int64_t* hist2d) {
     if (!shift || !edges || !hist1d) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (bins < 1 || bins > kMaxBins) return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= bins <= 128");
     if (lcf_status st = check_samples(in, n)) return st;
@@ -289,14 +262,14 @@ lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, c
         if (!(e[0] < e[bins])) return fail(LCF_ERR_INVALID_ARGUMENT, "the first edge must be below the last");
     }
     int n_cu = 1;
-    if (lcf_status st = device_cus(device, &n_cu)) return st;
+    if (lcf_status st = use_device(device, &n_cu)) return st;
 
     // Pairs per group: what fits the LDS budget beside the columns' counters, but at least one pair (128 bins: 64 KiB
     // a pair; the launch is then granted more than the default).  LCF_CORNER_GROUP_PAIRS (tests): fewer.
     const size_t nb2 = (size_t)bins * bins;
     const char* env = std::getenv("LCF_CORNER_GROUP_PAIRS");
     const long long forced = env ? std::atoll(env) : 0;
-    std::vector<CornerSeg> segs = corner_segments(in, n);
+    std::vector<CornerSeg> segs = corner_segments(in, n, discard, thin);
     size_t lds_counters = 0;
     long long n_work = 0;
     for (int32_t g = 0; g < n; ++g) {
@@ -315,7 +288,7 @@ lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, c
     }
     if (n_work > (1LL << 30)) return fail(LCF_ERR_INVALID_ARGUMENT, "too many samples");
 
-    CornerBuf mem;
+    DevBuf mem;
     double *d_shift, *d_edges;
     unsigned long long *d_h1, *d_h2;
     lcf_status st;
@@ -357,27 +330,14 @@ lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, c
     return LCF_OK;
 }
 
-}  // namespace lcf
-
-namespace {
-
-// n host samples P[n][ld] on `device` for as long as `run` takes.
-template <class Run>
-lcf_status with_uploaded(int32_t device, const double* P, int64_t n, int32_t ld, int32_t n_dim, Run run) {
+// n host samples P[n][ld] as one step of n walkers, on `device` for as long as `mem` lives.
+lcf_status uploaded_samples(int32_t device, const double* P, int64_t n, int32_t ld, int32_t n_dim, DevBuf& mem,
+                            ChainView* in) {
     if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
     if (n_dim < 1 || n_dim > kMaxDim) return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= n_dim <= 16 columns");
     if (ld < n_dim) return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than n_dim");
     if (n > (1LL << 40) / ld) return fail(LCF_ERR_INVALID_ARGUMENT, "too many samples");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
-    CornerBuf mem;
-    double* dP;
-    if (lcf_status st = mem.put(&dP, P, (size_t)n * ld)) return st;
-    const CornerSamples in{dP, n, n, 0, ld, n_dim};
-    return run(in);
+    return upload_chain(device, ChainView{P, nullptr, 1, n, ld, n_dim}, mem, in);
 }
 
 }  // namespace
@@ -387,17 +347,37 @@ extern "C" {
 lcf_status lcf_chain_range(int32_t device, const double* P, int64_t n, int32_t ld, int32_t n_dim, double* lo,
                            double* hi, int64_t* n_nan) {
     if (!lo || !hi || !n_nan) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    return with_uploaded(device, P, n, ld, n_dim,
-                         [&](const CornerSamples& in) { return corner_range_run(device, &in, 1, lo, hi, n_nan); });
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(device, P, n, ld, n_dim, mem, &in)) return st;
+    return corner_range_run(device, &in, 1, 0, 1, lo, hi, n_nan);
+}
+
+lcf_status lcf_samplers_chain_range(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double* lo, double* hi,
+                                    int64_t* n_nan) {
+    if (!lo || !hi || !n_nan) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<ChainView> in;
+    int32_t device = 0;
+    if (lcf_status st = stored_chains(s, n, discard, thin, &in, &device)) return st;
+    return corner_range_run(device, in.data(), n, discard, thin, lo, hi, n_nan);
 }
 
 lcf_status lcf_chain_hist(int32_t device, const double* P, int64_t n, int32_t ld, int32_t n_dim, const double* shift,
                           const double* edges, int32_t bins, int64_t* hist1d, int64_t* hist2d) {
     if (!shift || !edges || !hist1d) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (bins < 1 || bins > kMaxBins) return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= bins <= 128");
-    return with_uploaded(device, P, n, ld, n_dim, [&](const CornerSamples& in) {
-        return corner_hist_run(device, &in, 1, shift, edges, bins, hist1d, hist2d);
-    });
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(device, P, n, ld, n_dim, mem, &in)) return st;
+    return corner_hist_run(device, &in, 1, 0, 1, shift, edges, bins, hist1d, hist2d);
+}
+
+lcf_status lcf_samplers_chain_hist(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, const double* shift,
+                                   const double* edges, int32_t bins, int64_t* hist1d, int64_t* hist2d) {
+    std::vector<ChainView> in;
+    int32_t device = 0;
+    if (lcf_status st = stored_chains(s, n, discard, thin, &in, &device)) return st;
+    return corner_hist_run(device, in.data(), n, discard, thin, shift, edges, bins, hist1d, hist2d);
 }
 
 }  // extern "C"

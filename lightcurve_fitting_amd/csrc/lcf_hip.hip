@@ -26,7 +26,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <dlfcn.h>
-#include <functional>
 #include <cstring>
 #include <mutex>
 #include <numeric>
@@ -2682,11 +2681,7 @@ lcf_status lcf_engine_create(const lcf_problem* pr, int32_t device, lcf_engine**
                 if (a[f] < -1 || a[f] >= n_dim) return fail(LCF_ERR_INVALID_ARGUMENT, "factor parameter index out of range");
     }
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
+    if (lcf_status st = use_device(device)) return st;
 
     auto* e = new lcf_engine();
     e->device = device;
@@ -4440,156 +4435,6 @@ lcf_status lcf_population_run(lcf_sampler** ss, int32_t n, int64_t first_step, i
     if (r == LCF_OK && repeat)
         r = population_run(ss, n, first_step, n_steps, split_mode, store_chain, elapsed_ms, false, &repeat);
     return r;
-}
-
-// What both predictive entry points check before the device is touched.
-static lcf_status predict_check(const lcf_engine* grid, int32_t component, const double* q, int32_t n_q,
-                                const double* out, const int64_t* n_valid) {
-    if (!grid || !q || !out || !n_valid) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = custom_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
-    if (lcf_status st = central_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
-    if (n_q < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one percentile");
-    for (int32_t j = 0; j < n_q; ++j)
-        if (!(q[j] >= 0. && q[j] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");
-    const bool companion = grid->dp.model >= kCompanion && grid->dp.model <= kCompanion3;
-    if (component != 0 && !(component == 1 && companion))
-        return fail(LCF_ERR_INVALID_ARGUMENT, "component: 0 = the model, 1 = the SiFTO term of a companion-shocking model");
-    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no points");
-    return LCF_OK;
-}
-
-// The grid engine's points as a (time, filter) table and the run itself.
-static lcf_status predict_impl(lcf_engine* grid, const PredictSamples& in, int32_t component, const double* q,
-                               int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
-    const DevProblem& dp = grid->dp;
-    const int N = dp.n_points, NF = dp.n_filters;
-    std::vector<int> filt(N), orig(N), epoch(N);
-    LCF_HIP(hipMemcpy(filt.data(), dp.pt_filt, N * sizeof(int), hipMemcpyDeviceToHost));
-    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
-    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<int32_t> table((size_t)dp.n_epochs * NF, -1);
-    for (int i = 0; i < N; ++i) {
-        int32_t& slot = table[(size_t)epoch[i] * NF + filt[i]];
-        if (slot >= 0) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine holds a (time, filter) pair twice");
-        slot = orig[i];
-    }
-    return predict_run(grid->device, dp, in, table.data(), component, q, n_q, workspace_bytes, out, n_valid);
-}
-
-// n host samples P[n][ld] on the grid engine's device for as long as `run` takes.
-static lcf_status with_uploaded_samples(lcf_engine* grid, const double* P, int64_t n, int32_t ld,
-                                        const std::function<lcf_status(const PredictSamples&)>& run) {
-    if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
-    if (ld < 1 || ld < grid->dp.n_par) return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than the model's parameter count");
-    if (n > (1LL << 40) / ld) return fail(LCF_ERR_INVALID_ARGUMENT, "too many samples");
-    LCF_HIP(hipSetDevice(grid->device));
-    double* dP = nullptr;
-    LCF_HIP(hipMalloc((void**)&dP, (size_t)n * ld * sizeof(double)));
-    lcf_status st = LCF_OK;
-    if (hipMemcpy(dP, P, (size_t)n * ld * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        st = fail(LCF_ERR_HIP, "copying the samples to the device failed");
-    if (!st) st = run(PredictSamples{dP, n, n, 0, ld});
-    hipFree(dP);
-    return st;
-}
-
-// Rows discard, discard + thin, ... of the sampler's last stored run as samples, where they lie.
-static lcf_status stored_samples(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, PredictSamples* in) {
-    if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
-    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
-    if (!s->ds.store_chain || s->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
-    if (discard >= s->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
-    if (s->e->device != grid->device) return fail(LCF_ERR_UNSUPPORTED, "sampler and grid engine are on different devices");
-    if (s->ds.n_dim < grid->dp.n_par)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "the chain has fewer columns than the model has parameters");
-    if (lcf_status st = settle(s)) return st;  // (the trailing commit writes the last chain row)
-    LCF_HIP(hipSetDevice(grid->device));
-    const DevSampler& ds = s->ds;
-    const int64_t row = (int64_t)ds.n_walkers * ds.n_dim, steps = (s->run_steps - discard + thin - 1) / thin;
-    *in = PredictSamples{ds.chain + discard * row, steps * ds.n_walkers, ds.n_walkers, thin * row, ds.n_dim};
-    return LCF_OK;
-}
-
-lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t component,
-                                 const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
-    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
-    return with_uploaded_samples(grid, P, n, ld, [&](const PredictSamples& in) {
-        return predict_impl(grid, in, component, q, n_q, workspace_bytes, out, n_valid);
-    });
-}
-
-lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin,
-                                         int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
-                                         double* out, int64_t* n_valid) {
-    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
-    PredictSamples in;
-    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
-    return predict_impl(grid, in, component, q, n_q, workspace_bytes, out, n_valid);
-}
-
-// What both thermal entry points check before the device is touched.
-static lcf_status thermal_check(const lcf_engine* grid, const double* q, int32_t n_q, const double* out,
-                                const int64_t* n_valid, const int64_t* n_cold, const int64_t* n_inside) {
-    if (!n_cold || !n_inside) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (lcf_status st = predict_check(grid, 0, q, n_q, out, n_valid)) return st;
-    if (grid->dp.model == kBlackbody)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "the blackbody model has no thermal evolution or validity window");
-    if (grid->dp.n_points != grid->dp.n_epochs)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine must hold one point per distinct time");
-    return LCF_OK;
-}
-
-// The grid engine's times in the caller's order and the run itself.
-static lcf_status thermal_impl(lcf_engine* grid, const PredictSamples& in, const double* q, int32_t n_q, double T_floor,
-                               int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_cold,
-                               int64_t* n_inside) {
-    const DevProblem& dp = grid->dp;
-    const int N = dp.n_points;
-    std::vector<int> orig(N), epoch(N);
-    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
-    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<int32_t> time_orig(N);
-    for (int i = 0; i < N; ++i) time_orig[epoch[i]] = orig[i];   // (N points on N distinct times: a bijection)
-    return predict_thermal_run(grid->device, dp, in, time_orig.data(), q, n_q, T_floor, workspace_bytes, out, n_valid,
-                               n_cold, n_inside);
-}
-
-lcf_status lcf_predict_thermal(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
-                               double T_floor, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_cold,
-                               int64_t* n_inside) {
-    if (lcf_status st = thermal_check(grid, q, n_q, out, n_valid, n_cold, n_inside)) return st;
-    return with_uploaded_samples(grid, P, n, ld, [&](const PredictSamples& in) {
-        return thermal_impl(grid, in, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
-    });
-}
-
-lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, const double* q,
-                                       int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
-                                       int64_t* n_valid, int64_t* n_cold, int64_t* n_inside) {
-    if (lcf_status st = thermal_check(grid, q, n_q, out, n_valid, n_cold, n_inside)) return st;
-    PredictSamples in;
-    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
-    return thermal_impl(grid, in, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
-}
-
-lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
-                                  int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
-                                  double* L_peak, int32_t* i_peak) {
-    if (!grid || !q || !out || !n_valid || !n_dark) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if ((L_peak == nullptr) != (i_peak == nullptr))
-        return fail(LCF_ERR_INVALID_ARGUMENT, "L_peak and i_peak are given together or not at all");
-    if (!is_central(grid->dp.model))
-        return fail(LCF_ERR_UNSUPPORTED, "lcf_predict_luminosity takes a central-engine engine (LCF_MODEL_ARNETT, "
-                                         "LCF_MODEL_MAGNETAR); the bands of a photometric model are lcf_predict_quantiles "
-                                         "and lcf_predict_thermal");
-    if (n_q < 1 || n_q > 512) return fail(LCF_ERR_INVALID_ARGUMENT, "need between 1 and 512 percentiles");
-    for (int32_t j = 0; j < n_q; ++j)
-        if (!(q[j] >= 0. && q[j] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");
-    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no epochs");
-    return with_uploaded_samples(grid, P, n, ld, [&](const PredictSamples& in) {
-        return predict_luminosity_run(grid->device, grid->dp, in, q, n_q, workspace_bytes, out, n_valid, n_dark, L_peak,
-                                      i_peak);
-    });
 }
 
 }  // extern "C"

@@ -184,30 +184,8 @@ __global__ __launch_bounds__(kRasterThreads) void k_history_raster(const History
     }
 }
 
-struct HistoryBuf {
-    std::vector<void*> p;
-    ~HistoryBuf() {
-        for (void* q : p) hipFree(q);
-    }
-    template <class T>
-    lcf_status alloc(T** d, size_t n) {
-        *d = nullptr;
-        LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
-        p.push_back(*d);
-        return LCF_OK;
-    }
-    template <class T>
-    lcf_status put(T** d, const T* h, size_t n) {
-        if (lcf_status st = alloc(d, n)) return st;
-        if (n) LCF_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
-        return LCF_OK;
-    }
-};
-
-long long kept_steps(const HistoryChain& c, int64_t discard, int64_t thin) { return (c.n_t - discard + thin - 1) / thin; }
-
 // What needs no device: the limits of both passes.
-lcf_status check_chains(const HistoryChain* in, int32_t n, int64_t discard, int64_t thin) {
+lcf_status check_chains(const ChainView* in, int32_t n, int64_t discard, int64_t thin) {
     if (!in || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
     for (int32_t g = 0; g < n; ++g) {
@@ -217,28 +195,25 @@ lcf_status check_chains(const HistoryChain* in, int32_t n, int64_t discard, int6
             return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one step and one walker");
         if (in[g].n_w > kMaxWalkers) return fail(LCF_ERR_UNSUPPORTED, "need n_w <= 16384 walkers");
         if (discard >= in[g].n_t) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
-        if (in[g].n_t > (1LL << 40) / ((long long)in[g].n_w * in[g].n_dim))
+        if (in[g].n_t > (1LL << 40) / (in[g].n_w * in[g].n_dim))
             return fail(LCF_ERR_INVALID_ARGUMENT, "too many steps");
     }
     return LCF_OK;
 }
 
-lcf_status check_percentiles(const double* q, int32_t n_q) {
+lcf_status check_history_percentiles(const double* q, int32_t n_q) {
     if (!q) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_q < 1 || n_q > kMaxQ) return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= n_q <= 16 percentiles");
-    for (int32_t i = 0; i < n_q; ++i)
-        if (!(q[i] >= 0. && q[i] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");
-    return LCF_OK;
+    return check_percentiles(q, n_q, kMaxQ, "need 1 <= n_q <= 16 percentiles");
 }
 
-lcf_status check_raster(const HistoryChain* in, int32_t n, int64_t discard, int64_t thin, int32_t t_bins,
+lcf_status check_raster(const ChainView* in, int32_t n, int64_t discard, int64_t thin, int32_t t_bins,
                         const double* edges, int32_t v_bins) {
     if (!edges) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (v_bins < 1 || v_bins > kMaxVBins) return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= v_bins <= 256");
     if (t_bins < 1 || t_bins > kMaxTBins) return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= t_bins <= min(n_keep, 4096)");
     size_t col = 0;
     for (int32_t g = 0; g < n; ++g) {
-        if (t_bins > kept_steps(in[g], discard, thin))
+        if (t_bins > kept_steps(in[g], discard, thin).n)
             return fail(LCF_ERR_INVALID_ARGUMENT, "need 1 <= t_bins <= min(n_keep, 4096)");
         for (int d = 0; d < in[g].n_dim; ++d, ++col) {
             const double* e = edges + col * (v_bins + 1);
@@ -251,14 +226,14 @@ lcf_status check_raster(const HistoryChain* in, int32_t n, int64_t discard, int6
     return LCF_OK;
 }
 
-std::vector<HistorySeg> history_segments(const HistoryChain* in, int32_t n, int64_t discard, int64_t thin) {
+std::vector<HistorySeg> history_segments(const ChainView* in, int32_t n, int64_t discard, int64_t thin) {
     std::vector<HistorySeg> segs(n, HistorySeg{});
     for (int32_t g = 0; g < n; ++g) {
         HistorySeg& a = segs[g];
         a.chain = in[g].chain;
         a.lp = in[g].log_prob;
         a.n_w = in[g].n_w;
-        a.n_keep = kept_steps(in[g], discard, thin);
+        a.n_keep = kept_steps(in[g], discard, thin).n;
         a.discard = discard;
         a.thin = thin;
         a.n_dim = in[g].n_dim;
@@ -268,23 +243,15 @@ std::vector<HistorySeg> history_segments(const HistoryChain* in, int32_t n, int6
     return segs;
 }
 
-lcf_status use_device(int32_t device, int* n_cu) {
-    LCF_HIP(hipSetDevice(device));
-    LCF_HIP(hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, device));
-    if (*n_cu < 1) *n_cu = 1;
-    return LCF_OK;
-}
-
-}  // namespace
-
-namespace lcf {
-
-lcf_status history_steps_run(int32_t device, const HistoryChain* in, int32_t n, int64_t discard, int64_t thin,
+// Both runs: per entry of `in` a whole chain [n_t][n_w][n_dim] (ld = n_dim) and its log-probabilities, if any, in device
+// memory.  Inputs and outputs (host) hold the entries' parts one after another, as lcf_samplers_chain_history /
+// lcf_samplers_chain_raster describe them.
+lcf_status history_steps_run(int32_t device, const ChainView* in, int32_t n, int64_t discard, int64_t thin,
                              const double* q, int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
                              int64_t* n_moved) {
     if (!stat_lo || !stat_hi || !n_valid || !n_moved) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = check_chains(in, n, discard, thin)) return st;
-    if (lcf_status st = check_percentiles(q, n_q)) return st;
+    if (lcf_status st = check_history_percentiles(q, n_q)) return st;
     int n_cu = 1;
     if (lcf_status st = use_device(device, &n_cu)) return st;
     std::vector<HistorySeg> segs = history_segments(in, n, discard, thin);
@@ -296,7 +263,7 @@ lcf_status history_steps_run(int32_t device, const HistoryChain* in, int32_t n, 
         n_pad = std::max(n_pad, a.n_pad);
     }
     if (steps > (1u << 30)) return fail(LCF_ERR_INVALID_ARGUMENT, "too many steps");
-    HistoryBuf mem;
+    DevBuf mem;
     unsigned long long* d_stat;
     long long *d_valid, *d_moved;
     double* d_qf;
@@ -352,7 +319,7 @@ lcf_status history_steps_run(int32_t device, const HistoryChain* in, int32_t n, 
     return LCF_OK;
 }
 
-lcf_status history_raster_run(int32_t device, const HistoryChain* in, int32_t n, int64_t discard, int64_t thin,
+lcf_status history_raster_run(int32_t device, const ChainView* in, int32_t n, int64_t discard, int64_t thin,
                               int32_t t_bins, const double* edges, int32_t v_bins, int64_t* counts) {
     if (!counts) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (lcf_status st = check_chains(in, n, discard, thin)) return st;
@@ -363,7 +330,7 @@ lcf_status history_raster_run(int32_t device, const HistoryChain* in, int32_t n,
     size_t cols = 0;
     for (const HistorySeg& a : segs) cols += a.n_dim;
     const size_t per_col = (size_t)t_bins * v_bins;
-    HistoryBuf mem;
+    DevBuf mem;
     double* d_edges;
     unsigned long long* d_counts;
     lcf_status st;
@@ -408,32 +375,6 @@ lcf_status history_raster_run(int32_t device, const HistoryChain* in, int32_t n,
     return LCF_OK;
 }
 
-}  // namespace lcf
-
-namespace {
-
-// The host chain [n_t][n_w][n_dim] (and its log-probabilities, if any) on `device` for as long as `run` takes; every
-// limit `check` knows is decided before the first HIP call.
-template <class Check, class Run>
-lcf_status with_uploaded(int32_t device, const double* chain, const double* log_prob, int64_t n_t, int32_t n_w,
-                         int32_t n_dim, Check check, Run run) {
-    HistoryChain in{chain, log_prob, n_t, n_w, n_dim};
-    if (lcf_status st = check(in)) return st;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
-    HistoryBuf mem;
-    double *d_chain, *d_lp = nullptr;
-    if (lcf_status st = mem.put(&d_chain, chain, (size_t)n_t * n_w * n_dim)) return st;
-    if (log_prob)
-        if (lcf_status st = mem.put(&d_lp, log_prob, (size_t)n_t * n_w)) return st;
-    in.chain = d_chain;
-    in.log_prob = d_lp;
-    return run(in);
-}
-
 }  // namespace
 
 extern "C" {
@@ -442,30 +383,43 @@ lcf_status lcf_chain_history(int32_t device, const double* chain, const double* 
                              int32_t n_dim, int64_t discard, int64_t thin, const double* q, int32_t n_q, double* stat_lo,
                              double* stat_hi, int64_t* n_valid, int64_t* n_moved) {
     if (!stat_lo || !stat_hi || !n_valid || !n_moved) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    return with_uploaded(
-        device, chain, log_prob, n_t, n_w, n_dim,
-        [&](const HistoryChain& in) {
-            if (lcf_status st = check_chains(&in, 1, discard, thin)) return st;
-            return check_percentiles(q, n_q);
-        },
-        [&](const HistoryChain& in) {
-            return history_steps_run(device, &in, 1, discard, thin, q, n_q, stat_lo, stat_hi, n_valid, n_moved);
-        });
+    const ChainView host{chain, log_prob, n_t, n_w, n_dim, n_dim};
+    if (lcf_status st = check_chains(&host, 1, discard, thin)) return st;
+    if (lcf_status st = check_history_percentiles(q, n_q)) return st;
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = upload_chain(device, host, mem, &in)) return st;
+    return history_steps_run(device, &in, 1, discard, thin, q, n_q, stat_lo, stat_hi, n_valid, n_moved);
+}
+
+lcf_status lcf_samplers_chain_history(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, const double* q,
+                                      int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
+                                      int64_t* n_moved) {
+    std::vector<ChainView> in;
+    int32_t device = 0;
+    if (lcf_status st = stored_chains(s, n, discard, thin, &in, &device)) return st;
+    return history_steps_run(device, in.data(), n, discard, thin, q, n_q, stat_lo, stat_hi, n_valid, n_moved);
 }
 
 lcf_status lcf_chain_raster(int32_t device, const double* chain, int64_t n_t, int32_t n_w, int32_t n_dim,
                             int64_t discard, int64_t thin, int32_t t_bins, const double* edges, int32_t v_bins,
                             int64_t* counts) {
     if (!counts) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    return with_uploaded(
-        device, chain, nullptr, n_t, n_w, n_dim,
-        [&](const HistoryChain& in) {
-            if (lcf_status st = check_chains(&in, 1, discard, thin)) return st;
-            return check_raster(&in, 1, discard, thin, t_bins, edges, v_bins);
-        },
-        [&](const HistoryChain& in) {
-            return history_raster_run(device, &in, 1, discard, thin, t_bins, edges, v_bins, counts);
-        });
+    const ChainView host{chain, nullptr, n_t, n_w, n_dim, n_dim};
+    if (lcf_status st = check_chains(&host, 1, discard, thin)) return st;
+    if (lcf_status st = check_raster(&host, 1, discard, thin, t_bins, edges, v_bins)) return st;
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = upload_chain(device, host, mem, &in)) return st;
+    return history_raster_run(device, &in, 1, discard, thin, t_bins, edges, v_bins, counts);
+}
+
+lcf_status lcf_samplers_chain_raster(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, int32_t t_bins,
+                                     const double* edges, int32_t v_bins, int64_t* counts) {
+    std::vector<ChainView> in;
+    int32_t device = 0;
+    if (lcf_status st = stored_chains(s, n, discard, thin, &in, &device)) return st;
+    return history_raster_run(device, in.data(), n, discard, thin, t_bins, edges, v_bins, counts);
 }
 
 }  // extern "C"

@@ -111,59 +111,99 @@ lcf_status upload(const std::vector<T>& h, T** d, UploadArena& arena) {
     return arena.put(h.data(), h.size() * sizeof(T), (void**)d);
 }
 
-// Autocorrelation time (lcf_autocorr.hip): one series per walker and parameter; element t of series (w, d) at
-// chain[t * row_stride + w * n_d + d] in device memory.  tau / window receive n_d entries per entry of `in`, in order.
-struct AutocorrSeries {
-    const double* chain;
-    int64_t n_t, row_stride;
-    int32_t n_w, n_d;
-};
-lcf_status autocorr_run(int32_t device, const AutocorrSeries* in, int32_t n, double c, double* tau, int64_t* window);
+// ---- what a chain analysis is made of --------------------------------------------------------------------------------
+// A chain analysis (autocorrelation time, predictive bands, corner histograms, chain history) is ONE file: its kernels,
+// its run over ChainViews and both of its C entry points -- the host-array form, which checks its own limits and then
+// calls upload_chain, and the sampler form, which calls stored_chains.  It asks for its device with use_device and takes
+// every scratch buffer from a DevBuf.  (Objects that own device memory for their lifetime -- engine, samplers, SED engine
+// -- keep their `owned` lists.)
 
-// Posterior-predictive quantiles (lcf_predict.hip): n samples in device memory, sample s being the ld-strided row at
-// base + (s / n_w) * step_stride + (s % n_w) * ld (a stored chain read in place: n_w walkers per kept step).
-struct DevProblem;
-struct PredictSamples {
-    const double* base;
-    int64_t n, n_w, step_stride;
-    int32_t ld;
-};
-// `dp`: the engine of the grid points; orig[n_epochs][n_filters] (host): the index of the point (time, filter) in the
-// caller's order, -1 where the grid has no such point.  out[n_q][n_points], n_valid[n_points] (host).
-lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig,
-                       int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
-                       int64_t* n_valid);
-// Thermal form: quantiles of T, R_bb, L_bol and the validity counters on the distinct times of `dp`; time_orig
-// [n_epochs] (host): the time's index in the caller's order.  out[3][n_q][n_epochs], n_valid[3][n_epochs],
-// n_cold[n_epochs], n_inside[n_epochs] (host, caller's order).
-lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* time_orig,
-                               const double* q, int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
-                               int64_t* n_valid, int64_t* n_cold, int64_t* n_inside);
+// The device a call runs on: LCF_ERR_NO_DEVICE without one, then the range check, then it is made current.  n_cu: its
+// compute units (at least 1).
+inline lcf_status use_device(int32_t device, int* n_cu = nullptr) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
+    LCF_HIP(hipSetDevice(device));
+    if (n_cu) {
+        LCF_HIP(hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, device));
+        if (*n_cu < 1) *n_cu = 1;
+    }
+    return LCF_OK;
+}
 
-// Corner histograms (lcf_corner.hip): per entry of `in`, n samples of n_dim columns in device memory, sample s being
-// the ld-strided row at base + (s / n_w) * step_stride + (s % n_w) * ld.  Inputs and outputs (host) hold the entries'
-// parts one after another, as lcf_samplers_chain_range / lcf_samplers_chain_hist describe them.
-struct CornerSamples {
-    const double* base;
-    int64_t n, n_w, step_stride;
+// Device memory for as long as a call takes: freed when the buffer goes out of scope.
+struct DevBuf {
+    std::vector<void*> p;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        for (void* q : p) hipFree(q);
+    }
+    template <class T>
+    lcf_status alloc(T** d, size_t n) {   // (n = 0: one element, so that the pointer is one)
+        *d = nullptr;
+        LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
+        p.push_back(*d);
+        return LCF_OK;
+    }
+    template <class T>
+    lcf_status put(T** d, const T* h, size_t n) {
+        if (lcf_status st = alloc(d, n)) return st;
+        if (n) LCF_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
+        return LCF_OK;
+    }
+};
+
+// Rows of a chain where they lie: n_t steps of n_w walkers, walker w of step t being the n_dim columns at
+// chain + (t * n_w + w) * ld, its log-probability at log_prob[t * n_w + w] (or nullptr).  n host samples P[n][ld] are
+// one step of n walkers.
+struct ChainView {
+    const double *chain, *log_prob;
+    int64_t n_t, n_w;
     int32_t ld, n_dim;
 };
-lcf_status corner_range_run(int32_t device, const CornerSamples* in, int32_t n, double* lo, double* hi, int64_t* n_nan);
-lcf_status corner_hist_run(int32_t device, const CornerSamples* in, int32_t n, const double* shift, const double* edges,
-                           int32_t bins, int64_t* hist1d, int64_t* hist2d);
-
-// Chain history (lcf_history.hip): per entry of `in`, a whole stored chain [n_t][n_w][n_dim] and its log-probabilities
-// [n_t][n_w] (or nullptr) in device memory; the kept steps are discard, discard + thin, ...  Inputs and outputs (host)
-// hold the entries' parts one after another, as lcf_samplers_chain_history / lcf_samplers_chain_raster describe them.
-struct HistoryChain {
-    const double *chain, *log_prob;
-    int64_t n_t;
-    int32_t n_w, n_dim;
+// The kept steps discard, discard + thin, ... of a view: the first one, how many, the doubles from one to the next.
+// Their walkers read as samples: sample s of `samples` is the row at base + (s / n_w) * step_stride + (s % n_w) * ld;
+// a chain of one step (n host samples) has nothing to step over, and the kernels are handed 0 for it.
+struct KeptSteps {
+    const double* base;
+    int64_t n, stride;
+    int64_t samples, step_stride;
 };
-lcf_status history_steps_run(int32_t device, const HistoryChain* in, int32_t n, int64_t discard, int64_t thin,
-                             const double* q, int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
-                             int64_t* n_moved);
-lcf_status history_raster_run(int32_t device, const HistoryChain* in, int32_t n, int64_t discard, int64_t thin,
-                              int32_t t_bins, const double* edges, int32_t v_bins, int64_t* counts);
+inline KeptSteps kept_steps(const ChainView& c, int64_t discard, int64_t thin) {
+    const int64_t row = c.n_w * c.ld, n = (c.n_t - discard + thin - 1) / thin;
+    return KeptSteps{c.chain + discard * row, n, thin * row, n * c.n_w, c.n_t > 1 ? thin * row : 0};
+}
+
+// lcf_sampler.hip: the last stored run of every sampler as a view, checked (null, discard / thin, "no stored chain",
+// "discard leaves no chain", one device) and settled, and the device they are on.
+lcf_status stored_chains(lcf_sampler* const* s, int32_t n, int64_t discard, int64_t thin, std::vector<ChainView>* out,
+                         int32_t* device);
+
+// The host arrays of `host` on `device` (checked here: use_device) for as long as `mem` lives; *dev is the chain there.
+// The caller's own limits come first: nothing above is asked of a device.
+inline lcf_status upload_chain(int32_t device, const ChainView& host, DevBuf& mem, ChainView* dev) {
+    if (lcf_status st = use_device(device)) return st;
+    const size_t rows = (size_t)host.n_t * host.n_w;
+    double *d_chain, *d_lp = nullptr;
+    if (lcf_status st = mem.put(&d_chain, host.chain, rows * host.ld)) return st;
+    if (host.log_prob)
+        if (lcf_status st = mem.put(&d_lp, host.log_prob, rows)) return st;
+    *dev = host;
+    dev->chain = d_chain;
+    dev->log_prob = d_lp;
+    return LCF_OK;
+}
+
+// The percentiles q[n_q] of a call that takes 1 ... max of them (`what`: the feature's words for that limit).
+inline lcf_status check_percentiles(const double* q, int32_t n_q, int32_t max, const char* what) {
+    if (n_q < 1 || n_q > max) return fail(LCF_ERR_INVALID_ARGUMENT, what);
+    for (int32_t i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0. && q[i] <= 100.)) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles must be in [0, 100]");
+    return LCF_OK;
+}
 
 }  // namespace lcf

@@ -9,6 +9,8 @@
 
 namespace lcf {
 
+struct DevProblem;
+
 // doubles ordered as unsigned integers (-inf < ... < -0 < +0 < ... < +inf); pq_value is the inverse, NaNs included
 __device__ __forceinline__ unsigned long long pq_key(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
@@ -18,15 +20,9 @@ __device__ __forceinline__ double pq_value(unsigned long long k) {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
-// lcf_central.hip: keys[i * in.n + s] = pq_key(L of sample s at epoch ep0 + i of `dp`), i < n_ep, on the null stream.
-// n_cus sizes the grid.
-lcf_status central_keys_launch(const DevProblem& dp, const PredictSamples& in, int ep0, int n_ep,
+// lcf_central.hip: keys[i * n + s] = pq_key(L of sample s at epoch ep0 + i of `dp`), i < n_ep, on the null stream; the
+// n samples are the walkers of the kept steps of `in`.  n_cus sizes the grid.
+lcf_status central_keys_launch(const DevProblem& dp, const ChainView& in, int64_t discard, int64_t thin, int ep0, int n_ep,
                                unsigned long long* keys, int n_cus);
-
-// lcf_predict.hip: the luminosity form on the epochs of `dp` (a central-engine problem), in their order.  out[n_q]
-// [n_points], n_valid / n_dark[n_points], L_peak / i_peak[in.n] or both nullptr (host).
-lcf_status predict_luminosity_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const double* q,
-                                  int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
-                                  double* L_peak, int32_t* i_peak);
 
 }  // namespace lcf

@@ -45,6 +45,7 @@
 #include "lcf.h"
 #include "lcf_device.h"
 #include "lcf_host.h"
+#include "lcf_internal.h"
 #include "lcf_keys.h"
 
 using namespace lcf;
@@ -626,20 +627,6 @@ __global__ __launch_bounds__(256) void k_pq_finish(const PqSearch* __restrict__ 
     *dst = t >= 0.5 ? __dsub_rn(hi, __dmul_rn(diff, __dsub_rn(1., t))) : __dadd_rn(lo, __dmul_rn(diff, t));
 }
 
-struct PqBuf {
-    std::vector<void*> p;
-    ~PqBuf() {
-        for (void* q : p) hipFree(q);
-    }
-    template <class T>
-    lcf_status alloc(T** d, size_t n) {
-        *d = nullptr;
-        LCF_HIP(hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)));
-        p.push_back(*d);
-        return LCF_OK;
-    }
-};
-
 int hist_bits(long long n_hist, int max_bits) {
     int b = kPqMinBits;
     while (b < max_bits && (n_hist << (b + 1)) * 4 <= kPqHistBytes) ++b;
@@ -655,7 +642,7 @@ struct PqForm {
     size_t lds_head;       // dynamic LDS of a pass in front of the searches' words and the histograms
     bool coef = true;      // the samples' walker_coefficients are wanted ([kNCoef][n], part of sample_bytes)
     int tile = 0;          // times per tile, set by quantile_run in front of prepare
-    virtual lcf_status prepare(PqBuf& mem, PqArgs& a, double* d_coef) = 0;   // ... and whatever else the passes read
+    virtual lcf_status prepare(DevBuf& mem, PqArgs& a, double* d_coef) = 0;   // ... and whatever else the passes read
     virtual lcf_status pass(const PqArgs& a, int n_ep, size_t lds) = 0;
     virtual ~PqForm() {}
 };
@@ -676,7 +663,7 @@ struct LightCurveForm : PqForm {
         time_bytes = 0;
         lds_head = kExpTabSize * sizeof(double);
     }
-    lcf_status prepare(PqBuf&, PqArgs& a, double* d_coef) override {
+    lcf_status prepare(DevBuf&, PqArgs& a, double* d_coef) override {
         hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
         LCF_HIP(hipGetLastError());
         return LCF_OK;
@@ -697,7 +684,7 @@ struct ThermalForm : PqForm {
         lds_head = 0;
         th.T_floor = T_floor;
     }
-    lcf_status prepare(PqBuf& mem, PqArgs& a, double* d_coef) override {
+    lcf_status prepare(DevBuf& mem, PqArgs& a, double* d_coef) override {
         lcf_status st;
         if ((st = mem.alloc(&th.win, (size_t)a.n * 2)) || (st = mem.alloc(&th.n_cold, (size_t)dp.n_epochs * 2))) return st;
         th.n_inside = th.n_cold + dp.n_epochs;
@@ -715,22 +702,23 @@ struct ThermalForm : PqForm {
 // Every (sample, time) value is evaluated once per tile, in front of the tile's first pass; the passes read the keys.
 struct LuminosityForm : PqForm {
     const DevProblem& dp;
-    const PredictSamples& in;
+    const ChainView& in;
+    const int64_t discard, thin;
     const bool peak;
     int n_cus = 1;
     unsigned long long* keys = nullptr;
     KqArgs kq{};
     LqPeak pk{};
-    LuminosityForm(const DevProblem& d, const PredictSamples& s, bool want_peak, int cus)
-        : dp(d), in(s), peak(want_peak), n_cus(cus) {
+    LuminosityForm(const DevProblem& d, const ChainView& s, int64_t discard_, int64_t thin_, bool want_peak, int cus)
+        : dp(d), in(s), discard(discard_), thin(thin_), peak(want_peak), n_cus(cus) {
         nf = 1;
         sample_bytes = want_peak ? sizeof(double) + sizeof(int) : 0;   // the largest L so far and where
         time_bytes = sizeof(unsigned long long);                      // the dark counter
-        tile_bytes = (size_t)s.n * sizeof(unsigned long long);         // the keys
+        tile_bytes = (size_t)kept_steps(s, discard, thin).samples * sizeof(unsigned long long);   // the keys
         lds_head = 0;
         coef = false;
     }
-    lcf_status prepare(PqBuf& mem, PqArgs& a, double*) override {
+    lcf_status prepare(DevBuf& mem, PqArgs& a, double*) override {
         lcf_status st;
         if ((st = mem.alloc(&keys, (size_t)tile * a.n)) || (st = mem.alloc(&kq.n_dark, (size_t)dp.n_points))) return st;
         kq.keys = keys;
@@ -746,7 +734,7 @@ struct LuminosityForm : PqForm {
     }
     lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
         if (a.mode == 0) {   // the tile's first pass: its keys, then the peaks so far (all on the null stream, in order)
-            if (lcf_status st = central_keys_launch(dp, in, a.ep0, n_ep, keys, n_cus)) return st;
+            if (lcf_status st = central_keys_launch(dp, in, discard, thin, a.ep0, n_ep, keys, n_cus)) return st;
             if (peak) {
                 pk.ep0 = a.ep0;
                 pk.n_ep = n_ep;
@@ -761,17 +749,20 @@ struct LuminosityForm : PqForm {
     }
 };
 
-// The searches of every point (time x series of `form`), the times in tiles that fit the workspace.  orig_host
-// [n_ep_all][nf]: where the point's results go, -1 = no such point.  out[n_q][n_points], n_valid[n_points] (host).
-lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_points, const PredictSamples& in,
-                        const int32_t* orig_host, int32_t component, const double* q, int32_t n_q,
-                        int64_t workspace_bytes, PqBuf& mem, double* out, int64_t* n_valid) {
-    LCF_HIP(hipSetDevice(device));
+// The searches of every point (time x series of `form`), the times in tiles that fit the workspace, over the walkers of
+// the kept steps of `chain` (device memory) as samples.  orig_host[n_ep_all][nf]: where the point's results go, -1 = no
+// such point.  out[n_q][n_points], n_valid[n_points] (host).
+lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_points, const ChainView& chain,
+                        int64_t discard, int64_t thin, const int32_t* orig_host, int32_t component, const double* q,
+                        int32_t n_q, int64_t workspace_bytes, DevBuf& mem, double* out, int64_t* n_valid) {
+    if (lcf_status st = use_device(device)) return st;
+    const KeptSteps kept = kept_steps(chain, discard, thin);
+    const long long n_samples = kept.samples;
     const int nf = form.nf, ns = nf * n_q;
     const int bits0 = hist_bits(nf, kPqMaxBits), bits1 = hist_bits(ns, kPqMaxBits);
     const size_t lds_head = form.lds_head + (size_t)ns * 24;
     // device memory: per sample the coefficients (and window), per point the results, per time of a tile the rest
-    const size_t fixed = (size_t)in.n * form.sample_bytes + (size_t)n_points * (n_q + 1) * 8 +
+    const size_t fixed = (size_t)n_samples * form.sample_bytes + (size_t)n_points * (n_q + 1) * 8 +
                          (size_t)n_ep_all * (nf * 4 + form.time_bytes) + 4096;
     const size_t hist_ep = std::max((size_t)nf << bits0, (size_t)ns << bits1) * 4;
     const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8) + form.tile_bytes;
@@ -788,7 +779,7 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
     unsigned long long* d_buf;
     lcf_status st;
     form.tile = tile;
-    if ((st = mem.alloc(&d_coef, form.coef ? (size_t)in.n * kNCoef : 0)) || (st = mem.alloc(&d_q, n_q)) ||
+    if ((st = mem.alloc(&d_coef, form.coef ? (size_t)n_samples * kNCoef : 0)) || (st = mem.alloc(&d_q, n_q)) ||
         (st = mem.alloc(&d_out, (size_t)n_points * n_q)) || (st = mem.alloc(&d_nv, n_points)) ||
         (st = mem.alloc(&d_orig, (size_t)n_ep_all * nf)) || (st = mem.alloc(&d_hist, (size_t)tile * hist_ep / 4)) ||
         (st = mem.alloc(&d_active, 1)) || (st = mem.alloc(&d_search, (size_t)tile * ns)) ||
@@ -801,11 +792,11 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
     LCF_HIP(hipMemset(d_nv, 0, n_points * sizeof(long long)));
 
     PqArgs a{};
-    a.base = in.base;
-    a.n = in.n;
-    a.n_w = in.n_w;
-    a.step_stride = in.step_stride;
-    a.ld = in.ld;
+    a.base = kept.base;
+    a.n = n_samples;
+    a.n_w = chain.n_w;
+    a.step_stride = kept.step_stride;
+    a.ld = chain.ld;
     a.coef = d_coef;
     a.orig = d_orig;
     a.n_q = n_q;
@@ -819,9 +810,9 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
         const int n_ep = std::min(tile, n_ep_all - ep0);
         // samples per workgroup: enough workgroups to fill the device, few enough that merging a workgroup's
         // histogram stays small next to its evaluations (whole multiples of the workgroup; at most 65535 chunks)
-        long long chunk = (in.n * n_ep / 4096 + kPqThreads - 1) / kPqThreads * kPqThreads;
+        long long chunk = (n_samples * n_ep / 4096 + kPqThreads - 1) / kPqThreads * kPqThreads;
         chunk = std::min<long long>(std::max<long long>(chunk, 4 * kPqThreads), 64 * kPqThreads);
-        chunk = std::max<long long>(chunk, ((in.n + 65534) / 65535 + kPqThreads - 1) / kPqThreads * kPqThreads);
+        chunk = std::max<long long>(chunk, ((n_samples + 65534) / 65535 + kPqThreads - 1) / kPqThreads * kPqThreads);
         a.ep0 = ep0;
         a.chunk = chunk;
         PqPick pk{d_hist, d_search, d_orig + (size_t)ep0 * nf, d_q, d_nv, d_active, n_q, bits0, 0};
@@ -866,36 +857,79 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
     return LCF_OK;
 }
 
-}  // namespace
-
-namespace lcf {
-
-lcf_status predict_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* orig_host,
-                       int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
-                       int64_t* n_valid) {
-    if (dp.n_filters * n_q > kPqMaxSearch)
-        return fail(LCF_ERR_UNSUPPORTED, "filters x percentiles of one call must not exceed 512");
-    LightCurveForm form(dp);
-    PqBuf mem;
-    return quantile_run(device, form, dp.n_epochs, dp.n_points, in, orig_host, component, q, n_q, workspace_bytes, mem,
-                        out, n_valid);
+// What both predictive entry points check before the device is touched.
+lcf_status predict_check(const lcf_engine* grid, int32_t component, const double* q, int32_t n_q, const double* out,
+                         const int64_t* n_valid) {
+    if (!grid || !q || !out || !n_valid) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = custom_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
+    if (lcf_status st = central_refuse(grid, "a predictive band (lcf_predict_*, lcf_sampler_predict_*)")) return st;
+    if (lcf_status st = check_percentiles(q, n_q, INT32_MAX, "need at least one percentile")) return st;
+    const bool companion = grid->dp.model >= kCompanion && grid->dp.model <= kCompanion3;
+    if (component != 0 && !(component == 1 && companion))
+        return fail(LCF_ERR_INVALID_ARGUMENT, "component: 0 = the model, 1 = the SiFTO term of a companion-shocking model");
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no points");
+    return LCF_OK;
 }
 
-lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const int32_t* time_orig,
-                               const double* q, int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
-                               int64_t* n_valid, int64_t* n_cold, int64_t* n_inside) {
+// The grid engine's points as a (time, filter) table -- orig[n_epochs][n_filters]: the index of the point in the
+// caller's order, -1 where the grid has no such point -- and the run itself.  out[n_q][n_points], n_valid[n_points].
+lcf_status predict_run(lcf_engine* grid, const ChainView& in, int64_t discard, int64_t thin, int32_t component,
+                       const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points, NF = dp.n_filters;
+    std::vector<int> filt(N), orig(N), epoch(N);
+    LCF_HIP(hipMemcpy(filt.data(), dp.pt_filt, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int32_t> table((size_t)dp.n_epochs * NF, -1);
+    for (int i = 0; i < N; ++i) {
+        int32_t& slot = table[(size_t)epoch[i] * NF + filt[i]];
+        if (slot >= 0) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine holds a (time, filter) pair twice");
+        slot = orig[i];
+    }
+    if (NF * n_q > kPqMaxSearch)
+        return fail(LCF_ERR_UNSUPPORTED, "filters x percentiles of one call must not exceed 512");
+    LightCurveForm form(dp);
+    DevBuf mem;
+    return quantile_run(grid->device, form, dp.n_epochs, N, in, discard, thin, table.data(), component, q, n_q,
+                        workspace_bytes, mem, out, n_valid);
+}
+
+// What both thermal entry points check before the device is touched.
+lcf_status thermal_check(const lcf_engine* grid, const double* q, int32_t n_q, const double* out, const int64_t* n_valid,
+                         const int64_t* n_cold, const int64_t* n_inside) {
+    if (!n_cold || !n_inside) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = predict_check(grid, 0, q, n_q, out, n_valid)) return st;
+    if (grid->dp.model == kBlackbody)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the blackbody model has no thermal evolution or validity window");
+    if (grid->dp.n_points != grid->dp.n_epochs)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine must hold one point per distinct time");
+    return LCF_OK;
+}
+
+// Thermal form: quantiles of T, R_bb, L_bol and the validity counters on the distinct times of the grid engine.
+// out[3][n_q][n_times], n_valid[3][n_times], n_cold[n_times], n_inside[n_times] (host, caller's order).
+lcf_status thermal_run(lcf_engine* grid, const ChainView& in, int64_t discard, int64_t thin, const double* q, int32_t n_q,
+                       double T_floor, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_cold,
+                       int64_t* n_inside) {
+    const DevProblem& dp = grid->dp;
+    const int nt = dp.n_points;
+    std::vector<int> pt_orig(nt), epoch(nt);
+    LCF_HIP(hipMemcpy(pt_orig.data(), dp.pt_orig, nt * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, nt * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int32_t> time_orig(nt);   // the time's index in the caller's order
+    for (int i = 0; i < nt; ++i) time_orig[epoch[i]] = pt_orig[i];   // (N points on N distinct times: a bijection)
     if (kThSeries * n_q > kPqMaxSearch)
         return fail(LCF_ERR_UNSUPPORTED, "3 x percentiles of one call must not exceed 512");
-    const int nt = dp.n_epochs;
     // the three quantities take the place of a time's filters: point index = quantity * n_times + time
     std::vector<int32_t> orig((size_t)nt * kThSeries);
     for (int ep = 0; ep < nt; ++ep)
         for (int f = 0; f < kThSeries; ++f) orig[(size_t)ep * kThSeries + f] = f * nt + time_orig[ep];
     std::vector<double> by_q((size_t)n_q * kThSeries * nt);
     ThermalForm form(dp, T_floor);
-    PqBuf mem;
-    if (lcf_status st = quantile_run(device, form, nt, (long long)kThSeries * nt, in, orig.data(), 0, q, n_q,
-                                     workspace_bytes, mem, by_q.data(), n_valid))
+    DevBuf mem;
+    if (lcf_status st = quantile_run(grid->device, form, nt, (long long)kThSeries * nt, in, discard, thin, orig.data(), 0,
+                                     q, n_q, workspace_bytes, mem, by_q.data(), n_valid))
         return st;
     for (int f = 0; f < kThSeries; ++f)   // [n_q][3][n_times] -> [3][n_q][n_times]
         for (int j = 0; j < n_q; ++j)
@@ -910,29 +944,112 @@ lcf_status predict_thermal_run(int32_t device, const DevProblem& dp, const Predi
     return LCF_OK;
 }
 
-lcf_status predict_luminosity_run(int32_t device, const DevProblem& dp, const PredictSamples& in, const double* q,
-                                  int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
-                                  double* L_peak, int32_t* i_peak) {
-    if (n_q > kPqMaxSearch) return fail(LCF_ERR_INVALID_ARGUMENT, "percentiles of one call must not exceed 512");
+// The luminosity form on the epochs of the grid engine (a central-engine problem), in their order.  out[n_q][n_points],
+// n_valid / n_dark[n_points], L_peak / i_peak[samples] or both nullptr (host).
+lcf_status luminosity_run(lcf_engine* grid, const ChainView& in, int64_t discard, int64_t thin, const double* q,
+                          int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
+                          double* L_peak, int32_t* i_peak) {
+    const DevProblem& dp = grid->dp;
     const int nt = dp.n_points;
+    const int64_t n = kept_steps(in, discard, thin).samples;
     int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 64;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, grid->device) != hipSuccess || cus <= 0) cus = 64;
     std::vector<int32_t> orig(nt);   // one series per epoch, in the engine's own order
     for (int ep = 0; ep < nt; ++ep) orig[ep] = ep;
-    LuminosityForm form(dp, in, L_peak != nullptr, cus);
-    PqBuf mem;
-    if (lcf_status st = quantile_run(device, form, nt, nt, in, orig.data(), 0, q, n_q, workspace_bytes, mem, out, n_valid))
+    LuminosityForm form(dp, in, discard, thin, L_peak != nullptr, cus);
+    DevBuf mem;
+    if (lcf_status st = quantile_run(grid->device, form, nt, nt, in, discard, thin, orig.data(), 0, q, n_q,
+                                     workspace_bytes, mem, out, n_valid))
         return st;
     std::vector<unsigned long long> dark(nt);
     LCF_HIP(hipMemcpy(dark.data(), form.kq.n_dark, (size_t)nt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int ep = 0; ep < nt; ++ep) n_dark[ep] = (int64_t)dark[ep];
     if (L_peak) {
-        LCF_HIP(hipMemcpy(L_peak, form.pk.best, (size_t)in.n * sizeof(double), hipMemcpyDeviceToHost));
-        LCF_HIP(hipMemcpy(i_peak, form.pk.at, (size_t)in.n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int64_t s = 0; s < in.n; ++s)
+        LCF_HIP(hipMemcpy(L_peak, form.pk.best, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        LCF_HIP(hipMemcpy(i_peak, form.pk.at, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t s = 0; s < n; ++s)
             if (i_peak[s] < 0) L_peak[s] = std::nan("");
     }
     return LCF_OK;
 }
 
-}  // namespace lcf
+// n host samples P[n][ld] as one step of n walkers, on the grid engine's device for as long as `mem` lives.
+lcf_status uploaded_samples(const lcf_engine* grid, const double* P, int64_t n, int32_t ld, DevBuf& mem, ChainView* in) {
+    if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
+    if (ld < 1 || ld < grid->dp.n_par) return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than the model's parameter count");
+    if (n > (1LL << 40) / ld) return fail(LCF_ERR_INVALID_ARGUMENT, "too many samples");
+    return upload_chain(grid->device, ChainView{P, nullptr, 1, n, ld, ld}, mem, in);
+}
+
+// The sampler's last stored run, where it lies, if it can be read with the grid engine.
+lcf_status stored_samples(const lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, ChainView* in) {
+    std::vector<ChainView> chains;
+    int32_t device = 0;
+    if (lcf_status st = stored_chains(&s, 1, discard, thin, &chains, &device)) return st;
+    if (device != grid->device) return fail(LCF_ERR_UNSUPPORTED, "sampler and grid engine are on different devices");
+    if (chains[0].n_dim < grid->dp.n_par)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the chain has fewer columns than the model has parameters");
+    *in = chains[0];
+    return LCF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lcf_status lcf_predict_quantiles(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t component,
+                                 const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid) {
+    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return predict_run(grid, in, 0, 1, component, q, n_q, workspace_bytes, out, n_valid);
+}
+
+lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin,
+                                         int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
+                                         double* out, int64_t* n_valid) {
+    if (lcf_status st = predict_check(grid, component, q, n_q, out, n_valid)) return st;
+    ChainView in;
+    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
+    return predict_run(grid, in, discard, thin, component, q, n_q, workspace_bytes, out, n_valid);
+}
+
+lcf_status lcf_predict_thermal(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                               double T_floor, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_cold,
+                               int64_t* n_inside) {
+    if (lcf_status st = thermal_check(grid, q, n_q, out, n_valid, n_cold, n_inside)) return st;
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return thermal_run(grid, in, 0, 1, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
+}
+
+lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, const double* q,
+                                       int32_t n_q, double T_floor, int64_t workspace_bytes, double* out,
+                                       int64_t* n_valid, int64_t* n_cold, int64_t* n_inside) {
+    if (lcf_status st = thermal_check(grid, q, n_q, out, n_valid, n_cold, n_inside)) return st;
+    ChainView in;
+    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
+    return thermal_run(grid, in, discard, thin, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
+}
+
+lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                                  int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
+                                  double* L_peak, int32_t* i_peak) {
+    if (!grid || !q || !out || !n_valid || !n_dark) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if ((L_peak == nullptr) != (i_peak == nullptr))
+        return fail(LCF_ERR_INVALID_ARGUMENT, "L_peak and i_peak are given together or not at all");
+    if (!is_central(grid->dp.model))
+        return fail(LCF_ERR_UNSUPPORTED, "lcf_predict_luminosity takes a central-engine engine (LCF_MODEL_ARNETT, "
+                                         "LCF_MODEL_MAGNETAR); the bands of a photometric model are lcf_predict_quantiles "
+                                         "and lcf_predict_thermal");
+    if (lcf_status st = check_percentiles(q, n_q, kPqMaxSearch, "need between 1 and 512 percentiles")) return st;
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no epochs");
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return luminosity_run(grid, in, 0, 1, q, n_q, workspace_bytes, out, n_valid, n_dark, L_peak, i_peak);
+}
+
+}  // extern "C"

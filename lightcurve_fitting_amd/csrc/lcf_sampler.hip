@@ -442,6 +442,27 @@ lcf_status settle(lcf_sampler* s) {
     return LCF_OK;
 }
 
+// The last stored run of every sampler where it lies, for the chain analyses (lcf_host.h).
+lcf_status stored_chains(lcf_sampler* const* s, int32_t n, int64_t discard, int64_t thin, std::vector<ChainView>* out,
+                         int32_t* device) {
+    if (!s || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
+    for (int32_t i = 0; i < n; ++i) {
+        if (!s[i]) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
+        if (!s[i]->ds.store_chain || s[i]->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
+        if (discard >= s[i]->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
+        if (s[i]->e->device != s[0]->e->device) return fail(LCF_ERR_UNSUPPORTED, "the samplers are on different devices");
+    }
+    out->resize(n);
+    for (int32_t i = 0; i < n; ++i) {
+        if (lcf_status st = settle(s[i])) return st;  // (the trailing commit writes the last chain row)
+        const DevSampler& ds = s[i]->ds;
+        (*out)[i] = ChainView{ds.chain, ds.chain_lp, s[i]->run_steps, ds.n_walkers, ds.n_dim, ds.n_dim};
+    }
+    *device = s[0]->e->device;
+    return LCF_OK;
+}
+
 // Whatever changes the state on the device makes the host's copy stale.
 static void invalidate_snapshot(lcf_sampler* s) { s->snap_enqueued = s->snap_valid = false; }
 
@@ -913,93 +934,6 @@ lcf_status lcf_sampler_get_chain(lcf_sampler* s, double* chain, double* log_prob
     if (log_prob)
         LCF_HIP(hipMemcpy(log_prob, ds.chain_lp, (size_t)s->run_steps * ds.n_walkers * sizeof(double), hipMemcpyDeviceToHost));
     return LCF_OK;
-}
-
-lcf_status lcf_samplers_autocorr_time(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double c,
-                                      double* tau, int64_t* window) {
-    if (!s || n < 1 || !tau || !window) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
-    if (!std::isfinite(c)) return fail(LCF_ERR_INVALID_ARGUMENT, "c must be finite");
-    for (int32_t i = 0; i < n; ++i) {
-        if (!s[i]) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
-        if (!s[i]->ds.store_chain || s[i]->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
-        if (discard >= s[i]->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
-        if (s[i]->e->device != s[0]->e->device) return fail(LCF_ERR_UNSUPPORTED, "the samplers are on different devices");
-    }
-    std::vector<AutocorrSeries> series(n);
-    for (int32_t i = 0; i < n; ++i) {
-        if (lcf_status st = settle(s[i])) return st;  // (the trailing commit writes the last chain row)
-        const DevSampler& ds = s[i]->ds;
-        const int64_t row = (int64_t)ds.n_walkers * ds.n_dim;
-        series[i] = AutocorrSeries{ds.chain + discard * row, (s[i]->run_steps - discard + thin - 1) / thin, thin * row,
-                                   ds.n_walkers, ds.n_dim};
-    }
-    return autocorr_run(s[0]->e->device, series.data(), n, c, tau, window);
-}
-
-// Rows discard, discard + thin, ... of every sampler's last stored run as the samples of a corner pass, where they lie.
-static lcf_status corner_samples(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin,
-                                 std::vector<CornerSamples>* in) {
-    if (!s || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    if (discard < 0 || thin < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need discard >= 0 and thin >= 1");
-    for (int32_t i = 0; i < n; ++i) {
-        if (!s[i]) return fail(LCF_ERR_INVALID_ARGUMENT, "null sampler");
-        if (!s[i]->ds.store_chain || s[i]->run_steps == 0) return fail(LCF_ERR_STATE, "no stored chain");
-        if (discard >= s[i]->run_steps) return fail(LCF_ERR_INVALID_ARGUMENT, "discard leaves no chain");
-        if (s[i]->e->device != s[0]->e->device) return fail(LCF_ERR_UNSUPPORTED, "the samplers are on different devices");
-    }
-    in->resize(n);
-    for (int32_t i = 0; i < n; ++i) {
-        if (lcf_status st = settle(s[i])) return st;  // (the trailing commit writes the last chain row)
-        const DevSampler& ds = s[i]->ds;
-        const int64_t row = (int64_t)ds.n_walkers * ds.n_dim, steps = (s[i]->run_steps - discard + thin - 1) / thin;
-        (*in)[i] = CornerSamples{ds.chain + discard * row, steps * ds.n_walkers, ds.n_walkers, thin * row, ds.n_dim,
-                                 ds.n_dim};
-    }
-    return LCF_OK;
-}
-
-lcf_status lcf_samplers_chain_range(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, double* lo, double* hi,
-                                    int64_t* n_nan) {
-    if (!lo || !hi || !n_nan) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    std::vector<CornerSamples> in;
-    if (lcf_status st = corner_samples(s, n, discard, thin, &in)) return st;
-    return corner_range_run(s[0]->e->device, in.data(), n, lo, hi, n_nan);
-}
-
-lcf_status lcf_samplers_chain_hist(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, const double* shift,
-                                   const double* edges, int32_t bins, int64_t* hist1d, int64_t* hist2d) {
-    std::vector<CornerSamples> in;
-    if (lcf_status st = corner_samples(s, n, discard, thin, &in)) return st;
-    return corner_hist_run(s[0]->e->device, in.data(), n, shift, edges, bins, hist1d, hist2d);
-}
-
-// Every sampler's last stored run, whole, as the chains of a history pass, where they lie.
-static lcf_status history_chains(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin,
-                                 std::vector<HistoryChain>* in) {
-    std::vector<CornerSamples> rows;   // (the checks, the status codes and the settling of corner_samples)
-    if (lcf_status st = corner_samples(s, n, discard, thin, &rows)) return st;
-    in->resize(n);
-    for (int32_t i = 0; i < n; ++i) {
-        const DevSampler& ds = s[i]->ds;
-        (*in)[i] = HistoryChain{ds.chain, ds.chain_lp, s[i]->run_steps, ds.n_walkers, ds.n_dim};
-    }
-    return LCF_OK;
-}
-
-lcf_status lcf_samplers_chain_history(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, const double* q,
-                                      int32_t n_q, double* stat_lo, double* stat_hi, int64_t* n_valid,
-                                      int64_t* n_moved) {
-    std::vector<HistoryChain> in;
-    if (lcf_status st = history_chains(s, n, discard, thin, &in)) return st;
-    return history_steps_run(s[0]->e->device, in.data(), n, discard, thin, q, n_q, stat_lo, stat_hi, n_valid, n_moved);
-}
-
-lcf_status lcf_samplers_chain_raster(lcf_sampler** s, int32_t n, int64_t discard, int64_t thin, int32_t t_bins,
-                                     const double* edges, int32_t v_bins, int64_t* counts) {
-    std::vector<HistoryChain> in;
-    if (lcf_status st = history_chains(s, n, discard, thin, &in)) return st;
-    return history_raster_run(s[0]->e->device, in.data(), n, discard, thin, t_bins, edges, v_bins, counts);
 }
 
 lcf_status lcf_sampler_get_naccepted(lcf_sampler* s, int64_t* n_accepted) {

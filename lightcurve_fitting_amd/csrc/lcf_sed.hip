@@ -394,11 +394,7 @@ lcf_status lcf_sed_create(int32_t n_filters, const int32_t* tab_off, const doubl
         if (have_ctab && (ctab_off[f + 1] < ctab_off[f] || ctab_off[0] != 0))
             return fail(LCF_ERR_INVALID_ARGUMENT, "ctab_off must start at 0 and be non-decreasing");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LCF_ERR_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LCF_ERR_INVALID_ARGUMENT, "device index out of range");
-    LCF_HIP(hipSetDevice(device));
+    if (lcf_status st = use_device(device)) return st;
     std::vector<double2> htab;
     std::vector<float2> htab32;
     std::vector<int4> hdesc(n_filters);

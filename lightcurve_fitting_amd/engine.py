@@ -234,6 +234,15 @@ def _ptr(a, typ=_dp):
     return a.ctypes.data_as(typ)
 
 
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _handles(native_samplers):
+    """The ``lcf_sampler**`` of a call that takes several :class:`NativeSampler` objects."""
+    return (C.c_void_p * len(native_samplers))(*[s._h for s in native_samplers])
+
+
 class Engine:
     """One light curve + one model instance resident on one MI355X.
 
@@ -611,7 +620,7 @@ class NativeSampler:
 
     def naccepted(self):
         out = np.empty(self.nwalkers, dtype=np.int64)
-        _check(self._lib.lcf_sampler_get_naccepted(self._h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        _check(self._lib.lcf_sampler_get_naccepted(self._h, _i64p(out)))
         return out
 
     def last_run_ms(self):
@@ -706,7 +715,7 @@ def population_run(native_samplers, first_step, nsteps, split='random', store=Tr
     """One batched native run over several :class:`NativeSampler` objects (population mode).  Returns device ms."""
     lib = load_library()
     n = len(native_samplers)
-    arr = (C.c_void_p * n)(*[s._h for s in native_samplers])
+    arr = _handles(native_samplers)
     mode = {'identity': SPLIT_IDENTITY, 'random': SPLIT_RANDOM}[split]
     ms = C.c_double()
     _check(lib.lcf_population_run(arr, n, int(first_step), int(nsteps), mode, int(bool(store)), C.byref(ms)))
@@ -870,8 +879,7 @@ def autocorr_time(chain, c=5., device=0):
         raise ValueError('chain must have shape (n_t, n_w, n_d)')
     n_t, n_w, n_d = x.shape
     tau, window = np.empty(n_d), np.empty(n_d, dtype=np.int64)
-    _check(lib.lcf_autocorr_time(int(device), _ptr(x), n_t, n_w, n_d, float(c), _ptr(tau),
-                                 window.ctypes.data_as(C.POINTER(C.c_int64))))
+    _check(lib.lcf_autocorr_time(int(device), _ptr(x), n_t, n_w, n_d, float(c), _ptr(tau), _i64p(window)))
     return tau, window
 
 
@@ -879,12 +887,10 @@ def samplers_autocorr_time(native_samplers, discard=0, thin=1, c=5.):
     """``lcf_samplers_autocorr_time``: the same for the device-resident chains of the last stored run of several
     :class:`NativeSampler` objects (one sequence of launches for all).  Returns a list of ``(tau, window)``."""
     lib = load_library()
-    n = len(native_samplers)
-    arr = (C.c_void_p * n)(*[s._h for s in native_samplers])
     total = sum(s.ndim for s in native_samplers)
     tau, window = np.empty(total), np.empty(total, dtype=np.int64)
-    _check(lib.lcf_samplers_autocorr_time(arr, n, int(discard), int(thin), float(c), _ptr(tau),
-                                          window.ctypes.data_as(C.POINTER(C.c_int64))))
+    _check(lib.lcf_samplers_autocorr_time(_handles(native_samplers), len(native_samplers), int(discard), int(thin),
+                                          float(c), _ptr(tau), _i64p(window)))
     out, k = [], 0
     for s in native_samplers:
         out.append((tau[k:k + s.ndim].copy(), window[k:k + s.ndim].copy()))
@@ -900,6 +906,18 @@ PREDICT_MAX_SEARCHES = 512
 PREDICT_WORKSPACE_BYTES = 1 << 30
 
 
+def _predict_call(lib, name, grid_engine, samples, discard, thin, tail):
+    """``lcf_sampler_<name>`` on the last stored run of a :class:`NativeSampler` (rows ``discard::thin``, read in
+    place), else ``lcf_<name>`` on a host array (n, ld); ``tail``: the arguments behind the samples."""
+    if isinstance(samples, NativeSampler):
+        _check(getattr(lib, 'lcf_sampler_' + name)(grid_engine.handle, samples._h, int(discard), int(thin), *tail))
+    else:
+        P = _f64(samples)
+        if P.ndim != 2:
+            raise ValueError('samples must have shape (n, n_columns)')
+        _check(getattr(lib, 'lcf_' + name)(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
+
+
 def predict_quantiles(grid_engine, samples, percentiles, component=COMPONENT_MODEL, workspace_bytes=None, discard=0,
                       thin=1):
     """``lcf_predict_quantiles`` / ``lcf_sampler_predict_quantiles``: percentiles over all samples of the model on
@@ -911,14 +929,8 @@ def predict_quantiles(grid_engine, samples, percentiles, component=COMPONENT_MOD
     out = np.empty((len(q), grid_engine.npoints))
     n_valid = np.empty(grid_engine.npoints, dtype=np.int64)
     ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
-    tail = (int(component), _ptr(q), len(q), ws, _ptr(out), n_valid.ctypes.data_as(C.POINTER(C.c_int64)))
-    if isinstance(samples, NativeSampler):
-        _check(lib.lcf_sampler_predict_quantiles(grid_engine.handle, samples._h, int(discard), int(thin), *tail))
-    else:
-        P = _f64(samples)
-        if P.ndim != 2:
-            raise ValueError('samples must have shape (n, n_columns)')
-        _check(lib.lcf_predict_quantiles(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
+    _predict_call(lib, 'predict_quantiles', grid_engine, samples, discard, thin,
+                  (int(component), _ptr(q), len(q), ws, _ptr(out), _i64p(n_valid)))
     return out, n_valid
 
 
@@ -938,15 +950,8 @@ def predict_thermal(grid_engine, samples, percentiles, T_floor=8.12, workspace_b
     n_valid = np.empty((THERMAL_SERIES, n_t), dtype=np.int64)
     n_cold, n_inside = np.empty(n_t, dtype=np.int64), np.empty(n_t, dtype=np.int64)
     ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
-    tail = (_ptr(q), len(q), float(T_floor), ws, _ptr(out)) + tuple(a.ctypes.data_as(C.POINTER(C.c_int64))
-                                                                   for a in (n_valid, n_cold, n_inside))
-    if isinstance(samples, NativeSampler):
-        _check(lib.lcf_sampler_predict_thermal(grid_engine.handle, samples._h, int(discard), int(thin), *tail))
-    else:
-        P = _f64(samples)
-        if P.ndim != 2:
-            raise ValueError('samples must have shape (n, n_columns)')
-        _check(lib.lcf_predict_thermal(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], *tail))
+    _predict_call(lib, 'predict_thermal', grid_engine, samples, discard, thin,
+                  (_ptr(q), len(q), float(T_floor), ws, _ptr(out), _i64p(n_valid), _i64p(n_cold), _i64p(n_inside)))
     return out, n_valid, n_cold, n_inside
 
 
@@ -993,17 +998,21 @@ def predict_luminosity(grid_engine, samples, percentiles, workspace_bytes=None, 
 CORNER_MAX_DIM, CORNER_MAX_BINS = 16, 128
 
 
-def _i64p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int64))
+def _native_list(samples):
+    """One :class:`NativeSampler` or a non-empty list of them as a list; None for anything else (a host array)."""
+    if isinstance(samples, NativeSampler):
+        samples = [samples]
+    if isinstance(samples, (list, tuple)) and samples and all(isinstance(s, NativeSampler) for s in samples):
+        return list(samples)
+    return None
 
 
 def _corner_sources(samples, device):
     """``(native samplers or None, host array or None, column counts)`` of what a corner call reads: one host array
     (n, n_columns), one :class:`NativeSampler` or a list of them."""
-    if isinstance(samples, NativeSampler):
-        samples = [samples]
-    if isinstance(samples, (list, tuple)) and samples and all(isinstance(s, NativeSampler) for s in samples):
-        return list(samples), None, [s.ndim for s in samples]
+    natives = _native_list(samples)
+    if natives is not None:
+        return natives, None, [s.ndim for s in natives]
     P = _f64(samples)
     if P.ndim != 2:
         raise ValueError('samples must have shape (n, n_columns)')
@@ -1023,8 +1032,7 @@ def chain_range(samples, discard=0, thin=1, device=0):
         _check(lib.lcf_chain_range(int(device), _ptr(P), P.shape[0], P.shape[1], P.shape[1], _ptr(lo), _ptr(hi),
                                    _i64p(n_nan)))
         return lo, hi, n_nan
-    arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
-    _check(lib.lcf_samplers_chain_range(arr, len(natives), int(discard), int(thin), _ptr(lo), _ptr(hi), _i64p(n_nan)))
+    _check(lib.lcf_samplers_chain_range(_handles(natives), len(natives), int(discard), int(thin), _ptr(lo), _ptr(hi), _i64p(n_nan)))
     at = np.concatenate([[0], np.cumsum(dims)])
     out = [(lo[i:j].copy(), hi[i:j].copy(), n_nan[i:j].copy()) for i, j in zip(at[:-1], at[1:])]
     return out if isinstance(samples, (list, tuple)) else out[0]
@@ -1057,9 +1065,8 @@ def chain_hist(samples, shift, edges, discard=0, thin=1, device=0):
         _check(lib.lcf_chain_hist(int(device), _ptr(P), P.shape[0], P.shape[1], P.shape[1], _ptr(sh), _ptr(ed), bins,
                                   _i64p(h1), h2p))
     else:
-        arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
-        _check(lib.lcf_samplers_chain_hist(arr, len(natives), int(discard), int(thin), _ptr(sh), _ptr(ed), bins,
-                                           _i64p(h1), h2p))
+        _check(lib.lcf_samplers_chain_hist(_handles(natives), len(natives), int(discard), int(thin), _ptr(sh), _ptr(ed),
+                                           bins, _i64p(h1), h2p))
     out, i, j = [], 0, 0
     for d, p in zip(dims, pairs):
         out.append((h1[i:i + d * bins].reshape(d, bins).copy(), h2[j:j + p * bins * bins].reshape(p, bins, bins).copy()))
@@ -1075,17 +1082,16 @@ def _history_sources(samples, discard, thin):
     """``(native samplers or None, host chain or None, [(n_keep, n_dim)])`` of what a history call reads: one host
     chain (n_t, n_w, n_dim), one :class:`NativeSampler` or a list of them.  ``n_keep`` is 0 where the native call will
     refuse (no stored run, ``discard`` past it)."""
-    if isinstance(samples, NativeSampler):
-        samples = [samples]
-    if isinstance(samples, (list, tuple)) and samples and all(isinstance(s, NativeSampler) for s in samples):
-        steps = [s._last[0] if getattr(s, '_last', (0, False))[1] else 0 for s in samples]
-        return list(samples), None, [(len(range(int(discard), n_t, int(thin))) if thin >= 1 and discard >= 0 else 0,
-                                      s.ndim) for n_t, s in zip(steps, samples)]
+    def n_keep(n_t):
+        return len(range(int(discard), n_t, int(thin))) if thin >= 1 and discard >= 0 else 0
+    natives = _native_list(samples)
+    if natives is not None:
+        steps = [s._last[0] if getattr(s, '_last', (0, False))[1] else 0 for s in natives]
+        return natives, None, [(n_keep(n_t), s.ndim) for n_t, s in zip(steps, natives)]
     x = _f64(samples)
     if x.ndim != 3:
         raise ValueError('chain must have shape (n_t, n_w, n_dim)')
-    n_keep = len(range(int(discard), x.shape[0], int(thin))) if thin >= 1 and discard >= 0 else 0
-    return None, x, [(n_keep, x.shape[2])]
+    return None, x, [(n_keep(x.shape[0]), x.shape[2])]
 
 
 def chain_history(samples, percentiles, log_prob=None, discard=0, thin=1, device=0):
@@ -1117,9 +1123,8 @@ def chain_history(samples, percentiles, log_prob=None, discard=0, thin=1, device
     else:
         if log_prob is not None:
             raise ValueError('log_prob goes with a host chain; a sampler brings its own')
-        arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
-        _check(lib.lcf_samplers_chain_history(arr, len(natives), int(discard), int(thin), _ptr(q), n_q, _ptr(lo),
-                                              _ptr(hi), _i64p(n_valid), _i64p(n_moved)))
+        _check(lib.lcf_samplers_chain_history(_handles(natives), len(natives), int(discard), int(thin), _ptr(q), n_q,
+                                              _ptr(lo), _ptr(hi), _i64p(n_valid), _i64p(n_moved)))
     out, c, k = [], 0, 0
     for (n_keep, n_dim), n_cell in zip(shapes, cells):
         shape = (n_q, n_keep, n_dim + 1)
@@ -1153,9 +1158,8 @@ def chain_raster(samples, t_bins, edges, discard=0, thin=1, device=0):
         _check(lib.lcf_chain_raster(int(device), _ptr(x), x.shape[0], x.shape[1], x.shape[2], int(discard), int(thin),
                                     t_bins, _ptr(ed), v_bins, _i64p(counts)))
     else:
-        arr = (C.c_void_p * len(natives))(*[s._h for s in natives])
-        _check(lib.lcf_samplers_chain_raster(arr, len(natives), int(discard), int(thin), t_bins, _ptr(ed), v_bins,
-                                             _i64p(counts)))
+        _check(lib.lcf_samplers_chain_raster(_handles(natives), len(natives), int(discard), int(thin), t_bins, _ptr(ed),
+                                             v_bins, _i64p(counts)))
     out, i = [], 0
     for (_, n_dim), size in zip(shapes, sizes):
         out.append(counts[i:i + size].reshape(n_dim, t_bins, v_bins).copy())
