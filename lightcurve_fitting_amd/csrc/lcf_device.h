@@ -307,7 +307,10 @@ __device__ inline double band_sum_fast(TabPtr tab, int cnt, double invT, const E
 // MODEL > 0: the model is a compile-time constant (kernels specialised for one model: the other models' code is not
 // even in the instruction stream); 0: pb.model decides at run time.
 // PB: DevProblem, or anything else with its `consts` and `model` (a resident launch's copy of them in LDS).
-template <int MODEL = 0, class PB = DevProblem>
+// POSITIVE (ShockCooling only): the caller has made the test for positive parameters itself and found it true; the
+// other branch -- pw, pow, sqrt, log -- is then not in the caller's instruction stream (the resident head calls it out
+// of line).
+template <int MODEL = 0, class PB = DevProblem, bool POSITIVE = false>
 __device__ inline void walker_coefficients(const PB& pb, const double* __restrict__ p,
                                            const double* __restrict__ lq, double* __restrict__ c,
                                            bool log_only = false) {
@@ -327,7 +330,7 @@ __device__ inline void walker_coefficients(const PB& pb, const double* __restric
             } else {
                 c[0] = p[4];
             }
-            if (v > 0. && M > 0. && f > 0. && R > 0. && v < 1e100 && M < 1e100 && f < 1e100 && R < 1e100) {
+            if (POSITIVE || (v > 0. && M > 0. && f > 0. && R > 0. && v < 1e100 && M < 1e100 && f < 1e100 && R < 1e100)) {
                 // all bases positive: every power() is a plain power; share the four logarithms
                 const double lv = lq[0], lM = lq[1], lf = lq[2], lR = lq[3];
                 const double a1 = eps1 * (2. * lv - lf) + 0.25 * lR, a2 = -eps2 * (lv - lf) + 2. * lv + lR;

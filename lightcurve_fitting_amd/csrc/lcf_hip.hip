@@ -1357,6 +1357,73 @@ template <bool AGENT = false>
 __device__ inline double board_take(const DevSampler& sm, unsigned int tag, int wid, int col, unsigned int arrive_goal = 0u) {
     return board_take_at<AGENT>(sm, board_entry(sm.board, sm, tag, wid, col), tag, wid, col, arrive_goal);
 }
+// ---- the poll of the resident kernels' head (k_solo_run): TWO entries per lane -------------------------------------
+// What board_take_at looks at on every 16th look, out of line: the poll loop of the one wave everybody waits for is then
+// a load pair, the tag tests and a sleep.  Same order, bounds and error words as board_take_at.
+// Returns 0: keep waiting; 2: keep waiting, and every workgroup of the launch is known to have started; 1: the launch
+// is aborted.  `seen`: the entry as last loaded (what an abort leaves for diagnosis).
+template <bool AGENT>
+__device__ __attribute__((noinline)) int board_wait_check(const DevSampler* smp, unsigned long long t0, bool resident,
+                                                          unsigned int arrive_goal, unsigned int tag, int wid, int col,
+                                                          lcf_u32x4 seen) {
+    const DevSampler& sm = *smp;
+    if (board_aborted<AGENT>(sm)) return 1;
+    int state = 0;
+    if (!resident && wall_clock64() - t0 > sm.resident_ticks) {
+        const unsigned int there = __hip_atomic_load(board_arrivals(sm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((int)(there - arrive_goal) < 0) {
+            board_abort(sm, 3u, tag, (unsigned int)wid, there);
+            return 1;
+        }
+        state = 2;
+    }
+    if (wall_clock64() - t0 > sm.wait_ticks) {
+        const bool was_first = !board_aborted<AGENT>(sm);
+        board_abort(sm, 1u, tag, (unsigned int)wid, (unsigned int)col);
+        if (was_first) {   // (what the entry holds instead: an older tag = never posted)
+            unsigned int* out = board_arrivals(sm) + 1;
+            out[0] = seen.x;
+            out[1] = seen.y;
+            out[2] = seen.z;
+            out[3] = seen.w;
+        }
+        return 1;
+    }
+    return state;
+}
+// The numbers of the entries `pa` (tag `tag_a`, walker `wid_a`) and `pb_` (`tag_b`, `wid_b`), both column `col`, once BOTH
+// are there: each look requests the two 16-byte entries back to back and waits once, so every entry is still sampled
+// once per look, on the lane that uses it.  (A lane with one entry to wait for passes it twice.)  NaN after an abort.
+template <bool AGENT>
+__device__ __forceinline__ void board_take_pair(const DevSampler& sm, const unsigned long long* pa, const unsigned long long* pb_,
+                                                unsigned int tag_a, unsigned int tag_b, int wid_a, int wid_b, int col,
+                                                unsigned int arrive_goal, double& va, double& vb) {
+    const unsigned long long t0 = wall_clock64();
+    bool resident = arrive_goal == 0u;
+    for (int spin = 0;; ++spin) {
+        lcf_u32x4 a, b;
+        asm volatile("global_load_dwordx4 %0, %2, off sc0 sc1\n\tglobal_load_dwordx4 %1, %3, off sc0 sc1\n\ts_waitcnt vmcnt(0)"
+                     : "=&v"(a), "=&v"(b) : "v"(pa), "v"(pb_) : "memory");
+        const bool a_ok = a.y == tag_a && a.w == tag_a, b_ok = b.y == tag_b && b.w == tag_b;
+        if (a_ok && b_ok) {
+            va = __hiloint2double((int)a.z, (int)a.x);
+            vb = __hiloint2double((int)b.z, (int)b.x);
+            return;
+        }
+        if ((spin & 15) == 15) {
+            // (the entry this lane still waits for)
+            const int state = board_wait_check<AGENT>(&sm, t0, resident, arrive_goal, a_ok ? tag_b : tag_a, a_ok ? wid_b : wid_a,
+                                                      col, a_ok ? b : a);
+            if (state == 1) {
+                va = vb = qnan();
+                return;
+            }
+            resident = resident || state == 2;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+}
+
 // Version of a row a half-step G asks for: the walker's last move was `age` half-steps ago; rows nobody has moved in
 // this run carry the run's start tag.
 __device__ inline unsigned int board_tag(long long G, int age, long long g_run0) {
@@ -1422,14 +1489,12 @@ struct HeadRows {
     PriorDev prior;         // lane d: the prior of parameter d
 };
 
-// RES (the resident k_solo_run): what does not change within a launch comes from the launch's block in LDS, `ru`
-// (RunUniforms), not through scalar loads from `pb` / `sm`.
-template <int ND, int BOARD = 0, bool RES = false>
+// (The resident k_solo_run has a head of its own: lane_head_fetch / lane_head below.)
+template <int ND, int BOARD = 0>
 __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSampler& sm, const DrawRec& dr, int lane,
-                                           HeadRows<ND>& h, long long G = 0, long long g_run0 = 0, unsigned int arrive_goal = 0u,
-                                           const RunUniforms* ru = nullptr) {
+                                           HeadRows<ND>& h, long long G = 0, long long g_run0 = 0, unsigned int arrive_goal = 0u) {
     constexpr int kD = ND > 0 ? ND : kMaxDim;
-    const int nd = ND > 0 ? ND : RES ? __builtin_amdgcn_readfirstlane(ru->nd) : sm.n_dim;
+    const int nd = ND > 0 ? ND : sm.n_dim;
     const double* xs = sm.X + (size_t)dr.wid * nd;
     const double* cs_ = sm.X + (size_t)dr.pid * nd;
     h.got = 0.;
@@ -1439,10 +1504,7 @@ __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSample
         if (own ? col <= nd + 1 : col < nd) {
             const unsigned int tag = board_tag(G, own ? dr.wage : dr.page, g_run0);
             const int who = own ? dr.wid : dr.pid;
-            if constexpr (RES)
-                h.got = board_take_at<BOARD == 2>(sm, board_entry(ru->board, *ru, tag, who, col), tag, who, col, arrive_goal);
-            else
-                h.got = board_take<BOARD == 2>(sm, tag, who, col, arrive_goal);
+            h.got = board_take<BOARD == 2>(sm, tag, who, col, arrive_goal);
         }
     }
     h.lp_i = BOARD ? lane_value(h.got, 16 + nd) : sm.LP[dr.wid];
@@ -1453,25 +1515,16 @@ __device__ __forceinline__ void head_fetch(const DevProblem& pb, const DevSample
     }
     // (measured: requesting the prior in FRONT of the poll instead changes nothing -- 5.45 against 5.43 us; its way from L2
     // is hidden behind the logarithms either way)
-    if constexpr (RES) {
-        // (the block holds a flat prior where the problem has none; lanes >= kMaxDim read the entry of lane - 16, 32, 48
-        // and never use it: proposal_head takes a prior's term from lanes below n_dim only)
-        h.prior = ru->priors[not_hoisted(lane) & (kMaxDim - 1)];
-    } else {
-        h.prior = PriorDev{0, 0, 0., 0., 0., 1.};
-        if (lane < pb.n_dim && pb.has_priors) h.prior = pb.priors[lane];
-    }
+    h.prior = PriorDev{0, 0, 0., 0., 0., 1.};
+    if (lane < pb.n_dim && pb.has_priors) h.prior = pb.priors[lane];
 }
 
-template <int ND, int BOARD = 0, int MODEL = 0, bool RES = false>
+template <int ND, int BOARD = 0, int MODEL = 0>
 __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSampler& sm, const DrawRec& dr, int lane,
                                               double* __restrict__ sc, double* __restrict__ sq, double* __restrict__ sx,
-                                              const HeadRows<ND>& h, const RunUniforms* ru = nullptr) {
+                                              const HeadRows<ND>& h) {
     constexpr int kD = ND > 0 ? ND : kMaxDim;
-    const int nd = ND > 0 ? ND : RES ? __builtin_amdgcn_readfirstlane(ru->nd) : sm.n_dim;
-    // (RES: the head's share of the block, requested together; has_priors as a scalar, for the branch)
-    int n_par_r = 0, n_dim_r = 0, has_priors_r = 0;
-    if constexpr (RES) n_par_r = ru->n_par, n_dim_r = ru->n_dim, has_priors_r = __builtin_amdgcn_readfirstlane(ru->has_priors);
+    const int nd = ND > 0 ? ND : sm.n_dim;
     const PriorDev my_prior = h.prior;
     double x[kD], q[kMaxDim], lq[kMaxDim];
 #pragma unroll
@@ -1484,7 +1537,7 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
         x[d] = h.x[d];
         const double cj = h.cj[d];
         q[d] = d < nd ? cj - (cj - x[d]) * dr.z : 0.;   // emcee: c_j - (c_j - x_i) z
-        if (lane == d && d < (RES ? n_par_r : pb.n_par)) arg = q[d];
+        if (lane == d && d < pb.n_par) arg = q[d];
     }
 #ifdef LCF_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1495,18 +1548,15 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
     for (int d = 0; d < kD; ++d) lq[d] = lane_value(lg, d);
     LCF_STAMP(0, 3);
     double c[kNCoef];
-    if constexpr (RES)
-        walker_coefficients<MODEL>(ConstsView{ru->consts, MODEL ? MODEL : ru->model}, q, lq, c, MODEL ? true : pb.use_itab != 0);
-    else
-        walker_coefficients<MODEL>(pb, q, lq, c, MODEL ? true : pb.use_itab != 0);
+    walker_coefficients<MODEL>(pb, q, lq, c, MODEL ? true : pb.use_itab != 0);
     LCF_STAMP(0, 4);
     double lpr = 0.;
-    if (RES ? has_priors_r : pb.has_priors) {
+    if (pb.has_priors) {
         double qv = 0.;
 #pragma unroll
         for (int d = 0; d < kD; ++d)
             if (lane == d) qv = q[d];
-        const double mine = lane < (RES ? n_dim_r : pb.n_dim) ? prior_term(my_prior, qv) : 0.;
+        const double mine = lane < pb.n_dim ? prior_term(my_prior, qv) : 0.;
 #pragma unroll
         for (int d = 0; d < kD; ++d)
             if (d < nd) lpr += lane_value(mine, d);   // the same ordered sum as walker_log_prior
@@ -1524,6 +1574,121 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
             }
         sx[kMaxDim] = lp_i;
         if (BOARD) sx[kMaxDim + 1] = count;   // the walker's acceptance count so far
+    }
+    LCF_STAMP(0, 5);
+}
+
+// ---- the head of the RESIDENT kernels (k_solo_run), lane-parallel ---------------------------------------------------
+// The same numbers as head_fetch + proposal_head, operation for operation, but every value stays on the lane that uses
+// it: lane d < nd polls for the partner's coordinate d AND the walker's (lanes nd, nd + 1: the walker's log-posterior and
+// acceptance count), computes its own coordinate of the proposal and its logarithm, takes its own prior's term, and
+// writes its own words of sq / sx.  Only what the coefficients read and the terms of the log-prior -- summed in order --
+// travel through scalar registers; lane 0 writes coefficients and log-prior.  The LDS layout is proposal_head's.
+// What does not change within a launch comes from the launch's block in LDS, `ru` (RunUniforms).
+struct LaneRows {
+    double cj, x;     // lane d < nd: coordinate d of the partner, of the walker; lanes nd, nd + 1: x = log-posterior, count
+    PriorDev prior;   // lane d: the prior of parameter d
+};
+
+template <int ND, int BOARD>
+__device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const DrawRec& dr, int lane_in, LaneRows& h, long long G,
+                                                long long g_run0, unsigned int arrive_goal, const RunUniforms* ru) {
+    const int nd = ND > 0 ? ND : __builtin_amdgcn_readfirstlane(ru->nd);
+    const int lane = not_hoisted(lane_in);   // (lane masks and addresses: computed here, not carried across the launch)
+    h.cj = h.x = 0.;
+    if (lane <= nd + 1) {
+        const unsigned int wtag = board_tag(G, dr.wage, g_run0), ptag = board_tag(G, dr.page, g_run0);
+        // (lanes nd, nd + 1 have no entry of the partner's to wait for: they ask for their own twice)
+        const bool both = lane < nd;
+        const unsigned int tag_l = both ? ptag : wtag;
+        const int wid_l = both ? dr.pid : dr.wid;
+        board_take_pair<BOARD == 2>(sm, board_entry(ru->board, *ru, tag_l, wid_l, lane), board_entry(ru->board, *ru, wtag, dr.wid, lane),
+                                    tag_l, wtag, wid_l, dr.wid, lane, arrive_goal, h.cj, h.x);
+    }
+    // (the block holds a flat prior where the problem has none; lanes >= kMaxDim read the entry of lane - 16, 32, 48 and
+    // never use it: a prior's term is taken from lanes below n_dim only)
+    h.prior = ru->priors[lane & (kMaxDim - 1)];
+}
+
+// ShockCooling with a parameter that is not positive: the coefficients through pw / pow / sqrt / log, ~1300 instructions
+// that a fit hardly ever executes, out of line as cold_column is.  `p_mem`: the proposal (sq), `c_mem`: where the
+// coefficients go (sc), both in LDS; lane 0 (`write`) stores them.
+template <int MODEL>
+__device__ __attribute__((noinline)) void cold_coefficients(const double* consts, const double* p_mem, double* c_mem, bool write) {
+    static_assert(MODEL == kShockCooling, "the model whose coefficients have a branch worth moving out");
+    double p[kMaxDim], lq[kMaxDim], c[kNCoef];
+#pragma unroll
+    for (int d = 0; d < kMaxDim; ++d) p[d] = lq[d] = 0.;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) p[d] = p_mem[d];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) lq[d] = flog(p[d]);   // (as the one-thread-per-walker callers take them; this branch reads none)
+    walker_coefficients<MODEL>(ConstsView{consts, MODEL}, p, lq, c, true);
+    if (write) {
+#pragma unroll
+        for (int k = 0; k < kNCoef; ++k) c_mem[k] = c[k];
+    }
+}
+
+template <int ND, int BOARD, int MODEL>
+__device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& dr, int lane_in, double* __restrict__ sc,
+                                          double* __restrict__ sq, double* __restrict__ sx, const LaneRows& h,
+                                          const RunUniforms* ru) {
+    constexpr int kD = ND > 0 ? ND : kMaxDim;
+    const int nd = ND > 0 ? ND : __builtin_amdgcn_readfirstlane(ru->nd);
+    const int lane = not_hoisted(lane_in);
+    // (the head's share of the block, requested together; has_priors as a scalar, for the branch)
+    const int n_par = ru->n_par, n_dim = ru->n_dim, has_priors = __builtin_amdgcn_readfirstlane(ru->has_priors);
+    const double cj = h.cj, x = h.x;
+    const double q = lane < nd ? cj - (cj - x) * dr.z : 0.;   // emcee: c_j - (c_j - x_i) z
+#ifdef LCF_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    LCF_STAMP(0, 2);
+    // proposal, position, log-posterior and count: one store each, from the lanes that hold them
+    if (lane < nd) sq[lane] = q;
+    if (lane <= nd + 1) sx[lane < nd ? lane : lane - nd + kMaxDim] = x;
+    const double lg = flog(lane < n_par ? q : 1.);
+    // what the coefficients read, wave-uniform (a kernel compiled for one model keeps only the broadcasts its model uses)
+    double p[kMaxDim], lq[kMaxDim];
+#pragma unroll
+    for (int d = 0; d < kMaxDim; ++d) p[d] = lq[d] = 0.;
+#pragma unroll
+    for (int d = 0; d < kD; ++d) {
+        p[d] = lane_value(q, d);
+        lq[d] = lane_value(lg, d);
+    }
+    LCF_STAMP(0, 3);
+    double c[kNCoef];
+    bool c_stored = false;
+    if constexpr (MODEL == kShockCooling) {
+        // (walker_coefficients' own test, made here so that only its plain-power branch is inlined)
+        const double v = p[0], M = p[1], f = p[2], R = p[3];
+        if (v > 0. && M > 0. && f > 0. && R > 0. && v < 1e100 && M < 1e100 && f < 1e100 && R < 1e100) {
+            walker_coefficients<MODEL, ConstsView, true>(ConstsView{ru->consts, MODEL}, p, lq, c, true);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kNCoef; ++k) c[k] = 0.;
+            cold_coefficients<MODEL>(ru->consts, sq, sc, lane == 0);
+            c_stored = true;
+        }
+    } else {
+        walker_coefficients<MODEL>(ConstsView{ru->consts, MODEL ? MODEL : ru->model}, p, lq, c, MODEL ? true : pb.use_itab != 0);
+    }
+    LCF_STAMP(0, 4);
+    double lpr = 0.;
+    if (has_priors) {
+        const double mine = lane < n_dim ? prior_term(h.prior, q) : 0.;
+#pragma unroll
+        for (int d = 0; d < kD; ++d)
+            if (d < nd) lpr += lane_value(mine, d);   // the same ordered sum as walker_log_prior
+    }
+    if (lane == 0) {
+        if (!c_stored) {
+#pragma unroll
+            for (int k = 0; k < kNCoef; k += 2) *reinterpret_cast<double2*>(sc + k) = make_double2(c[k], c[k + 1]);
+        }
+        sc[kNCoef] = lpr;
     }
     LCF_STAMP(0, 5);
 }
@@ -1612,10 +1777,17 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         // per half-step both workgroups are in their heads at once and the priority only starves the staging waves:
         // 8.06 against 7.71 us)
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);
-        HeadRows<ND> rows;
-        head_fetch<ND, BOARD, RES>(pb, sm, dr, tid, rows, G, g_run0, arrive_goal, ru);
-        if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
-        proposal_head<ND, BOARD, MODEL, RES>(pb, sm, dr, tid, sc, sq, sx, rows, ru);
+        if constexpr (RES) {
+            LaneRows rows;
+            lane_head_fetch<ND, BOARD>(sm, dr, tid, rows, G, g_run0, arrive_goal, ru);
+            if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
+            lane_head<ND, BOARD, MODEL>(pb, dr, tid, sc, sq, sx, rows, ru);
+        } else {
+            HeadRows<ND> rows;
+            head_fetch<ND, BOARD>(pb, sm, dr, tid, rows, G, g_run0, arrive_goal);
+            if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
+            proposal_head<ND, BOARD, MODEL>(pb, sm, dr, tid, sc, sq, sx, rows);
+        }
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(0);
     } else {
         if (LCF_HEAD_START > 0) __builtin_amdgcn_s_sleep(LCF_HEAD_START);
