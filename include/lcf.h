@@ -250,6 +250,12 @@ int32_t lcf_sampler_last_run_kernel(const lcf_sampler* s);
 /* Launches of that kernel in the last single-GPU run (lcf_sampler_run / _run_async): two per step, or -- k_solo_run --
  * one per block of up to 128 steps (between ranks: 32); lcf_population_run: launches per run of the kernel it took. */
 int64_t lcf_sampler_last_run_launches(const lcf_sampler* s);
+/* The template instance <ND, NP, M, ranks> the last run's half-step kernel was launched with: ND the compile-time fit
+ * dimension (0: the generic kernel, dimension at run time), NP the parts per workgroup (2, 4, or 8 = the 1024-thread
+ * form; 0 for lcf_population_run, whose kernels take the parts at run time), M the model whose own kernel it was (0:
+ * none), ranks 1 for a row-board run.  Four times -1 where no such kernel ran: k_fused, the separate launches, no run yet.
+ * Host bookkeeping for tests and measurements: which row of the instantiation table a problem shape reaches. */
+void lcf_sampler_last_run_instance(const lcf_sampler* s, int32_t out[4]);
 
 /* Multi-GPU building blocks: one half-step split into phases so that the caller can all-gather the shard's new
  * log-probabilities (RCCL) between phase 2 and phase 3.  All enqueue on `stream` without host sync.

@@ -3562,7 +3562,8 @@ static size_t solo_lds_bytes(const lcf_engine* e) {
 static size_t run_lds_bytes(const lcf_engine* e) { return solo_lds_bytes(e) + sizeof(RunUniforms); }
 
 bool solo_eligible(const lcf_sampler* s) {
-    static const bool disabled = std::getenv("LCF_NO_SOLO") != nullptr;
+    // (LCF_NO_FUSED=1 asks for the separate launches: neither one-launch form then, as set_half_step_kernel('phases'))
+    static const bool disabled = std::getenv("LCF_NO_SOLO") != nullptr || std::getenv("LCF_NO_FUSED") != nullptr;
     const lcf_engine* e = s->e;
     // (the libm band sum, variant 0, exists to mirror the reference instruction for instruction: it keeps k_fused)
     // (and light curves without shared epochs -- thermal state per point, inside the point loop -- keep k_fused too: there
@@ -3605,6 +3606,7 @@ lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board
     const auto go = [&](auto nd, auto np_, auto m) {
         constexpr int ND = decltype(nd)::value, NP = decltype(np_)::value, M = decltype(m)::value;
         const auto kernel = board ? k_solo<ND, 1, true, NP, true, M> : k_solo<ND, 1, true, NP, false, M>;
+        s->set_instance(ND, NP, M, board ? 1 : 0);
         if ((err = prepare_kernel(kernel, lds)) == hipSuccess)
             hipLaunchKernelGGL(kernel, grid, dim3(kBlock * (NP == 8 ? 4 : 2)), lds, st, e->d_dp, ds, row, draws, draws_next, G,
                                g_run0, lo);
@@ -3646,15 +3648,19 @@ static bool wide_runs() {
     const char* env = std::getenv("LCF_WIDE_RUNS");
     return !(env && env[0] == '0');
 }
+// (the launches that take them -- and with LCF_NO_WIDE_SOLO=1 the same launches, resident all the same, at 512 threads)
+static bool run_wide_size(const lcf_sampler* s, int proposals) {
+    return s->e->dp.n_parts > 2 && proposals <= s->e->n_cus && has_dim(WideRuns{}, s->ds.n_dim);
+}
 static bool run_wide(const lcf_sampler* s, int proposals) {
     static const bool no_wide = std::getenv("LCF_NO_WIDE_SOLO") != nullptr;
-    return !no_wide && s->e->dp.n_parts > 2 && proposals <= s->e->n_cus && has_dim(WideRuns{}, s->ds.n_dim);
+    return !no_wide && run_wide_size(s, proposals);
 }
 // Launches of `width` proposals that take resident workgroups: up to `slots` proposals where a light curve has more
 // than two parts (the rank's share of a row-board run: up to two slots per workgroup, rows_resident_eligible).
 static bool resident_size(const lcf_sampler* s, int width, int slots) {
     if (s->e->dp.n_parts <= 2) return width <= 4 * kRunSlots;
-    return (width > s->e->n_cus || (wide_runs() && run_wide(s, width))) && width <= slots;
+    return (width > s->e->n_cus || (wide_runs() && run_wide_size(s, width))) && width <= slots;
 }
 bool run_eligible(const lcf_sampler* s) {
     static const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr;
@@ -3832,6 +3838,7 @@ lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, b
             return;
         }
         if (dry) return;
+        s->set_instance(ND, NP, M, decltype(ranks_)::value ? 1 : 0);
         const int n_wg = std::min(hi - lo, cap);
         const dim3 grid((unsigned)(test_missing && n_wg > 1 ? n_wg - 1 : n_wg));
         arrivals += (unsigned int)n_wg;   // (0 = "no check": skipped when the count wraps onto it)
@@ -4307,6 +4314,7 @@ struct PopPlan {
     decltype(&k_pop_run<0, 1, kPopRunGroup, 0>) run_kernel = nullptr;
     int cap = 0, chunk = 0, run_grid = 0;
     RunClaim claim{0, nullptr, false};
+    int instance[4] = {-1, -1, -1, -1};        // <ND, 0, M, 0> of the k_pop / k_pop_run taken (no NP: parts at run time)
     // the run's GenItems (batched generation only) and items in device memory, freed with the plan on every way out
     GenItem* d_gen = nullptr;
     MultiItem* d_items = nullptr;
@@ -4344,7 +4352,10 @@ lcf_status plan_resident(lcf_sampler** ss, int n, long long g, PopPlan& p) {
     if (p.run_lds > kLdsPerCU) return LCF_OK;
     const auto own = [&](auto nd, auto m) {
         p.run_kernel = k_pop_run<decltype(nd)::value, 1, kPopRunGroup, decltype(m)::value>;
+        p.instance[0] = decltype(nd)::value;
+        p.instance[2] = decltype(m)::value;
     };
+    p.instance[0] = p.instance[1] = p.instance[2] = p.instance[3] = 0;
     if (!dispatch_model(PopRunModels{}, p.same_dim, p.pop_spec, own)) p.run_kernel = k_pop_run<0, 1, kPopRunGroup, 0>;
     int per_cu = 0;
     LCF_HIP(prepare_kernel(p.run_kernel, p.run_lds, 64 * kPopRunGroup, &per_cu));
@@ -4452,11 +4463,16 @@ lcf_status enqueue_pop_run(lcf_sampler** ss, int n, PopPlan& p, int64_t n_steps,
 }
 
 // One launch per half-step: k_pop, a workgroup per kPopGroup proposals, accept test included.
-lcf_status enqueue_pop(lcf_sampler** ss, int n, const PopPlan& p, int64_t n_steps, hipStream_t st) {
+lcf_status enqueue_pop(lcf_sampler** ss, int n, PopPlan& p, int64_t n_steps, hipStream_t st) {
     const int nh = ss[0]->ds.n_half;
     const dim3 grid((unsigned)((nh + kPopGroup - 1) / kPopGroup), (unsigned)n), block(64 * kPopGroup);
     decltype(&k_pop<0, 1, kPopGroup, 0>) kernel = nullptr;   // k_pop<ND, 1, kPopGroup, M> of the population's shape
-    const auto own = [&](auto nd, auto m) { kernel = k_pop<decltype(nd)::value, 1, kPopGroup, decltype(m)::value>; };
+    const auto own = [&](auto nd, auto m) {
+        kernel = k_pop<decltype(nd)::value, 1, kPopGroup, decltype(m)::value>;
+        p.instance[0] = decltype(nd)::value;
+        p.instance[2] = decltype(m)::value;
+    };
+    p.instance[1] = p.instance[3] = 0;
     dispatch(PopDims{}, p.same_dim, [&](auto nd) {
         if (!dispatch_model(SpecialisedModels{}, nd, p.pop_spec, own)) own(nd, Int<0>{});
     });
@@ -4566,6 +4582,8 @@ lcf_status population_run(lcf_sampler** ss, int n, int64_t first_step, int64_t n
         ss[t]->last_rows = false;
         ss[t]->last_kernel = p.form;
         ss[t]->last_launches = launches;
+        if (p.form == LCF_KERNEL_POPULATION_PHASES) ss[t]->set_instance(-1, -1, -1, -1);
+        else ss[t]->set_instance(p.instance[0], p.instance[1], p.instance[2], p.instance[3]);
         gave_up = gave_up || (p.form == LCF_KERNEL_POPULATION_RUN && (reported_error(ss[t]) & 2));
     }
     if (gave_up) {   // (rewind_resident_run; the caller repeats the steps with a launch per half-step)

@@ -311,6 +311,14 @@ struct lcf_sampler {
     int last_kernel = -1;     // what the last run's half-steps were (lcf_sampler_last_run_kernel)
     bool last_rows = false;   // ... and whether it was a row-board run (between ranks)
     long long last_launches = 0;   // launches of that kernel in the last run (lcf_sampler_last_run_launches)
+    // <ND, NP, M, ranks> of the half-step kernel launched last (lcf_sampler_last_run_instance; -1: k_fused / phases)
+    int last_instance[4] = {-1, -1, -1, -1};
+    void set_instance(int nd, int np, int m, int ranks) {
+        last_instance[0] = nd;
+        last_instance[1] = np;
+        last_instance[2] = m;
+        last_instance[3] = ranks;
+    }
     unsigned long long* mailbox = nullptr;   // this rank's peer mailbox (uncached device memory), see DevSampler
     size_t mailbox_cap = 0;
     void* board_mem = nullptr;               // this rank's row board (uncached device memory), see DevSampler

@@ -749,6 +749,10 @@ int32_t lcf_sampler_last_run_kernel(const lcf_sampler* s) { return s ? s->last_k
 
 int64_t lcf_sampler_last_run_launches(const lcf_sampler* s) { return s ? s->last_launches : 0; }
 
+void lcf_sampler_last_run_instance(const lcf_sampler* s, int32_t out[4]) {
+    for (int k = 0; out && k < 4; ++k) out[k] = s ? s->last_instance[k] : -1;
+}
+
 int32_t lcf_sampler_one_launch(const lcf_sampler* s) { return s && (solo_eligible(s) || fused_eligible(s)) ? 1 : 0; }
 
 lcf_status lcf_sampler_half_step_rows(lcf_sampler* s, int64_t step, int32_t half, int32_t lo, int32_t hi,
@@ -880,6 +884,7 @@ lcf_status lcf_sampler_run_async(lcf_sampler* s, int64_t first_step, int64_t n_s
     const bool fused = fused_eligible(s);
     s->last_kernel = solo_eligible(s) ? LCF_KERNEL_SOLO : fused ? LCF_KERNEL_FUSED : LCF_KERNEL_PHASES;
     s->last_launches = 2 * n_steps;
+    s->set_instance(-1, -1, -1, -1);   // (k_solo's launches record theirs)
     if (solo_eligible(s)) {  // one workgroup per proposal, nothing pending between launches
         for (int64_t k = 0; k < 2 * n_steps; ++k)
             if (lcf_status r = launch_solo(s, k, st)) return r;

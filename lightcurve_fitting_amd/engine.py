@@ -109,6 +109,7 @@ SIGNATURES = [
     ('lcf_sampler_set_half_step_kernel', C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     ('lcf_sampler_last_run_kernel', C.c_int32, [C.c_void_p]),
     ('lcf_sampler_last_run_launches', C.c_int64, [C.c_void_p]),
+    ('lcf_sampler_last_run_instance', None, [C.c_void_p, C.POINTER(C.c_int32)]),
     ('lcf_sampler_half_step_rows', C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ('lcf_sampler_rows_ptr', C.c_void_p, [C.c_void_p, C.POINTER(C.c_int32)]),
     ('lcf_sampler_check', C.c_int, [C.c_void_p]),
@@ -572,6 +573,14 @@ class NativeSampler:
         a population) | 'population-run' (k_pop_run: resident workgroups for all transients) | 'population-phases'
         (None: no run yet)."""
         return KERNEL_NAMES.get(self._lib.lcf_sampler_last_run_kernel(self._h))
+
+    def last_run_instance(self):
+        """``(ND, NP, M, ranks)`` of the template instance the last run's half-step kernel was launched with: the
+        compile-time fit dimension (0: generic), parts per workgroup (8: 1024 threads; 0: a population's kernels), the
+        model whose own kernel it was (0: none), 1 for a row-board run.  Four times -1 for 'fused' / 'phases' / no run."""
+        out = (C.c_int32 * 4)()
+        self._lib.lcf_sampler_last_run_instance(self._h, out)
+        return tuple(int(v) for v in out)
 
     def last_run_launches(self):
         """Launches of the half-step kernel in the last single-GPU run (two per step; 'run': one per block of steps)."""

@@ -151,6 +151,18 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(E.LcfPrior) == 40
 
 
+def test_last_run_instance_is_bound_and_answers_without_a_sampler():
+    """`lcf_sampler_last_run_instance` (read-only host bookkeeping; the ABI version stays): declared, bound with its
+    prototype, and four times -1 where there is no sampler -- as for a sampler that has not run."""
+    header = open(os.path.join(ROOT, 'include', 'lcf.h')).read()
+    assert re.search(r'void lcf_sampler_last_run_instance\(const lcf_sampler\* s, int32_t out\[4\]\);', header)
+    assert ('lcf_sampler_last_run_instance', None, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]) in E.SIGNATURES
+    out = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    E.load_library().lcf_sampler_last_run_instance(None, out)
+    assert list(out) == [-1, -1, -1, -1]
+    assert E.load_library().lcf_abi_version() == E.LCF_ABI_VERSION == 8 and hasattr(E.NativeSampler, 'last_run_instance')
+
+
 def test_engine_fails_loudly_without_gpu():
     lib = E.load_library()
     if lib.lcf_device_count() > 0:
