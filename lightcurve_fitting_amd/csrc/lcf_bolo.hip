@@ -128,33 +128,37 @@ __global__ __launch_bounds__(kLstsqBlock) void k_bb_lstsq(long long n_epochs, co
         } else {
             s1 = -P.g1 / m11;
         }
-        if (!isfinite(s0) || !isfinite(s1)) {   // (a singular free block: damp harder)
+        bool accepted = false;
+        if (isfinite(s0) && isfinite(s1)) {
+            const double Tn = fmin(fmax(T + s0, lo0), hi0), Rn = fmin(fmax(R + s1, lo1), hi1);
+            const double dT = Tn - T, dR = Rn - R;
+            if (fabs(dT) <= xtol * fabs(T) && fabs(dR) <= xtol * fabs(R)) {
+                st = 1;
+                break;
+            }
+            const Pass Q = bb_pass(freq, lum, i0, i1, zp1, cut, s, Tn, Rn);
+            // reduction the linear model predicts for the projected step
+            const double pred =
+                -(P.g0 * dT + P.g1 * dR) - 0.5 * (P.a00 * dT * dT + 2. * P.a01 * dT * dR + P.a11 * dR * dR);
+            if (isfinite(Q.cost) && Q.cost < P.cost) {
+                const double rho = pred > 0. ? (P.cost - Q.cost) / pred : 1.;
+                const double t = 2. * rho - 1.;
+                lambda *= fmax(1. / 3., 1. - t * t * t);
+                nu = 2.;
+                T = Tn;
+                R = Rn;
+                P = Q;
+                accepted = true;
+            }
+        }
+        if (!accepted) {   // a rejected step, or a singular free block: damp harder
             lambda *= nu;
             nu *= 2.;
-            continue;
         }
-        const double Tn = fmin(fmax(T + s0, lo0), hi0), Rn = fmin(fmax(R + s1, lo1), hi1);
-        const double dT = Tn - T, dR = Rn - R;
-        if (fabs(dT) <= xtol * fabs(T) && fabs(dR) <= xtol * fabs(R)) {
-            st = 1;
-            break;
-        }
-        const Pass Q = bb_pass(freq, lum, i0, i1, zp1, cut, s, Tn, Rn);
-        // reduction the linear model predicts for the projected step
-        const double pred = -(P.g0 * dT + P.g1 * dR) - 0.5 * (P.a00 * dT * dT + 2. * P.a01 * dT * dR + P.a11 * dR * dR);
-        if (isfinite(Q.cost) && Q.cost < P.cost) {
-            const double rho = pred > 0. ? (P.cost - Q.cost) / pred : 1.;
-            const double t = 2. * rho - 1.;
-            lambda *= fmax(1. / 3., 1. - t * t * t);
-            nu = 2.;
-            T = Tn;
-            R = Rn;
-            P = Q;
-        } else {
-            lambda *= nu;
-            nu *= 2.;
-        }
-        if (!(lambda < 1e300)) {   // no step of any length lowers the cost: the optimum to rounding
+        // no step of any length lowers the cost: the optimum to rounding.  (Also where the free block stays singular
+        // whatever the damping: J^T J underflowed to 0 under a gradient that did not, and the model is far below the
+        // data's last bit.)
+        if (!(lambda < 1e300)) {
             st = 1;
             break;
         }

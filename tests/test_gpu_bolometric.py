@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from bolometric_reference import projected_gradient as _projected_gradient
 from conftest import golden
 from lightcurve_fitting_amd import bolometric as B
 from lightcurve_fitting_amd import engine as E
@@ -33,23 +34,6 @@ def _golden_fit():
         r = B.blackbody_lstsq_epochs(eps, z, setup[idx][:, 2:4], (Tlo, Thi), (Rlo, Rhi), cut)
         out += [(e, eps[k], setup[e], {n: v[k] for n, v in r.items()}) for k, e in enumerate(idx)]
     return g, sorted(out, key=lambda t: t[0])
-
-
-def _projected_gradient(f, y, z, cut, T, R, lo, hi):
-    """Gradient of 1/2 sum r^2 in (T, R), relative to |J| |r|, with the components that point out of the box at an
-    active bound removed."""
-    nu = f * (1. + z)
-    m = _planck(nu, T, R, cut)
-    a = c1 * nu / T
-    with np.errstate(over='ignore', invalid='ignore'):
-        dT = np.where(m > 0, m * a / T * (1. + 1. / np.expm1(a)), 0.)
-    J = np.column_stack([dT, 2. * m / R])
-    r = m - y
-    g = J.T @ r / (np.linalg.norm(J, axis=0) * max(np.linalg.norm(r), 1e-300 * np.linalg.norm(y)))
-    for i, x in enumerate((T, R)):
-        if (x <= lo[i] and g[i] > 0) or (x >= hi[i] and g[i] < 0):
-            g[i] = 0.
-    return g
 
 
 def test_lstsq_matches_reference_curve_fit():
