@@ -289,7 +289,8 @@ __device__ inline double band_sum_fast(TabPtr tab, int cnt, double invT, const E
 // ---------------------------------------------------------------------------------------------------------------
 // Per-walker derived coefficients (wave-uniform).  One thread per walker computes them once; the likelihood kernel
 // reads them through scalar loads.
-//   c[0] = explosion time t_0
+//   c[0] = explosion time t_0 (a coordinate of the walker itself: p[4] for ShockCooling, p[3] for ShockCooling2 -- which the
+//          resident half-step restates as kT0, solo_half_step in lcf_hip.hip: change both together)
 //   power-law thermal models (ShockCooling, ShockCooling2):
 //     T_K(t) = c[1] t^eT,  L(t) = c[2] t^eL exp(-(g t)^alpha) with c[3] = alpha ln g (NaN: no cut-off term),
 //     c[4] != 0: a negative phase yields NaN (L < 0 before the explosion)
@@ -612,12 +613,13 @@ __device__ inline void encode_linear(double invT, double pref, double& x, double
 // from one logarithm and at most one exponential; lL = ln(c3^2 L), NaN where L < 0 or NaN (and everything is NaN for
 // t <= 0: the callers decide on the phase themselves).  c3, c6, c7 = the walker's coefficients c[3], c[6], c[7].
 // (PB: DevProblem, or anything else with its `consts`)
-template <class PB>
+// HAVE_LT: `t` is lt = tlog(t) already, from a caller that took the logarithm of the phase earlier.
+template <bool HAVE_LT = false, class PB>
 __device__ __forceinline__ void powerlaw_log_state(const PB& pb, double c3, double c6, double c7, double t,
                                                    const ExpTab et, double& u, double& lp, double& lL) {
     const double* k = pb.consts;
     const double eps1 = k[3], eps2 = k[4], alpha = k[2];
-    const double lt = tlog(t);
+    const double lt = HAVE_LT ? t : tlog(t);
     // (the exponential through the 2^(j/256) table: same arithmetic whether `et` points to LDS or memory)
     // (argument clamped from above: beyond e^1100 the table exponential overflows to +inf through its ldexp, as libm's
     // does -- an infinite argument, M_env = 0, would otherwise be inf - inf = NaN inside it, where the reference's

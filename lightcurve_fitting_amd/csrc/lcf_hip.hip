@@ -523,12 +523,14 @@ __device__ __attribute__((noinline)) double cold_column_with_state(const DevProb
 // fast branch, operation for operation.  Returns false (wave-uniform) where a state of the wave is outside the
 // interpolants: the caller then takes the general path for the column.
 // PB: DevProblem, or what a resident launch holds of it in LDS (ColumnView: consts, itab_u0, itab_inv_h, itab_m, itab).
-template <int MODEL, class PB>
+// HAVE_LT: `lt` = tlog(first.t - sc[0]) was taken in front of the barrier the coefficients arrive behind (the resident
+// half-step's early phase logarithm); the phase itself is still formed here, for the test of its sign alone.
+template <int MODEL, bool HAVE_LT = false, class PB>
 __device__ __forceinline__ bool lean_column(const PB& pb, const double* __restrict__ sc, const ColumnOperands& first,
-                                            const ExpTab et, int itab_at, double& acc) {
+                                            const ExpTab et, int itab_at, double& acc, double lt = 0.) {
     const double t = first.t - sc[0];
     double u, lp, lL;
-    powerlaw_log_state(pb, sc[3], sc[6], sc[7], t, et, u, lp, lL);
+    powerlaw_log_state<HAVE_LT>(pb, sc[3], sc[6], sc[7], HAVE_LT ? lt : t, et, u, lp, lL);
     const double r = (u - pb.itab_u0) * pb.itab_inv_h;
     // exactly where thermal_state_log leaves a log-space pair (lL NaN makes lp NaN: every comparison fails)
     const bool ok = t > 0. && r >= 0. && r < (double)pb.itab_m && lp >= -600. && lp <= 600.;
@@ -1232,6 +1234,10 @@ __device__ inline unsigned long long* board_entry(unsigned long long* board, con
 #ifndef LCF_EARLY_POST
 #define LCF_EARLY_POST 0
 #endif
+// The resident half-step's early phase logarithm (solo_half_step, kEarly): 0 = the columns take it behind barrier 1 (A/B).
+#ifndef LCF_EARLY_LOG
+#define LCF_EARLY_LOG 1
+#endif
 // A value the loop optimiser must not compute ahead of the loop over the half-steps: what it hoists there lives across
 // the whole launch and comes back from scratch memory on the path every other workgroup waits for.
 __device__ __forceinline__ int not_hoisted(int v) {
@@ -1630,7 +1636,9 @@ __device__ __attribute__((noinline)) void cold_coefficients(const double* consts
     }
 }
 
-template <int ND, int BOARD, int MODEL>
+// EARLY: the other waves stand at a barrier ("barrier 0") directly behind the store of the proposal, and take the
+// logarithm of their columns' phases from its t_0 while this wave computes the rest of the head.
+template <int ND, int BOARD, int MODEL, bool EARLY = false>
 __device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& dr, int lane_in, double* __restrict__ sc,
                                           double* __restrict__ sq, double* __restrict__ sx, const LaneRows& h,
                                           const RunUniforms* ru) {
@@ -1647,6 +1655,7 @@ __device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& d
     LCF_STAMP(0, 2);
     // proposal, position, log-posterior and count: one store each, from the lanes that hold them
     if (lane < nd) sq[lane] = q;
+    if constexpr (EARLY) __syncthreads();   // barrier 0: the wait is this store's
     if (lane <= nd + 1) sx[lane < nd ? lane : lane - nd + kMaxDim] = x;
     const double lg = flog(lane < n_par ? q : 1.);
     // what the coefficients read, wave-uniform (a kernel compiled for one model keeps only the broadcasts its model uses)
@@ -1771,6 +1780,19 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
     // same path -- start once they are out: rows + proposal 3.8 k cycles with everything requested at once, 2.1 k alone)
     // (model-specialised kernels only: the generic ones need the registers for the point-by-point path)
     constexpr bool kFetch = MODEL != 0;
+    // The early phase logarithm (resident kernels that can take lean columns): a column's tlog(t - t_0) needs nothing of
+    // the head but the proposal's t_0, which exists one multiply-add behind the poll -- and the seven other waves stand
+    // idle until the head is through.  Wave 0 therefore passes a barrier of its own ("barrier 0") right behind the store of
+    // the proposal, and the others take the logarithm of their column between that barrier and barrier 1, in the shadow
+    // of wave 0's own logarithm, coefficients and priors; behind barrier 1 lean_column starts from it.  Every wave
+    // passes barrier 0 on every path that passes barrier 1; an excluded proposal, a shape that is not lean and an
+    // aborted launch drop the value.  t_0 is coordinate kT0 of the proposal: c[0] of walker_coefficients, per model.
+    constexpr bool kEarly = RES && MODEL != 0 && NPARTS <= 2 && LCF_EARLY_LOG != 0;
+    constexpr int kT0 = MODEL == kShockCooling ? 4 : MODEL == kShockCooling2 ? 3 : -1;
+    static_assert(!kEarly || kT0 >= 0, "a model-specialised resident kernel names the coordinate that is t_0");
+    // (Wave 0 is the head and takes the logarithm of its own columns behind barrier 1.  Measured and dropped: a wave of
+    // another SIMD that takes them too and hands them over in 64 doubles of LDS -- DESIGN section 5.)
+    double lt_early = 0.;
     if (tid < 64) {
         // Resident workgroups drift apart, so this head shares its SIMD with column waves of the CU's other workgroup:
         // the one wave that everybody behind it waits for goes first (5.75 against 6.03 us per half-step; with a launch
@@ -1781,7 +1803,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             LaneRows rows;
             lane_head_fetch<ND, BOARD>(sm, dr, tid, rows, G, g_run0, arrive_goal, ru);
             if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
-            lane_head<ND, BOARD, MODEL>(pb, dr, tid, sc, sq, sx, rows, ru);
+            lane_head<ND, BOARD, MODEL, kEarly>(pb, dr, tid, sc, sq, sx, rows, ru);
         } else {
             HeadRows<ND> rows;
             head_fetch<ND, BOARD>(pb, sm, dr, tid, rows, G, g_run0, arrive_goal);
@@ -1811,10 +1833,23 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             (void)nxt[0];
             (void)nxt[sizeof(DrawRec) / sizeof(int) - 1];
         }
-        if (!reddened && first) stage_tables<VARIANT, true>(pb, exptab, ltab, 0., tid - 64, kThreads - 64);
-        LCF_STAMP(1, 11);
+        // (the abort word: requested while wave 0 still polls, in front of barrier 0 -- these waves reach this place while
+        // wave 0 is in the previous half-step's accept and post, so the round trip is over before wave 0 arrives)
         if constexpr (RES)
             if (tid == 64) sctl[0] = board_aborted_at<BOARD == 2>(ru->abort_word) ? 1 : 0;   // (in the shadow of the head)
+        if constexpr (kEarly) {
+            const int tid_e = not_hoisted(tid);
+            // (only a wave that will take lean columns needs the value: the group's record is a launch invariant, and a
+            // wave without columns has no operands -- have_o)
+            const bool lean_e = __builtin_amdgcn_readfirstlane(ru->group[__builtin_amdgcn_readfirstlane(tid_e / kBlock)].lean) != 0;
+            const bool mine = lean_e && first_col.have_o;
+            __syncthreads();   // barrier 0: wave 0 has stored the proposal
+            const double t0 = sq[kT0];
+            if (mine) lt_early = tlog(first_col.t - t0);
+        }
+        // (the tables of the launch's first half-step stay behind barrier 0: in front of it wave 0 would wait for them)
+        if (!reddened && first) stage_tables<VARIANT, true>(pb, exptab, ltab, 0., tid - 64, kThreads - 64);
+        LCF_STAMP(1, 11);
         if (BOARD == 1 && tid < 128) {
             // In the shadow of the head: has every rank finished half-step G - 2 (lane = rank)?  has this rank given up?
             const int lane = tid - 64;
@@ -1888,7 +1923,12 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             if (c0 + (ltid & ~63) < c1) {   // (a virtual wave without columns adds nothing)
                 const bool live = c0 + ltid < c1;
                 bool in_grid;
-                if constexpr (RES)
+                if constexpr (kEarly) {
+                    if (__builtin_amdgcn_readfirstlane(tid_c >> 6) == 0)   // (wave 0 was the head)
+                        lt_early = tlog(first_col.t - sc[0]);
+                    in_grid = lean_column<MODEL, true>(ColumnView{col_consts, col_grid.x, col_grid.y, col_itab.x, nullptr}, sc,
+                                                       first_col, ExpTab{exptab}, col_itab.y, acc, lt_early);
+                } else if constexpr (RES)
                     in_grid = lean_column<MODEL>(ColumnView{col_consts, col_grid.x, col_grid.y, col_itab.x, nullptr}, sc, first_col,
                                                  ExpTab{exptab}, col_itab.y, acc);
                 else
