@@ -565,6 +565,36 @@ lcf_status lcf_tempered_get_beta_history(lcf_tempered* t, double* betas);
 lcf_status lcf_tempered_stepping_stones(lcf_tempered* t, int64_t discard, int32_t n_batches, double* max, double* sum,
                                         double* count);
 
+/* Moves other than the stretch move (emcee's moves=): a step of a rung makes ONE kind of move in both of its half-steps.
+ * With n_moves > 0, rung k at step s makes the first move m with um < cum_weights[m], um = u01(r0, r1) of Philox(counter
+ * (0, s, 4, 0), key of rung k).  The colouring, the active walker of every slot and ln u stay the generators'; the new
+ * numbers of walker w are P2 = Philox((w, s, half, 2)) and P3 = Philox((w, s, half, 3)) under the rung's key: ua =
+ * u01(P2[0], P2[1]), ub = u01(P2[2], P2[3]), uc = u01(P3[0], P3[1]), ud = u01(P3[2], P3[3]).  c[0 .. n): the complementary
+ * colour of the half-step, in the order of the step's permutation (what the stretch move's partner index points into).
+ *   LCF_MOVE_STRETCH  as without moves.  params: unused.
+ *   LCF_MOVE_DE       (ter Braak 2006; emcee's DEMove) params (sigma >= 0, gamma0 > 0).  j1 = min(int(ua n), n - 1),
+ *                     j2 = min(int(ub (n - 1)), n - 2), j2 += (j2 >= j1); g = sqrt(-2 ln uc) cos(2 pi ud);
+ *                     q = x + gamma0 (1 + sigma g) (c[j1] - c[j2]); log proposal factor 0.  Needs n >= 2.
+ *   LCF_MOVE_SNOOKER  (ter Braak & Vrugt 2008; emcee's DESnookerMove) params (gammas > 0, unused).  j0, j1 as DE's j1, j2;
+ *                     j2 = min(int(uc (n - 2)), n - 3), bumped past the smaller and then the larger of j0, j1.  z = c[j0],
+ *                     d = x - z, u = d / |d|, q = x + u gammas (u.c[j1] - u.c[j2]); log proposal factor (n_dim - 1)
+ *                     (ln |q - z| - ln |d|).  |d| = 0 or |q - z| = 0: never accepted.  Needs n >= 3.
+ * The accept test takes the move's log proposal factor in place of (n_dim - 1) ln z; swaps, storing, adaptation and the
+ * stepping stones are what they were.  cum_weights[n_moves]: ascending in (0, 1], the last exactly 1; params[n_moves][2].
+ * n_moves = 0 (the pointers may be NULL) restores the default: the handle then launches what it launched before moves
+ * existed.  At most LCF_MAX_MOVES entries.  Callable before the first run and between runs: waits for the engine's stream
+ * and changes neither state nor counts.  LCF_ERR_INVALID_ARGUMENT (with the reason in lcf_last_error) for null pointers,
+ * too many entries, unknown kinds, bad weights or parameters, and ensembles too small for a listed move (n is at least
+ * n_walkers - ceil(n_walkers / 2)). */
+#define LCF_MOVE_STRETCH 0
+#define LCF_MOVE_DE 1
+#define LCF_MOVE_SNOOKER 2
+#define LCF_MAX_MOVES 8
+lcf_status lcf_tempered_set_moves(lcf_tempered* t, int32_t n_moves, const int32_t* kinds, const double* cum_weights,
+                                  const double* params /* [n_moves][2] */);
+/* kinds[n_stored][n_temps]: the kind of move every rung made in every stored step (LCF_MOVE_STRETCH without moves). */
+lcf_status lcf_tempered_get_move_history(lcf_tempered* t, int32_t* kinds);
+
 /* ---- custom models: a user-written photosphere T(t), R(t), compiled at run time for the GPU ----------------------- */
 /* What the reference's `Model` subclasses are to lightcurve_mcmc (models.py: temperature_radius, then
  * blackbody_to_filters), for the models the library has no kernel of its own for.  `source` is HIP device code that

@@ -7,6 +7,9 @@
 // An adapting run (lcf_tempered_run_adaptive) launches k_t_adapt behind the k_t_swap of every odd step: the ladder moves
 // on the device, from the swap counts since the last adaptation, and the host reads nothing until the run has ended.
 // k_t_stone reduces the stored ln L to the stepping-stone partials of every (pair, batch).
+// Moves (lcf_tempered_set_moves): a handle with a list of moves launches k_t_propose_moves in place of k_t_propose, which
+// makes the step's move of every rung (stretch, differential evolution or snooker) and leaves the move's log proposal
+// factor in FAC for k_t_accept.  Without a list nothing changes: the same kernels, the same numbers.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,6 +27,15 @@ struct DevTempered {
     long long* nacc;                 // [n_temps][n_walkers] accepted moves, by slot
     unsigned long long *swap_acc, *swap_prop;   // [n_temps - 1] per pair (k, k + 1)
     int* err;                        // 1: a proposal inside the prior had a NaN likelihood
+};
+
+// The moves of lcf_tempered_set_moves, by value to k_t_propose_moves.
+struct DevMoves {
+    int n;                           // 0: none set (the stretch move through k_t_propose)
+    int kind[LCF_MAX_MOVES];         // LCF_MOVE_*
+    double cum[LCF_MAX_MOVES];       // cumulative weights, the last exactly 1
+    double p0[LCF_MAX_MOVES];        // DE: sigma; snooker: gammas
+    double p1[LCF_MAX_MOVES];        // DE: gamma0
 };
 
 // ln prior of n rows.
@@ -55,9 +67,120 @@ __global__ void k_t_propose(const DevProblem pb, const DevTempered tp, const Dra
     tp.QPR[idx] = walker_log_prior(pb, q);
 }
 
+// Index into a complement of n walkers from a uniform draw.
+__device__ inline int pick(double u, int n) { return min((int)(u * (double)n), n - 1); }
+
+// k_t_propose for a handle with moves.  Rung k makes ONE kind of move in both halves of step `step`: the first m with
+// um < cum[m], um from Philox(0, step, 4, 0) under the rung's key (seed + k 0x9E3779B97F4A7C15), so a wave diverges only
+// where it spans two rungs.  The active walker and ln u stay the draw record's; a stretch move takes its partner and z
+// too.  The others draw from P2 = Philox(wid, step, half, 2) and P3 = Philox(wid, step, half, 3) under the same key, and
+// their partners c[j] from the complementary colour in the order of the step's permutation (`perm`: rung 0's row of this
+// step, rung k's perm_stride entries further per rung):
+//   DE       j1 = pick(ua, n), j2 = pick(ub, n - 1) bumped past j1; g = sqrt(-2 ln uc) cos(2 pi ud);
+//            q = x + gamma0 (1 + sigma g) (c[j1] - c[j2]); factor 0.
+//   snooker  j0, j1 likewise, j2 = pick(uc, n - 2) bumped past the smaller, then the larger of them; z = c[j0],
+//            d = x - z, u = d / |d|, q = x + u gammas (u.c[j1] - u.c[j2]); factor (n_dim - 1) (ln |q - z| - ln |d|);
+//            |d| = 0 or |q - z| = 0: q = x with log-prior -inf, never accepted.
+// FAC gets the factor (a stretch move's (n_dim - 1) ln z); kinds_row (or null) the kind rung k made, [n_temps].
+__global__ void k_t_propose_moves(const DevProblem pb, const DevTempered tp, const DevMoves mv,
+                                  const DrawRec* __restrict__ draws, long long rung_stride, const int* __restrict__ perm,
+                                  long long perm_stride, long long step, int half, double* __restrict__ FAC,
+                                  int* __restrict__ kinds_row) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= tp.n_temps * tp.n_half) return;
+    const int k = idx / tp.n_half, i = idx - k * tp.n_half;
+    const DrawRec d = draws[(size_t)k * rung_stride + i];
+    const double* Xk = tp.X + (size_t)k * tp.n_walkers * tp.n_dim;
+    double* q = tp.Q + (size_t)idx * tp.n_dim;
+    const unsigned long long sk =
+        (((unsigned long long)tp.key1 << 32) | tp.key0) + (unsigned long long)k * 0x9E3779B97F4A7C15ull;
+    const uint32_t k0 = (uint32_t)(sk & 0xffffffffu), k1 = (uint32_t)(sk >> 32);
+    uint32_t r[4];
+    philox4x32(0u, (uint32_t)step, 4u, 0u, k0, k1, r);
+    const double um = u01(r[0], r[1]);
+    int m = 0;
+    while (m < mv.n - 1 && !(um < mv.cum[m])) ++m;
+    const int kind = mv.kind[m];
+    if (kinds_row && i == 0 && half == 0) kinds_row[k] = kind;
+    if (d.wid < 0) {
+        for (int c = 0; c < tp.n_dim; ++c) q[c] = Xk[c];
+        tp.QPR[idx] = -INFINITY;
+        FAC[idx] = 0.;
+        return;
+    }
+    const double* x = Xk + (size_t)d.wid * tp.n_dim;
+    if (kind == LCF_MOVE_STRETCH) {
+        const double* partner = Xk + (size_t)d.pid * tp.n_dim;
+        for (int c = 0; c < tp.n_dim; ++c) q[c] = partner[c] - (partner[c] - x[c]) * d.z;
+        tp.QPR[idx] = walker_log_prior(pb, q);
+        FAC[idx] = d.zl;
+        return;
+    }
+    // the complementary colour: colour 0 is the first n_half entries of the permutation and moves in half 0
+    const int n = half == 0 ? tp.n_walkers - tp.n_half : tp.n_half;
+    const int* other = perm + (size_t)k * perm_stride + (half == 0 ? tp.n_half : 0);
+    uint32_t p2[4], p3[4];
+    philox4x32((uint32_t)d.wid, (uint32_t)step, (uint32_t)half, 2u, k0, k1, p2);
+    philox4x32((uint32_t)d.wid, (uint32_t)step, (uint32_t)half, 3u, k0, k1, p3);
+    const double ua = u01(p2[0], p2[1]), ub = u01(p2[2], p2[3]), uc = u01(p3[0], p3[1]), ud = u01(p3[2], p3[3]);
+    const int ja = pick(ua, n);
+    int jb = pick(ub, n - 1);
+    jb += jb >= ja ? 1 : 0;
+    const double* ca = Xk + (size_t)other[ja] * tp.n_dim;
+    const double* cb = Xk + (size_t)other[jb] * tp.n_dim;
+    if (kind == LCF_MOVE_DE) {
+        const double g = sqrt(-2. * log(uc)) * cos(6.283185307179586 * ud);
+        const double scale = mv.p1[m] * (1. + mv.p0[m] * g);
+        for (int c = 0; c < tp.n_dim; ++c) q[c] = x[c] + scale * (ca[c] - cb[c]);
+        tp.QPR[idx] = walker_log_prior(pb, q);
+        FAC[idx] = 0.;
+        return;
+    }
+    // snooker: ca is z, cb is z1
+    int jc = pick(uc, n - 2);
+    jc += jc >= min(ja, jb) ? 1 : 0;
+    jc += jc >= max(ja, jb) ? 1 : 0;
+    const double* cc = Xk + (size_t)other[jc] * tp.n_dim;
+    double dd = 0.;
+    for (int c = 0; c < tp.n_dim; ++c) {
+        const double t = x[c] - ca[c];
+        dd += t * t;
+    }
+    const double norm = sqrt(dd);
+    double qn = 0.;
+    if (norm > 0.) {
+        double a1 = 0., a2 = 0.;
+        for (int c = 0; c < tp.n_dim; ++c) {
+            const double u = (x[c] - ca[c]) / norm;
+            a1 += u * cb[c];
+            a2 += u * cc[c];
+        }
+        const double proj = a1 - a2;
+        double qq = 0.;
+        for (int c = 0; c < tp.n_dim; ++c) {
+            const double u = (x[c] - ca[c]) / norm;
+            const double v = x[c] + u * mv.p0[m] * proj;
+            const double t = v - ca[c];
+            q[c] = v;
+            qq += t * t;
+        }
+        qn = sqrt(qq);
+    }
+    if (!(norm > 0.) || !(qn > 0.)) {
+        for (int c = 0; c < tp.n_dim; ++c) q[c] = x[c];
+        tp.QPR[idx] = -INFINITY;
+        FAC[idx] = 0.;
+        return;
+    }
+    tp.QPR[idx] = walker_log_prior(pb, q);
+    FAC[idx] = (double)(tp.n_dim - 1) * (log(qn) - log(norm));
+}
+
 // Half-step, last part: accept iff the proposal's prior is finite, its likelihood is above -inf and
 // (n_dim - 1) ln z + beta (ln L(q) - ln L(x)) + (ln prior(q) - ln prior(x)) > ln u.  beta = 0 takes no product at all.
-__global__ void k_t_accept(const DevTempered tp, const DrawRec* __restrict__ draws, long long rung_stride) {
+// `fac` (a handle with moves; else null): the log proposal factor of k_t_propose_moves in place of (n_dim - 1) ln z.
+__global__ void k_t_accept(const DevTempered tp, const DrawRec* __restrict__ draws, long long rung_stride,
+                           const double* __restrict__ fac) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= tp.n_temps * tp.n_half) return;
     const int k = idx / tp.n_half, i = idx - k * tp.n_half;
@@ -73,7 +196,8 @@ __global__ void k_t_accept(const DevTempered tp, const DrawRec* __restrict__ dra
     const size_t w = (size_t)k * tp.n_walkers + d.wid;
     const double beta = tp.betas[k];
     const double dl = beta > 0. ? beta * (lq - tp.LL[w]) : 0.;
-    if (!(d.zl + dl + (pq - tp.LPR[w]) > d.lnu)) return;
+    const double factor = fac ? fac[idx] : d.zl;
+    if (!(factor + dl + (pq - tp.LPR[w]) > d.lnu)) return;
     double* x = tp.X + w * tp.n_dim;
     const double* q = tp.Q + (size_t)idx * tp.n_dim;
     for (int c = 0; c < tp.n_dim; ++c) x[c] = q[c];
@@ -264,6 +388,11 @@ struct lcf_tempered {
     bool window_open = false;       // the last run adapted: the next adapting run goes on in its window
     double* d_stone = nullptr;      // [3][n_temps - 1][stone_cap] of k_t_stone
     int64_t stone_cap = 0;
+    // moves (lcf_tempered_set_moves)
+    DevMoves mv{};
+    double* d_fac = nullptr;        // [n_temps][n_half] log proposal factors of a half-step, beside QLL / QPR
+    int* chain_kinds = nullptr;     // [chain_cap][n_temps]: the kind of move every stored step made (zero: stretch)
+    bool kinds_written = false;     // a run with moves has stored kinds: a run without clears its rows
 
     ~lcf_tempered() {
         hipSetDevice(device);
@@ -271,6 +400,7 @@ struct lcf_tempered {
         if (chain) hipFree(chain);
         if (chain_ll) hipFree(chain_ll);
         if (chain_betas) hipFree(chain_betas);
+        if (chain_kinds) hipFree(chain_kinds);
         if (d_stone) hipFree(d_stone);
     }
     size_t rows() const { return (size_t)dt.n_temps * dt.n_walkers; }
@@ -292,19 +422,31 @@ lcf_status reserve_chain(lcf_tempered* t, int64_t steps, int64_t keep) {
     size_t free_b = 0, total_b = 0;
     LCF_HIP(hipStreamSynchronize(t->e->stream));
     LCF_HIP(hipMemGetInfo(&free_b, &total_b));
-    const auto bytes = [&](int64_t s) { return (size_t)s * (per_step * (nd + 1) + K) * sizeof(double); };
+    const auto bytes = [&](int64_t s) { return (size_t)s * (per_step * (nd + 1) + 2 * K) * sizeof(double); };
     if (keep > 0 && bytes(std::max(steps, 2 * t->chain_cap)) <= free_b / 2) cap = std::max(steps, 2 * t->chain_cap);
     if (bytes(cap) > free_b)
         return fail(LCF_ERR_OUT_OF_MEMORY, "the chain of the run needs " + std::to_string(bytes(cap)) + " bytes of device memory, " +
                                                std::to_string(free_b) + " are free");
     double *c = nullptr, *l = nullptr, *b = nullptr;
+    int* m = nullptr;
     LCF_HIP(hipMalloc((void**)&c, (size_t)cap * per_step * nd * sizeof(double)));
     hipError_t err = hipMalloc((void**)&l, (size_t)cap * per_step * sizeof(double));
     if (!err) err = hipMalloc((void**)&b, (size_t)cap * K * sizeof(double));
+    if (!err) err = hipMalloc((void**)&m, (size_t)cap * K * sizeof(int));
     if (err) {
         hipFree(c);
         if (l) hipFree(l);
+        if (b) hipFree(b);
         return fail(err == hipErrorOutOfMemory ? LCF_ERR_OUT_OF_MEMORY : LCF_ERR_HIP, hipGetErrorString(err));
+    }
+    err = hipMemset(m, 0, (size_t)cap * K * sizeof(int));
+    if (!err && keep > 0) err = hipMemcpy(m, t->chain_kinds, (size_t)keep * K * sizeof(int), hipMemcpyDeviceToDevice);
+    if (err) {
+        hipFree(c);
+        hipFree(l);
+        hipFree(b);
+        hipFree(m);
+        return fail(LCF_ERR_HIP, hipGetErrorString(err));
     }
     if (keep > 0) {
         err = hipMemcpy(c, t->chain, (size_t)keep * per_step * nd * sizeof(double), hipMemcpyDeviceToDevice);
@@ -314,12 +456,15 @@ lcf_status reserve_chain(lcf_tempered* t, int64_t steps, int64_t keep) {
             hipFree(c);
             hipFree(l);
             hipFree(b);
+            hipFree(m);
             return fail(LCF_ERR_HIP, hipGetErrorString(err));
         }
     }
     if (t->chain) hipFree(t->chain);
     if (t->chain_ll) hipFree(t->chain_ll);
     if (t->chain_betas) hipFree(t->chain_betas);
+    if (t->chain_kinds) hipFree(t->chain_kinds);
+    t->chain_kinds = m;
     t->chain = c;
     t->chain_ll = l;
     t->chain_betas = b;
@@ -367,7 +512,7 @@ lcf_status lcf_tempered_create(lcf_engine* e, int32_t n_temps, const double* bet
     AL(dt.Q, nh * nd); AL(dt.QLL, nh); AL(dt.QPR, nh);
     AL(dt.swap_acc, K); AL(dt.swap_prop, K); AL(dt.err, 1);
     AL(t->d_perm, nw * t->blk_cap); AL(t->d_draws, 2 * nh * t->blk_cap); AL(t->d_items, K); AL(t->d_mean, K);
-    AL(t->seen_acc, K); AL(t->seen_prop, K);
+    AL(t->seen_acc, K); AL(t->seen_prop, K); AL(t->d_fac, nh);
 #undef AL
     dt.betas = d_betas;
     t->ends_at_prior = betas[n_temps - 1] == 0.;
@@ -488,6 +633,12 @@ lcf_status run_steps(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32
     t->window_open = adapt;
     const size_t n_prop = (size_t)dt.n_temps * dt.n_half;
     const long long rung_stride = (long long)t->blk_cap * 2 * dt.n_half;
+    const DevMoves& mv = t->mv;
+    const long long perm_stride = (long long)t->blk_cap * dt.n_walkers;
+    const double* fac = mv.n ? t->d_fac : nullptr;
+    if (store && mv.n) t->kinds_written = true;
+    if (store && !mv.n && t->kinds_written && n_steps > 0)   // (rows a run with moves may have left: stretch moves now)
+        LCF_HIP(hipMemsetAsync(t->chain_kinds + (size_t)row0 * dt.n_temps, 0, (size_t)n_steps * dt.n_temps * sizeof(int), st));
     for (int64_t k0 = 0; k0 < n_steps; k0 += t->blk_cap) {
         const int64_t len = std::min<int64_t>(t->blk_cap, n_steps - k0);
         if (lcf_status r = generate_multi(t->d_items, dt.n_temps, dt.n_walkers, dt.n_half, first_step + k0, len, 0, -1, st))
@@ -495,9 +646,15 @@ lcf_status run_steps(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32
         for (int64_t j = 0; j < len; ++j) {
             for (int half = 0; half < 2; ++half) {
                 const DrawRec* draws = t->d_draws + (size_t)(2 * j + half) * dt.n_half;
-                hipLaunchKernelGGL(k_t_propose, dim3(blocks_for(n_prop)), dim3(256), 0, st, e->dp, dt, draws, rung_stride);
+                if (mv.n)
+                    hipLaunchKernelGGL(k_t_propose_moves, dim3(blocks_for(n_prop)), dim3(256), 0, st, e->dp, dt, mv, draws,
+                                       rung_stride, t->d_perm + (size_t)j * dt.n_walkers, perm_stride,
+                                       (long long)(first_step + k0 + j), half, t->d_fac,
+                                       store ? t->chain_kinds + (size_t)(row0 + k0 + j) * dt.n_temps : nullptr);
+                else
+                    hipLaunchKernelGGL(k_t_propose, dim3(blocks_for(n_prop)), dim3(256), 0, st, e->dp, dt, draws, rung_stride);
                 if (lcf_status r = lcf_log_likelihood_dev(e, (int64_t)n_prop, dt.Q, dt.QLL, st)) return r;
-                hipLaunchKernelGGL(k_t_accept, dim3(blocks_for(n_prop)), dim3(256), 0, st, dt, draws, rung_stride);
+                hipLaunchKernelGGL(k_t_accept, dim3(blocks_for(n_prop)), dim3(256), 0, st, dt, draws, rung_stride, fac);
             }
             const int64_t step = first_step + k0 + j;
             hipLaunchKernelGGL(k_t_swap, dim3(blocks_for(t->rows())), dim3(256), 0, st, dt, (long long)step,
@@ -529,6 +686,59 @@ lcf_status lcf_tempered_run(lcf_tempered* t, int64_t first_step, int64_t n_steps
 lcf_status lcf_tempered_run_adaptive(lcf_tempered* t, int64_t first_step, int64_t n_steps, int32_t store, double lag,
                                      double time, int64_t t0) {
     return run_steps(t, first_step, n_steps, store, true, lag, time, t0);
+}
+
+lcf_status lcf_tempered_set_moves(lcf_tempered* t, int32_t n_moves, const int32_t* kinds, const double* cum_weights,
+                                  const double* params) {
+    if (!t) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_moves < 0 || n_moves > LCF_MAX_MOVES)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "n_moves must be from 0 to " + std::to_string(LCF_MAX_MOVES));
+    if (n_moves > 0 && (!kinds || !cum_weights || !params)) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    DevMoves mv{};
+    mv.n = n_moves;
+    const int complement = t->dt.n_walkers - t->dt.n_half;   // the smaller colour: what the first half draws partners from
+    for (int m = 0; m < n_moves; ++m) {
+        const double p0 = params[2 * m], p1 = params[2 * m + 1], w = cum_weights[m];
+        const std::string at = "move " + std::to_string(m) + ": ";
+        if (!(w > 0.) || !(w <= 1.) || (m > 0 && !(w >= cum_weights[m - 1])))
+            return fail(LCF_ERR_INVALID_ARGUMENT, at + "cum_weights must ascend within (0, 1]");
+        switch (kinds[m]) {
+            case LCF_MOVE_STRETCH:
+                break;
+            case LCF_MOVE_DE:
+                if (!(p0 >= 0.) || !std::isfinite(p0)) return fail(LCF_ERR_INVALID_ARGUMENT, at + "sigma must be finite and >= 0");
+                if (!(p1 > 0.) || !std::isfinite(p1)) return fail(LCF_ERR_INVALID_ARGUMENT, at + "gamma0 must be finite and > 0");
+                if (complement < 2)
+                    return fail(LCF_ERR_INVALID_ARGUMENT, at + "the DE move needs 2 partners in either colour: at least 4 walkers");
+                break;
+            case LCF_MOVE_SNOOKER:
+                if (!(p0 > 0.) || !std::isfinite(p0)) return fail(LCF_ERR_INVALID_ARGUMENT, at + "gammas must be finite and > 0");
+                if (complement < 3)
+                    return fail(LCF_ERR_INVALID_ARGUMENT, at + "the snooker move needs 3 partners in either colour: at least 6 walkers");
+                break;
+            default:
+                return fail(LCF_ERR_INVALID_ARGUMENT, at + "unknown kind " + std::to_string(kinds[m]));
+        }
+        mv.kind[m] = kinds[m];
+        mv.cum[m] = w;
+        mv.p0[m] = p0;
+        mv.p1[m] = p1;
+    }
+    if (n_moves > 0 && cum_weights[n_moves - 1] != 1.)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "cum_weights must end at exactly 1");
+    LCF_HIP(hipSetDevice(t->device));
+    LCF_HIP(hipStreamSynchronize(t->e->stream));
+    t->mv = mv;
+    return LCF_OK;
+}
+
+lcf_status lcf_tempered_get_move_history(lcf_tempered* t, int32_t* kinds) {
+    if (!t || !kinds) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (t->chain_steps == 0) return fail(LCF_ERR_STATE, "no chain is stored");
+    LCF_HIP(hipSetDevice(t->device));
+    LCF_HIP(hipStreamSynchronize(t->e->stream));
+    LCF_HIP(hipMemcpy(kinds, t->chain_kinds, (size_t)t->chain_steps * t->dt.n_temps * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LCF_OK;
 }
 
 lcf_status lcf_tempered_get_betas(lcf_tempered* t, double* betas) {

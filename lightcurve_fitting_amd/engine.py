@@ -29,6 +29,7 @@ MODEL_MAGNETAR = 11
 PRIOR_UNIFORM, PRIOR_LOG_UNIFORM, PRIOR_GAUSSIAN = 0, 1, 2
 SIGMA_RELATIVE, SIGMA_ABSOLUTE = 0, 1
 SPLIT_IDENTITY, SPLIT_RANDOM, SPLIT_HOST = 0, 1, 2
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MAX_MOVES = 0, 1, 2, 8   # lcf_tempered_set_moves (include/lcf.h)
 
 STATUS_NAMES = {0: 'LCF_OK', 1: 'LCF_ERR_INVALID_ARGUMENT', 2: 'LCF_ERR_HIP', 3: 'LCF_ERR_NO_DEVICE',
                 4: 'LCF_ERR_OUT_OF_MEMORY', 5: 'LCF_ERR_UNSUPPORTED', 6: 'LCF_ERR_NAN_LOGPROB', 7: 'LCF_ERR_STATE'}
@@ -183,6 +184,8 @@ SIGNATURES = [
     ('lcf_tempered_get_betas', C.c_int, [C.c_void_p, _dp]),
     ('lcf_tempered_get_beta_history', C.c_int, [C.c_void_p, _dp]),
     ('lcf_tempered_stepping_stones', C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp]),
+    ('lcf_tempered_set_moves', C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
+    ('lcf_tempered_get_move_history', C.c_int, [C.c_void_p, _ip]),
     ('lcf_custom_compile', C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
     ('lcf_custom_log', C.c_char_p, [C.c_void_p]),
     ('lcf_custom_code', C.c_void_p, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -718,6 +721,21 @@ class NativeTempered:
         m, s, n = (np.empty((self.ntemps - 1, int(batches))) for _ in range(3))
         _check(self._lib.lcf_tempered_stepping_stones(self._h, int(discard), int(batches), _ptr(m), _ptr(s), _ptr(n)))
         return m, s, n
+
+    def set_moves(self, kinds, cum_weights, params):
+        """The moves of the steps from the next run on: ``kinds`` (n,) of ``MOVE_*``, ``cum_weights`` (n,) ascending to
+        exactly 1, ``params`` (n, 2).  ``n = 0`` restores the stretch move alone.  State and counts stay."""
+        kinds, cum, params = _i32(kinds).ravel(), _f64(cum_weights).ravel(), _f64(params).reshape(-1, 2)
+        if not len(kinds) == len(cum) == len(params):
+            raise ValueError('kinds, cum_weights and params must have one length')
+        _check(self._lib.lcf_tempered_set_moves(self._h, len(kinds), _ptr(kinds, _ip), _ptr(cum), _ptr(params)))
+
+    def get_move_history(self, nstored):
+        """(nstored, K) of ``MOVE_*``: the kind of move every rung made in every stored step."""
+        out = np.zeros((int(nstored), self.ntemps), dtype=np.int32)
+        if nstored:
+            _check(self._lib.lcf_tempered_get_move_history(self._h, _ptr(out, _ip)))
+        return out
 
 
 def population_run(native_samplers, first_step, nsteps, split='random', store=True):

@@ -87,7 +87,7 @@ def _check_start_box(names, priors, p_lo, p_up):
 def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p_up=None,
                     nwalkers=100, nsteps=1000, nsteps_burnin=1000, model_kwargs=None,
                     show=False, save_plot_as='', save_sampler_as='', use_sigma=False, sigma_type='relative',
-                    seed=None, ntemps=None, betas=None, Tmax=None, adapt=False):
+                    seed=None, ntemps=None, betas=None, Tmax=None, adapt=False, moves=None):
     """Fit an analytical model to observed photometry with an affine-invariant ensemble sampler on the GPU.
 
     Arguments as in the reference (fitting.py:16-58).  ``seed`` (extension) keys the counter-based RNG; by default
@@ -101,6 +101,12 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     ``adapt=True`` (tempered fits only, ``ValueError`` otherwise; needs ``ntemps >= 3`` and ``Tmax=inf``): the ladder
     adapts during the burn-in until neighbouring rungs swap equally often, and is frozen for the stored run, so that
     ``sampler.log_evidence(method='stepping_stone')`` is over one ladder.
+
+    ``moves`` (extension; emcee's argument: a move, or a list of moves or ``(move, weight)`` pairs of
+    :class:`~lightcurve_fitting_amd.sampler.StretchMove`, :class:`~lightcurve_fitting_amd.sampler.DEMove` and
+    :class:`~lightcurve_fitting_amd.sampler.DESnookerMove`), for posteriors with curved or narrow ridges: when given, the
+    fit goes through :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` too -- on one rung at ``beta = 1`` unless a
+    ladder is asked for as well -- and the keyword is passed on to it; None is not passed on.
 
     A :class:`~lightcurve_fitting_amd.models.CustomModel` is always fitted by that sampler -- without the tempering
     arguments on one rung at ``beta = 1``, which makes the ensemble sampler's moves -- because the resident sampler's
@@ -138,12 +144,15 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks.append(('engine', time.perf_counter()))
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
-    if isinstance(model, (CustomModel, BaseCentralEngine)) and ntemps is None and betas is None and Tmax is None:
-        betas = [1.]   # the resident sampler's kernels are compiled per photometric model: one rung is the same ensemble
+    if (isinstance(model, (CustomModel, BaseCentralEngine)) or moves is not None) and ntemps is None and betas is None \
+            and Tmax is None:
+        # the resident sampler's kernels are compiled per photometric model and make the stretch move: one rung is the
+        # same ensemble
+        betas = [1.]
     if ntemps is not None or betas is not None or Tmax is not None:
         from .sampler import TemperedSampler
         sampler = TemperedSampler(nwalkers, ndim, engine, ntemps=ntemps, betas=betas, Tmax=Tmax, seed=seed,
-                                  names=model.input_names)
+                                  names=model.input_names, **({} if moves is None else {'moves': moves}))
         start = p_lo + (p_up - p_lo) * np.random.rand(sampler.ntemps, nwalkers, ndim)
         marks.append(('sampler', time.perf_counter()))
         sampler.run_mcmc(start, nsteps_burnin, store=False, adapt=bool(adapt))

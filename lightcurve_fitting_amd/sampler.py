@@ -964,6 +964,99 @@ def check_adaptive(betas):
         raise ValueError('an adaptive ladder needs at least 3 rungs and a last rung at beta = 0 (Tmax=inf)')
 
 
+MAX_MOVES = 8    # entries of a mixture of moves the native driver takes (include/lcf.h)
+
+
+class StretchMove:
+    """The stretch move (Goodman & Weare 2010), what the sampler makes without ``moves``; its scale is the sampler's
+    ``a``."""
+    kind, needs = 0, 1    # LCF_MOVE_STRETCH; partners the move draws from the complementary colour
+
+    def native_params(self, ndim):
+        return (0., 0.)
+
+    def __repr__(self):
+        return 'StretchMove()'
+
+
+class DEMove:
+    """The differential-evolution move (ter Braak 2006; emcee's ``DEMove``, its names and defaults): the proposal is
+    ``x + gamma0 (1 + sigma g) (c1 - c2)`` with two distinct walkers of the complementary colour and ``g`` standard
+    normal.  ``gamma0=None``: ``2.38 / sqrt(2 ndim)``."""
+    kind, needs = 1, 2    # LCF_MOVE_DE
+
+    def __init__(self, sigma=1.0e-5, gamma0=None):
+        if not (np.isfinite(sigma) and sigma >= 0.):
+            raise ValueError('sigma must be finite and >= 0')
+        if gamma0 is not None and not (np.isfinite(gamma0) and gamma0 > 0.):
+            raise ValueError('gamma0 must be finite and > 0')
+        self.sigma, self.gamma0 = float(sigma), None if gamma0 is None else float(gamma0)
+
+    def native_params(self, ndim):
+        return (self.sigma, 2.38 / np.sqrt(2. * ndim) if self.gamma0 is None else self.gamma0)
+
+    def __repr__(self):
+        return f'DEMove(sigma={self.sigma!r}, gamma0={self.gamma0!r})'
+
+
+class DESnookerMove:
+    """The snooker move (ter Braak & Vrugt 2008; emcee's ``DESnookerMove``): the walker moves along its line to a walker
+    ``z`` of the complementary colour, by ``gammas`` times the distance between the projections of two more walkers
+    onto that line."""
+    kind, needs = 2, 3    # LCF_MOVE_SNOOKER
+
+    def __init__(self, gammas=1.7):
+        if not (np.isfinite(gammas) and gammas > 0.):
+            raise ValueError('gammas must be finite and > 0')
+        self.gammas = float(gammas)
+
+    def native_params(self, ndim):
+        return (self.gammas, 0.)
+
+    def __repr__(self):
+        return f'DESnookerMove(gammas={self.gammas!r})'
+
+
+def check_moves(moves, nwalkers):
+    """``moves`` as emcee takes it -- one move, or a list of moves or ``(move, weight)`` pairs -- as the list of
+    ``(move, weight)`` with the weights normalised, or ``ValueError``: unknown objects, weights that are not positive and
+    finite, more than ``MAX_MOVES`` entries, or fewer walkers than a move needs (either colour of the split must hold the
+    partners it draws: 4 walkers for ``DEMove``, 6 for ``DESnookerMove``)."""
+    kinds = (StretchMove, DEMove, DESnookerMove)
+    if isinstance(moves, kinds):
+        moves = [moves]
+    try:
+        entries = [m if isinstance(m, (tuple, list)) else (m, 1.) for m in moves]
+    except TypeError:
+        raise ValueError(f'moves must be a move or a list of moves or (move, weight) pairs, not {moves!r}') from None
+    if not 1 <= len(entries) <= MAX_MOVES:
+        raise ValueError(f'moves must have 1 to {MAX_MOVES} entries, not {len(entries)}')
+    for entry in entries:
+        if len(entry) != 2 or not isinstance(entry[0], kinds):
+            raise ValueError(f'not a move or a (move, weight) pair: {entry!r} (StretchMove, DEMove and DESnookerMove '
+                             f'are the moves there are)')
+    try:
+        w = np.array([float(weight) for _, weight in entries])
+    except (TypeError, ValueError):
+        raise ValueError('the weights of moves must be numbers') from None
+    if not (np.all(np.isfinite(w)) and np.all(w > 0.)):
+        raise ValueError(f'the weights of moves must be positive and finite, not {w.tolist()}')
+    smaller = int(nwalkers) - (int(nwalkers) + 1) // 2
+    for move, _ in entries:
+        if smaller < move.needs:
+            raise ValueError(f'{move!r} draws {move.needs} distinct partners from either colour of the split: it needs '
+                             f'at least {2 * move.needs} walkers, not {nwalkers}')
+    return [(move, float(x)) for (move, _), x in zip(entries, w / w.sum())]
+
+
+def native_moves(moves, ndim):
+    """``(kinds, cum_weights, params)`` of ``NativeTempered.set_moves`` for a list from :func:`check_moves`: the
+    cumulative weights by ``np.cumsum``, the last set to exactly 1."""
+    cum = np.cumsum([w for _, w in moves])
+    cum[-1] = 1.
+    return ([m.kind for m, _ in moves], cum, np.array([m.native_params(ndim) for m, _ in moves], dtype=np.float64))
+
+
 class TemperedSampler:
     """A parallel-tempered ensemble on one engine: ``ntemps`` rungs of inverse temperature ``betas`` (1 first), each
     an ensemble of ``nwalkers`` walkers that makes the stretch move on ``prior * L**beta``; after every step
@@ -983,10 +1076,16 @@ class TemperedSampler:
     defaults): after every second step, from the swaps since the last adaptation, the gaps ``1 / beta_{k+1} -
     1 / beta_k`` are scaled by ``exp(kappa (A_k - A_{k+1}))`` with ``kappa = lag / (t + lag) / time`` and ``t`` the
     adapting steps made so far (``adaptation_steps``, never reset).  Needs ``ntemps >= 3`` and a last rung at
-    ``beta = 0``.  A moving ladder samples no fixed distribution: adapt during burn-in, then run frozen."""
+    ``beta = 0``.  A moving ladder samples no fixed distribution: adapt during burn-in, then run frozen.
+
+    ``moves`` (as emcee's): a move, or a list of moves or ``(move, weight)`` pairs of :class:`StretchMove`,
+    :class:`DEMove` and :class:`DESnookerMove` (:func:`check_moves`); None: the stretch move, as ever.  Every step, each
+    rung draws ONE kind of move by the weights and makes it in both half-steps; the colouring, the order of the walkers
+    and the accept test's ``ln u`` are the same whatever the moves.  ``moves`` holds the normalised list,
+    :meth:`set_moves` changes it between runs, :meth:`get_move_kinds` says what the stored steps made."""
 
     def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, Tmax=None, seed=0, a=2.0, names=None,
-                 adaptation_lag=10000, adaptation_time=100):
+                 adaptation_lag=10000, adaptation_time=100, moves=None):
         from .engine import NativeTempered
         if nwalkers < 2 * ndim:
             raise ValueError('It is unadvisable to use a red-blue move with fewer walkers than twice the number of '
@@ -1007,7 +1106,10 @@ class TemperedSampler:
         self.ntemps, self.nwalkers, self.ndim = len(self.betas), int(nwalkers), int(ndim)
         self.engine = engine
         self.seed = int(seed)
+        self.moves = [(StretchMove(), 1.)] if moves is None else check_moves(moves, nwalkers)
         self._tempered = NativeTempered(engine, self.betas, nwalkers, seed, a)
+        if moves is not None:
+            self._tempered.set_moves(*native_moves(self.moves, self.ndim))
         self._steps_done = 0      # RNG step counter: never reset
         self._stored = 0          # steps of the stored chain (on the device)
         self._host = None         # (chain, lnL) once read, until the next stored run
@@ -1019,6 +1121,22 @@ class TemperedSampler:
 
     def close(self):
         self._tempered.close()
+
+    def set_moves(self, moves):
+        """The moves of the steps from the next run on (None: the stretch move, through the kernels of a sampler that
+        never had moves).  The state, the counts and the stored chain stay."""
+        if moves is None:
+            self._tempered.set_moves([], [], np.empty((0, 2)))
+            self.moves = [(StretchMove(), 1.)]
+        else:
+            new = check_moves(moves, self.nwalkers)
+            self._tempered.set_moves(*native_moves(new, self.ndim))
+            self.moves = new
+
+    def get_move_kinds(self, discard=0, thin=1):
+        """(nsteps, ntemps) integers: the kind of move every rung made in every stored step (the ``kind`` of the move
+        classes: 0 stretch, 1 differential evolution, 2 snooker), as the device recorded it."""
+        return self._tempered.get_move_history(self._stored)[discard::thin]
 
     def reset(self):
         """Forget the stored chain and the counts (not the RNG position)."""

@@ -18,19 +18,30 @@ profiles/tempered_adaptive.json``): the same configuration frozen and adapting, 
 clock); and, at 8 and 16 rungs, the swap fractions and the log-evidence by both methods on the fixed ladder and on the
 ladder adapted during ``--burn`` steps.
 
+``--moves LIST`` (``stretch``, ``de``, ``snooker``, ``mix`` -- 0.8 DE / 0.2 snooker -- or ``all``, comma-separated;
+default ``--json profiles/moves_timing.json``) measures the moves of ``TemperedSampler(moves=)`` instead: ms per step of
+the same fit for the sampler without moves (``default``) and for each listed move, medians of ``--repeats`` alternating
+repetitions; with ``--parent DIR`` (a built checkout of the parent commit) the default path of this tree next to the
+parent's, each repetition a fresh process, alternating; and ``get_autocorr_time`` of the cold chain (``--autocorr-steps``
+stored steps after ``--burn``) for the default sampler, DE and the mixture.
+
 Usage:  python tools/tempered_timing.py [--steps 300] [--json profiles/tempered_timing.json] [--kernel-stats CSV]
-        python tools/tempered_timing.py --adapt [--repeats 5] [--burn 1000]"""
+        python tools/tempered_timing.py --adapt [--repeats 5] [--burn 1000]
+        python tools/tempered_timing.py --moves all [--parent DIR] [--repeats 5] [--burn 1000] [--autocorr-steps 2000]"""
 import argparse
 import csv
 import json
 import os
+import subprocess
 import sys
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# (--package-root DIR, the child processes of --parent: the package of that tree, the golden light curve of this one)
+PACKAGE_ROOT = sys.argv[sys.argv.index('--package-root') + 1] if '--package-root' in sys.argv[:-1] else ROOT
+sys.path.insert(0, PACKAGE_ROOT)
 from lightcurve_fitting_amd import models as M  # noqa: E402
 from lightcurve_fitting_amd.sampler import EnsembleSampler, TemperedSampler, default_betas  # noqa: E402
 
@@ -153,8 +164,73 @@ def run_adaptive(walkers, ntemps, steps, warmup, repeats, burn, lag, time_):
     return res
 
 
+def move_list(name):
+    from lightcurve_fitting_amd.sampler import DEMove, DESnookerMove, StretchMove
+    return {'default': None, 'stretch': StretchMove(), 'de': DEMove(), 'snooker': DESnookerMove(),
+            'mix': [(DEMove(), 0.8), (DESnookerMove(), 0.2)]}[name]
+
+
+def stats(v):
+    return {'median': float(np.median(v)), 'min': float(min(v)), 'max': float(max(v)), 'runs': [float(x) for x in v]}
+
+
+def default_path_once(walkers, ntemps, steps, warmup):
+    """ms per step of the sampler without moves, through nothing the parent commit lacks (a child of --parent)."""
+    eng = M.ShockCooling(redshift=0.).engine_for(lc_case(), priors=PRIORS)
+    s = TemperedSampler(walkers, eng.ndim, eng, betas=default_betas(eng.ndim, ntemps, Tmax=np.inf), seed=1)
+    s.run_mcmc(LO + (HI - LO) * np.random.default_rng(1).random((ntemps, walkers, eng.ndim)), warmup, store=False)
+    return 1e3 * timed(lambda: s.run_mcmc(None, steps)) / steps
+
+
+def run_moves(names, walkers, ntemps, steps, warmup, repeats, burn, autocorr_steps, parent):
+    eng = M.ShockCooling(redshift=0.).engine_for(lc_case(), priors=PRIORS)
+    betas = default_betas(eng.ndim, ntemps, Tmax=np.inf)
+    x0 = LO + (HI - LO) * np.random.default_rng(1).random((ntemps, walkers, eng.ndim))
+    new = lambda name: TemperedSampler(walkers, eng.ndim, eng, betas=betas, seed=1,
+                                       **({} if name == 'default' else {'moves': move_list(name)}))
+    samplers = {name: new(name) for name in ['default'] + names}
+    for s in samplers.values():
+        s.run_mcmc(x0, warmup, store=False)
+    ms = {name: [] for name in samplers}
+    for _ in range(repeats):          # interleaved: every sampler sees the same drift of the machine
+        for name, s in samplers.items():
+            s.reset()
+            ms[name].append(1e3 * timed(lambda: s.run_mcmc(None, steps)) / steps)
+    res = {'walkers': walkers, 'ntemps': ntemps, 'steps': steps, 'warmup': warmup, 'repeats': repeats,
+           'n_points': int(eng.npoints), 'mix': '0.8 DEMove + 0.2 DESnookerMove',
+           'ms_per_step': {name: stats(v) for name, v in ms.items()},
+           'acceptance_cold_rung': {name: float(s.acceptance_fraction[0].mean()) for name, s in samplers.items()}}
+    for s in samplers.values():
+        s.close()
+    if parent:
+        runs = {'this_commit': [], 'parent_commit': []}
+        for _ in range(repeats):      # a fresh process each, alternating
+            for key, root in (('this_commit', ROOT), ('parent_commit', os.path.abspath(parent))):
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), '--default-path-once', '--walkers', str(walkers),
+                                      '--ntemps', str(ntemps), '--steps', str(steps), '--warmup', str(warmup),
+                                      '--package-root', root], check=True, capture_output=True, text=True, timeout=300)
+                runs[key].append(float(out.stdout.strip().splitlines()[-1]))
+        res['default_path_ms_per_step'] = {k: stats(v) for k, v in runs.items()}
+    res['autocorr'] = {}
+    for name in [n for n in ('default', 'de', 'mix') if n in samplers]:
+        s = new(name)
+        s.run_mcmc(x0, burn, store=False)
+        s.run_mcmc(None, autocorr_steps)
+        tau = s.get_autocorr_time(quiet=True)
+        res['autocorr'][name] = {'burn': burn, 'steps': autocorr_steps, 'tau': [float(t) for t in np.atleast_1d(tau)],
+                                 'steps_over_tau_max': float(autocorr_steps / np.max(tau)),
+                                 'acceptance_cold_rung': float(s.acceptance_fraction[0].mean())}
+        s.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--moves', default=None, help='measure these moves: stretch, de, snooker, mix (comma-separated) or all')
+    ap.add_argument('--parent', default=None, help='--moves: a built checkout of the parent commit to time the default path of')
+    ap.add_argument('--autocorr-steps', type=int, default=2000)
+    ap.add_argument('--default-path-once', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--package-root', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--adapt', action='store_true', help='measure the adaptive ladder and the stepping stones')
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--burn', type=int, default=1000, help='--adapt: burn-in steps of the evidence cases')
@@ -168,7 +244,14 @@ def main():
     ap.add_argument('--kernel-stats', default=None, help='kernel statistics (CSV) of a rocprofv3 --kernel-trace --stats run')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
-    if a.adapt:
+    if a.default_path_once:
+        print(default_path_once(a.walkers, a.ntemps, a.steps, a.warmup))
+        return
+    if a.moves:
+        names = ['stretch', 'de', 'snooker', 'mix'] if a.moves == 'all' else a.moves.split(',')
+        res = run_moves(names, a.walkers, a.ntemps, a.steps, a.warmup, a.repeats, a.burn, a.autocorr_steps, a.parent)
+        a.json = a.json or os.path.join(ROOT, 'profiles', 'moves_timing.json')
+    elif a.adapt:
         res = run_adaptive(a.walkers, a.ntemps, a.steps, a.warmup, a.repeats, a.burn, a.lag, a.time)
         a.json = a.json or os.path.join(ROOT, 'profiles', 'tempered_adaptive.json')
     else:
