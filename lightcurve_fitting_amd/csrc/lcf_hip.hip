@@ -1244,9 +1244,131 @@ __device__ __forceinline__ int not_hoisted(int v) {
     asm volatile("" : "+v"(v));
     return v;
 }
+// ---- the resident half-step's record and LDS batches (k_solo_run; each switch: 0 = the form before it, for the A/B) ------
+// LCF_SCALAR_DRAW: the draw records are read through a constant-address-space pointer -- scalar loads, served from the
+// scalar cache that the hint of the previous half-step has filled -- and the accept test reloads what it needs of the
+// record behind barrier 2 instead of carrying it across the columns.
+// LCF_BATCH_HEAD / _COMMIT: the LDS operands of a phase are requested by ONE statement and waited for once.
+// Written as instructions because the compiler orders plain LDS reads by their first use and sinks them below
+// branches: the source's "one batch" became two to four dependent round trips on the wave everybody waits for.
+// (Measured and dropped: the same for the column entry behind barrier 1 -- nine reads, one wait, then the branch on the
+// abort word: 0.01 us per half-step SLOWER in every alternation, DESIGN section 5.  All eight waves pass there at once,
+// and each then waits for operands it would otherwise have had in its own time.)
+#ifndef LCF_SCALAR_DRAW
+#define LCF_SCALAR_DRAW 1
+#endif
+#ifndef LCF_BATCH_HEAD
+#define LCF_BATCH_HEAD 1
+#endif
+#ifndef LCF_BATCH_COMMIT
+#define LCF_BATCH_COMMIT 1
+#endif
+typedef unsigned int lcf_u32x4 __attribute__((ext_vector_type(4)));
+typedef int lcf_i32x4 __attribute__((ext_vector_type(4)));
+// A draw record.  SCALAR (the resident kernels): every field through a constant-address-space pointer -- scalar loads of
+// the 48 bytes, out of the scalar cache where the hint of the previous half-step has put them -- because through the
+// ordinary pointer the compiler must assume that the half-step's own stores and statements change the record, and reads
+// it with vector loads, field by field where it is used.  What makes the constant view sound: the records of a launch are
+// written by k_draws in EARLIER kernels of the same stream and by nothing while the launch runs (the generation of the
+// next block goes behind the launch in the stream), and a kernel starts with the scalar cache invalidated.
+template <bool SCALAR>
+__device__ __forceinline__ DrawRec draw_record(const DrawRec* p) {
+    if constexpr (SCALAR) {
+        typedef const DrawRec __attribute__((address_space(4)))* DrawPtr;
+        const DrawPtr c = (DrawPtr)p;
+        DrawRec r;
+        r.wid = c->wid, r.pid = c->pid, r.wprev = c->wprev, r.pprev = c->pprev;
+        r.z = c->z, r.zl = c->zl, r.lnu = c->lnu;
+        r.wage = c->wage, r.page = c->page;
+        // What the head reads is requested HERE, together, and held in scalar registers: left to itself the compiler sinks
+        // every one of these loads to its use -- the partner's age into the head, z behind the poll, each a round trip
+        // of its own on the path everybody waits for.  ((n_dim - 1) ln z and ln u are not held: the commit reloads them.)
+        int z_lo = __double2loint(r.z), z_hi = __double2hiint(r.z);
+        asm volatile("" : "+s"(r.wid), "+s"(r.pid), "+s"(z_lo), "+s"(z_hi), "+s"(r.wage), "+s"(r.page));
+        r.z = __hiloint2double(z_hi, z_lo);
+        return r;
+    } else {
+        return *p;
+    }
+}
+// Byte offset of an object of the workgroup's LDS, as the address operand of an LDS instruction.
+__device__ __forceinline__ unsigned int lds_offset(const void* p) {
+    typedef const __attribute__((address_space(3))) unsigned char* LdsBytes;
+    return (unsigned int)(__SIZE_TYPE__)(LdsBytes)p;
+}
+__device__ __forceinline__ double f64_of(unsigned int lo, unsigned int hi) { return __hiloint2double((int)hi, (int)lo); }
+// The half-step's scratch words (sc: coefficients, log-prior | abort word; sq; sx) and the launch's block behind them
+// (solo_half_step's layout), in bytes from `sc`.
+constexpr int kScProposal = (kNCoef + 2) * 8;
+constexpr int kScPosition = kScProposal + (kMaxDim + (kMaxDim & 1)) * 8;
+constexpr int kScLogPost = kScPosition + kMaxDim * 8;                  // log-posterior | acceptance count
+constexpr int kScUniforms = (kNCoef + 2 + 2 * (kMaxDim + (kMaxDim & 1)) + 4) * 8;
+static_assert(kScLogPost % 16 == 0 && kScUniforms % 16 == 0, "16-byte reads");
+static_assert(offsetof(RunUniforms, ring_mask) == 8 && offsetof(RunUniforms, row_bytes) == 12 && offsetof(RunUniforms, ver_bytes) == 16 &&
+              offsetof(RunUniforms, sum0) == 32 && offsetof(RunUniforms, n_parts) == 40,
+              "the groups the batch below reads with one instruction each");
+// The commit, behind barrier 2: the eight wave sums (`red_at`), log-posterior | count, this lane's number of the proposal
+// and of the position (`mine_at`: sc + 8 mine), the block's words for the sum and for the row's address -- and, in the same
+// wait, (n_dim - 1) ln z | ln u and the walker of the draw record `rec`, by scalar loads (LCF_SCALAR_DRAW; they stand
+// behind the LDS reads: the record's address may be fresh from a vector instruction).
+struct CommitOperands {
+    lcf_u32x4 a0, a1, b0, b1, lc, sums, geo;   // sums: sum0 | n_parts, n_walkers; geo: board | ring_mask, row_bytes
+    double ver_bytes, q_mine, x_mine;          // (ver_bytes: its bits)
+    lcf_u32x4 zl_lnu;
+    int wid;
+};
+template <bool RECORD>
+__device__ __forceinline__ void commit_batch(unsigned int red_at, unsigned int sc_at, unsigned int mine_at, const void* rec,
+                                             CommitOperands& c) {
+    if constexpr (RECORD)
+        asm volatile("ds_read_b128 %0, %12\n\t"
+                     "ds_read_b128 %1, %12 offset:16\n\t"
+                     "ds_read_b128 %2, %12 offset:32\n\t"
+                     "ds_read_b128 %3, %12 offset:48\n\t"
+                     "ds_read_b128 %4, %13 offset:%16\n\t"
+                     "ds_read_b128 %5, %13 offset:%17\n\t"
+                     "ds_read_b128 %6, %13 offset:%18\n\t"
+                     "ds_read_b64 %7, %13 offset:%19\n\t"
+                     "ds_read_b64 %8, %14 offset:%20\n\t"
+                     "ds_read_b64 %9, %14 offset:%21\n\t"
+                     "s_load_dwordx4 %10, %15, 0x18\n\t"
+                     "s_load_dword %11, %15, 0x0\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
+                       "=&v"(c.q_mine), "=&v"(c.x_mine), "=&s"(c.zl_lnu), "=&s"(c.wid)
+                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "s"(rec), "n"(kScLogPost), "n"(kScUniforms + 32), "n"(kScUniforms),
+                       "n"(kScUniforms + 16), "n"(kScProposal), "n"(kScPosition)
+                     : "memory");
+    else
+        asm volatile("ds_read_b128 %0, %10\n\t"
+                     "ds_read_b128 %1, %10 offset:16\n\t"
+                     "ds_read_b128 %2, %10 offset:32\n\t"
+                     "ds_read_b128 %3, %10 offset:48\n\t"
+                     "ds_read_b128 %4, %11 offset:%13\n\t"
+                     "ds_read_b128 %5, %11 offset:%14\n\t"
+                     "ds_read_b128 %6, %11 offset:%15\n\t"
+                     "ds_read_b64 %7, %11 offset:%16\n\t"
+                     "ds_read_b64 %8, %12 offset:%17\n\t"
+                     "ds_read_b64 %9, %12 offset:%18\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
+                       "=&v"(c.q_mine), "=&v"(c.x_mine)
+                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "n"(kScLogPost), "n"(kScUniforms + 32), "n"(kScUniforms),
+                       "n"(kScUniforms + 16), "n"(kScProposal), "n"(kScPosition)
+                     : "memory");
+}
+// (n_dim - 1) ln z | ln u and the walker of the record alone (LCF_SCALAR_DRAW without the commit's batch)
+__device__ __forceinline__ void record_reload(const void* rec, lcf_u32x4& zl_lnu, int& wid) {
+    asm volatile("s_nop 4\n\ts_load_dwordx4 %0, %2, 0x18\n\ts_load_dword %1, %2, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(zl_lnu), "=&s"(wid) : "s"(rec) : "memory");
+}
 // ... from a resident launch's block of invariants (RunUniforms): the same address, multiplied out once per launch
+__device__ __forceinline__ size_t board_entry_bytes(unsigned int ring_mask, unsigned long long ver_bytes, unsigned int row_bytes,
+                                                    unsigned int tag, int wid, int col) {
+    return (tag & ring_mask) * ver_bytes + ((size_t)(unsigned int)wid * row_bytes + 16u * (unsigned int)col);
+}
 __device__ __forceinline__ size_t board_entry_bytes(const RunUniforms& u, unsigned int tag, int wid, int col) {
-    return (tag & u.ring_mask) * u.ver_bytes + ((size_t)(unsigned int)wid * u.row_bytes + 16u * (unsigned int)col);
+    return board_entry_bytes(u.ring_mask, u.ver_bytes, u.row_bytes, tag, wid, col);
 }
 __device__ __forceinline__ unsigned long long* board_entry(unsigned long long* board, const RunUniforms& u, unsigned int tag,
                                                            int wid, int col) {
@@ -1260,8 +1382,6 @@ __device__ inline unsigned int* board_progress(unsigned long long* board, const 
 // is on).  The store is not waited for; the load is (a poll has nothing else to do).  Written as instructions because
 // the language has no 16-byte atomic: the hardware moves an aligned 16-byte lane access as one piece, and the tags make
 // even 8-byte pieces safe.
-typedef unsigned int lcf_u32x4 __attribute__((ext_vector_type(4)));
-typedef int lcf_i32x4 __attribute__((ext_vector_type(4)));
 // AGENT: the board of a one-launch run lives in this GPU's ordinary memory and is shared by its own workgroups only.
 // Its 16-byte accesses are nevertheless issued at system scope (sc0 sc1), like those of the inter-rank boards: with sc1
 // alone (device scope) the same run takes TWICE as long (0.70 against 0.37 ms per launch of 64 half-steps at configs[1]
@@ -1594,6 +1714,7 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
 struct LaneRows {
     double cj, x;     // lane d < nd: coordinate d of the partner, of the walker; lanes nd, nd + 1: x = log-posterior, count
     PriorDev prior;   // lane d: the prior of parameter d
+    int n_par, n_dim, has_priors;   // the block's words for lane_head, requested in front of the poll (LCF_BATCH_HEAD)
 };
 
 template <int ND, int BOARD>
@@ -1602,14 +1723,29 @@ __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const Draw
     const int nd = ND > 0 ? ND : __builtin_amdgcn_readfirstlane(ru->nd);
     const int lane = not_hoisted(lane_in);   // (lane masks and addresses: computed here, not carried across the launch)
     h.cj = h.x = 0.;
+    // (lane_head's share of the block goes out with the board's geometry, in front of the poll: the poll's statements
+    // order memory, so behind them the read would be a round trip of its own in front of the store of the proposal)
+    h.n_par = h.n_dim = h.has_priors = 0;
+    unsigned char* board = reinterpret_cast<unsigned char*>(ru->board);
+    unsigned int ring_mask = ru->ring_mask, row_bytes = ru->row_bytes;
+    unsigned long long ver_bytes = ru->ver_bytes;
+    if constexpr (LCF_BATCH_HEAD != 0) {
+        h.n_par = ru->n_par, h.n_dim = ru->n_dim, h.has_priors = ru->has_priors;
+        // ONE wait for the board's geometry and lane_head's words, here, on every lane: a value that is still on its
+        // way at the poll is waited for behind it, with everything requested since
+        asm volatile("" : "+v"(board), "+v"(ring_mask), "+v"(row_bytes), "+v"(ver_bytes), "+v"(h.n_par), "+v"(h.n_dim), "+v"(h.has_priors));
+    }
     if (lane <= nd + 1) {
         const unsigned int wtag = board_tag(G, dr.wage, g_run0), ptag = board_tag(G, dr.page, g_run0);
         // (lanes nd, nd + 1 have no entry of the partner's to wait for: they ask for their own twice)
         const bool both = lane < nd;
         const unsigned int tag_l = both ? ptag : wtag;
         const int wid_l = both ? dr.pid : dr.wid;
-        board_take_pair<BOARD == 2>(sm, board_entry(ru->board, *ru, tag_l, wid_l, lane), board_entry(ru->board, *ru, wtag, dr.wid, lane),
-                                    tag_l, wtag, wid_l, dr.wid, lane, arrive_goal, h.cj, h.x);
+        const unsigned long long* const pa =
+            reinterpret_cast<const unsigned long long*>(board + board_entry_bytes(ring_mask, ver_bytes, row_bytes, tag_l, wid_l, lane));
+        const unsigned long long* const pw =
+            reinterpret_cast<const unsigned long long*>(board + board_entry_bytes(ring_mask, ver_bytes, row_bytes, wtag, dr.wid, lane));
+        board_take_pair<BOARD == 2>(sm, pa, pw, tag_l, wtag, wid_l, dr.wid, lane, arrive_goal, h.cj, h.x);
     }
     // (the block holds a flat prior where the problem has none; lanes >= kMaxDim read the entry of lane - 16, 32, 48 and
     // never use it: a prior's term is taken from lanes below n_dim only)
@@ -1645,8 +1781,10 @@ __device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& d
     constexpr int kD = ND > 0 ? ND : kMaxDim;
     const int nd = ND > 0 ? ND : __builtin_amdgcn_readfirstlane(ru->nd);
     const int lane = not_hoisted(lane_in);
-    // (the head's share of the block, requested together; has_priors as a scalar, for the branch)
-    const int n_par = ru->n_par, n_dim = ru->n_dim, has_priors = __builtin_amdgcn_readfirstlane(ru->has_priors);
+    // (the head's share of the block, requested together -- by lane_head_fetch, in front of the poll; has_priors as a
+    // scalar, for the branch)
+    const int n_par = LCF_BATCH_HEAD != 0 ? h.n_par : ru->n_par, n_dim = LCF_BATCH_HEAD != 0 ? h.n_dim : ru->n_dim;
+    const int has_priors = __builtin_amdgcn_readfirstlane(LCF_BATCH_HEAD != 0 ? h.has_priors : ru->has_priors);
     const double cj = h.cj, x = h.x;
     const double q = lane < nd ? cj - (cj - x) * dr.z : 0.;   // emcee: c_j - (c_j - x_i) z
 #ifdef LCF_STAMPS
@@ -1739,7 +1877,8 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                                                const DrawRec* __restrict__ draws, const DrawRec* draws_next, long long G,
                                                long long g_run0, int i, unsigned char* smem, ColumnOperands& first_col,
                                                bool first, bool write_state, const int tid, const int run_flags = 0,
-                                               const unsigned int arrive_goal = 0u, const RunUniforms* ru = nullptr) {
+                                               const unsigned int arrive_goal = 0u, const RunUniforms* ru = nullptr,
+                                               const DrawRec* held = nullptr) {
     // RES (k_solo_run): the launch's invariants come from its block in LDS, `ru` (RunUniforms, right behind the words
     // below), wherever the half-step would otherwise load a field of `pb` / `sm`; the cold paths keep `pb`.
     constexpr bool RES = BOARD >= 2;
@@ -1766,7 +1905,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
 #ifdef LCF_STAMPS
     if (tid == 0 && blockIdx.x < 1024) g_wall[((G & 1) * 1024 + blockIdx.x) * 2] = wall_clock64();
 #endif
-    const DrawRec dr = draws[i];     // wave-uniform
+    const DrawRec dr = held != nullptr ? *held : draws[i];     // wave-uniform (`held`: the caller has read it, draw_record)
     if (BOARD == 1 && blockIdx.x == 0 && tid < sm.n_board_ranks)
         // This launch runs, so every launch in front of it in the stream has finished: tell every rank that this rank
         // is through with all half-steps before G (stream order does the counting; no atomics).
@@ -1818,10 +1957,13 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         // to launch, so the record is then in this XCD's L2 instead of HBM when the next serial head starts with it
         // (a hint only: nothing depends on the value or on the placement).
         if (BOARD >= 2) {
-            // Resident launches: the record is read by a SCALAR load at the top of the next half-step, so it is the scalar
-            // cache of this CU that should hold it by then -- two scalar loads (the record may straddle a line), waited for
-            // here, by a wave that has nothing else to do in the shadow of the head (5.51 -> 5.42 us per half-step against
-            // the vector touch below, which only brings the record into the XCD's L2).
+            // Resident launches: the record is read by scalar loads at the top of the next half-step (k_solo_run reads
+            // the records through a constant-address-space pointer; while they went through an ordinary pointer the
+            // compiler read them with vector loads, which this hint only served from the XCD's L2), so it is the scalar
+            // cache of this CU that should hold it by then -- two scalar loads, of the record's first and last word: a
+            // 48-byte record sits at offset 0, 16, 32 or 48 of a 64-byte line and straddles two of them at 32 and 48 --
+            // waited for here, by a wave that has nothing else to do in the shadow of the head (5.51 -> 5.42 us per
+            // half-step against the vector touch below, which only brings the record into the XCD's L2).
             if (tid >= 64 && tid < 128 && draws_next != nullptr) {
                 const int* nxt = reinterpret_cast<const int*>(draws_next + i);
                 int a_, b_;
@@ -1989,35 +2131,67 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         if (tid >= 64) return false;
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);   // (the row's readers wait for this)
         if constexpr (RES) {
-            // Every LDS read between here and the post is requested NOW -- the wave sums, the walker's log-posterior and
-            // count, this lane's number of the proposal and of the position, the block's words for the sum and for the
-            // row's address -- and waited for once; the sum keeps its order, (w0 + w1) + (w2 + w3) per part, parts in order.
-            const double2* red2 = reinterpret_cast<const double2*>(red);
-            const double2 lc = *reinterpret_cast<const double2*>(sx + kMaxDim);   // log-posterior | acceptance count
+            // Every LDS read between here and the post -- the wave sums, the walker's log-posterior and count, this lane's
+            // number of the proposal and of the position, the block's words for the sum and for the row's address -- and
+            // the record's words for the accept test and the post, which nobody has carried across the columns.
+            // The sum keeps its order, (w0 + w1) + (w2 + w3) per part, parts in order.
             const int col = not_hoisted(tid);
             const int mine = col < nd ? col : 0;
-            const double q_mine = sq[mine], x_mine = sx[mine];
-            const double sum0 = ru->sum0;
             const unsigned int tag = (unsigned int)(G + 1);
-            const size_t entry = LCF_EARLY_POST != 0 ? entry_early : board_entry_bytes(*ru, tag, dr.wid, col);   // (the same on every rank's board)
-            unsigned char* const own_board = reinterpret_cast<unsigned char*>(ru->board);
-            double sum = sum0;
-            if (NPARTS <= 2) {
-                const int n_parts = ru->n_parts;
-                const double2 a0 = red2[0], a1 = red2[1], b0 = red2[2], b1 = red2[3];
-                const double s1 = sum + ((a0.x + a0.y) + (a1.x + a1.y));
+            constexpr bool kRecord = LCF_SCALAR_DRAW != 0;
+            int wid = dr.wid;
+            double zl = dr.zl, lnu = dr.lnu, sum, lp_i, count0, q_mine, x_mine;
+            size_t entry;   // (the same on every rank's board)
+            unsigned char* own_board;
+            if constexpr (NPARTS <= 2 && LCF_BATCH_COMMIT != 0) {
+                // ONE statement requests all of it, the record's words by scalar loads, and waits once (commit_batch)
+                const unsigned int sc_at = lds_offset(sc);
+                CommitOperands c;
+                commit_batch<kRecord>(lds_offset(red), sc_at, sc_at + 8u * (unsigned int)mine, draws + i, c);
+                if constexpr (kRecord) wid = c.wid, zl = f64_of(c.zl_lnu.x, c.zl_lnu.y), lnu = f64_of(c.zl_lnu.z, c.zl_lnu.w);
+                // (board_entry_bytes, from the batch's words)
+                entry = (tag & c.geo.z) * (unsigned long long)__double_as_longlong(c.ver_bytes) +
+                        ((size_t)(unsigned int)wid * c.geo.w + 16u * (unsigned int)col);
+                own_board = reinterpret_cast<unsigned char*>((size_t)c.geo.x | ((size_t)c.geo.y << 32));
+                sum = f64_of(c.sums.x, c.sums.y);
+                const int n_parts = (int)c.sums.z;
+                const double s1 = sum + ((f64_of(c.a0.x, c.a0.y) + f64_of(c.a0.z, c.a0.w)) + (f64_of(c.a1.x, c.a1.y) + f64_of(c.a1.z, c.a1.w)));
                 sum = n_parts > 0 ? s1 : sum;
-                const double s2 = sum + ((b0.x + b0.y) + (b1.x + b1.y));
+                const double s2 = sum + ((f64_of(c.b0.x, c.b0.y) + f64_of(c.b0.z, c.b0.w)) + (f64_of(c.b1.x, c.b1.y) + f64_of(c.b1.z, c.b1.w)));
                 sum = n_parts > 1 ? s2 : sum;
+                lp_i = f64_of(c.lc.x, c.lc.y), count0 = f64_of(c.lc.z, c.lc.w);
+                q_mine = c.q_mine, x_mine = c.x_mine;
             } else {
-                const int n_parts = __builtin_amdgcn_readfirstlane(ru->n_parts);
-                for (int k = 0; k < n_parts; ++k) sum += (red2[2 * k].x + red2[2 * k].y) + (red2[2 * k + 1].x + red2[2 * k + 1].y);
+                // Plain LDS reads (the four-group kernels; LCF_BATCH_COMMIT = 0: the compiler requests them in two
+                // batches around the accept arithmetic)
+                if constexpr (kRecord) {
+                    lcf_u32x4 r;
+                    record_reload(draws + i, r, wid);
+                    zl = f64_of(r.x, r.y), lnu = f64_of(r.z, r.w);
+                }
+                const double2* red2 = reinterpret_cast<const double2*>(red);
+                const double2 lc = *reinterpret_cast<const double2*>(sx + kMaxDim);   // log-posterior | acceptance count
+                q_mine = sq[mine], x_mine = sx[mine];
+                entry = LCF_EARLY_POST != 0 ? entry_early : board_entry_bytes(*ru, tag, wid, col);
+                own_board = reinterpret_cast<unsigned char*>(ru->board);
+                sum = ru->sum0;
+                if (NPARTS <= 2) {
+                    const int n_parts = ru->n_parts;
+                    const double2 a0 = red2[0], a1 = red2[1], b0 = red2[2], b1 = red2[3];
+                    const double s1 = sum + ((a0.x + a0.y) + (a1.x + a1.y));
+                    sum = n_parts > 0 ? s1 : sum;
+                    const double s2 = sum + ((b0.x + b0.y) + (b1.x + b1.y));
+                    sum = n_parts > 1 ? s2 : sum;
+                } else {
+                    const int n_parts = __builtin_amdgcn_readfirstlane(ru->n_parts);
+                    for (int k = 0; k < n_parts; ++k) sum += (red2[2 * k].x + red2[2 * k].y) + (red2[2 * k + 1].x + red2[2 * k + 1].y);
+                }
+                lp_i = lc.x, count0 = lc.y;
             }
             const double scored = lpr - 0.5 * sum;
             const double nlp = excluded ? -INFINITY : scored;
-            const double lp_i = lc.x;
-            const bool ok = (dr.zl + nlp - lp_i) > dr.lnu;
-            const double count = lc.y + (ok ? 1. : 0.);
+            const bool ok = (zl + nlp - lp_i) > lnu;
+            const double count = count0 + (ok ? 1. : 0.);
             if (tid <= nd + 1) {
                 const double v = tid < nd ? (ok ? q_mine : x_mine) : tid == nd ? (ok ? nlp : lp_i) : count;
                 // the row first: its readers wait for it; state, snapshot and chain follow
@@ -2032,21 +2206,21 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                 }
                 if (BOARD == 2 && write_state) {   // (the set of state buffers the run did NOT start from: chosen by the fill)
                     if (tid < nd)
-                        ru->X[(size_t)dr.wid * nd + tid] = v;
+                        ru->X[(size_t)wid * nd + tid] = v;
                     else if (tid == nd)
-                        ru->LP[dr.wid] = v;
+                        ru->LP[wid] = v;
                     else
-                        ru->nacc[dr.wid] = (long long)v;
+                        ru->nacc[wid] = (long long)v;
                     unsigned long long* const snap = ru->snap_out;
                     if (snap) {   // ... and the host's copy of it
                         const size_t nw = ru->n_walkers;
-                        if (tid < nd) snap[1 + (size_t)dr.wid * nd + tid] = (unsigned long long)__double_as_longlong(v);
-                        else if (tid == nd) snap[1 + nw * nd + dr.wid] = (unsigned long long)__double_as_longlong(v);
-                        else snap[1 + nw * nd + nw + dr.wid] = (unsigned long long)(long long)v;
+                        if (tid < nd) snap[1 + (size_t)wid * nd + tid] = (unsigned long long)__double_as_longlong(v);
+                        else if (tid == nd) snap[1 + nw * nd + wid] = (unsigned long long)__double_as_longlong(v);
+                        else snap[1 + nw * nd + nw + wid] = (unsigned long long)(long long)v;
                     }
                 }
                 if (BOARD == 2 && (run_flags & kRunStoreChain)) {   // (one GPU: every walker's row is decided here)
-                    const size_t at = (size_t)row * ru->n_walkers + dr.wid;
+                    const size_t at = (size_t)row * ru->n_walkers + wid;
                     if (tid < nd) ru->chain[at * nd + tid] = v;
                     else if (tid == nd) ru->chain_lp[at] = v;
                 }
@@ -2323,14 +2497,17 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
         const DrawRec* draws = draws0 + (size_t)h * n_half;
 #pragma unroll 1
         for (int i = slot_lo + blockIdx.x; i < slot_end; i += n_wg) {
-            if (draws[i].wid < 0) continue;   // (uniform) an odd ensemble's smaller colour leaves its last slot empty
+            // the record, once for this test and for the half-step (LCF_SCALAR_DRAW = 0: the half-step reads it itself)
+            const DrawRec rec = draw_record<LCF_SCALAR_DRAW != 0>(draws + i);
+            if (rec.wid < 0) continue;   // (uniform) an odd ensemble's smaller colour leaves its last slot empty
             // the record this workgroup needs next: its next slot of this half-step, else its first of the next one
             const bool more = i + n_wg < slot_end;
             const DrawRec* hint = more ? draws + n_wg : h + 1 < n_hs ? draws + n_half + (slot_lo + (int)blockIdx.x - i) : nullptr;
             const int tid = threadIdx.x;
             if (solo_half_step<ND, VARIANT, THERM, NPARTS, kBoard, MODEL>(pb, pbp, sm, (rel0 + h) >> 1, draws, hint,
                                                                           g_run0 + rel0 + h, g_run0, i, smem, first_col, first,
-                                                                          rel0 + h >= state_from, tid, run_flags, arrive_goal, ru))
+                                                                          rel0 + h >= state_from, tid, run_flags, arrive_goal, ru,
+                                                                          LCF_SCALAR_DRAW != 0 ? &rec : nullptr))
                 return;
             first = false;
         }
