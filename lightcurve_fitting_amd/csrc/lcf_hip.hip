@@ -276,6 +276,14 @@ __device__ unsigned int g_progress[64 * 16];
 #else
 #define LCF_STAMP(W, k) do {} while (0)
 #endif
+// Diagnostic build (-DLCF_POLL_LOOKS; never shipped): how many looks the polls of the resident kernels' heads needed.
+// A look is one pass of board_take_pair's loop on wave 0 -- one round trip to memory; a poll's number is that of its
+// slowest lane.  Wave 0 counts in LDS (polls of 1, 2, 3 and more looks, and the looks in total) and adds the workgroup's
+// counts to g_poll_looks when it leaves the launch (lcf_debug_read_poll_looks; tools/debug/poll_looks.py).
+#ifdef LCF_POLL_LOOKS
+__device__ unsigned long long g_poll_looks[4];
+__shared__ unsigned int s_poll_looks[4], s_poll_now;   // (s_poll_now: the looks of the poll under way, the maximum over its lanes)
+#endif
 
 // ---- epoch-major likelihood: one lane per COLUMN (an observation time and its points, DevProblem::em_*) ----------------
 // The lane computes the column's thermal state in registers and walks the column's points itself: no hand-off of the
@@ -1263,6 +1271,17 @@ __device__ __forceinline__ int not_hoisted(int v) {
 #ifndef LCF_BATCH_COMMIT
 #define LCF_BATCH_COMMIT 1
 #endif
+// LCF_COMMIT_WAVE: the wave that runs what stands behind barrier 2 -- accept test, post, state, snapshot, chain.  1: wave 0
+// leaves at barrier 2 for the loop top and the poll of the workgroup's next item, whose rows come from the board and
+// never from this workgroup's registers or LDS; the commit reloads every operand anyway.  0 = wave 0 commits, then polls.
+// LCF_SHADOW_WAVE: the wave that loads the abort word and hints the next draw record in the head's shadow (1 = the form
+// before: the committing wave would then reach barrier 0 a round trip behind its commit).
+#ifndef LCF_COMMIT_WAVE
+#define LCF_COMMIT_WAVE 1
+#endif
+#ifndef LCF_SHADOW_WAVE
+#define LCF_SHADOW_WAVE 2
+#endif
 typedef unsigned int lcf_u32x4 __attribute__((ext_vector_type(4)));
 typedef int lcf_i32x4 __attribute__((ext_vector_type(4)));
 // A draw record.  SCALAR (the resident kernels): every field through a constant-address-space pointer -- scalar loads of
@@ -1297,19 +1316,20 @@ __device__ __forceinline__ unsigned int lds_offset(const void* p) {
     return (unsigned int)(__SIZE_TYPE__)(LdsBytes)p;
 }
 __device__ __forceinline__ double f64_of(unsigned int lo, unsigned int hi) { return __hiloint2double((int)hi, (int)lo); }
-// The half-step's scratch words (sc: coefficients, log-prior | abort word; sq; sx) and the launch's block behind them
-// (solo_half_step's layout), in bytes from `sc`.
+// The half-step's scratch words (sc: coefficients, log-prior | abort word; sq; sx; solo_half_step's layout), in bytes
+// from `sc`.  The resident kernels keep TWO copies of them (kScBlock bytes each) in front of the launch's block: wave 1
+// commits item n out of one copy while wave 0 writes the head of item n + 1 into the other (solo_half_step, `copy`).
 constexpr int kScProposal = (kNCoef + 2) * 8;
 constexpr int kScPosition = kScProposal + (kMaxDim + (kMaxDim & 1)) * 8;
 constexpr int kScLogPost = kScPosition + kMaxDim * 8;                  // log-posterior | acceptance count
-constexpr int kScUniforms = (kNCoef + 2 + 2 * (kMaxDim + (kMaxDim & 1)) + 4) * 8;
-static_assert(kScLogPost % 16 == 0 && kScUniforms % 16 == 0, "16-byte reads");
+constexpr int kScBlock = (kNCoef + 2 + 2 * (kMaxDim + (kMaxDim & 1)) + 4) * 8;
+static_assert(kScLogPost % 16 == 0 && kScBlock % 16 == 0, "16-byte reads");
 static_assert(offsetof(RunUniforms, ring_mask) == 8 && offsetof(RunUniforms, row_bytes) == 12 && offsetof(RunUniforms, ver_bytes) == 16 &&
               offsetof(RunUniforms, sum0) == 32 && offsetof(RunUniforms, n_parts) == 40,
               "the groups the batch below reads with one instruction each");
 // The commit, behind barrier 2: the eight wave sums (`red_at`), log-posterior | count, this lane's number of the proposal
-// and of the position (`mine_at`: sc + 8 mine), the block's words for the sum and for the row's address -- and, in the same
-// wait, (n_dim - 1) ln z | ln u and the walker of the draw record `rec`, by scalar loads (LCF_SCALAR_DRAW; they stand
+// and of the position (`mine_at`: sc + 8 mine), the launch block's words (`ru_at`) for the sum and for the row's address --
+// and, in the same wait, (n_dim - 1) ln z | ln u and the walker of the draw record `rec`, by scalar loads (LCF_SCALAR_DRAW; they stand
 // behind the LDS reads: the record's address may be fresh from a vector instruction).
 struct CommitOperands {
     lcf_u32x4 a0, a1, b0, b1, lc, sums, geo;   // sums: sum0 | n_parts, n_walkers; geo: board | ring_mask, row_bytes
@@ -1318,43 +1338,41 @@ struct CommitOperands {
     int wid;
 };
 template <bool RECORD>
-__device__ __forceinline__ void commit_batch(unsigned int red_at, unsigned int sc_at, unsigned int mine_at, const void* rec,
-                                             CommitOperands& c) {
+__device__ __forceinline__ void commit_batch(unsigned int red_at, unsigned int sc_at, unsigned int mine_at, unsigned int ru_at,
+                                             const void* rec, CommitOperands& c) {
     if constexpr (RECORD)
         asm volatile("ds_read_b128 %0, %12\n\t"
                      "ds_read_b128 %1, %12 offset:16\n\t"
                      "ds_read_b128 %2, %12 offset:32\n\t"
                      "ds_read_b128 %3, %12 offset:48\n\t"
-                     "ds_read_b128 %4, %13 offset:%16\n\t"
-                     "ds_read_b128 %5, %13 offset:%17\n\t"
-                     "ds_read_b128 %6, %13 offset:%18\n\t"
-                     "ds_read_b64 %7, %13 offset:%19\n\t"
-                     "ds_read_b64 %8, %14 offset:%20\n\t"
-                     "ds_read_b64 %9, %14 offset:%21\n\t"
-                     "s_load_dwordx4 %10, %15, 0x18\n\t"
-                     "s_load_dword %11, %15, 0x0\n\t"
+                     "ds_read_b128 %4, %13 offset:%17\n\t"
+                     "ds_read_b128 %5, %15 offset:32\n\t"
+                     "ds_read_b128 %6, %15\n\t"
+                     "ds_read_b64 %7, %15 offset:16\n\t"
+                     "ds_read_b64 %8, %14 offset:%18\n\t"
+                     "ds_read_b64 %9, %14 offset:%19\n\t"
+                     "s_load_dwordx4 %10, %16, 0x18\n\t"
+                     "s_load_dword %11, %16, 0x0\n\t"
                      "s_waitcnt lgkmcnt(0)"
                      : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
                        "=&v"(c.q_mine), "=&v"(c.x_mine), "=&s"(c.zl_lnu), "=&s"(c.wid)
-                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "s"(rec), "n"(kScLogPost), "n"(kScUniforms + 32), "n"(kScUniforms),
-                       "n"(kScUniforms + 16), "n"(kScProposal), "n"(kScPosition)
+                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "v"(ru_at), "s"(rec), "n"(kScLogPost), "n"(kScProposal), "n"(kScPosition)
                      : "memory");
     else
         asm volatile("ds_read_b128 %0, %10\n\t"
                      "ds_read_b128 %1, %10 offset:16\n\t"
                      "ds_read_b128 %2, %10 offset:32\n\t"
                      "ds_read_b128 %3, %10 offset:48\n\t"
-                     "ds_read_b128 %4, %11 offset:%13\n\t"
-                     "ds_read_b128 %5, %11 offset:%14\n\t"
-                     "ds_read_b128 %6, %11 offset:%15\n\t"
-                     "ds_read_b64 %7, %11 offset:%16\n\t"
-                     "ds_read_b64 %8, %12 offset:%17\n\t"
-                     "ds_read_b64 %9, %12 offset:%18\n\t"
+                     "ds_read_b128 %4, %11 offset:%14\n\t"
+                     "ds_read_b128 %5, %13 offset:32\n\t"
+                     "ds_read_b128 %6, %13\n\t"
+                     "ds_read_b64 %7, %13 offset:16\n\t"
+                     "ds_read_b64 %8, %12 offset:%15\n\t"
+                     "ds_read_b64 %9, %12 offset:%16\n\t"
                      "s_waitcnt lgkmcnt(0)"
                      : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
                        "=&v"(c.q_mine), "=&v"(c.x_mine)
-                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "n"(kScLogPost), "n"(kScUniforms + 32), "n"(kScUniforms),
-                       "n"(kScUniforms + 16), "n"(kScProposal), "n"(kScPosition)
+                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "v"(ru_at), "n"(kScLogPost), "n"(kScProposal), "n"(kScPosition)
                      : "memory");
 }
 // (n_dim - 1) ln z | ln u and the walker of the record alone (LCF_SCALAR_DRAW without the commit's batch)
@@ -1534,6 +1552,9 @@ __device__ __forceinline__ void board_take_pair(const DevSampler& sm, const unsi
         if (a_ok && b_ok) {
             va = __hiloint2double((int)a.z, (int)a.x);
             vb = __hiloint2double((int)b.z, (int)b.x);
+#ifdef LCF_POLL_LOOKS
+            atomicMax(&s_poll_now, (unsigned int)spin + 1u);
+#endif
             return;
         }
         if ((spin & 15) == 15) {
@@ -1735,6 +1756,9 @@ __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const Draw
         // way at the poll is waited for behind it, with everything requested since
         asm volatile("" : "+v"(board), "+v"(ring_mask), "+v"(row_bytes), "+v"(ver_bytes), "+v"(h.n_par), "+v"(h.n_dim), "+v"(h.has_priors));
     }
+#ifdef LCF_POLL_LOOKS
+    if (lane == 0) atomicExch(&s_poll_now, 0u);
+#endif
     if (lane <= nd + 1) {
         const unsigned int wtag = board_tag(G, dr.wage, g_run0), ptag = board_tag(G, dr.page, g_run0);
         // (lanes nd, nd + 1 have no entry of the partner's to wait for: they ask for their own twice)
@@ -1747,6 +1771,15 @@ __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const Draw
             reinterpret_cast<const unsigned long long*>(board + board_entry_bytes(ring_mask, ver_bytes, row_bytes, wtag, dr.wid, lane));
         board_take_pair<BOARD == 2>(sm, pa, pw, tag_l, wtag, wid_l, dr.wid, lane, arrive_goal, h.cj, h.x);
     }
+#ifdef LCF_POLL_LOOKS
+    if (lane == 0) {   // (an aborted poll counts nothing)
+        const unsigned int looks = atomicAdd(&s_poll_now, 0u);
+        if (looks > 0u) {
+            atomicAdd(&s_poll_looks[looks < 3u ? looks - 1u : 2u], 1u);
+            atomicAdd(&s_poll_looks[3], looks);
+        }
+    }
+#endif
     // (the block holds a flat prior where the problem has none; lanes >= kMaxDim read the entry of lane - 16, 32, 48 and
     // never use it: a prior's term is taken from lanes below n_dim only)
     h.prior = ru->priors[lane & (kMaxDim - 1)];
@@ -1852,6 +1885,7 @@ __device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& d
 // Within a launch X[wid] is read and written by the walker's own workgroup only (partners come from the
 // complementary colour, which this half-step does not move), so there is nothing to synchronise.
 constexpr int kSoloScratch = kNCoef + 2 + 2 * (kMaxDim + (kMaxDim & 1));  // doubles: coefficients, log-prior, q, x
+static_assert(kScBlock == (kSoloScratch + 4) * (int)sizeof(double), "one copy of the scratch words");
 
 // BOARD (multi-GPU, lcf_sampler_run_rows): the launch covers this rank's slots [slot_lo, slot_lo + gridDim.x) of
 // half-step G; rows come from this rank's row board and the commit posts the walker's new row on EVERY rank's board.
@@ -1878,9 +1912,12 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                                                long long g_run0, int i, unsigned char* smem, ColumnOperands& first_col,
                                                bool first, bool write_state, const int tid, const int run_flags = 0,
                                                const unsigned int arrive_goal = 0u, const RunUniforms* ru = nullptr,
-                                               const DrawRec* held = nullptr) {
+                                               const DrawRec* held = nullptr, const int copy = 0) {
     // RES (k_solo_run): the launch's invariants come from its block in LDS, `ru` (RunUniforms, right behind the words
     // below), wherever the half-step would otherwise load a field of `pb` / `sm`; the cold paths keep `pb`.
+    // `copy` (RES; 0 or 1, wave-uniform): which of the two copies of the scratch words this item uses -- the parity of
+    // the workgroup's count of items.  Behind barrier 2 wave 1 alone commits the item, out of this copy, while wave 0
+    // is already in the head of the workgroup's next item and writes the other one.
     constexpr bool RES = BOARD >= 2;
     double* exptab = reinterpret_cast<double*>(smem);
     double* red = exptab + kExpTabSize;                                     // 4 wave sums per part (32 reserved)
@@ -1890,7 +1927,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
     if constexpr (!RES)
         itab_at = pb.n_itab_lds > 0
                       ? (int)(kLdsHead * sizeof(double) + (pb.n_lds_tab + kFdD2 * pb.n_filters) * sizeof(double2)) : -1;
-    double* sc = RES ? reinterpret_cast<double*>(const_cast<RunUniforms*>(ru)) - (kSoloScratch + 4)
+    double* sc = RES ? reinterpret_cast<double*>(const_cast<RunUniforms*>(ru)) - (copy ? kSoloScratch + 4 : 2 * (kSoloScratch + 4))
                      : reinterpret_cast<double*>(ltab + pb.stage_d2);  // coefficients, then log-prior
     double* sq = sc + kNCoef + 2;                                           // the proposal
     double* sx = sq + kMaxDim + (kMaxDim & 1);                              // the walker's current position, lp, draw
@@ -1964,7 +2001,9 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             // 48-byte record sits at offset 0, 16, 32 or 48 of a 64-byte line and straddles two of them at 32 and 48 --
             // waited for here, by a wave that has nothing else to do in the shadow of the head (5.51 -> 5.42 us per
             // half-step against the vector touch below, which only brings the record into the XCD's L2).
-            if (tid >= 64 && tid < 128 && draws_next != nullptr) {
+            // (Wave 2's duty, as the abort word below: wave 1 comes here from the commit of the previous item, and a
+            // round trip of its own in front of barrier 0 would make wave 0 wait for it.)
+            if (tid >= 64 * LCF_SHADOW_WAVE && tid < 64 * LCF_SHADOW_WAVE + 64 && draws_next != nullptr) {
                 const int* nxt = reinterpret_cast<const int*>(draws_next + i);
                 int a_, b_;
                 asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %2, 0x2c\n\ts_waitcnt lgkmcnt(0)"
@@ -1976,9 +2015,9 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             (void)nxt[sizeof(DrawRec) / sizeof(int) - 1];
         }
         // (the abort word: requested while wave 0 still polls, in front of barrier 0 -- these waves reach this place while
-        // wave 0 is in the previous half-step's accept and post, so the round trip is over before wave 0 arrives)
+        // wave 0 is still in its poll, so the round trip is over before wave 0 arrives; into THIS item's copy of the words)
         if constexpr (RES)
-            if (tid == 64) sctl[0] = board_aborted_at<BOARD == 2>(ru->abort_word) ? 1 : 0;   // (in the shadow of the head)
+            if (tid == 64 * LCF_SHADOW_WAVE) sctl[0] = board_aborted_at<BOARD == 2>(ru->abort_word) ? 1 : 0;   // (in the shadow of the head)
         if constexpr (kEarly) {
             const int tid_e = not_hoisted(tid);
             // (only a wave that will take lean columns needs the value: the group's record is a launch invariant, and a
@@ -2117,25 +2156,31 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             if ((tid & 63) == 0) red[tid >> 6] = ws;
         }
     }
-    // (LCF_EARLY_POST, measurement only: wave 0 multiplies the row's address out in front of barrier 2, in the shadow of the
+    // (LCF_EARLY_POST, measurement only: the committing wave multiplies the row's address out in front of barrier 2, in the shadow of the
     // columns, and carries it across -- two more vector registers there; DESIGN section 5 has the A/B)
     size_t entry_early = 0;
     if constexpr (RES && LCF_EARLY_POST != 0)
-        if (tid < 64) entry_early = board_entry_bytes(*ru, (unsigned int)(G + 1), dr.wid, not_hoisted(tid));
+        if (tid >= 64 * LCF_COMMIT_WAVE && tid < 64 * LCF_COMMIT_WAVE + 64)   // (the committing wave)
+            entry_early = board_entry_bytes(*ru, (unsigned int)(G + 1), dr.wid, not_hoisted(tid - 64 * LCF_COMMIT_WAVE));
     __syncthreads();
     LCF_STAMP(0, 9);
     if (BOARD) {
-        // ---- accept / reject by wave 0; lanes 0 .. nd+1 post the row (position, log-posterior, acceptance count) on every
-        // rank's board; this rank's X / LP / counts follow for its own walkers (the others' come from the board when
-        // the run ends, and the chain is written from the board)
-        if (tid >= 64) return false;
+        // ---- accept / reject by ONE wave (wave 0; the resident kernels: wave 1); lanes 0 .. nd+1 post the row (position,
+        // log-posterior, acceptance count) on every rank's board; this rank's X / LP / counts follow for its own walkers
+        // (the others' come from the board when the run ends, and the chain is written from the board)
+        // (RES: by the committing wave, wave 1 -- LCF_COMMIT_WAVE.  Wave 0 is the head of the workgroup's next item and
+        // leaves here for its poll: nothing below needs it, every operand is reloaded from LDS and the draw record, and
+        // `lpr` / `excluded` were read behind barrier 1 by every wave.  Every wave still passes the same barriers per item.)
+        constexpr int kCommit0 = RES ? 64 * LCF_COMMIT_WAVE : 0;   // the committing wave's first thread
+        if (tid < kCommit0 || tid >= kCommit0 + 64) return false;
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);   // (the row's readers wait for this)
         if constexpr (RES) {
             // Every LDS read between here and the post -- the wave sums, the walker's log-posterior and count, this lane's
             // number of the proposal and of the position, the block's words for the sum and for the row's address -- and
             // the record's words for the accept test and the post, which nobody has carried across the columns.
             // The sum keeps its order, (w0 + w1) + (w2 + w3) per part, parts in order.
-            const int col = not_hoisted(tid);
+            const int ctid = tid - kCommit0;   // the lane: column of the row
+            const int col = not_hoisted(ctid);
             const int mine = col < nd ? col : 0;
             const unsigned int tag = (unsigned int)(G + 1);
             constexpr bool kRecord = LCF_SCALAR_DRAW != 0;
@@ -2147,7 +2192,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                 // ONE statement requests all of it, the record's words by scalar loads, and waits once (commit_batch)
                 const unsigned int sc_at = lds_offset(sc);
                 CommitOperands c;
-                commit_batch<kRecord>(lds_offset(red), sc_at, sc_at + 8u * (unsigned int)mine, draws + i, c);
+                commit_batch<kRecord>(lds_offset(red), sc_at, sc_at + 8u * (unsigned int)mine, lds_offset(ru), draws + i, c);
                 if constexpr (kRecord) wid = c.wid, zl = f64_of(c.zl_lnu.x, c.zl_lnu.y), lnu = f64_of(c.zl_lnu.z, c.zl_lnu.w);
                 // (board_entry_bytes, from the batch's words)
                 entry = (tag & c.geo.z) * (unsigned long long)__double_as_longlong(c.ver_bytes) +
@@ -2192,8 +2237,8 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             const double nlp = excluded ? -INFINITY : scored;
             const bool ok = (zl + nlp - lp_i) > lnu;
             const double count = count0 + (ok ? 1. : 0.);
-            if (tid <= nd + 1) {
-                const double v = tid < nd ? (ok ? q_mine : x_mine) : tid == nd ? (ok ? nlp : lp_i) : count;
+            if (ctid <= nd + 1) {
+                const double v = ctid < nd ? (ok ? q_mine : x_mine) : ctid == nd ? (ok ? nlp : lp_i) : count;
                 // the row first: its readers wait for it; state, snapshot and chain follow
                 if (BOARD == 2) {
                     board_post_at<true>(reinterpret_cast<unsigned long long*>(own_board + entry), tag, v);
@@ -2205,32 +2250,32 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                                           tag, v);
                 }
                 if (BOARD == 2 && write_state) {   // (the set of state buffers the run did NOT start from: chosen by the fill)
-                    if (tid < nd)
-                        ru->X[(size_t)wid * nd + tid] = v;
-                    else if (tid == nd)
+                    if (ctid < nd)
+                        ru->X[(size_t)wid * nd + ctid] = v;
+                    else if (ctid == nd)
                         ru->LP[wid] = v;
                     else
                         ru->nacc[wid] = (long long)v;
                     unsigned long long* const snap = ru->snap_out;
                     if (snap) {   // ... and the host's copy of it
                         const size_t nw = ru->n_walkers;
-                        if (tid < nd) snap[1 + (size_t)wid * nd + tid] = (unsigned long long)__double_as_longlong(v);
-                        else if (tid == nd) snap[1 + nw * nd + wid] = (unsigned long long)__double_as_longlong(v);
+                        if (ctid < nd) snap[1 + (size_t)wid * nd + ctid] = (unsigned long long)__double_as_longlong(v);
+                        else if (ctid == nd) snap[1 + nw * nd + wid] = (unsigned long long)__double_as_longlong(v);
                         else snap[1 + nw * nd + nw + wid] = (unsigned long long)(long long)v;
                     }
                 }
                 if (BOARD == 2 && (run_flags & kRunStoreChain)) {   // (one GPU: every walker's row is decided here)
                     const size_t at = (size_t)row * ru->n_walkers + wid;
-                    if (tid < nd) ru->chain[at * nd + tid] = v;
-                    else if (tid == nd) ru->chain_lp[at] = v;
+                    if (ctid < nd) ru->chain[at * nd + ctid] = v;
+                    else if (ctid == nd) ru->chain_lp[at] = v;
                 }
             }
-            if (tid == 0 && nlp != nlp) {
+            if (ctid == 0 && nlp != nlp) {
                 atomicOr(sm.err, 1);
                 if (BOARD == 2 && sm.snap_flags) sm.snap_flags[blockIdx.x & (kSnapFlags - 1)] = 1u;
             }
             __builtin_amdgcn_s_setprio(0);
-            LCF_STAMP(0, 10);
+            LCF_STAMP(LCF_COMMIT_WAVE, 10);
             return false;
         }
         double nlp = -INFINITY;
@@ -2431,8 +2476,9 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
     // Filled HERE, not by the launch's first executed half-step (`first` below): that half-step's head reads the block
     // in front of its first barrier like every other one.  So the block does not depend on `first`, nor on whether a
     // workgroup's first slot is an empty one; what `first` still guards is the staging of the tables and the first columns.
+    // (in front of it: the two copies of the half-step's scratch words)
     RunUniforms* const ru = reinterpret_cast<RunUniforms*>(smem + kLdsHead * sizeof(double) + (size_t)pb.stage_d2 * sizeof(double2) +
-                                                           (kSoloScratch + 4) * sizeof(double));
+                                                           2 * (kSoloScratch + 4) * sizeof(double));
     if (threadIdx.x >= 64 && threadIdx.x < 128) fill_run_uniforms(pb, sm, ru, run_flags, RANKS, threadIdx.x - 64);
     if (!RANKS) __syncthreads();   // (RANKS: the barrier below)
     // "this workgroup has started": what a workgroup that waits unusually long for a row looks at (board_take)
@@ -2492,6 +2538,14 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
     // into LDS, or as a scalar load carried in registers across the half-step -- instead of the touch that only brings
     // it into this XCD's L2: 5.80 / 5.94 against 5.51 us per half-step.  The record's two round trips are hidden
     // already; what the extra live registers cost is not.)
+    // Which copy of the scratch words an item uses: the parity of the workgroup's count of executed items (an empty slot
+    // is no item), so that the committing wave reads item n's words while wave 0 writes item n + 1's.  Counted from 0 in
+    // every launch: nothing in LDS outlives one.
+    int copy = 0;
+#ifdef LCF_POLL_LOOKS
+    if (threadIdx.x == 0)   // (wave 0 alone touches the counts)
+        for (int k = 0; k < 4; ++k) atomicExch(&s_poll_looks[k], 0u);
+#endif
 #pragma unroll 1
     for (int h = 0; h < n_hs; ++h) {
         const DrawRec* draws = draws0 + (size_t)h * n_half;
@@ -2507,11 +2561,16 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
             if (solo_half_step<ND, VARIANT, THERM, NPARTS, kBoard, MODEL>(pb, pbp, sm, (rel0 + h) >> 1, draws, hint,
                                                                           g_run0 + rel0 + h, g_run0, i, smem, first_col, first,
                                                                           rel0 + h >= state_from, tid, run_flags, arrive_goal, ru,
-                                                                          LCF_SCALAR_DRAW != 0 ? &rec : nullptr))
+                                                                          LCF_SCALAR_DRAW != 0 ? &rec : nullptr, copy))
                 return;
             first = false;
+            copy ^= 1;
         }
     }
+#ifdef LCF_POLL_LOOKS
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 4; ++k) atomicAdd(&g_poll_looks[k], (unsigned long long)atomicAdd(&s_poll_looks[k], 0u));
+#endif
 }
 
 // The images of DevProblem / DevSampler that kernels read through constant-address-space pointers are WRITTEN BY A
@@ -3775,8 +3834,11 @@ static size_t solo_lds_bytes(const lcf_engine* e) {
            (kSoloScratch + 4) * sizeof(double);
 }
 
-// ... of a resident launch (k_solo_run): the block of launch invariants behind it (RunUniforms)
-static size_t run_lds_bytes(const lcf_engine* e) { return solo_lds_bytes(e) + sizeof(RunUniforms); }
+// ... of a resident launch (k_solo_run): a second copy of the scratch words (the committing wave reads one item's while
+// wave 0 writes the next one's), and the block of launch invariants behind them (RunUniforms)
+static size_t run_lds_bytes(const lcf_engine* e) {
+    return solo_lds_bytes(e) + (kSoloScratch + 4) * sizeof(double) + sizeof(RunUniforms);
+}
 
 bool solo_eligible(const lcf_sampler* s) {
     // (LCF_NO_FUSED=1 asks for the separate launches: neither one-launch form then, as set_half_step_kernel('phases'))
@@ -4849,6 +4911,17 @@ lcf_status lcf_population_run(lcf_sampler** ss, int32_t n, int64_t first_step, i
 #ifdef LCF_PROGRESS
 extern "C" int lcf_debug_read_progress(unsigned int* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_progress), sizeof(unsigned int) * 64 * 16);
+}
+#endif
+#ifdef LCF_POLL_LOOKS
+// (polls of 1, 2, 3 and more looks, looks in total; `reset` != 0: cleared afterwards)
+extern "C" int lcf_debug_read_poll_looks(unsigned long long* out, int reset) {
+    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_poll_looks), sizeof(unsigned long long) * 4);
+    if (reset) {
+        static unsigned long long zeros[4];
+        rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_poll_looks), zeros, sizeof zeros);
+    }
+    return rc;
 }
 #endif
 #ifdef LCF_STAMPS
