@@ -46,9 +46,6 @@
 #ifndef LCF_KPRE_SOLO
 #define LCF_KPRE_SOLO 2  // the same in the one-workgroup-per-proposal kernel (4: 3.73e7 walker-steps/s, 3: 3.74e7, 2: 3.78e7)
 #endif
-#ifndef LCF_HEAD_START
-#define LCF_HEAD_START 0  // k_solo: the waves beside the serial head wait 64 x this many cycles before their first loads
-#endif
 #ifndef LCF_WAVES
 #define LCF_WAVES 4  // occupancy the register allocator is asked to keep (waves per SIMD)
 #endif
@@ -1239,76 +1236,51 @@ __device__ inline unsigned long long* board_entry(unsigned long long* board, con
                                                   int col) {
     return board + 2 * ((((size_t)(tag & (unsigned int)(sm.ring - 1)) * sm.n_walkers) + wid) * board_row_entries(sm.n_dim) + col);
 }
-#ifndef LCF_EARLY_POST
-#define LCF_EARLY_POST 0
-#endif
-// The resident half-step's early phase logarithm (solo_half_step, kEarly): 0 = the columns take it behind barrier 1 (A/B).
-#ifndef LCF_EARLY_LOG
-#define LCF_EARLY_LOG 1
-#endif
 // A value the loop optimiser must not compute ahead of the loop over the half-steps: what it hoists there lives across
 // the whole launch and comes back from scratch memory on the path every other workgroup waits for.
 __device__ __forceinline__ int not_hoisted(int v) {
     asm volatile("" : "+v"(v));
     return v;
 }
-// ---- the resident half-step's record and LDS batches (k_solo_run; each switch: 0 = the form before it, for the A/B) ------
-// LCF_SCALAR_DRAW: the draw records are read through a constant-address-space pointer -- scalar loads, served from the
-// scalar cache that the hint of the previous half-step has filled -- and the accept test reloads what it needs of the
-// record behind barrier 2 instead of carrying it across the columns.
-// LCF_BATCH_HEAD / _COMMIT: the LDS operands of a phase are requested by ONE statement and waited for once.
+// ---- the resident half-step's record and LDS batches (k_solo_run) -----------------------------------------------------
+// The draw records are read through a constant-address-space pointer -- scalar loads, served from the scalar cache that
+// the hint of the previous half-step has filled -- and the accept test reloads what it needs of the record behind
+// barrier 2 instead of carrying it across the columns.
+// The LDS operands of the head and of the commit are requested by ONE statement per phase and waited for once.
 // Written as instructions because the compiler orders plain LDS reads by their first use and sinks them below
 // branches: the source's "one batch" became two to four dependent round trips on the wave everybody waits for.
 // (Measured and dropped: the same for the column entry behind barrier 1 -- nine reads, one wait, then the branch on the
 // abort word: 0.01 us per half-step SLOWER in every alternation, DESIGN section 5.  All eight waves pass there at once,
 // and each then waits for operands it would otherwise have had in its own time.)
-#ifndef LCF_SCALAR_DRAW
-#define LCF_SCALAR_DRAW 1
-#endif
-#ifndef LCF_BATCH_HEAD
-#define LCF_BATCH_HEAD 1
-#endif
-#ifndef LCF_BATCH_COMMIT
-#define LCF_BATCH_COMMIT 1
-#endif
-// LCF_COMMIT_WAVE: the wave that runs what stands behind barrier 2 -- accept test, post, state, snapshot, chain.  1: wave 0
+// kCommitWave: the wave that runs what stands behind barrier 2 -- accept test, post, state, snapshot, chain.  Wave 0
 // leaves at barrier 2 for the loop top and the poll of the workgroup's next item, whose rows come from the board and
-// never from this workgroup's registers or LDS; the commit reloads every operand anyway.  0 = wave 0 commits, then polls.
-// LCF_SHADOW_WAVE: the wave that loads the abort word and hints the next draw record in the head's shadow (1 = the form
-// before: the committing wave would then reach barrier 0 a round trip behind its commit).
-#ifndef LCF_COMMIT_WAVE
-#define LCF_COMMIT_WAVE 1
-#endif
-#ifndef LCF_SHADOW_WAVE
-#define LCF_SHADOW_WAVE 2
-#endif
+// never from this workgroup's registers or LDS; the commit reloads every operand anyway.
+// kShadowWave: the wave that loads the abort word and hints the next draw record in the head's shadow (not the
+// committing wave: it would then reach barrier 0 a round trip behind its commit).
+constexpr int kCommitWave = 1;
+constexpr int kShadowWave = 2;
 typedef unsigned int lcf_u32x4 __attribute__((ext_vector_type(4)));
 typedef int lcf_i32x4 __attribute__((ext_vector_type(4)));
-// A draw record.  SCALAR (the resident kernels): every field through a constant-address-space pointer -- scalar loads of
+// A draw record of the resident kernels: every field through a constant-address-space pointer -- scalar loads of
 // the 48 bytes, out of the scalar cache where the hint of the previous half-step has put them -- because through the
 // ordinary pointer the compiler must assume that the half-step's own stores and statements change the record, and reads
 // it with vector loads, field by field where it is used.  What makes the constant view sound: the records of a launch are
 // written by k_draws in EARLIER kernels of the same stream and by nothing while the launch runs (the generation of the
 // next block goes behind the launch in the stream), and a kernel starts with the scalar cache invalidated.
-template <bool SCALAR>
 __device__ __forceinline__ DrawRec draw_record(const DrawRec* p) {
-    if constexpr (SCALAR) {
-        typedef const DrawRec __attribute__((address_space(4)))* DrawPtr;
-        const DrawPtr c = (DrawPtr)p;
-        DrawRec r;
-        r.wid = c->wid, r.pid = c->pid, r.wprev = c->wprev, r.pprev = c->pprev;
-        r.z = c->z, r.zl = c->zl, r.lnu = c->lnu;
-        r.wage = c->wage, r.page = c->page;
-        // What the head reads is requested HERE, together, and held in scalar registers: left to itself the compiler sinks
-        // every one of these loads to its use -- the partner's age into the head, z behind the poll, each a round trip
-        // of its own on the path everybody waits for.  ((n_dim - 1) ln z and ln u are not held: the commit reloads them.)
-        int z_lo = __double2loint(r.z), z_hi = __double2hiint(r.z);
-        asm volatile("" : "+s"(r.wid), "+s"(r.pid), "+s"(z_lo), "+s"(z_hi), "+s"(r.wage), "+s"(r.page));
-        r.z = __hiloint2double(z_hi, z_lo);
-        return r;
-    } else {
-        return *p;
-    }
+    typedef const DrawRec __attribute__((address_space(4)))* DrawPtr;
+    const DrawPtr c = (DrawPtr)p;
+    DrawRec r;
+    r.wid = c->wid, r.pid = c->pid, r.wprev = c->wprev, r.pprev = c->pprev;
+    r.z = c->z, r.zl = c->zl, r.lnu = c->lnu;
+    r.wage = c->wage, r.page = c->page;
+    // What the head reads is requested HERE, together, and held in scalar registers: left to itself the compiler sinks
+    // every one of these loads to its use -- the partner's age into the head, z behind the poll, each a round trip
+    // of its own on the path everybody waits for.  ((n_dim - 1) ln z and ln u are not held: the commit reloads them.)
+    int z_lo = __double2loint(r.z), z_hi = __double2hiint(r.z);
+    asm volatile("" : "+s"(r.wid), "+s"(r.pid), "+s"(z_lo), "+s"(z_hi), "+s"(r.wage), "+s"(r.page));
+    r.z = __hiloint2double(z_hi, z_lo);
+    return r;
 }
 // Byte offset of an object of the workgroup's LDS, as the address operand of an LDS instruction.
 __device__ __forceinline__ unsigned int lds_offset(const void* p) {
@@ -1329,7 +1301,7 @@ static_assert(offsetof(RunUniforms, ring_mask) == 8 && offsetof(RunUniforms, row
               "the groups the batch below reads with one instruction each");
 // The commit, behind barrier 2: the eight wave sums (`red_at`), log-posterior | count, this lane's number of the proposal
 // and of the position (`mine_at`: sc + 8 mine), the launch block's words (`ru_at`) for the sum and for the row's address --
-// and, in the same wait, (n_dim - 1) ln z | ln u and the walker of the draw record `rec`, by scalar loads (LCF_SCALAR_DRAW; they stand
+// and, in the same wait, (n_dim - 1) ln z | ln u and the walker of the draw record `rec`, by scalar loads (they stand
 // behind the LDS reads: the record's address may be fresh from a vector instruction).
 struct CommitOperands {
     lcf_u32x4 a0, a1, b0, b1, lc, sums, geo;   // sums: sum0 | n_parts, n_walkers; geo: board | ring_mask, row_bytes
@@ -1337,45 +1309,27 @@ struct CommitOperands {
     lcf_u32x4 zl_lnu;
     int wid;
 };
-template <bool RECORD>
 __device__ __forceinline__ void commit_batch(unsigned int red_at, unsigned int sc_at, unsigned int mine_at, unsigned int ru_at,
                                              const void* rec, CommitOperands& c) {
-    if constexpr (RECORD)
-        asm volatile("ds_read_b128 %0, %12\n\t"
-                     "ds_read_b128 %1, %12 offset:16\n\t"
-                     "ds_read_b128 %2, %12 offset:32\n\t"
-                     "ds_read_b128 %3, %12 offset:48\n\t"
-                     "ds_read_b128 %4, %13 offset:%17\n\t"
-                     "ds_read_b128 %5, %15 offset:32\n\t"
-                     "ds_read_b128 %6, %15\n\t"
-                     "ds_read_b64 %7, %15 offset:16\n\t"
-                     "ds_read_b64 %8, %14 offset:%18\n\t"
-                     "ds_read_b64 %9, %14 offset:%19\n\t"
-                     "s_load_dwordx4 %10, %16, 0x18\n\t"
-                     "s_load_dword %11, %16, 0x0\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
-                       "=&v"(c.q_mine), "=&v"(c.x_mine), "=&s"(c.zl_lnu), "=&s"(c.wid)
-                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "v"(ru_at), "s"(rec), "n"(kScLogPost), "n"(kScProposal), "n"(kScPosition)
-                     : "memory");
-    else
-        asm volatile("ds_read_b128 %0, %10\n\t"
-                     "ds_read_b128 %1, %10 offset:16\n\t"
-                     "ds_read_b128 %2, %10 offset:32\n\t"
-                     "ds_read_b128 %3, %10 offset:48\n\t"
-                     "ds_read_b128 %4, %11 offset:%14\n\t"
-                     "ds_read_b128 %5, %13 offset:32\n\t"
-                     "ds_read_b128 %6, %13\n\t"
-                     "ds_read_b64 %7, %13 offset:16\n\t"
-                     "ds_read_b64 %8, %12 offset:%15\n\t"
-                     "ds_read_b64 %9, %12 offset:%16\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
-                       "=&v"(c.q_mine), "=&v"(c.x_mine)
-                     : "v"(red_at), "v"(sc_at), "v"(mine_at), "v"(ru_at), "n"(kScLogPost), "n"(kScProposal), "n"(kScPosition)
-                     : "memory");
+    asm volatile("ds_read_b128 %0, %12\n\t"
+                 "ds_read_b128 %1, %12 offset:16\n\t"
+                 "ds_read_b128 %2, %12 offset:32\n\t"
+                 "ds_read_b128 %3, %12 offset:48\n\t"
+                 "ds_read_b128 %4, %13 offset:%17\n\t"
+                 "ds_read_b128 %5, %15 offset:32\n\t"
+                 "ds_read_b128 %6, %15\n\t"
+                 "ds_read_b64 %7, %15 offset:16\n\t"
+                 "ds_read_b64 %8, %14 offset:%18\n\t"
+                 "ds_read_b64 %9, %14 offset:%19\n\t"
+                 "s_load_dwordx4 %10, %16, 0x18\n\t"
+                 "s_load_dword %11, %16, 0x0\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(c.a0), "=&v"(c.a1), "=&v"(c.b0), "=&v"(c.b1), "=&v"(c.lc), "=&v"(c.sums), "=&v"(c.geo), "=&v"(c.ver_bytes),
+                   "=&v"(c.q_mine), "=&v"(c.x_mine), "=&s"(c.zl_lnu), "=&s"(c.wid)
+                 : "v"(red_at), "v"(sc_at), "v"(mine_at), "v"(ru_at), "s"(rec), "n"(kScLogPost), "n"(kScProposal), "n"(kScPosition)
+                 : "memory");
 }
-// (n_dim - 1) ln z | ln u and the walker of the record alone (LCF_SCALAR_DRAW without the commit's batch)
+// (n_dim - 1) ln z | ln u and the walker of the record alone (the four-group kernels' commit, which has no batch)
 __device__ __forceinline__ void record_reload(const void* rec, lcf_u32x4& zl_lnu, int& wid) {
     asm volatile("s_nop 4\n\ts_load_dwordx4 %0, %2, 0x18\n\ts_load_dword %1, %2, 0x0\n\ts_waitcnt lgkmcnt(0)"
                  : "=&s"(zl_lnu), "=&s"(wid) : "s"(rec) : "memory");
@@ -1735,7 +1689,7 @@ __device__ __forceinline__ void proposal_head(const DevProblem& pb, const DevSam
 struct LaneRows {
     double cj, x;     // lane d < nd: coordinate d of the partner, of the walker; lanes nd, nd + 1: x = log-posterior, count
     PriorDev prior;   // lane d: the prior of parameter d
-    int n_par, n_dim, has_priors;   // the block's words for lane_head, requested in front of the poll (LCF_BATCH_HEAD)
+    int n_par, n_dim, has_priors;   // the block's words for lane_head, requested in front of the poll
 };
 
 template <int ND, int BOARD>
@@ -1746,16 +1700,13 @@ __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const Draw
     h.cj = h.x = 0.;
     // (lane_head's share of the block goes out with the board's geometry, in front of the poll: the poll's statements
     // order memory, so behind them the read would be a round trip of its own in front of the store of the proposal)
-    h.n_par = h.n_dim = h.has_priors = 0;
     unsigned char* board = reinterpret_cast<unsigned char*>(ru->board);
     unsigned int ring_mask = ru->ring_mask, row_bytes = ru->row_bytes;
     unsigned long long ver_bytes = ru->ver_bytes;
-    if constexpr (LCF_BATCH_HEAD != 0) {
-        h.n_par = ru->n_par, h.n_dim = ru->n_dim, h.has_priors = ru->has_priors;
-        // ONE wait for the board's geometry and lane_head's words, here, on every lane: a value that is still on its
-        // way at the poll is waited for behind it, with everything requested since
-        asm volatile("" : "+v"(board), "+v"(ring_mask), "+v"(row_bytes), "+v"(ver_bytes), "+v"(h.n_par), "+v"(h.n_dim), "+v"(h.has_priors));
-    }
+    h.n_par = ru->n_par, h.n_dim = ru->n_dim, h.has_priors = ru->has_priors;
+    // ONE wait for the board's geometry and lane_head's words, here, on every lane: a value that is still on its
+    // way at the poll is waited for behind it, with everything requested since
+    asm volatile("" : "+v"(board), "+v"(ring_mask), "+v"(row_bytes), "+v"(ver_bytes), "+v"(h.n_par), "+v"(h.n_dim), "+v"(h.has_priors));
 #ifdef LCF_POLL_LOOKS
     if (lane == 0) atomicExch(&s_poll_now, 0u);
 #endif
@@ -1816,8 +1767,8 @@ __device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& d
     const int lane = not_hoisted(lane_in);
     // (the head's share of the block, requested together -- by lane_head_fetch, in front of the poll; has_priors as a
     // scalar, for the branch)
-    const int n_par = LCF_BATCH_HEAD != 0 ? h.n_par : ru->n_par, n_dim = LCF_BATCH_HEAD != 0 ? h.n_dim : ru->n_dim;
-    const int has_priors = __builtin_amdgcn_readfirstlane(LCF_BATCH_HEAD != 0 ? h.has_priors : ru->has_priors);
+    const int n_par = h.n_par, n_dim = h.n_dim;
+    const int has_priors = __builtin_amdgcn_readfirstlane(h.has_priors);
     const double cj = h.cj, x = h.x;
     const double q = lane < nd ? cj - (cj - x) * dr.z : 0.;   // emcee: c_j - (c_j - x_i) z
 #ifdef LCF_STAMPS
@@ -1887,6 +1838,43 @@ __device__ __forceinline__ void lane_head(const DevProblem& pb, const DrawRec& d
 constexpr int kSoloScratch = kNCoef + 2 + 2 * (kMaxDim + (kMaxDim & 1));  // doubles: coefficients, log-prior, q, x
 static_assert(kScBlock == (kSoloScratch + 4) * (int)sizeof(double), "one copy of the scratch words");
 
+// The commit of a plain launch (k_solo without BOARD), by thread 0: accept / reject and commit (models.py:121-135 ->
+// fitting.py:121-128 -> emcee's stretch move).  `red`: the wave sums, 4 per part; `sq` / `sx`: the proposal and the
+// walker's position, log-posterior behind it; `lpr`: the proposal's log-prior (`excluded`: it is -inf, no likelihood).
+template <int ND>
+__device__ __forceinline__ void plain_commit(const DevProblem& pb, const DevSampler& sm, const DrawRec& dr, long long row,
+                                             long long G, const double* red, const double* sq, const double* sx, double lpr,
+                                             bool excluded, const int nd) {
+    constexpr int kD = ND > 0 ? ND : kMaxDim;
+    double nlp = -INFINITY;
+    if (!excluded) {
+        double sum = pb.use_sigma ? 0. : pb.log_norm_const;   // fixed order: parts, each (w0 + w1) + (w2 + w3)
+        for (int k = 0; k < pb.n_parts; ++k) sum += (red[4 * k] + red[4 * k + 1]) + (red[4 * k + 2] + red[4 * k + 3]);
+        nlp = lpr - 0.5 * sum;
+    }
+    const double lp_i = sx[kMaxDim];
+    const bool ok = (dr.zl + nlp - lp_i) > dr.lnu;   // emcee: (ndim - 1) ln z + lp_new - lp_old > ln u
+    if (nlp != nlp) atomicOr(sm.err, 1);
+    if (ok) {
+#pragma unroll
+        for (int d = 0; d < kD; ++d)
+            if (d < nd) sm.X[(size_t)dr.wid * nd + d] = sq[d];
+        sm.LP[dr.wid] = nlp;
+        atomicAdd(reinterpret_cast<unsigned long long*>(&sm.nacc[dr.wid]), 1ull);  // (no return value: nothing waits)
+    }
+    if (sm.store_chain) {
+        double* crow = sm.chain + ((size_t)row * sm.n_walkers + dr.wid) * nd;
+#pragma unroll
+        for (int d = 0; d < kD; ++d)
+            if (d < nd) crow[d] = ok ? sq[d] : sx[d];
+        sm.chain_lp[(size_t)row * sm.n_walkers + dr.wid] = ok ? nlp : lp_i;
+    }
+    LCF_STAMP(0, 10);
+#ifdef LCF_STAMPS
+    if (blockIdx.x < 1024) g_wall[((G & 1) * 1024 + blockIdx.x) * 2 + 1] = wall_clock64();
+#endif
+}
+
 // BOARD (multi-GPU, lcf_sampler_run_rows): the launch covers this rank's slots [slot_lo, slot_lo + gridDim.x) of
 // half-step G; rows come from this rank's row board and the commit posts the walker's new row on EVERY rank's board.
 // No rank computes anything about another rank's proposals, and nothing but these rows travels.
@@ -1935,7 +1923,6 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
     int* sctl = reinterpret_cast<int*>(sc + (RES ? kNCoef + 1 : kSoloScratch + 2));
     constexpr int kGroups = NPARTS == 8 ? 4 : 2;     // groups of 256 threads, each walks one part at a time
     constexpr int kThreads = kBlock * kGroups;
-    constexpr int kD = ND > 0 ? ND : kMaxDim;
     const int nd = ND > 0 ? ND : RES ? __builtin_amdgcn_readfirstlane(ru->nd) : sm.n_dim;
     const bool reddened = !MODEL && (RES ? __builtin_amdgcn_readfirstlane(ru->model) : pb.model) == kShockCooling3;
     LCF_STAMP(0, 0);
@@ -1963,7 +1950,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
     // of wave 0's own logarithm, coefficients and priors; behind barrier 1 lean_column starts from it.  Every wave
     // passes barrier 0 on every path that passes barrier 1; an excluded proposal, a shape that is not lean and an
     // aborted launch drop the value.  t_0 is coordinate kT0 of the proposal: c[0] of walker_coefficients, per model.
-    constexpr bool kEarly = RES && MODEL != 0 && NPARTS <= 2 && LCF_EARLY_LOG != 0;
+    constexpr bool kEarly = RES && MODEL != 0 && NPARTS <= 2;
     constexpr int kT0 = MODEL == kShockCooling ? 4 : MODEL == kShockCooling2 ? 3 : -1;
     static_assert(!kEarly || kT0 >= 0, "a model-specialised resident kernel names the coordinate that is t_0");
     // (Wave 0 is the head and takes the logarithm of its own columns behind barrier 1.  Measured and dropped: a wave of
@@ -1988,7 +1975,6 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         }
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(0);
     } else {
-        if (LCF_HEAD_START > 0) __builtin_amdgcn_s_sleep(LCF_HEAD_START);
         if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
         // Touch the draw record this block index needs in the NEXT launch: block -> XCD placement repeats from launch
         // to launch, so the record is then in this XCD's L2 instead of HBM when the next serial head starts with it
@@ -2003,7 +1989,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             // half-step against the vector touch below, which only brings the record into the XCD's L2).
             // (Wave 2's duty, as the abort word below: wave 1 comes here from the commit of the previous item, and a
             // round trip of its own in front of barrier 0 would make wave 0 wait for it.)
-            if (tid >= 64 * LCF_SHADOW_WAVE && tid < 64 * LCF_SHADOW_WAVE + 64 && draws_next != nullptr) {
+            if (tid >= 64 * kShadowWave && tid < 64 * kShadowWave + 64 && draws_next != nullptr) {
                 const int* nxt = reinterpret_cast<const int*>(draws_next + i);
                 int a_, b_;
                 asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %2, 0x2c\n\ts_waitcnt lgkmcnt(0)"
@@ -2017,7 +2003,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         // (the abort word: requested while wave 0 still polls, in front of barrier 0 -- these waves reach this place while
         // wave 0 is still in its poll, so the round trip is over before wave 0 arrives; into THIS item's copy of the words)
         if constexpr (RES)
-            if (tid == 64 * LCF_SHADOW_WAVE) sctl[0] = board_aborted_at<BOARD == 2>(ru->abort_word) ? 1 : 0;   // (in the shadow of the head)
+            if (tid == 64 * kShadowWave) sctl[0] = board_aborted_at<BOARD == 2>(ru->abort_word) ? 1 : 0;   // (in the shadow of the head)
         if constexpr (kEarly) {
             const int tid_e = not_hoisted(tid);
             // (only a wave that will take lean columns needs the value: the group's record is a launch invariant, and a
@@ -2156,22 +2142,16 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             if ((tid & 63) == 0) red[tid >> 6] = ws;
         }
     }
-    // (LCF_EARLY_POST, measurement only: the committing wave multiplies the row's address out in front of barrier 2, in the shadow of the
-    // columns, and carries it across -- two more vector registers there; DESIGN section 5 has the A/B)
-    size_t entry_early = 0;
-    if constexpr (RES && LCF_EARLY_POST != 0)
-        if (tid >= 64 * LCF_COMMIT_WAVE && tid < 64 * LCF_COMMIT_WAVE + 64)   // (the committing wave)
-            entry_early = board_entry_bytes(*ru, (unsigned int)(G + 1), dr.wid, not_hoisted(tid - 64 * LCF_COMMIT_WAVE));
     __syncthreads();
     LCF_STAMP(0, 9);
     if (BOARD) {
         // ---- accept / reject by ONE wave (wave 0; the resident kernels: wave 1); lanes 0 .. nd+1 post the row (position,
         // log-posterior, acceptance count) on every rank's board; this rank's X / LP / counts follow for its own walkers
         // (the others' come from the board when the run ends, and the chain is written from the board)
-        // (RES: by the committing wave, wave 1 -- LCF_COMMIT_WAVE.  Wave 0 is the head of the workgroup's next item and
+        // (RES: by the committing wave, wave 1 -- kCommitWave.  Wave 0 is the head of the workgroup's next item and
         // leaves here for its poll: nothing below needs it, every operand is reloaded from LDS and the draw record, and
         // `lpr` / `excluded` were read behind barrier 1 by every wave.  Every wave still passes the same barriers per item.)
-        constexpr int kCommit0 = RES ? 64 * LCF_COMMIT_WAVE : 0;   // the committing wave's first thread
+        constexpr int kCommit0 = RES ? 64 * kCommitWave : 0;   // the committing wave's first thread
         if (tid < kCommit0 || tid >= kCommit0 + 64) return false;
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);   // (the row's readers wait for this)
         if constexpr (RES) {
@@ -2183,17 +2163,16 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             const int col = not_hoisted(ctid);
             const int mine = col < nd ? col : 0;
             const unsigned int tag = (unsigned int)(G + 1);
-            constexpr bool kRecord = LCF_SCALAR_DRAW != 0;
             int wid = dr.wid;
             double zl = dr.zl, lnu = dr.lnu, sum, lp_i, count0, q_mine, x_mine;
             size_t entry;   // (the same on every rank's board)
             unsigned char* own_board;
-            if constexpr (NPARTS <= 2 && LCF_BATCH_COMMIT != 0) {
+            if constexpr (NPARTS <= 2) {
                 // ONE statement requests all of it, the record's words by scalar loads, and waits once (commit_batch)
                 const unsigned int sc_at = lds_offset(sc);
                 CommitOperands c;
-                commit_batch<kRecord>(lds_offset(red), sc_at, sc_at + 8u * (unsigned int)mine, lds_offset(ru), draws + i, c);
-                if constexpr (kRecord) wid = c.wid, zl = f64_of(c.zl_lnu.x, c.zl_lnu.y), lnu = f64_of(c.zl_lnu.z, c.zl_lnu.w);
+                commit_batch(lds_offset(red), sc_at, sc_at + 8u * (unsigned int)mine, lds_offset(ru), draws + i, c);
+                wid = c.wid, zl = f64_of(c.zl_lnu.x, c.zl_lnu.y), lnu = f64_of(c.zl_lnu.z, c.zl_lnu.w);
                 // (board_entry_bytes, from the batch's words)
                 entry = (tag & c.geo.z) * (unsigned long long)__double_as_longlong(c.ver_bytes) +
                         ((size_t)(unsigned int)wid * c.geo.w + 16u * (unsigned int)col);
@@ -2207,30 +2186,18 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                 lp_i = f64_of(c.lc.x, c.lc.y), count0 = f64_of(c.lc.z, c.lc.w);
                 q_mine = c.q_mine, x_mine = c.x_mine;
             } else {
-                // Plain LDS reads (the four-group kernels; LCF_BATCH_COMMIT = 0: the compiler requests them in two
-                // batches around the accept arithmetic)
-                if constexpr (kRecord) {
-                    lcf_u32x4 r;
-                    record_reload(draws + i, r, wid);
-                    zl = f64_of(r.x, r.y), lnu = f64_of(r.z, r.w);
-                }
+                // Plain LDS reads (the four-group kernels)
+                lcf_u32x4 r;
+                record_reload(draws + i, r, wid);
+                zl = f64_of(r.x, r.y), lnu = f64_of(r.z, r.w);
                 const double2* red2 = reinterpret_cast<const double2*>(red);
                 const double2 lc = *reinterpret_cast<const double2*>(sx + kMaxDim);   // log-posterior | acceptance count
                 q_mine = sq[mine], x_mine = sx[mine];
-                entry = LCF_EARLY_POST != 0 ? entry_early : board_entry_bytes(*ru, tag, wid, col);
+                entry = board_entry_bytes(*ru, tag, wid, col);
                 own_board = reinterpret_cast<unsigned char*>(ru->board);
                 sum = ru->sum0;
-                if (NPARTS <= 2) {
-                    const int n_parts = ru->n_parts;
-                    const double2 a0 = red2[0], a1 = red2[1], b0 = red2[2], b1 = red2[3];
-                    const double s1 = sum + ((a0.x + a0.y) + (a1.x + a1.y));
-                    sum = n_parts > 0 ? s1 : sum;
-                    const double s2 = sum + ((b0.x + b0.y) + (b1.x + b1.y));
-                    sum = n_parts > 1 ? s2 : sum;
-                } else {
-                    const int n_parts = __builtin_amdgcn_readfirstlane(ru->n_parts);
-                    for (int k = 0; k < n_parts; ++k) sum += (red2[2 * k].x + red2[2 * k].y) + (red2[2 * k + 1].x + red2[2 * k + 1].y);
-                }
+                const int n_parts = __builtin_amdgcn_readfirstlane(ru->n_parts);
+                for (int k = 0; k < n_parts; ++k) sum += (red2[2 * k].x + red2[2 * k].y) + (red2[2 * k + 1].x + red2[2 * k + 1].y);
                 lp_i = lc.x, count0 = lc.y;
             }
             const double scored = lpr - 0.5 * sum;
@@ -2249,6 +2216,8 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                             board_post_at(reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(sm.peer_board[r]) + entry),
                                           tag, v);
                 }
+                // (a one-launch run writes the state in its last step only: every walker moves exactly once there, while two
+                // moves of a walker in one launch come from different workgroups, and whose store reaches memory last is open)
                 if (BOARD == 2 && write_state) {   // (the set of state buffers the run did NOT start from: chosen by the fill)
                     if (ctid < nd)
                         ru->X[(size_t)wid * nd + ctid] = v;
@@ -2275,9 +2244,10 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                 if (BOARD == 2 && sm.snap_flags) sm.snap_flags[blockIdx.x & (kSnapFlags - 1)] = 1u;
             }
             __builtin_amdgcn_s_setprio(0);
-            LCF_STAMP(LCF_COMMIT_WAVE, 10);
+            LCF_STAMP(kCommitWave, 10);
             return false;
         }
+        // (from here on BOARD = 1 alone: the resident forms have returned)
         double nlp = -INFINITY;
         if (!excluded) {
             double sum = pb.use_sigma ? 0. : pb.log_norm_const;
@@ -2289,76 +2259,27 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         const double count = sx[kMaxDim + 1] + (ok ? 1. : 0.);
         if (tid <= nd + 1) {
             const double v = tid < nd ? (ok ? sq[tid] : sx[tid]) : tid == nd ? (ok ? nlp : lp_i) : count;
-            if (BOARD == 2) {
-                board_post<true>(sm.board, sm, (unsigned int)(G + 1), dr.wid, tid, v);
-            } else {
 #pragma unroll
-                for (int r = 0; r < kMaxPeers; ++r)
-                    if (r < sm.n_board_ranks) board_post(sm.peer_board[r], sm, (unsigned int)(G + 1), dr.wid, tid, v);
-            }
-            // (a one-launch run writes the state in its last step only: every walker moves exactly once there, while two
-            // moves of a walker in one launch come from different workgroups, and whose store reaches memory last is open)
-            if (BOARD == 1 || (BOARD == 2 && write_state)) {
-                // (one-launch runs: into the set of state buffers the run did NOT start from -- kRunFlip says which)
-                const bool to_out = BOARD == 2 && !(run_flags & kRunFlip);
-                double* X = to_out ? sm.X_out : sm.X;
-                double* LP = to_out ? sm.LP_out : sm.LP;
-                long long* nacc = to_out ? sm.nacc_out : sm.nacc;
-                if (tid < nd)
-                    X[(size_t)dr.wid * nd + tid] = v;
-                else if (tid == nd)
-                    LP[dr.wid] = v;
-                else
-                    nacc[dr.wid] = (long long)v;
-                if (BOARD == 2 && sm.snap_out) {   // ... and the host's copy of it
-                    const size_t nw = sm.n_walkers;
-                    if (tid < nd) sm.snap_out[1 + (size_t)dr.wid * nd + tid] = (unsigned long long)__double_as_longlong(v);
-                    else if (tid == nd) sm.snap_out[1 + nw * nd + dr.wid] = (unsigned long long)__double_as_longlong(v);
-                    else sm.snap_out[1 + nw * nd + nw + dr.wid] = (unsigned long long)(long long)v;
-                }
-            }
-            if (BOARD == 2 && (run_flags & kRunStoreChain)) {   // (one GPU: every walker's row is decided here)
-                if (tid < nd) sm.chain[((size_t)row * sm.n_walkers + dr.wid) * nd + tid] = v;
-                else if (tid == nd) sm.chain_lp[(size_t)row * sm.n_walkers + dr.wid] = v;
-            }
+            for (int r = 0; r < kMaxPeers; ++r)
+                if (r < sm.n_board_ranks) board_post(sm.peer_board[r], sm, (unsigned int)(G + 1), dr.wid, tid, v);
+            // (the three pointers are read HERE, in front of the branches, on purpose: read where they are used, the
+            // same instructions come out in another order in all 25 BOARD = 1 kernels -- tools/isa_diff.py)
+            double* X = sm.X;
+            double* LP = sm.LP;
+            long long* nacc = sm.nacc;
+            if (tid < nd)
+                X[(size_t)dr.wid * nd + tid] = v;
+            else if (tid == nd)
+                LP[dr.wid] = v;
+            else
+                nacc[dr.wid] = (long long)v;
         }
-        if (tid == 0 && nlp != nlp) {
-            atomicOr(sm.err, 1);
-            if (BOARD == 2 && sm.snap_flags) sm.snap_flags[blockIdx.x & (kSnapFlags - 1)] = 1u;
-        }
-        if (BOARD >= 2) __builtin_amdgcn_s_setprio(0);
+        if (tid == 0 && nlp != nlp) atomicOr(sm.err, 1);
         LCF_STAMP(0, 10);
         return false;
     }
     if (tid != 0) return false;
-    // ---- accept / reject and commit (models.py:121-135 -> fitting.py:121-128 -> emcee's stretch move)
-    double nlp = -INFINITY;
-    if (!excluded) {
-        double sum = pb.use_sigma ? 0. : pb.log_norm_const;   // fixed order: parts, each (w0 + w1) + (w2 + w3)
-        for (int k = 0; k < pb.n_parts; ++k) sum += (red[4 * k] + red[4 * k + 1]) + (red[4 * k + 2] + red[4 * k + 3]);
-        nlp = lpr - 0.5 * sum;
-    }
-    const double lp_i = sx[kMaxDim];
-    const bool ok = (dr.zl + nlp - lp_i) > dr.lnu;   // emcee: (ndim - 1) ln z + lp_new - lp_old > ln u
-    if (nlp != nlp) atomicOr(sm.err, 1);
-    if (ok) {
-#pragma unroll
-        for (int d = 0; d < kD; ++d)
-            if (d < nd) sm.X[(size_t)dr.wid * nd + d] = sq[d];
-        sm.LP[dr.wid] = nlp;
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sm.nacc[dr.wid]), 1ull);  // (no return value: nothing waits)
-    }
-    if (sm.store_chain) {
-        double* crow = sm.chain + ((size_t)row * sm.n_walkers + dr.wid) * nd;
-#pragma unroll
-        for (int d = 0; d < kD; ++d)
-            if (d < nd) crow[d] = ok ? sq[d] : sx[d];
-        sm.chain_lp[(size_t)row * sm.n_walkers + dr.wid] = ok ? nlp : lp_i;
-    }
-    LCF_STAMP(0, 10);
-#ifdef LCF_STAMPS
-    if (blockIdx.x < 1024) g_wall[((G & 1) * 1024 + blockIdx.x) * 2 + 1] = wall_clock64();
-#endif
+    plain_commit<ND>(pb, sm, dr, row, G, red, sq, sx, lpr, excluded, nd);
     return false;
 }
 
@@ -2551,8 +2472,8 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
         const DrawRec* draws = draws0 + (size_t)h * n_half;
 #pragma unroll 1
         for (int i = slot_lo + blockIdx.x; i < slot_end; i += n_wg) {
-            // the record, once for this test and for the half-step (LCF_SCALAR_DRAW = 0: the half-step reads it itself)
-            const DrawRec rec = draw_record<LCF_SCALAR_DRAW != 0>(draws + i);
+            // the record, once for this test and for the half-step
+            const DrawRec rec = draw_record(draws + i);
             if (rec.wid < 0) continue;   // (uniform) an odd ensemble's smaller colour leaves its last slot empty
             // the record this workgroup needs next: its next slot of this half-step, else its first of the next one
             const bool more = i + n_wg < slot_end;
@@ -2561,7 +2482,7 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
             if (solo_half_step<ND, VARIANT, THERM, NPARTS, kBoard, MODEL>(pb, pbp, sm, (rel0 + h) >> 1, draws, hint,
                                                                           g_run0 + rel0 + h, g_run0, i, smem, first_col, first,
                                                                           rel0 + h >= state_from, tid, run_flags, arrive_goal, ru,
-                                                                          LCF_SCALAR_DRAW != 0 ? &rec : nullptr, copy))
+                                                                          &rec, copy))
                 return;
             first = false;
             copy ^= 1;
