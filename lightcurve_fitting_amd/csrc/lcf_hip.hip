@@ -277,9 +277,18 @@ __device__ unsigned int g_progress[64 * 16];
 // A look is one pass of board_take_pair's loop on wave 0 -- one round trip to memory; a poll's number is that of its
 // slowest lane.  Wave 0 counts in LDS (polls of 1, 2, 3 and more looks, and the looks in total) and adds the workgroup's
 // counts to g_poll_looks when it leaves the launch (lcf_debug_read_poll_looks; tools/debug/poll_looks.py).
+// The same four counts are also kept PER WORKGROUP AND LAUNCH, with the place the workgroup ran at: when it leaves, wave 0
+// appends one record of kPollWgWords words to g_poll_wg -- the launch's first half-step (what tells launches apart),
+// blockIdx.x, the hardware-id register of wave 0 as read at kernel entry (compute unit, shader array and shader engine in
+// bits 8 .. 15), the XCC id, and the counts.  Two workgroups of one launch with the same place shared a compute unit for
+// the whole launch (lcf_debug_read_poll_wg; tools/debug/poll_looks_by_cu.py).  Records beyond kPollWgMax are dropped;
+// g_poll_wg_n counts them all.
 #ifdef LCF_POLL_LOOKS
 __device__ unsigned long long g_poll_looks[4];
 __shared__ unsigned int s_poll_looks[4], s_poll_now;   // (s_poll_now: the looks of the poll under way, the maximum over its lanes)
+constexpr int kPollWgWords = 8, kPollWgMax = 16384;
+__device__ unsigned int g_poll_wg[kPollWgMax * kPollWgWords];
+__device__ unsigned int g_poll_wg_n;
 #endif
 
 // ---- epoch-major likelihood: one lane per COLUMN (an observation time and its points, DevProblem::em_*) ----------------
@@ -1492,10 +1501,11 @@ __device__ __attribute__((noinline)) int board_wait_check(const DevSampler* smp,
 // The numbers of the entries `pa` (tag `tag_a`, walker `wid_a`) and `pb_` (`tag_b`, `wid_b`), both column `col`, once BOTH
 // are there: each look requests the two 16-byte entries back to back and waits once, so every entry is still sampled
 // once per look, on the lane that uses it.  (A lane with one entry to wait for passes it twice.)  NaN after an abort.
+// `waited`: this lane needed more than one look (or the launch is aborted).
 template <bool AGENT>
 __device__ __forceinline__ void board_take_pair(const DevSampler& sm, const unsigned long long* pa, const unsigned long long* pb_,
                                                 unsigned int tag_a, unsigned int tag_b, int wid_a, int wid_b, int col,
-                                                unsigned int arrive_goal, double& va, double& vb) {
+                                                unsigned int arrive_goal, double& va, double& vb, bool& waited) {
     const unsigned long long t0 = wall_clock64();
     bool resident = arrive_goal == 0u;
     for (int spin = 0;; ++spin) {
@@ -1506,6 +1516,7 @@ __device__ __forceinline__ void board_take_pair(const DevSampler& sm, const unsi
         if (a_ok && b_ok) {
             va = __hiloint2double((int)a.z, (int)a.x);
             vb = __hiloint2double((int)b.z, (int)b.x);
+            waited = spin != 0;
 #ifdef LCF_POLL_LOOKS
             atomicMax(&s_poll_now, (unsigned int)spin + 1u);
 #endif
@@ -1517,6 +1528,7 @@ __device__ __forceinline__ void board_take_pair(const DevSampler& sm, const unsi
                                                       col, a_ok ? b : a);
             if (state == 1) {
                 va = vb = qnan();
+                waited = true;
                 return;
             }
             resident = resident || state == 2;
@@ -1694,7 +1706,8 @@ struct LaneRows {
 
 template <int ND, int BOARD>
 __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const DrawRec& dr, int lane_in, LaneRows& h, long long G,
-                                                long long g_run0, unsigned int arrive_goal, const RunUniforms* ru) {
+                                                long long g_run0, unsigned int arrive_goal, const RunUniforms* ru,
+                                                int* late_word) {
     const int nd = ND > 0 ? ND : __builtin_amdgcn_readfirstlane(ru->nd);
     const int lane = not_hoisted(lane_in);   // (lane masks and addresses: computed here, not carried across the launch)
     h.cj = h.x = 0.;
@@ -1710,6 +1723,7 @@ __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const Draw
 #ifdef LCF_POLL_LOOKS
     if (lane == 0) atomicExch(&s_poll_now, 0u);
 #endif
+    bool waited = false;   // (lanes that do not poll do not wait)
     if (lane <= nd + 1) {
         const unsigned int wtag = board_tag(G, dr.wage, g_run0), ptag = board_tag(G, dr.page, g_run0);
         // (lanes nd, nd + 1 have no entry of the partner's to wait for: they ask for their own twice)
@@ -1720,7 +1734,16 @@ __device__ __forceinline__ void lane_head_fetch(const DevSampler& sm, const Draw
             reinterpret_cast<const unsigned long long*>(board + board_entry_bytes(ring_mask, ver_bytes, row_bytes, tag_l, wid_l, lane));
         const unsigned long long* const pw =
             reinterpret_cast<const unsigned long long*>(board + board_entry_bytes(ring_mask, ver_bytes, row_bytes, wtag, dr.wid, lane));
-        board_take_pair<BOARD == 2>(sm, pa, pw, tag_l, wtag, wid_l, dr.wid, lane, arrive_goal, h.cj, h.x);
+        board_take_pair<BOARD == 2>(sm, pa, pw, tag_l, wtag, wid_l, dr.wid, lane, arrive_goal, h.cj, h.x, waited);
+    }
+    // Is this item LATE?  Every polling lane found its rows at the first look: the producers were through before this
+    // workgroup asked, so it is behind them -- a workgroup that had to wait is ahead and has slack.  One wave-uniform bit,
+    // stored as the 4-byte word above the abort word (the upper half of the double beside the log-prior, which every
+    // wave reads behind barrier 1 anyway; the lower half is wave 2's), here and not at the head's end: the store is
+    // then long over at barrier 1.
+    {
+        const int late = __ballot(waited) == 0ull ? 1 : 0;
+        if (lane == 0) *late_word = late;
     }
 #ifdef LCF_POLL_LOOKS
     if (lane == 0) {   // (an aborted poll counts nothing)
@@ -1919,7 +1942,8 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
                      : reinterpret_cast<double*>(ltab + pb.stage_d2);  // coefficients, then log-prior
     double* sq = sc + kNCoef + 2;                                           // the proposal
     double* sx = sq + kMaxDim + (kMaxDim & 1);                              // the walker's current position, lp, draw
-    // BOARD: [0] = 1: the launch is aborted (RES: the word beside the log-prior, so that one LDS read brings both)
+    // BOARD: [0] = 1: the launch is aborted (RES: the word beside the log-prior, so that one LDS read brings both);
+    // RES: [1] = 1: the item is late -- its poll found every row at the first look (wave 0's word; lane_head_fetch)
     int* sctl = reinterpret_cast<int*>(sc + (RES ? kNCoef + 1 : kSoloScratch + 2));
     constexpr int kGroups = NPARTS == 8 ? 4 : 2;     // groups of 256 threads, each walks one part at a time
     constexpr int kThreads = kBlock * kGroups;
@@ -1964,7 +1988,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         if (BOARD >= 2) __builtin_amdgcn_s_setprio(3);
         if constexpr (RES) {
             LaneRows rows;
-            lane_head_fetch<ND, BOARD>(sm, dr, tid, rows, G, g_run0, arrive_goal, ru);
+            lane_head_fetch<ND, BOARD>(sm, dr, tid, rows, G, g_run0, arrive_goal, ru, sctl + 1);
             if (kFetch && first) fetch_column<VARIANT, MODEL>(pb, tid / kBlock, tid % kBlock, first_col);
             lane_head<ND, BOARD, MODEL, kEarly>(pb, dr, tid, sc, sq, sx, rows, ru);
         } else {
@@ -2061,6 +2085,10 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
         }
         lpr = la.x;
         if (__builtin_amdgcn_readfirstlane(__double2loint(la.y)) != 0) return true;
+        // The columns of a LATE item go first on their SIMDs: a CU holds two resident workgroups for a whole launch, and
+        // at equal priority the issue slots go to the OLDER wave -- launch-long to the same workgroup, whether it is
+        // behind or ahead.  (A scalar condition: s_setprio ignores EXEC.)  Back to 0 in front of barrier 2, on every path.
+        if (__builtin_amdgcn_readfirstlane(__double2hiint(la.y)) != 0) __builtin_amdgcn_s_setprio(1);
     } else {
         if (BOARD && sctl[0] != 0) return true;   // (uniform: everybody reads the same word)
         lpr = sc[kNCoef];
@@ -2142,6 +2170,7 @@ __device__ __forceinline__ bool solo_half_step(const DevProblem& pb, const DevPr
             if ((tid & 63) == 0) red[tid >> 6] = ws;
         }
     }
+    if constexpr (RES) __builtin_amdgcn_s_setprio(0);   // (a late item's columns ran at priority 1)
     __syncthreads();
     LCF_STAMP(0, 9);
     if (BOARD) {
@@ -2466,6 +2495,8 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
 #ifdef LCF_POLL_LOOKS
     if (threadIdx.x == 0)   // (wave 0 alone touches the counts)
         for (int k = 0; k < 4; ++k) atomicExch(&s_poll_looks[k], 0u);
+    // where this workgroup runs: HW_ID (register 4, all 32 bits) and XCC_ID (register 20, bits 0 .. 3) of wave 0
+    const unsigned int poll_hw_id = __builtin_amdgcn_s_getreg(4 | (31 << 11)), poll_xcc_id = __builtin_amdgcn_s_getreg(20 | (3 << 11));
 #endif
 #pragma unroll 1
     for (int h = 0; h < n_hs; ++h) {
@@ -2491,6 +2522,14 @@ void k_solo_run(const DevProblem* __restrict__ pbp, const DevSampler* __restrict
 #ifdef LCF_POLL_LOOKS
     if (threadIdx.x == 0)
         for (int k = 0; k < 4; ++k) atomicAdd(&g_poll_looks[k], (unsigned long long)atomicAdd(&s_poll_looks[k], 0u));
+    if (threadIdx.x == 0) {
+        const unsigned int at = atomicAdd(&g_poll_wg_n, 1u);
+        if (at < (unsigned int)kPollWgMax) {
+            unsigned int* rec = g_poll_wg + (size_t)at * kPollWgWords;
+            rec[0] = (unsigned int)(g_run0 + rel0), rec[1] = blockIdx.x, rec[2] = poll_hw_id, rec[3] = poll_xcc_id;
+            for (int k = 0; k < 4; ++k) rec[4 + k] = atomicAdd(&s_poll_looks[k], 0u);
+        }
+    }
 #endif
 }
 
@@ -4841,6 +4880,21 @@ extern "C" int lcf_debug_read_poll_looks(unsigned long long* out, int reset) {
     if (reset) {
         static unsigned long long zeros[4];
         rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_poll_looks), zeros, sizeof zeros);
+    }
+    return rc;
+}
+// (the per-workgroup records: `out` holds `max_records` of 8 words -- launch, blockIdx.x, HW_ID, XCC_ID, polls of 1, 2, 3
+// and more looks, looks in total; *n_records: how many workgroups have left a launch since the last reset, which may be
+// more than were kept; `reset` != 0: cleared afterwards)
+extern "C" int lcf_debug_read_poll_wg(unsigned int* out, int max_records, unsigned int* n_records, int reset) {
+    int rc = (int)hipMemcpyFromSymbol(n_records, HIP_SYMBOL(g_poll_wg_n), sizeof(unsigned int));
+    size_t keep = *n_records < (unsigned int)kPollWgMax ? *n_records : (size_t)kPollWgMax;
+    if (max_records < 0) max_records = 0;
+    if (keep > (size_t)max_records) keep = (size_t)max_records;
+    if (keep > 0) rc |= (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_poll_wg), sizeof(unsigned int) * kPollWgWords * keep);
+    if (reset) {
+        const unsigned int zero = 0u;
+        rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_poll_wg_n), &zero, sizeof zero);
     }
     return rc;
 }
