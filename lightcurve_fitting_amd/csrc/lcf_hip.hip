@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2899,9 +2900,10 @@ lcf_status lcf_engine::sync_dp() {
 namespace {
 
 // ---- the instantiation table: which kernels exist ---------------------------------------------------------------------
-// A launch site takes its family's instantiation for the fit dimension through dispatch(); a dimension outside the
-// family's list takes the generic kernel, ND = 0 (the dimension at run time).  Models with kernels of their own take
-// them through dispatch_model() at their own dimension.  Every instantiation costs compile time.
+// A launch site -- for k_solo and k_solo_run the plan of a run, once per run: take_solo(), take_run() -- takes its family's
+// instantiation for the fit dimension through dispatch(); a dimension outside the family's list takes the generic
+// kernel, ND = 0 (the dimension at run time).  Models with kernels of their own take them through dispatch_model() at
+// their own dimension, resident runs with rows of their own through dispatch_row().  Every instantiation costs compile time.
 template <int... V> struct Dims {};
 template <int M, int ND> struct Model {};              // model M's own kernels, at fit dimension ND
 template <class... S> struct Models {};
@@ -3746,12 +3748,27 @@ static size_t fused_lds_bytes(const lcf_engine* e) {
     return e->lds_bytes + kFusedScratch * sizeof(double);
 }
 
-bool fused_eligible(const lcf_sampler* s) {
-    static const bool disabled = std::getenv("LCF_NO_FUSED") != nullptr;
+// The environment's switches over how a run is executed, as they stand now: read when a run is planned (plan_run,
+// population_plan), so a switch holds for the runs planned while it is set.
+struct RunSwitches {
+    bool no_fused, no_solo, no_specialised, no_wide_solo, no_run_kernel, rows_per_half_step, run_any_size, run_test_missing;
+    int run_grid;   // LCF_RUN_GRID (tests): a resident launch has at most so many workgroups
+};
+static RunSwitches run_switches() {
+    const auto set = [](const char* name) { return std::getenv(name) != nullptr; };
+    const char* grid = std::getenv("LCF_RUN_GRID");
+    return RunSwitches{set("LCF_NO_FUSED"), set("LCF_NO_SOLO"), set("LCF_NO_SPECIALISED"), set("LCF_NO_WIDE_SOLO"),
+                       set("LCF_NO_RUN_KERNEL"), set("LCF_ROWS_PER_HALF_STEP"), set("LCF_RUN_ANY_SIZE"),
+                       set("LCF_RUN_TEST_MISSING"), grid ? std::atoi(grid) : INT_MAX};
+}
+
+static bool fused_eligible(const lcf_sampler* s, const RunSwitches& sw) {
     const lcf_engine* e = s->e;
-    return !disabled && s->half_step_kernel != LCF_HALF_STEP_PHASES && e->dp.tab_in_lds &&
+    return !sw.no_fused && s->half_step_kernel != LCF_HALF_STEP_PHASES && e->dp.tab_in_lds &&
            fused_lds_bytes(e) <= 80 * 1024;  // (two workgroups per CU; measured with 160 KiB allowed: no gain)
 }
+// (what the sharded, peer-mailbox and per-half-step drivers ask, half-step by half-step)
+bool fused_eligible(const lcf_sampler* s) { return fused_eligible(s, run_switches()); }
 
 // One launch for a whole half-step of a single-GPU run: commit half-step g_next - 1 (if pending), draw half-step
 // g_next and evaluate its likelihood.
@@ -3800,112 +3817,53 @@ static size_t run_lds_bytes(const lcf_engine* e) {
     return solo_lds_bytes(e) + (kSoloScratch + 4) * sizeof(double) + sizeof(RunUniforms);
 }
 
-bool solo_eligible(const lcf_sampler* s) {
-    // (LCF_NO_FUSED=1 asks for the separate launches: neither one-launch form then, as set_half_step_kernel('phases'))
-    static const bool disabled = std::getenv("LCF_NO_SOLO") != nullptr || std::getenv("LCF_NO_FUSED") != nullptr;
-    const lcf_engine* e = s->e;
-    // (the libm band sum, variant 0, exists to mirror the reference instruction for instruction: it keeps k_fused)
-    // (and light curves without shared epochs -- thermal state per point, inside the point loop -- keep k_fused too: there
-    // the serial head's registers on top of the point loop's do not fit 128 without spilling)
-    return !disabled && (s->half_step_kernel == LCF_HALF_STEP_AUTO || s->half_step_kernel == LCF_HALF_STEP_SOLO) &&
-           e->dp.variant != 0 && e->dp.use_therm && e->dp.tab_in_lds && e->dp.n_parts <= kMaxParts &&
-           solo_lds_bytes(e) <= kLdsPerCU;
-}
-
 // The model-specialised kernels (k_solo / k_pop <..., MODEL>) take engines of the shape the benchmarks have: a power-law
 // model (ShockCooling, ShockCooling2) without a fitted sigma, dense columns, interpolated band sums proved from their
 // first interval.  0: the generic kernel.
-static int specialised_model(const DevProblem& dp) {
-    static const bool disabled = std::getenv("LCF_NO_SPECIALISED") != nullptr;
-    if (disabled || !dp.use_therm || !dp.use_itab || dp.variant == 0 || !dp.em_dense || !dp.itab_uniform || dp.use_sigma)
+static int specialised_model(const DevProblem& dp, const RunSwitches& sw) {
+    if (sw.no_specialised || !dp.use_therm || !dp.use_itab || dp.variant == 0 || !dp.em_dense || !dp.itab_uniform || dp.use_sigma)
         return 0;
     return table_model(SpecialisedModels{}, dp.model, dp.n_dim);
 }
 
-// One half-step of a single-GPU run: ONE launch, one workgroup per proposal, accept test and commit included.
-// `board`: this rank's slots [lo, hi) only, rows from / to the row boards (lcf_sampler_run_rows).
-lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board, int lo, int hi) {
-    lcf_engine* e = s->e;
-    const DevSampler& ds = s->ds;
-    if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
-    const DrawRec* draws = s->rows(rel);
-    const bool next_here = rel + 1 < 2 * s->run_steps && s->block_of_step((rel + 1) / 2) == s->blk_current;
-    const DrawRec* draws_next = next_here ? draws + ds.n_half : nullptr;
-    const size_t lds = solo_lds_bytes(e);
-    const long long row = rel / 2, G = s->g_run0 + rel, g_run0 = s->g_run0;
-    const dim3 grid((unsigned)(board ? hi - lo : ds.n_half));
-    if (board && hi <= lo) return leave_half_step(&s, 1, st);
-    const int spec = specialised_model(e->dp);
-    // workgroups of 512 threads: one part per 256 threads (up to two parts) or two (three or four)
-    // ... or four (1024 threads) where the launch has at most one workgroup per CU
-    static const bool no_wide = std::getenv("LCF_NO_WIDE_SOLO") != nullptr;
-    const bool wide = !no_wide && e->dp.n_parts > 2 && (int)grid.x <= e->n_cus;
-    const int np = e->dp.n_parts <= 2 ? 2 : wide ? 8 : 4;   // (NP: parts per workgroup, 8 = the four of a proposal)
-    hipError_t err = hipSuccess;
+// ---- the instantiation table, walked: once per run, for its plan (plan_run) ------------------------------------------------
+// (Two walks, k_solo's here and k_solo_run's behind the sampler's images below: a kernel's place in the code object is the
+// place of its first use in this file, and timings at the 0.3 % level depend on where the resident kernels lie.)
+static void took(RunPlan& p, int nd, int np, int m) {
+    const int taken[4] = {nd, np, m, p.rows ? 1 : 0};
+    std::copy(taken, taken + 4, p.instance);
+    p.threads = kBlock * (np == 8 ? 4 : 2);
+}
+
+// The plan's instance of k_solo for the fit dimension, NP parts per workgroup and the model's own kernel `spec`.
+static void take_solo(RunPlan& p, int n_dim, int np, int spec) {
     const auto go = [&](auto nd, auto np_, auto m) {
         constexpr int ND = decltype(nd)::value, NP = decltype(np_)::value, M = decltype(m)::value;
-        const auto kernel = board ? k_solo<ND, 1, true, NP, true, M> : k_solo<ND, 1, true, NP, false, M>;
-        s->set_instance(ND, NP, M, board ? 1 : 0);
-        if ((err = prepare_kernel(kernel, lds)) == hipSuccess)
-            hipLaunchKernelGGL(kernel, grid, dim3(kBlock * (NP == 8 ? 4 : 2)), lds, st, e->d_dp, ds, row, draws, draws_next, G,
-                               g_run0, lo);
+        p.solo = p.rows ? k_solo<ND, 1, true, NP, true, M> : k_solo<ND, 1, true, NP, false, M>;
+        took(p, ND, NP, M);
     };
-    dispatch(SoloDims{}, ds.n_dim, [&](auto nd) {
+    dispatch(SoloDims{}, n_dim, [&](auto nd) {
         dispatch<8>(Dims<2, 4>{}, np, [&](auto np_) {
             const auto own = [&](auto snd, auto m) { go(snd, np_, m); };
             if constexpr (decltype(np_)::value == 8) go(nd, np_, Int<0>{});   // (no model has a 1024-thread kernel)
             else if (!dispatch_model(SpecialisedModels{}, nd, spec, own)) go(nd, np_, Int<0>{});
         });
     });
-    LCF_HIP(err);
-    LCF_HIP(hipGetLastError());
-    return leave_half_step(&s, 1, st);
 }
 
-// ---- a block of half-steps in ONE launch (k_solo_run) ---------------------------------------------------------------
-// Runs of one GPU whose half-steps k_solo can execute.  The launch's workgroups wait for each other's rows, so they must
-// all be resident at once: the grid is what the device holds (occupancy x CUs; each workgroup then takes several slots
-// of a half-step), and a process keeps ONE such launch in flight per device (`g_run_busy`): a second sampler's run
-// enqueued meanwhile on another stream takes a launch per half-step.
-// ... and whose proposals have a workgroup of their own (n_half <= kRunSlots: 2 workgroups of 512 threads per CU of an
-// MI355X) or, for light curves of at most two parts, share one with up to three others.  With several proposals per
-// workgroup and half-step the fixed share of each workgroup competes with the hardware's dispatch of one workgroup per
-// proposal, where a proposal that the prior excludes costs nothing: measured per half-step, k_solo_run against k_solo,
-// configs[1]'s light curve with 512 / 1024 / 2048 / 4096 walkers 4.9 / 6.0 / 11.8 / 22.7 against 6.1 / 7.8 / 13.5 /
-// 23.6 us; configs[2] (four parts, 2048 proposals) 80.7 against 76.9 us -- the boundary it saves is 2 % of that launch.
-// Light curves of more than two parts gain little (3000 observations at times of their own, 8 parts, 1024 walkers: 21.8
-// against 23.0 us) and lose below a few hundred proposals (100 walkers: 15.2 against 13.0 us -- the rows' way through the
-// board costs more than the boundary of so small a launch; configs[2]'s light curve with 512 walkers: 14.1 against the 12.8 us
-// of the 1024-thread workgroups that k_solo uses for launches of at most one workgroup per CU): they take it above one
-// proposal per CU, up to 512.
-constexpr int kRunSlots = 512;
-// Launches of at most one workgroup per CU of light curves with more than two parts (a rank's share of a strongly scaled
-// ensemble: configs[2] on 8 GPUs, 256 proposals): 1024-thread workgroups, all four parts of a proposal side by side, as
-// k_solo uses for such launches -- resident, for the eight-parameter models (the instantiation that exists).
-// (LCF_WIDE_RUNS=0: launches that k_solo's 1024-thread workgroups would take keep a launch per half-step)
-static bool wide_runs() {
-    const char* env = std::getenv("LCF_WIDE_RUNS");
-    return !(env && env[0] == '0');
-}
-// (the launches that take them -- and with LCF_NO_WIDE_SOLO=1 the same launches, resident all the same, at 512 threads)
-static bool run_wide_size(const lcf_sampler* s, int proposals) {
-    return s->e->dp.n_parts > 2 && proposals <= s->e->n_cus && has_dim(WideRuns{}, s->ds.n_dim);
-}
-static bool run_wide(const lcf_sampler* s, int proposals) {
-    static const bool no_wide = std::getenv("LCF_NO_WIDE_SOLO") != nullptr;
-    return !no_wide && run_wide_size(s, proposals);
-}
-// Launches of `width` proposals that take resident workgroups: up to `slots` proposals where a light curve has more
-// than two parts (the rank's share of a row-board run: up to two slots per workgroup, rows_resident_eligible).
-static bool resident_size(const lcf_sampler* s, int width, int slots) {
-    if (s->e->dp.n_parts <= 2) return width <= 4 * kRunSlots;
-    return (width > s->e->n_cus || (wide_runs() && run_wide_size(s, width))) && width <= slots;
-}
-bool run_eligible(const lcf_sampler* s) {
-    static const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr;
-    static const bool any_size = std::getenv("LCF_RUN_ANY_SIZE") != nullptr;   // (tests: several slots per workgroup)
-    return !disabled && !s->run_off && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) &&
-           run_lds_bytes(s->e) <= kLdsPerCU && s->ds.n_peers == 0 && (resident_size(s, s->ds.n_half, kRunSlots) || any_size);
+// One half-step of a k_solo plan: ONE launch, one workgroup per proposal, accept test and commit included (between
+// ranks: of this rank's slots only, rows from / to the row boards).
+lcf_status launch_solo(lcf_sampler* s, const RunPlan& plan, long long rel, hipStream_t st) {
+    const DevSampler& ds = s->ds;
+    if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
+    const DrawRec* draws = s->rows(rel);
+    const bool next_here = rel + 1 < 2 * s->run_steps && s->block_of_step((rel + 1) / 2) == s->blk_current;
+    const DrawRec* draws_next = next_here ? draws + ds.n_half : nullptr;
+    LCF_HIP(prepare_kernel(plan.solo, plan.lds));
+    hipLaunchKernelGGL(plan.solo, dim3((unsigned)(plan.hi - plan.lo)), dim3(plan.threads), plan.lds, st, s->e->d_dp, ds, rel / 2,
+                       draws, draws_next, s->g_run0 + rel, s->g_run0, plan.lo);
+    LCF_HIP(hipGetLastError());
+    return leave_half_step(&s, 1, st);
 }
 
 struct RunBusy { hipEvent_t ev = nullptr; hipStream_t stream = nullptr; bool used = false; bool enqueuing = false; };
@@ -3942,8 +3900,9 @@ void run_release(int dev, hipStream_t st) {   // behind the last launch of the r
 }
 
 // Workgroups of a resident launch, `per_cu` of them per CU: all on the device at once, on the compute units the engine's
-// stream may use (a CU mask on the stream -- or on the process -- leaves fewer than the device has).
-static int run_capacity(const lcf_engine* e, int per_cu) {
+// stream may use (a CU mask on the stream -- or on the process -- leaves fewer than the device has), `max_grid` at the most
+// (RunSwitches::run_grid).
+static int run_capacity(const lcf_engine* e, int per_cu, int max_grid) {
     int cus = e->n_cus;
     uint32_t mask[16] = {0};
     if (hipExtStreamGetCUMask(e->stream, 16, mask) == hipSuccess) {
@@ -3952,9 +3911,20 @@ static int run_capacity(const lcf_engine* e, int per_cu) {
         if (bits > 0 && bits < cus) cus = bits;
     }
     (void)hipGetLastError();
-    int cap = per_cu * cus;
-    if (const char* env = std::getenv("LCF_RUN_GRID")) cap = std::min(cap, std::atoi(env));  // (tests)
-    return cap;
+    return std::min(per_cu * cus, max_grid);
+}
+
+// What a resident plan asks of the device, once per run and ahead of its launches: the kernel's LDS attribute and how many
+// of its workgroups the device holds at once.  (What a process pays ONCE per kernel: lcf_sampler_board_connect does it
+// ahead of the first run, so that no rank's first launch makes such calls while another rank's resident workgroups
+// already wait for it.)
+lcf_status prepare_run(const lcf_engine* e, RunPlan& plan) {
+    int per_cu = 0;
+    if (hipError_t err = prepare_kernel(plan.run, plan.lds, plan.threads, &per_cu))
+        return fail(LCF_ERR_HIP, std::string("preparing k_solo_run: ") + hipGetErrorString(err));
+    plan.cap = run_capacity(e, per_cu, plan.max_grid);
+    if (plan.cap < 1) return fail(LCF_ERR_UNSUPPORTED, "k_solo_run does not fit the device");
+    return LCF_OK;
 }
 
 // The sampler as k_solo_run reads it, in device memory (a constant-address-space pointer in the kernel): written when a
@@ -4033,76 +4003,122 @@ static lcf_status rows_image(lcf_sampler* s, hipStream_t st, const DevSampler** 
     return LCF_OK;
 }
 
-// Half-steps [rel, rel + n_hs) of the run, all inside the current block of draw records.
-// `ranks`: this rank's slots [lo, hi) only, rows between the ranks' boards (lcf_sampler_run_rows); `need_progress`: see
-// k_solo_run<..., RANKS>.
-// `dry`: nothing is launched -- the kernel the launch would take is resolved, its LDS attribute set and its capacity on this
-// device asked (what a process pays ONCE per kernel: lcf_sampler_board_connect does it ahead of the first run, so that no
-// rank's first launch makes such calls while another rank's resident workgroups already wait for it).
-lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, bool ranks, int lo, int hi,
-                      long long need_progress, bool dry) {
-    lcf_engine* e = s->e;
-    const DevSampler* rs = nullptr;
-    int run_flags = 0;
-    if (dry) {
-        if (!ranks) hi = s->ds.n_half;
-    } else if (ranks) {
-        if (lcf_status r = rows_image(s, st, &rs)) return r;
-    } else {
-        if (lcf_status r = run_image(s, st, &rs, &run_flags)) return r;
-        lo = 0;
-        hi = s->ds.n_half;
-    }
-    const DrawRec* draws = dry ? nullptr : s->rows(rel);
-    const size_t lds = run_lds_bytes(e);
-    const long long g_run0 = s->g_run0;
-    const long long state_from = 2 * (s->run_steps - 1);   // X / LP / counts: written by the run's last step
-    // (test of the recovery from a launch whose workgroups are not all resident: the last one is not launched at all)
-    const bool test_missing = std::getenv("LCF_RUN_TEST_MISSING") != nullptr;
-    const int spec = specialised_model(e->dp);
-    unsigned int& arrivals = ranks ? s->rows_arrivals : s->run_arrivals;
-    lcf_status rc = LCF_OK;
-    const auto go = [&](auto nd, auto np_, auto m, auto ranks_) {
-        constexpr int ND = decltype(nd)::value, NP = decltype(np_)::value, M = decltype(m)::value;
-        const auto kernel = k_solo_run<ND, 1, true, NP, M, decltype(ranks_)::value>;
-        const int threads = kBlock * (NP == 8 ? 4 : 2);
-        int per_cu = 0;
-        if (hipError_t err = prepare_kernel(kernel, lds, threads, &per_cu)) {
-            rc = fail(LCF_ERR_HIP, std::string("preparing k_solo_run: ") + hipGetErrorString(err));
-            return;
-        }
-        const int cap = run_capacity(e, per_cu);
-        if (cap < 1) {
-            rc = fail(LCF_ERR_UNSUPPORTED, "k_solo_run does not fit the device");
-            return;
-        }
-        if (dry) return;
-        s->set_instance(ND, NP, M, decltype(ranks_)::value ? 1 : 0);
-        const int n_wg = std::min(hi - lo, cap);
-        const dim3 grid((unsigned)(test_missing && n_wg > 1 ? n_wg - 1 : n_wg));
-        arrivals += (unsigned int)n_wg;   // (0 = "no check": skipped when the count wraps onto it)
-        if (arrivals == 0u) arrivals = 1u;
-        hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, e->d_dp, rs, rel, draws, g_run0, n_hs, state_from, n_wg,
-                           run_flags, arrivals, lo, hi - lo, need_progress);
+// ... and its instance of k_solo_run: row by row where the family is listed so (between ranks; the wide size on one GPU),
+// else as k_solo's.  (NP = 8 where the table has a row for it, else the 512-thread form.)
+static void take_run(RunPlan& p, int n_dim, int np, int spec) {
+    const auto go = [&](auto nd, auto np_, auto m, auto ranks) {
+        p.run = k_solo_run<decltype(nd)::value, 1, true, decltype(np_)::value, decltype(m)::value, decltype(ranks)::value>;
+        took(p, nd, np_, m);
     };
-    // (NP = 8: 1024-thread workgroups, the four parts of a proposal side by side -- where the table has a row for it,
-    // else the 512-thread form)
-    const int np = e->dp.n_parts <= 2 ? 2 : run_wide(s, hi - lo) ? 8 : 4;
-    if (ranks) {
+    if (p.rows) {
         const auto row = [&](auto nd, auto np_, auto m) { go(nd, np_, m, std::true_type{}); };
-        if (!dispatch_row(RanksRuns{}, s->ds.n_dim, np, spec, row))
+        if (!dispatch_row(RanksRuns{}, n_dim, np, spec, row))
             dispatch<4>(Dims<2>{}, np, [&](auto np_) { go(Int<0>{}, np_, Int<0>{}, std::true_type{}); });
     } else {
         const auto row = [&](auto nd, auto np_, auto m) { go(nd, np_, m, std::false_type{}); };
-        if (!dispatch_row(WideRuns{}, s->ds.n_dim, np, spec, row))
-            dispatch(SoloDims{}, s->ds.n_dim, [&](auto nd) {
+        if (!dispatch_row(WideRuns{}, n_dim, np, spec, row))
+            dispatch(SoloDims{}, n_dim, [&](auto nd) {
                 dispatch<4>(Dims<2>{}, np, [&](auto np_) {
                     const auto own = [&](auto snd, auto m) { go(snd, np_, m, std::false_type{}); };
                     if (!dispatch_model(SpecialisedModels{}, nd, spec, own)) go(nd, np_, Int<0>{}, std::false_type{});
                 });
             });
     }
-    if (rc) return rc;
+}
+
+// ---- the plan of a run: which kernel, which instance of it ---------------------------------------------------------------
+// The forms, first that applies: a block of half-steps in ONE launch of resident workgroups (k_solo_run), ONE launch per
+// half-step with a workgroup per proposal (k_solo), ONE launch per half-step with a workgroup per part (k_fused), separate
+// launches.  A resident launch's workgroups wait for each other's rows, so they must all be on the device at once: the
+// grid is what the device holds (occupancy x CUs; each workgroup then takes several slots of a half-step), and a process
+// keeps ONE such launch in flight per device (`g_run_busy`): a second sampler's run enqueued meanwhile on another stream
+// takes a launch per half-step.
+// (proposals with a resident workgroup of their own: 2 workgroups of 512 threads per CU of an MI355X)
+constexpr int kRunSlots = 512;
+
+// The plan of a run of `s`: of one GPU (all slots of a half-step, [lo, hi) = [0, n_half)) or, `rows`, of the rank's slots
+// [lo, hi) of a row-board run.  `resident`: resident workgroups may be taken (the run has steps; the device is free).
+// Nothing is asked of the device and nothing in `s` changes.
+RunPlan plan_run(const lcf_sampler* s, bool rows, int lo, int hi, bool resident) {
+    const RunSwitches sw = run_switches();
+    const lcf_engine* e = s->e;
+    const DevProblem& dp = e->dp;
+    const int choice = s->half_step_kernel, n_dim = s->ds.n_dim, width = hi - lo;
+    RunPlan p{rows, lo, hi};
+    // 1. One workgroup per proposal?  Not the libm band sum (variant 0 exists to mirror the reference instruction for
+    // instruction: it keeps k_fused), and not light curves without shared epochs (thermal state per point, inside the
+    // point loop: the serial head's registers on top of the point loop's do not fit 128 without spilling).
+    // (LCF_NO_FUSED=1 asks for the separate launches: neither one-launch form then, as set_half_step_kernel('phases'))
+    const bool one_wg = !sw.no_solo && !sw.no_fused && (choice == LCF_HALF_STEP_AUTO || choice == LCF_HALF_STEP_SOLO) &&
+                        dp.variant != 0 && dp.use_therm && dp.tab_in_lds && dp.n_parts <= kMaxParts &&
+                        solo_lds_bytes(e) <= kLdsPerCU;
+    if (!one_wg) {
+        p.form = fused_eligible(s, sw) ? LCF_KERNEL_FUSED : LCF_KERNEL_PHASES;
+        return p;
+    }
+    // 2. The model's own kernel
+    const int spec = specialised_model(dp, sw);
+    // 3. Resident?  Launches of at most one workgroup per CU of light curves with more than two parts (a rank's share of a
+    // strongly scaled ensemble: configs[2] on 8 GPUs, 256 proposals) have a size of their own, the wide size: resident
+    // for the eight-parameter models (the instantiation that exists).
+    const bool wide_size = dp.n_parts > 2 && width <= e->n_cus && has_dim(WideRuns{}, n_dim);
+    // With several proposals per workgroup and half-step the fixed share of each workgroup competes with the hardware's
+    // dispatch of one workgroup per proposal, where a proposal that the prior excludes costs nothing.  Light curves of at
+    // most two parts share a workgroup with up to three others: measured per half-step, k_solo_run against k_solo,
+    // configs[1]'s light curve with 512 / 1024 / 2048 / 4096 walkers 4.9 / 6.0 / 11.8 / 22.7 against 6.1 / 7.8 / 13.5 /
+    // 23.6 us; configs[2] (four parts, 2048 proposals) 80.7 against 76.9 us -- the boundary it saves is 2 % of that launch.
+    // Light curves of more than two parts gain little (3000 observations at times of their own, 8 parts, 1024 walkers: 21.8
+    // against 23.0 us) and lose below a few hundred proposals (100 walkers: 15.2 against 13.0 us -- the rows' way through the
+    // board costs more than the boundary of so small a launch; configs[2]'s light curve with 512 walkers: 14.1 against the
+    // 12.8 us of the 1024-thread workgroups that k_solo uses for launches of at most one workgroup per CU): they take it
+    // above one proposal per CU, up to 512.  Between ranks up to TWO slots per workgroup -- a rank of a 2-GPU run of
+    // configs[2] has 1024 proposals: 36.1 us per half-step resident against 39.8 with a launch per half-step, whose row
+    // collection comes per half-step as well; on one GPU the two forms are level at that size, 36.6 / 36.5, and the
+    // hardware's dispatch of a workgroup per proposal wins beyond it.
+    const bool size = dp.n_parts <= 2 ? width <= 4 * kRunSlots
+                                      : (width > e->n_cus || wide_size) && width <= (rows ? 2 : 1) * kRunSlots;
+    // (LCF_RUN_ANY_SIZE, tests: several slots per workgroup at any size; LCF_ROWS_PER_HALF_STEP=1: never between ranks; a
+    // sampler whose resident launch gave up once, run_off, or whose rows travel through peer mailboxes: never on one GPU)
+    const bool may_stay = choice == LCF_HALF_STEP_AUTO && !sw.no_run_kernel && run_lds_bytes(e) <= kLdsPerCU &&
+                          (size || sw.run_any_size) && (rows ? !sw.rows_per_half_step : !s->run_off && s->ds.n_peers == 0);
+    const bool stay = resident && may_stay;
+    // (every form but k_solo reads the slots; and so that the records a run leaves for the next one serve it either way,
+    // so does k_solo where the sampler's runs are resident whenever they may be)
+    p.need_slots = rows || may_stay;
+    // 4. Parts per workgroup, NP.  Workgroups of 512 threads: one part per 256 threads (up to two parts) or two (three or
+    // four); or all four parts of a proposal side by side, 1024 threads, NP = 8, where the launch has at most one
+    // workgroup per CU (resident: at the wide size; LCF_NO_WIDE_SOLO=1: the same launches at 512 threads).
+    const bool wide = !sw.no_wide_solo && (stay ? wide_size : dp.n_parts > 2 && width <= e->n_cus);
+    const int np = dp.n_parts <= 2 ? 2 : wide ? 8 : 4;
+    // 5. The row of the instantiation table
+    p.form = stay ? LCF_KERNEL_RUN : LCF_KERNEL_SOLO;
+    p.lds = stay ? run_lds_bytes(e) : solo_lds_bytes(e);
+    if (!stay) {
+        take_solo(p, n_dim, np, spec);
+        return p;
+    }
+    p.span = rows ? kRunSpan : kRunSpanSolo;
+    p.max_grid = sw.run_grid;
+    p.test_missing = sw.run_test_missing;
+    take_run(p, n_dim, np, spec);
+    return p;
+}
+
+// Half-steps [rel, rel + n_hs) of a resident plan that prepare_run has seen, all inside the current block of draw records.
+// `need_progress`: see k_solo_run<..., RANKS> (0 on one GPU).
+lcf_status launch_run(lcf_sampler* s, const RunPlan& plan, long long rel, int n_hs, hipStream_t st, long long need_progress) {
+    const DevSampler* rs = nullptr;
+    int run_flags = 0;
+    if (lcf_status r = plan.rows ? rows_image(s, st, &rs) : run_image(s, st, &rs, &run_flags)) return r;
+    const long long state_from = 2 * (s->run_steps - 1);   // X / LP / counts: written by the run's last step
+    unsigned int& arrivals = plan.rows ? s->rows_arrivals : s->run_arrivals;
+    const int n_wg = std::min(plan.hi - plan.lo, plan.cap);
+    // (test of the recovery from a launch whose workgroups are not all resident: the last one is not launched at all)
+    const dim3 grid((unsigned)(plan.test_missing && n_wg > 1 ? n_wg - 1 : n_wg));
+    arrivals += (unsigned int)n_wg;   // (0 = "no check": skipped when the count wraps onto it)
+    if (arrivals == 0u) arrivals = 1u;
+    hipLaunchKernelGGL(plan.run, grid, dim3(plan.threads), plan.lds, st, s->e->d_dp, rs, rel, s->rows(rel), s->g_run0, n_hs,
+                       state_from, n_wg, run_flags, arrivals, plan.lo, plan.hi - plan.lo, need_progress);
     LCF_HIP(hipGetLastError());
     return LCF_OK;
 }
@@ -4379,17 +4395,14 @@ lcf_status lcf_sampler_run_peers(lcf_sampler* s, int64_t first_step, int64_t n_s
 }  // extern "C"
 
 namespace {
-// Row-board runs with RESIDENT workgroups (k_solo_run<..., RANKS>): where a single-GPU run of the rank's share would
-// take resident workgroups (run_eligible), and for the same reasons.  LCF_ROWS_PER_HALF_STEP=1: never.
-// (Light curves of more than two parts: up to TWO slots per workgroup -- a rank of a 2-GPU run of configs[2] has 1024
-// proposals: 36.1 us per half-step resident against 39.8 with a launch per half-step, whose row collection comes per
-// half-step as well; on one GPU the two forms are level at that size, 36.6 / 36.5, and the hardware's dispatch of a
-// workgroup per proposal wins beyond it.)
-bool rows_resident_eligible(const lcf_sampler* s, int width) {
-    const bool disabled = std::getenv("LCF_NO_RUN_KERNEL") != nullptr || std::getenv("LCF_ROWS_PER_HALF_STEP") != nullptr;
-    const bool any_size = std::getenv("LCF_RUN_ANY_SIZE") != nullptr;
-    return !disabled && s->half_step_kernel == LCF_HALF_STEP_AUTO && solo_eligible(s) && run_lds_bytes(s->e) <= kLdsPerCU &&
-           (resident_size(s, width, 2 * kRunSlots) || any_size);
+// The plan of this rank's share of a row-board run (resident workgroups, k_solo_run<..., RANKS>, where a single-GPU run
+// of the share would take them: plan_run) -- and only k_solo and k_solo_run read and post rows.
+lcf_status plan_rows(const lcf_sampler* s, int n_ranks, int rank, bool resident, RunPlan* plan) {
+    const int width = s->ds.n_half / n_ranks;
+    *plan = plan_run(s, true, rank * width, rank * width + width, resident);
+    if (plan->form != LCF_KERNEL_RUN && plan->form != LCF_KERNEL_SOLO)
+        return fail(LCF_ERR_UNSUPPORTED, "row-board runs need the one-workgroup-per-proposal half-step (k_solo)");
+    return LCF_OK;
 }
 
 lcf_status board_alloc(lcf_sampler* s) {
@@ -4416,8 +4429,8 @@ lcf_status lcf_sampler_board_connect(lcf_sampler* s, int32_t n_ranks, int32_t ra
         return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument (at most 8 ranks)");
     if (s->ds.n_half % n_ranks)
         return fail(LCF_ERR_INVALID_ARGUMENT, "the slots of a half-step must divide evenly over the ranks");
-    if (!solo_eligible(s))
-        return fail(LCF_ERR_UNSUPPORTED, "row-board runs need the one-workgroup-per-proposal half-step (k_solo)");
+    RunPlan plan;
+    if (lcf_status st = plan_rows(s, n_ranks, rank, true, &plan)) return st;
     if (lcf_status st = board_alloc(s)) return st;
     LCF_HIP(hipSetDevice(s->e->device));
     if (lcf_status st = map_blocks(s->board_mem, n_ranks, rank, handles, local_ptrs, s->board_opened, s->ds.peer_board,
@@ -4425,14 +4438,11 @@ lcf_status lcf_sampler_board_connect(lcf_sampler* s, int32_t n_ranks, int32_t ra
         return st;
     s->ds.n_board_ranks = n_ranks;
     s->ds.board_rank = rank;
-    // (the kernel a resident run of this rank will take, resolved now: see launch_run's `dry`; and the image of the
-    // sampler it reads, allocated now: an allocation made by one rank of a process while another rank's resident
-    // workgroups already wait for it can hold its launch back for seconds)
+    // (the kernel a resident run of this rank will take, prepared now: see prepare_run; and the image of the sampler it
+    // reads, allocated now: an allocation made by one rank of a process while another rank's resident workgroups already
+    // wait for it can hold its launch back for seconds)
     if (lcf_status st = put_image(s, s->rows_image, nullptr, nullptr)) return st;
-    const int width = s->ds.n_half / n_ranks;
-    if (rows_resident_eligible(s, width))
-        if (lcf_status st = launch_run(s, 0, 0, s->e->stream, true, rank * width, rank * width + width, 0, true)) return st;
-    return LCF_OK;
+    return plan.form == LCF_KERNEL_RUN ? prepare_run(s->e, plan) : LCF_OK;
 }
 
 // The sharded run in which nothing is replicated: rank r evaluates, accepts and commits the proposals
@@ -4446,8 +4456,8 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
                                       const int32_t* perm, int32_t store_chain) {
     if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
     if (s->ds.n_board_ranks < 1) return fail(LCF_ERR_STATE, "lcf_sampler_board_connect must be called first");
-    if (!solo_eligible(s))
-        return fail(LCF_ERR_UNSUPPORTED, "row-board runs need the one-workgroup-per-proposal half-step (k_solo)");
+    RunPlan plan;
+    if (lcf_status st = plan_rows(s, s->ds.n_board_ranks, s->ds.board_rank, n_steps > 0, &plan)) return st;
     static const bool trace = std::getenv("LCF_TRACE_RUN") != nullptr;   // (diagnostic: host time of the enqueue's parts)
     const auto t_in = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) {
@@ -4459,11 +4469,7 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
     mark("draw records enqueued");
     hipStream_t st = s->e->stream;
     DevSampler& ds = s->ds;
-    const int width = ds.n_half / ds.n_board_ranks, lo = ds.board_rank * width, hi = lo + width;
-    const bool resident = rows_resident_eligible(s, width) && n_steps > 0;
-    s->last_rows = true;
-    s->last_kernel = resident ? LCF_KERNEL_RUN : LCF_KERNEL_SOLO;
-    s->last_launches = resident ? 0 : 2 * n_steps;
+    long long launches = plan.form == LCF_KERNEL_RUN ? 0 : 2 * n_steps;   // (resident launches: counted below)
     LCF_HIP(hipEventRecord(s->ev0, st));
     const long long cells = (long long)ds.n_walkers * (ds.n_dim + 2);
     hipLaunchKernelGGL(k_board_init, dim3((unsigned)((std::max<long long>(cells, kBoardClear) + 255) / 256)), dim3(256), 0, st, ds,
@@ -4473,18 +4479,18 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
     // (k_board_collect: workgroups of four waves, each wave 64 / board_row_entries rows)
     const int collect_rpw = 64 / board_row_entries(ds.n_dim);
     auto collect_grid = [&](long long rows) { return dim3((unsigned)((rows + 4 * collect_rpw - 1) / (4 * collect_rpw))); };
-    if (resident) {
+    if (plan.form == LCF_KERNEL_RUN) {
         // The rank's workgroups stay for a block of up to kRunSpan half-steps (k_solo_run<..., RANKS>); behind every launch
         // the rows of its half-steps -- as every rank posted them -- go from the board into the chain, behind the last one
         // the rows of the last step into X / LP / counts.  A launch may start once every rank has reached the launch before
         // the previous one (need_progress).
+        if (lcf_status r = prepare_run(s->e, plan)) return r;
         long long starts[2] = {-1, -1};   // first half-steps (relative) of the two launches in front
-        for (long long rel = 0; rel < 2 * n_steps;) {
-            ++s->last_launches;
+        for (long long rel = 0; rel < 2 * n_steps; ++launches) {
             if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
-            const int n = s->block_span(rel, kRunSpan);
+            const int n = s->block_span(rel, plan.span);
             const long long need = starts[0] >= 0 ? s->g_run0 + starts[0] : 0;
-            if (lcf_status r = launch_run(s, rel, n, st, true, lo, hi, need)) return r;
+            if (lcf_status r = launch_run(s, plan, rel, n, st, need)) return r;
             mark("resident launch enqueued");
             if (store_chain) {
                 hipLaunchKernelGGL(k_board_collect, collect_grid((long long)n * ds.n_half), dim3(256), 0, st, ds,
@@ -4498,7 +4504,7 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
         }
     } else {
         for (int64_t k = 0; k < 2 * n_steps; ++k) {
-            if (lcf_status r = launch_solo(s, k, st, true, lo, hi)) return r;
+            if (lcf_status r = launch_solo(s, plan, k, st)) return r;
             if (store_chain && (k & 1)) {  // the rows of this step's two half-steps, from every rank, into the chain
                 hipLaunchKernelGGL(k_board_collect, collect_grid(2ll * ds.n_half), dim3(256), 0, st, ds,
                                    (long long)(s->g_run0 + k - 1), (long long)(k / 2), s->rows(k - 1), 2, 0, 1);
@@ -4513,6 +4519,7 @@ lcf_status lcf_sampler_run_rows_async(lcf_sampler* s, int64_t first_step, int64_
         LCF_HIP(hipGetLastError());
     }
     s->g_next += 2 * n_steps;
+    s->record_run(plan.form, true, launches, plan.instance);
     LCF_HIP(hipEventRecord(s->ev1, st));
     const lcf_status rc = enqueue_snapshot(s);
     mark("all enqueued");
@@ -4543,6 +4550,7 @@ bool g_pop_run_off = false;   // a resident launch of this process found its wor
 // How a population run goes, decided before any of it is enqueued.
 struct PopPlan {
     int form = LCF_KERNEL_POPULATION_PHASES;   // LCF_KERNEL_POPULATION_RUN, _POPULATION or _POPULATION_PHASES
+    const RunSwitches sw = run_switches();     // the environment's switches as the run found them
     std::vector<MultiItem> items;              // per transient: its sampler by value, the engine's parts merged
     int same_dim = 0;                          // compile-time walker dimension when every transient has the same
     int pop_spec = 0;                          // the model-specialised kernel when every transient takes the same
@@ -4598,7 +4606,7 @@ lcf_status plan_resident(lcf_sampler** ss, int n, long long g, PopPlan& p) {
     if (!dispatch_model(PopRunModels{}, p.same_dim, p.pop_spec, own)) p.run_kernel = k_pop_run<0, 1, kPopRunGroup, 0>;
     int per_cu = 0;
     LCF_HIP(prepare_kernel(p.run_kernel, p.run_lds, 64 * kPopRunGroup, &per_cu));
-    p.cap = run_capacity(s0->e, per_cu);
+    p.cap = run_capacity(s0->e, per_cu, p.sw.run_grid);
     if (p.cap < 1) return LCF_OK;
     p.claim.dev = s0->e->device;
     p.claim.st = s0->e->stream;
@@ -4657,9 +4665,9 @@ lcf_status population_plan(lcf_sampler** ss, int n, int64_t n_steps, long long g
         p.lds = std::max(p.lds, s->e->lds_bytes);
         p.max_parts = std::max(p.max_parts, np);
     }
-    p.pop_spec = specialised_model(p.items[0].pb);
+    p.pop_spec = specialised_model(p.items[0].pb, p.sw);
     for (int t = 1; t < n; ++t)
-        if (specialised_model(p.items[t].pb) != p.pop_spec) p.pop_spec = 0;
+        if (specialised_model(p.items[t].pb, p.sw) != p.pop_spec) p.pop_spec = 0;
     // k_pop where every transient has shared epochs, staged tables, the fast band sum, at most kPopMaxParts merged parts
     // and tables that do not depend on the proposal (ShockCooling3's reddened tables do)
     bool one_launch = std::getenv("LCF_NO_POP") == nullptr && p0.use_therm && p0.variant != 0 && p0.tab_in_lds &&
@@ -4670,8 +4678,7 @@ lcf_status population_plan(lcf_sampler** ss, int n, int64_t n_steps, long long g
     }
     if (!one_launch || p.pop_lds > kLdsPerCU) return LCF_OK;
     p.form = LCF_KERNEL_POPULATION;
-    const bool no_pop_run = std::getenv("LCF_NO_POP_RUN") != nullptr || std::getenv("LCF_NO_RUN_KERNEL") != nullptr;
-    if (!resident || no_pop_run || g_pop_run_off || n_steps == 0) return LCF_OK;
+    if (!resident || std::getenv("LCF_NO_POP_RUN") || p.sw.no_run_kernel || g_pop_run_off || n_steps == 0) return LCF_OK;
     return plan_resident(ss, n, g, p);
 }
 
@@ -4679,8 +4686,7 @@ lcf_status population_plan(lcf_sampler** ss, int n, int64_t n_steps, long long g
 lcf_status enqueue_pop_run(lcf_sampler** ss, int n, PopPlan& p, int64_t n_steps, int32_t store_chain, hipStream_t st,
                            long long* launches) {
     // (test of the recovery from a launch whose workgroups are not all resident: the last one is not launched at all)
-    const bool test_missing = std::getenv("LCF_RUN_TEST_MISSING") != nullptr;
-    const unsigned int n_wg = (unsigned int)(test_missing && p.run_grid > 1 ? p.run_grid - 1 : p.run_grid);
+    const unsigned int n_wg = (unsigned int)(p.sw.run_test_missing && p.run_grid > 1 ? p.run_grid - 1 : p.run_grid);
     const long long state_from = 2 * (long long)(n_steps - 1);   // X / LP / counts: written by the run's last step
     int run_launches = 0;
     for (long long rel = 0; rel < 2 * n_steps; ++run_launches) {
@@ -4818,11 +4824,7 @@ lcf_status population_run(lcf_sampler** ss, int n, int64_t first_step, int64_t n
         ss[t]->snap_enqueued = false;
         ss[t]->snap_valid = true;
         ss[t]->last_ms = ms;
-        ss[t]->last_rows = false;
-        ss[t]->last_kernel = p.form;
-        ss[t]->last_launches = launches;
-        if (p.form == LCF_KERNEL_POPULATION_PHASES) ss[t]->set_instance(-1, -1, -1, -1);
-        else ss[t]->set_instance(p.instance[0], p.instance[1], p.instance[2], p.instance[3]);
+        ss[t]->record_run(p.form, false, launches, p.instance);   // (_POPULATION_PHASES: no instance, the -1 it starts with)
         gave_up = gave_up || (p.form == LCF_KERNEL_POPULATION_RUN && (reported_error(ss[t]) & 2));
     }
     if (gave_up) {   // (rewind_resident_run; the caller repeats the steps with a launch per half-step)

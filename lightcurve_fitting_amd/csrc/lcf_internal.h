@@ -181,7 +181,32 @@ struct alignas(16) RunUniforms {
 };
 static_assert(sizeof(RunUniforms) % 16 == 0 && sizeof(RunUniforms) <= 1024, "a small block of 16-byte groups");
 
+// What every k_solo<...> and every k_solo_run<...> is to the host: one signature per family.
+using SoloKernel = void (*)(const DevProblem*, const DevSampler, long long, const DrawRec*, const DrawRec*, long long, long long, int);
+using SoloRunKernel = void (*)(const DevProblem*, const DevSampler*, long long, const DrawRec*, long long, int, long long, int, int,
+                               unsigned int, int, int, long long);
+
 }  // namespace
+
+// How the half-steps of ONE sampler's run are executed (a run of one GPU, or a rank's share of a row-board run): decided
+// by plan_run (lcf_hip.hip) before anything of the run is enqueued; the launchers take it and choose nothing.
+struct RunPlan {
+    // what is planned: a row-board run, of this rank's slots [lo, hi) (one GPU: all of a half-step's)
+    bool rows = false;
+    int lo = 0, hi = 0;
+    // what the plan is
+    int form = LCF_KERNEL_PHASES;         // LCF_KERNEL_RUN (k_solo_run), _SOLO (k_solo), _FUSED or _PHASES
+    int instance[4] = {-1, -1, -1, -1};   // <ND, NP, M, ranks> of the k_solo / k_solo_run taken (-1: k_fused / phases)
+    SoloKernel solo = nullptr;            // the kernel of that instance: form _SOLO ...
+    SoloRunKernel run = nullptr;          // ... form _RUN
+    int threads = 0;
+    size_t lds = 0;
+    bool need_slots = true;               // the draw records carry each walker's slot in the previous half-step
+    // resident plans: half-steps a launch covers at most; LCF_RUN_GRID and LCF_RUN_TEST_MISSING as the run found them;
+    // and the workgroups the device holds at once (prepare_run)
+    int span = 0, max_grid = 0, cap = 0;
+    bool test_missing = false;
+};
 
 struct lcf_engine {
     int device = 0;
@@ -313,11 +338,12 @@ struct lcf_sampler {
     long long last_launches = 0;   // launches of that kernel in the last run (lcf_sampler_last_run_launches)
     // <ND, NP, M, ranks> of the half-step kernel launched last (lcf_sampler_last_run_instance; -1: k_fused / phases)
     int last_instance[4] = {-1, -1, -1, -1};
-    void set_instance(int nd, int np, int m, int ranks) {
-        last_instance[0] = nd;
-        last_instance[1] = np;
-        last_instance[2] = m;
-        last_instance[3] = ranks;
+    // ... all four written where a run is enqueued, from its plan
+    void record_run(int kernel, bool rows, long long launches, const int instance[4]) {
+        last_kernel = kernel;
+        last_rows = rows;
+        last_launches = launches;
+        std::copy(instance, instance + 4, last_instance);
     }
     unsigned long long* mailbox = nullptr;   // this rank's peer mailbox (uncached device memory), see DevSampler
     size_t mailbox_cap = 0;
@@ -462,14 +488,13 @@ lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout,
 lcf_status launch_next(lcf_sampler* s, bool have_next, int lo, int hi, hipStream_t st);
 lcf_status launch_eval(lcf_sampler* s, int lo, int hi, bool finalize, hipStream_t st);
 lcf_status launch_fused(lcf_sampler* s, int lo, int hi, hipStream_t st);
-lcf_status launch_solo(lcf_sampler* s, long long rel, hipStream_t st, bool board = false, int lo = 0, int hi = 0);
-lcf_status launch_run(lcf_sampler* s, long long rel, int n_hs, hipStream_t st, bool ranks = false, int lo = 0, int hi = 0,
-                      long long need_progress = 0, bool dry = false);
+RunPlan plan_run(const lcf_sampler* s, bool rows, int lo, int hi, bool resident);
+lcf_status prepare_run(const lcf_engine* e, RunPlan& plan);
+lcf_status launch_solo(lcf_sampler* s, const RunPlan& plan, long long rel, hipStream_t st);
+lcf_status launch_run(lcf_sampler* s, const RunPlan& plan, long long rel, int n_hs, hipStream_t st, long long need_progress);
 lcf_status launch_half_step_sharded(lcf_sampler* s, int lo, int hi, hipStream_t st);
 lcf_status launch_half_step_rows(lcf_sampler* s, int lo, int hi, hipStream_t st);
 bool fused_eligible(const lcf_sampler* s);
-bool solo_eligible(const lcf_sampler* s);
-bool run_eligible(const lcf_sampler* s);
 bool run_claim(int dev, hipStream_t st);
 void run_release(int dev, hipStream_t st);
 lcf_status run_buffers(lcf_sampler* s);

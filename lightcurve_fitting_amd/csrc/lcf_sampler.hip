@@ -741,7 +741,9 @@ lcf_status lcf_sampler_set_half_step_kernel(lcf_sampler* s, int32_t choice, int3
     if (!s || choice < LCF_HALF_STEP_AUTO || choice > LCF_HALF_STEP_SOLO)
         return fail(LCF_ERR_INVALID_ARGUMENT, "bad half-step kernel choice");
     s->half_step_kernel = choice;
-    if (used) *used = run_eligible(s) ? 3 : solo_eligible(s) ? 2 : fused_eligible(s) ? 1 : 0;
+    static_assert(LCF_KERNEL_SOLO == 2 && LCF_KERNEL_FUSED == 1 && LCF_KERNEL_PHASES == 0, "what *used says of these");
+    const int form = plan_run(s, false, 0, s->ds.n_half, true).form;
+    if (used) *used = form == LCF_KERNEL_RUN ? 3 : form;
     return LCF_OK;
 }
 
@@ -753,7 +755,9 @@ void lcf_sampler_last_run_instance(const lcf_sampler* s, int32_t out[4]) {
     for (int k = 0; out && k < 4; ++k) out[k] = s ? s->last_instance[k] : -1;
 }
 
-int32_t lcf_sampler_one_launch(const lcf_sampler* s) { return s && (solo_eligible(s) || fused_eligible(s)) ? 1 : 0; }
+int32_t lcf_sampler_one_launch(const lcf_sampler* s) {
+    return s && plan_run(s, false, 0, s->ds.n_half, false).form != LCF_KERNEL_PHASES ? 1 : 0;
+}
 
 lcf_status lcf_sampler_half_step_rows(lcf_sampler* s, int64_t step, int32_t half, int32_t lo, int32_t hi,
                                       void* stream) {
@@ -845,30 +849,30 @@ lcf_status lcf_sampler_check(lcf_sampler* s) {
 lcf_status lcf_sampler_run_async(lcf_sampler* s, int64_t first_step, int64_t n_steps, int32_t split_mode,
                                  const int32_t* perm, int32_t store_chain) {
     if (!s) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    const bool one_launch = run_eligible(s) && n_steps > 0 && run_claim(s->e->device, s->e->stream);
-    RunClaim claim{s->e->device, s->e->stream, one_launch};
-    s->last_rows = false;
-    if (lcf_status st = sampler_begin(s, first_step, n_steps, split_mode, perm, store_chain,
-                                      !solo_eligible(s) || run_eligible(s))) return st;
+    // (resident workgroups where the plan takes them and no other stream's hold the device: else the plan without them)
+    RunPlan plan = plan_run(s, false, 0, s->ds.n_half, n_steps > 0);
+    RunClaim claim{s->e->device, s->e->stream, plan.form == LCF_KERNEL_RUN && run_claim(s->e->device, s->e->stream)};
+    if (plan.form == LCF_KERNEL_RUN && !claim.held) plan = plan_run(s, false, 0, s->ds.n_half, false);
+    if (lcf_status st = sampler_begin(s, first_step, n_steps, split_mode, perm, store_chain, plan.need_slots)) return st;
     hipStream_t st = s->e->stream;
     s->ds.inline_finalize = 1;  // single GPU: no separate finalize / accept launches
     LCF_HIP(hipEventRecord(s->ev0, st));
-    if (one_launch) {   // the workgroups stay for a block of half-steps and hand each other rows (k_solo_run)
+    if (plan.form == LCF_KERNEL_RUN) {   // the workgroups stay for a block of half-steps and hand each other rows (k_solo_run)
         if (lcf_status r = run_buffers(s)) return r;
+        if (lcf_status r = prepare_run(s->e, plan)) return r;
         s->replay_first = first_step;
         s->replay_steps = n_steps;
         s->replay_split = split_mode;
         s->replay_store = store_chain;
-        s->last_kernel = LCF_KERNEL_RUN;
-        s->last_launches = 0;
-        for (long long rel = 0; rel < 2 * n_steps;) {   // (the first launch posts the start state on the board itself)
-            ++s->last_launches;
+        long long launches = 0;
+        for (long long rel = 0; rel < 2 * n_steps; ++launches) {   // (the first launch posts the start state on the board itself)
             if (lcf_status r = enter_half_step(&s, 1, rel, st)) return r;
-            const int n = s->block_span(rel, kRunSpanSolo);
-            if (lcf_status r = launch_run(s, rel, n, st)) return r;
+            const int n = s->block_span(rel, plan.span);
+            if (lcf_status r = launch_run(s, plan, rel, n, st, 0)) return r;
             if (lcf_status r = leave_half_step(&s, 1, st)) return r;
             rel += n;
         }
+        s->record_run(plan.form, false, launches, plan.instance);
         s->g_next += 2 * n_steps;
         s->flip_state_sets();                  // the state behind this run is in the other set now
         LCF_HIP(hipEventRecord(s->ev1, st));
@@ -881,25 +885,22 @@ lcf_status lcf_sampler_run_async(lcf_sampler* s, int64_t first_step, int64_t n_s
     }
     // per half-step: ONE launch (k_fused) when everything a workgroup needs fits in LDS, else
     // [commit previous + draw + thermal states] -> [per-point likelihood]; one trailing commit
-    const bool fused = fused_eligible(s);
-    s->last_kernel = solo_eligible(s) ? LCF_KERNEL_SOLO : fused ? LCF_KERNEL_FUSED : LCF_KERNEL_PHASES;
-    s->last_launches = 2 * n_steps;
-    s->set_instance(-1, -1, -1, -1);   // (k_solo's launches record theirs)
-    if (solo_eligible(s)) {  // one workgroup per proposal, nothing pending between launches
+    if (plan.form == LCF_KERNEL_SOLO) {  // one workgroup per proposal, nothing pending between launches
         for (int64_t k = 0; k < 2 * n_steps; ++k)
-            if (lcf_status r = launch_solo(s, k, st)) return r;
+            if (lcf_status r = launch_solo(s, plan, k, st)) return r;
         s->g_next += 2 * n_steps;
+    } else if (plan.form == LCF_KERNEL_FUSED) {
+        for (int64_t k = 0; k < 2 * n_steps; ++k)
+            if (lcf_status r = launch_fused(s, 0, s->ds.n_half, st)) return r;
+        if (lcf_status r = flush_pending(s, st)) return r;
     } else {
         for (int64_t k = 0; k < 2 * n_steps; ++k) {
-            if (fused) {
-                if (lcf_status r = launch_fused(s, 0, s->ds.n_half, st)) return r;
-                continue;
-            }
             if (lcf_status r = launch_next(s, true, 0, s->ds.n_half, st)) return r;
             if (lcf_status r = launch_eval(s, 0, s->ds.n_half, false, st)) return r;
         }
         if (lcf_status r = flush_pending(s, st)) return r;
     }
+    s->record_run(plan.form, false, 2 * n_steps, plan.instance);
     LCF_HIP(hipEventRecord(s->ev1, st));
     if (lcf_status r = enqueue_snapshot(s)) return r;
     return speculate_continuation(s, st);

@@ -143,14 +143,14 @@ RANK_CASES = {
     8: ({}, (0, 2, 0, 1), (5, 2, 0, 1)),
     9: ({}, (0, 2, 0, 1), (6, 2, 0, 1)),
     1: ({}, (0, 2, 0, 1), (7, 2, 0, 1)),
-    # three parts below dimension 8: resident only with LCF_RUN_ANY_SIZE (read at every row-board run), 512 threads
+    # three parts below dimension 8: resident only with LCF_RUN_ANY_SIZE (read when a run is planned), 512 threads
     21: ({'LCF_RUN_ANY_SIZE': '1'}, (0, 4, 0, 1), (6, 8, 0, 1)),
     17: ({}, (5, 2, SC, 1), (5, 2, SC, 1)),
     26: ({}, (8, 2, 0, 1), (8, 2, 0, 1)),
     4: ({}, (8, 8, 0, 1), (8, 8, 0, 1)),
 }
 
-# process-wide switches (read once per process): environment -> [(case, form, (kernel, instance))]
+# process-wide switches (read when a run is planned; set here for a whole process): environment -> [(case, form, (kernel, instance))]
 SWITCHES = {
     'LCF_NO_SPECIALISED': ({'LCF_NO_SPECIALISED': '1'},
                            [(6, 'auto', ('run', (5, 2, 0, 0))), (7, 'auto', ('run', (4, 2, 0, 0))),
@@ -164,7 +164,7 @@ SWITCHES = {
                     [(6, 'auto', ('fused', NONE)), (1, 'auto', ('fused', NONE)), (8, 'auto', ('fused', NONE))]),
     'LCF_NO_FUSED': ({'LCF_NO_FUSED': '1'},
                      [(6, 'auto', ('phases', NONE)), (1, 'auto', ('phases', NONE)), (8, 'auto', ('phases', NONE))]),
-    # LCF_RUN_ANY_SIZE is read by the first single-GPU run of a process: resident workgroups for light curves of more than
+    # LCF_RUN_ANY_SIZE, here for the single-GPU runs of a process: resident workgroups for light curves of more than
     # two parts below a proposal per CU, two or three slots per workgroup; 512 threads where the table has no wide row
     'LCF_RUN_ANY_SIZE': ({'LCF_RUN_ANY_SIZE': '1'},
                          [(18, 'grid', ('run', (4, 4, SC2, 0))), (19, 'grid', ('run', (5, 4, SC, 0))),

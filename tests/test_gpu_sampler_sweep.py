@@ -21,7 +21,7 @@ from lightcurve_fitting_amd.sampler import EnsembleSampler, PopulationSampler
 pytestmark = pytest.mark.gpu
 
 ENV = ('LCF_PARTS', 'LCF_RUN_GRID', 'LCF_RUN_ANY_SIZE', 'LCF_NO_POP_RUN', 'LCF_NO_POP', 'LCF_DRAW_BLOCK', 'LCF_NO_RUN_KERNEL',
-       'LCF_ROWS_PER_HALF_STEP', 'LCF_POP_ITAB_LDS', 'LCF_SHARED_EPOCHS_ONLY', 'LCF_WIDE_RUNS')
+       'LCF_ROWS_PER_HALF_STEP', 'LCF_POP_ITAB_LDS', 'LCF_SHARED_EPOCHS_ONLY')
 STATE = ('chain', 'lp', 'nacc', 'x', 'lp_end')
 
 _SEEN = set()     # (kernel, instance) of every run of the module
