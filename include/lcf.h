@@ -609,7 +609,7 @@ lcf_status lcf_tempered_get_move_history(lcf_tempered* t, int32_t* kinds);
  * end of a run when inside the prior's support).  The function must return, and write nowhere but its two outputs.
  *
  * lcf_custom_compile: the program text is csrc/lcf_device.h, `#line 1 "user_model"`, the source, then the library's
- * kernel (csrc/lcf_custom_kernel.h), compiled by hiprtc with the library's own code-generation flags for `arch`
+ * kernels (csrc/lcf_custom_kernel.h, behind the key encoding of csrc/lcf_keys.h), compiled by hiprtc with the library's own code-generation flags for `arch`
  * ("gfx950"; NULL or "": the base name of the architecture of `device` -- with a name no device is needed).  hiprtc is
  * bound at run time: LCF_HIPRTC_LIB, <ROCM_PATH | HIP_PATH | /opt/rocm>/lib/libhiprtc.so, the directory the process's HIP
  * runtime was loaded from (PyTorch's lib), the loader's path; LCF_ERR_UNSUPPORTED with the paths tried when none loads.
@@ -630,10 +630,12 @@ void lcf_custom_destroy(lcf_custom* c);
  * lcf_log_likelihood / lcf_log_posterior and their _dev forms, lcf_model_evaluate, lcf_temperature_radius (T and R as
  * the state function returned them) and, through lcf_log_likelihood_dev, lcf_tempered_*: one workgroup per (row, part of
  * the light curve), one lane per data point, the band sum chosen per point as lcf_blackbody_to_filters chooses it, sums
- * in a fixed order -- a row's value does not depend on the rows evaluated with it.  Before a program is attached these
- * calls return LCF_ERR_STATE.  What is compiled per model -- lcf_sampler_create and with it every lcf_sampler_* and
- * population run, lcf_predict_*, lcf_sampler_predict_*, lcf_profile_loglike_kernel -- returns LCF_ERR_UNSUPPORTED for
- * such an engine, naming this route, and launches nothing. */
+ * in a fixed order -- a row's value does not depend on the rows evaluated with it.  It also serves lcf_predict_custom
+ * (below: the bands of the light curves, T, R and L over a whole chain).  Before a program is attached these calls
+ * return LCF_ERR_STATE.  What is compiled per model -- lcf_sampler_create and with it every lcf_sampler_* and population
+ * run, lcf_predict_quantiles, lcf_predict_thermal, lcf_predict_luminosity, lcf_sampler_predict_*,
+ * lcf_profile_loglike_kernel -- returns LCF_ERR_UNSUPPORTED for such an engine, naming this route, and launches
+ * nothing. */
 lcf_status lcf_engine_set_custom(lcf_engine* e, lcf_custom* c);
 /* The z handed to the state function (0 until set): the band tables carry 1 + z already, as for every model; the time
  * axis is the state function's own business. */
@@ -681,6 +683,33 @@ lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, 
                                   int64_t workspace_bytes, double* out /* [n_q][n_times] */,
                                   int64_t* n_valid /* [n_times] */, int64_t* n_dark /* [n_times] */,
                                   double* L_peak /* [n] or NULL */, int32_t* i_peak /* [n] or NULL */);
+
+/* ---- bands of a custom model: its light curves, T, R and L over ALL samples ---------------------------------------- */
+/* `grid` is an engine of LCF_MODEL_CUSTOM with a program attached (LCF_ERR_STATE without one) that holds the dense
+ * filters x distinct-times grid, every (time, filter) pair once (dummy y / dy, no sigma, no priors;
+ * LCF_ERR_INVALID_ARGUMENT for a pair held twice or missing).  Per (sample, time) the state function is called ONCE, and
+ * its T [kK] and R [1000 Rsun] give n_filters + 3 series: the band luminosity of every filter -- lcf_model_evaluate's,
+ * except that between the two forms of the band sum every sample chooses for itself (the main form where
+ * a_max / T < 170, else the safe one: the same bits wherever a whole wavefront of lcf_model_evaluate takes the main
+ * form) --, then T, R and L = 4 pi sigma_SB R^2 T^4 [W] of that pair.  A sample's
+ * values do not depend on the samples evaluated with it.
+ * Per (series, time), over the n host samples P[n][ld] (ld >= n_par; the first n_par columns are used): the percentiles
+ * q[n_q] (NaNs dropped; NumPy's nanpercentile, default method; NaN where no sample has a value; 1 <= n_q <= 512) and
+ * n_valid = the samples whose value is not NaN; per (filter, time) n_dark = the samples whose band luminosity is exactly
+ * +0 (T <= 0: not exploded yet); per time, when n_cold is given and T_floor >= 0, n_cold = the samples with
+ * T < T_floor (a NaN T is not cold, an exact 0 is; T_floor < 0 or NaN: nothing is counted and n_cold is zeroed).
+ * Series in the order of the engine's filters, then T, R, L; times in ascending order.
+ * Every value is kept as an 8-byte key while the percentiles of its time are searched: device memory beyond the
+ * samples is at most workspace_bytes, the times being worked through in tiles of as many times as fit,
+ * 8 n (n_filters + 3) bytes each besides the searches' own (LCF_ERR_INVALID_ARGUMENT, with the amount needed, if not even
+ * one time fits).  Results do not depend on the tiling and are bitwise reproducible.  An engine of another model:
+ * LCF_ERR_UNSUPPORTED, naming lcf_predict_quantiles / lcf_predict_luminosity. */
+lcf_status lcf_predict_custom(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                              double T_floor /* < 0 or NaN: no count */, int64_t workspace_bytes,
+                              double* out /* [n_q][n_filters + 3][n_times] */,
+                              int64_t* n_valid /* [n_filters + 3][n_times] */,
+                              int64_t* n_dark /* [n_filters][n_times]: model value exactly +0 */,
+                              int64_t* n_cold /* [n_times] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -1,16 +1,17 @@
 // Custom models (LCF_MODEL_CUSTOM): the user's T(t), R(t) in HIP device code, compiled at run time for the engine's GPU.
 //
 // The program handed to the run-time compiler (hiprtc, bound with dlopen like RCCL: the library loads without it) is
-//     lcf_device.h  |  #line 1 "user_model" + the user's source  |  lcf_custom_kernel.h
-// -- the two headers as they were when this library was built (the Makefile turns them into string literals,
-// lcf_custom_text.inc), so the compiler's log names the user's own line numbers, and the kernel is built from the very
-// DevProblem, band sums and interpolant lookup the precompiled kernels use.  -DLCF_DEVPROBLEM_BYTES carries this
+//     lcf_device.h  |  #line 1 "user_model" + the user's source  |  lcf_keys.h  |  lcf_custom_kernel.h
+// -- the three headers as they were when this library was built (the Makefile turns them into string literals,
+// lcf_custom_text.inc), so the compiler's log names the user's own line numbers, and the kernels are built from the very
+// DevProblem, band sums, interpolant lookup and key encoding the precompiled kernels use.  -DLCF_DEVPROBLEM_BYTES carries this
 // compiler's sizeof(DevProblem) over to a static_assert in the kernel header.  Code objects are cached per process
-// by (source, architecture); a module is loaded once per device.  The kernel is launched on the engine's stream with
-// hipModuleLaunchKernel, between the engine's own k_prepare (prior) and k_finalize.
+// by (source, architecture); a module is loaded once per device.  lcf_custom_points is launched on the engine's stream
+// with hipModuleLaunchKernel, between the engine's own k_prepare (prior) and k_finalize; lcf_custom_keys on the null
+// stream, in front of the passes of lcf_predict_custom over the keys it stores (lcf_predict.hip).
 //
-// The offline build compiles the kernel header too, behind a sample state function (ShockCooling2 restated): its
-// registers and scratch are in lcf_custom.resources.txt, and a change that breaks the header text breaks `make`.
+// The offline build compiles the kernel header too, behind a sample state function (ShockCooling2 restated): the
+// kernels' registers and scratch are in lcf_custom.resources.txt, and a change that breaks the header text breaks `make`.
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
@@ -22,6 +23,7 @@
 #include <mutex>
 
 #include "lcf_internal.h"
+#include "lcf_keys.h"
 
 // ---- the sample: ShockCooling2 (models.py:403-406) as a user would write it; exponents through consts ---------------
 // consts: A, a, alpha, epsilon_1, epsilon_2 (as for LCF_MODEL_SHOCK_COOLING2); p = T_1, L_1, t_tr, t_0
@@ -36,7 +38,7 @@ __device__ void lcf_user_state(double t_in, const double* p, const double* const
 
 namespace {
 
-#include "lcf_custom_text.inc"   // kDeviceText, kKernelText: lcf_device.h and lcf_custom_kernel.h as built
+#include "lcf_custom_text.inc"   // kDeviceText, kKeysText, kKernelText: the three headers as built
 
 // The Makefile's code-generation flags (CXXFLAGS there: a change of one is a change of the other).
 const char* const kCodegenFlags[] = {"-O3", "-std=c++17", "-ffp-contract=on", "-mllvm", "-disable-machine-licm"};
@@ -108,7 +110,7 @@ std::string rtc_error(hiprtcResult rc) {
 struct lcf_custom {
     std::string source, arch, log;
     std::vector<char> code;
-    struct Loaded { hipModule_t module; hipFunction_t points; };
+    struct Loaded { hipModule_t module; hipFunction_t points, keys; };
     std::map<int, Loaded> loaded;   // per device
 };
 
@@ -135,7 +137,8 @@ lcf_status resolve_arch(const char* arch, int device, std::string* out) {
 
 lcf_status compile(lcf_custom* c) {
     const std::string program = std::string("#line 1 \"lcf_device.h\"\n") + kDeviceText + "\n#line 1 \"user_model\"\n" +
-                                c->source + "\n#line 1 \"lcf_custom_kernel.h\"\n" + kKernelText;
+                                c->source + "\n#line 1 \"lcf_keys.h\"\n" + kKeysText +
+                                "\n#line 1 \"lcf_custom_kernel.h\"\n" + kKernelText;
     hiprtcProgram prog = nullptr;
     hiprtcResult rc = g_rtc.CreateProgram(&prog, program.c_str(), "lcf_custom_model.hip", 0, nullptr, nullptr);
     if (rc != HIPRTC_SUCCESS) return fail(LCF_ERR_HIP, "hiprtcCreateProgram: " + rtc_error(rc));
@@ -170,8 +173,8 @@ lcf_status compile(lcf_custom* c) {
 }
 
 const char kRoute[] = "a custom model (LCF_MODEL_CUSTOM) is evaluated by lcf_log_likelihood / lcf_log_posterior (and _dev), "
-                      "lcf_model_evaluate and lcf_temperature_radius, and sampled through lcf_tempered_* (TemperedSampler; one "
-                      "rung at beta = 1 is the ensemble sampler)";
+                      "lcf_model_evaluate and lcf_temperature_radius, sampled through lcf_tempered_* (TemperedSampler; one "
+                      "rung at beta = 1 is the ensemble sampler), and its bands over a chain are lcf_predict_custom";
 
 }  // namespace
 
@@ -198,6 +201,25 @@ lcf_status custom_launch(lcf_engine* e, int mode, int w_lo, int n, const double*
     void* args[] = {&pb, &mode, &w_lo, &n, &z, &dP, &lprior, &out0, &out1};
     LCF_HIP(hipModuleLaunchKernel(e->custom_points, (unsigned)((size_t)n * pb.n_parts), 1, 1, kBlock, 1, 1, 0, st,
                                   args, nullptr));
+    return LCF_OK;
+}
+
+// n_cus sizes the grid: the tile's times are spread over blockIdx.y while the samples alone leave the device short of
+// eight workgroups per CU.
+lcf_status custom_keys_launch(lcf_engine* e, const ChainView& in, int64_t discard, int64_t thin, int ep0, int n_ep,
+                              double T_floor, unsigned long long* keys, unsigned long long* n_cold) {
+    if (lcf_status s = custom_ready(e)) return s;
+    const KeptSteps k = kept_steps(in, discard, thin);
+    if (k.samples <= 0 || n_ep <= 0) return LCF_OK;
+    DevProblem pb = e->dp;
+    double z = e->custom_z;
+    const double* base = k.base;
+    long long n = k.samples, n_w = in.n_w, step_stride = k.step_stride;
+    int ld = in.ld;
+    const long long gx = (n + kBlock - 1) / kBlock;
+    const long long gy = std::min<long long>(n_ep, std::max<long long>(1, (long long)std::max(e->n_cus, 1) * 8 / gx));
+    void* args[] = {&pb, &z, &base, &n, &n_w, &step_stride, &ld, &ep0, &n_ep, &T_floor, &keys, &n_cold};
+    LCF_HIP(hipModuleLaunchKernel(e->custom_keys, (unsigned)gx, (unsigned)gy, 1, kBlock, 1, 1, 0, nullptr, args, nullptr));
     return LCF_OK;
 }
 
@@ -248,10 +270,12 @@ lcf_status lcf_engine_set_custom(lcf_engine* e, lcf_custom* c) {
         lcf_custom::Loaded l{};
         LCF_HIP(hipModuleLoadData(&l.module, c->code.data()));
         LCF_HIP(hipModuleGetFunction(&l.points, l.module, "lcf_custom_points"));
+        LCF_HIP(hipModuleGetFunction(&l.keys, l.module, "lcf_custom_keys"));
         it = c->loaded.emplace(e->device, l).first;
     }
     LCF_HIP(hipStreamSynchronize(e->stream));   // (launches in flight keep the program they were enqueued with)
     e->custom_points = it->second.points;
+    e->custom_keys = it->second.keys;
     return LCF_OK;
 }
 

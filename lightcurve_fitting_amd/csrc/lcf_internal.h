@@ -221,9 +221,9 @@ struct lcf_engine {
     bool have_ctab = false, have_itab = false;
     int n_cus = 256;             // compute units of the device (launch shapes depend on it)
     DevProblem* d_dp = nullptr;  // `dp` in device memory, for the kernels that read it through a pointer
-    // LCF_MODEL_CUSTOM: the likelihood / evaluation kernel of the attached program on this device (lcf_engine_set_custom;
-    // null: none yet) and the redshift its state function is handed
-    hipFunction_t custom_points = nullptr;
+    // LCF_MODEL_CUSTOM: the likelihood / evaluation kernel and the key kernel (lcf_predict_custom) of the attached program
+    // on this device (lcf_engine_set_custom; null: none yet) and the redshift its state function is handed
+    hipFunction_t custom_points = nullptr, custom_keys = nullptr;
     double custom_z = 0.;
     lcf_status sync_dp();        // after every change of `dp`
     // workspace for n walkers

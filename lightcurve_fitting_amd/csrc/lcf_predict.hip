@@ -36,6 +36,10 @@
 //   k_lq_peak     lane = sample: walks the tile's times in ascending order and keeps the sample's largest non-NaN L
 //                 and the first time it is attained (strict >).  Tiles follow each other on one stream, so the first
 //                 occurrence wins whatever the tiling.
+// The custom form (DESIGN.md "Bands of a custom model") stores keys as well: the program of a custom model evaluates
+// its state function once per (sample, time) and writes the keys of every filter's light curve, T, R and L
+// (lcf_custom_keys, lcf_custom_kernel.h), keys[tile time][series][n].  A (time, series) pair is a selection unit --
+// what a time is to k_kq_pass, which reads the keys as it reads the luminosity form's -- and a tile is whole times.
 // k_pq_pick and k_pq_finish serve all forms; the host driver (quantile_run) differs in the launches only.
 #include <hip/hip_runtime.h>
 
@@ -638,7 +642,8 @@ struct PqForm {
     int nf;                // series per time: the filters, T / R_bb / L_bol, or L
     size_t sample_bytes;   // device memory per sample ...
     size_t time_bytes;     // ... and per time of the whole grid, beyond what every form needs
-    size_t tile_bytes = 0; // ... and per time of a TILE, beyond the searches' (the luminosity form's stored keys)
+    size_t tile_bytes = 0; // ... and per time of a TILE, beyond the searches' (the stored keys)
+    int gran = 1;          // a tile is a whole multiple of this many "times" (the custom form's units of one time)
     size_t lds_head;       // dynamic LDS of a pass in front of the searches' words and the histograms
     bool coef = true;      // the samples' walker_coefficients are wanted ([kNCoef][n], part of sample_bytes)
     int tile = 0;          // times per tile, set by quantile_run in front of prepare
@@ -749,6 +754,47 @@ struct LuminosityForm : PqForm {
     }
 };
 
+// Every (sample, time) pair is evaluated once per tile by the custom model's own program, in front of the tile's first
+// pass.  What quantile_run and k_kq_pass call a time is here a unit: series u % (n_filters + 3) of time u / (n_filters + 3).
+struct CustomForm : PqForm {
+    lcf_engine* grid;
+    const ChainView& in;
+    const int64_t discard, thin;
+    const double T_floor;   // < 0: nothing is counted
+    unsigned long long *keys = nullptr, *n_cold = nullptr;
+    KqArgs kq{};
+    CustomForm(lcf_engine* g, const ChainView& s, int64_t discard_, int64_t thin_, double floor)
+        : grid(g), in(s), discard(discard_), thin(thin_), T_floor(floor) {
+        nf = 1;
+        gran = g->dp.n_filters + kThSeries;
+        sample_bytes = 0;
+        time_bytes = 2 * sizeof(unsigned long long);   // per unit: the dark counter; the cold one (used per time)
+        tile_bytes = (size_t)kept_steps(s, discard, thin).samples * sizeof(unsigned long long);   // a unit's keys
+        lds_head = 0;
+        coef = false;
+    }
+    lcf_status prepare(DevBuf& mem, PqArgs& a, double*) override {
+        const size_t n_units = (size_t)grid->dp.n_epochs * gran;
+        lcf_status st;
+        if ((st = mem.alloc(&keys, (size_t)tile * a.n)) || (st = mem.alloc(&kq.n_dark, n_units)) ||
+            (st = mem.alloc(&n_cold, (size_t)grid->dp.n_epochs)))
+            return st;
+        kq.keys = keys;
+        LCF_HIP(hipMemset(kq.n_dark, 0, n_units * sizeof(unsigned long long)));
+        LCF_HIP(hipMemset(n_cold, 0, (size_t)grid->dp.n_epochs * sizeof(unsigned long long)));
+        return LCF_OK;
+    }
+    lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
+        if (a.mode == 0)   // the tile's first pass: its keys (all on the null stream, in order)
+            if (lcf_status st = custom_keys_launch(grid, in, discard, thin, a.ep0 / gran, n_ep / gran, T_floor, keys, n_cold))
+                return st;
+        const unsigned chunks = (unsigned)((a.n + a.chunk - 1) / a.chunk);
+        hipLaunchKernelGGL(k_kq_pass, dim3((unsigned)n_ep, chunks), dim3(kPqThreads), lds, 0, a, kq);
+        LCF_HIP(hipGetLastError());
+        return LCF_OK;
+    }
+};
+
 // The searches of every point (time x series of `form`), the times in tiles that fit the workspace, over the walkers of
 // the kept steps of `chain` (device memory) as samples.  orig_host[n_ep_all][nf]: where the point's results go, -1 = no
 // such point.  out[n_q][n_points], n_valid[n_points] (host).
@@ -766,10 +812,11 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
                          (size_t)n_ep_all * (nf * 4 + form.time_bytes) + 4096;
     const size_t hist_ep = std::max((size_t)nf << bits0, (size_t)ns << bits1) * 4;
     const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8) + form.tile_bytes;
-    if (workspace_bytes < 0 || (size_t)workspace_bytes < fixed + per_ep)
+    const size_t gran = (size_t)form.gran;
+    if (workspace_bytes < 0 || (size_t)workspace_bytes < fixed + per_ep * gran)
         return fail(LCF_ERR_INVALID_ARGUMENT, "workspace_bytes too small: this call needs at least " +
-                                                  std::to_string(fixed + per_ep) + " bytes");
-    const int tile = (int)std::min<size_t>(((size_t)workspace_bytes - fixed) / per_ep, (size_t)n_ep_all);
+                                                  std::to_string(fixed + per_ep * gran) + " bytes");
+    const int tile = (int)(std::min<size_t>(((size_t)workspace_bytes - fixed) / per_ep, (size_t)n_ep_all) / gran * gran);
 
     double *d_coef, *d_q, *d_out;
     long long* d_nv;
@@ -973,6 +1020,45 @@ lcf_status luminosity_run(lcf_engine* grid, const ChainView& in, int64_t discard
     return LCF_OK;
 }
 
+// The custom form on the dense filters x distinct-times grid of the grid engine.  out[n_q][n_filters + 3][n_times],
+// n_valid[n_filters + 3][n_times], n_dark[n_filters][n_times], n_cold[n_times] or nullptr (host); times ascending.
+lcf_status custom_run(lcf_engine* grid, const ChainView& in, int64_t discard, int64_t thin, const double* q, int32_t n_q,
+                      double T_floor, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
+                      int64_t* n_cold) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points, NF = dp.n_filters, nt = dp.n_epochs, gran = NF + kThSeries;
+    std::vector<int> filt(N), epoch(N);
+    LCF_HIP(hipMemcpy(filt.data(), dp.pt_filt, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<char> seen((size_t)nt * NF, 0);
+    for (int i = 0; i < N; ++i) {
+        char& slot = seen[(size_t)epoch[i] * NF + filt[i]];
+        if (slot) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine holds a (time, filter) pair twice");
+        slot = 1;
+    }
+    if ((long long)N != (long long)nt * NF)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine must hold every filter at every distinct time");
+    if ((long long)nt * gran > INT32_MAX) return fail(LCF_ERR_INVALID_ARGUMENT, "too many (time, series) pairs");
+    const int n_units = nt * gran;
+    std::vector<int32_t> orig(n_units);   // unit (time, series) -> series * n_times + time
+    for (int ep = 0; ep < nt; ++ep)
+        for (int f = 0; f < gran; ++f) orig[(size_t)ep * gran + f] = f * nt + ep;
+    CustomForm form(grid, in, discard, thin, T_floor >= 0. ? T_floor : -1.);
+    DevBuf mem;
+    if (lcf_status st = quantile_run(grid->device, form, n_units, n_units, in, discard, thin, orig.data(), 0, q, n_q,
+                                     workspace_bytes, mem, out, n_valid))
+        return st;
+    std::vector<unsigned long long> cnt(n_units);
+    LCF_HIP(hipMemcpy(cnt.data(), form.kq.n_dark, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int ep = 0; ep < nt; ++ep)
+        for (int f = 0; f < NF; ++f) n_dark[(size_t)f * nt + ep] = (int64_t)cnt[(size_t)ep * gran + f];
+    if (n_cold) {
+        LCF_HIP(hipMemcpy(cnt.data(), form.n_cold, (size_t)nt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (int ep = 0; ep < nt; ++ep) n_cold[ep] = T_floor >= 0. ? (int64_t)cnt[ep] : 0;
+    }
+    return LCF_OK;
+}
+
 // n host samples P[n][ld] as one step of n walkers, on the grid engine's device for as long as `mem` lives.
 lcf_status uploaded_samples(const lcf_engine* grid, const double* P, int64_t n, int32_t ld, DevBuf& mem, ChainView* in) {
     if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
@@ -1050,6 +1136,23 @@ lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, 
     ChainView in;
     if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
     return luminosity_run(grid, in, 0, 1, q, n_q, workspace_bytes, out, n_valid, n_dark, L_peak, i_peak);
+}
+
+lcf_status lcf_predict_custom(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,
+                              double T_floor, int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark,
+                              int64_t* n_cold) {
+    if (!grid || !q || !out || !n_valid || !n_dark) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (grid->dp.model != LCF_MODEL_CUSTOM)
+        return fail(LCF_ERR_UNSUPPORTED, "lcf_predict_custom takes an engine of LCF_MODEL_CUSTOM; the bands of a built-in "
+                                         "photometric model are lcf_predict_quantiles and lcf_predict_thermal, those of a "
+                                         "central-engine model lcf_predict_luminosity");
+    if (lcf_status st = custom_ready(grid)) return st;
+    if (lcf_status st = check_percentiles(q, n_q, kPqMaxSearch, "need between 1 and 512 percentiles")) return st;
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no points");
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return custom_run(grid, in, 0, 1, q, n_q, T_floor, workspace_bytes, out, n_valid, n_dark, n_cold);
 }
 
 }  // extern "C"

@@ -154,6 +154,8 @@ SIGNATURES = [
                                               C.POINTER(C.c_int64)]),
     ('lcf_predict_luminosity', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_int64, _dp,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _ip]),
+    ('lcf_predict_custom', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, C.c_int64, _dp,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ('lcf_chain_range', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]),
     ('lcf_chain_hist', C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.c_int32,
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -326,6 +328,7 @@ class Engine:
         _check(lib.lcf_engine_create(C.byref(pr), int(device), C.byref(self._h)))
         self.ndim = n_dim
         self.npoints = pr.n_points
+        self.nfilters = pr.n_filters
         #: the prior descriptors the engine was created with (None: none)
         self.priors = None if priors is None else [tuple(p) for p in priors]
         self.device = int(device)
@@ -1019,6 +1022,49 @@ def predict_luminosity(grid_engine, samples, percentiles, workspace_bytes=None, 
                                       _i64p(n_valid), _i64p(n_dark), _ptr(L_peak) if peak else None,
                                       _ptr(i_peak, _ip) if peak else None))
     return out, n_valid, n_dark, L_peak, i_peak
+
+
+def custom_workspace(n_samples, n_times, n_filters, n_q, tile=1):
+    """Device memory [bytes] beyond the samples that :func:`predict_custom` needs to work through ``tile`` times at
+    once -- the least ``workspace_bytes`` for that tile ("Bands of a custom model").  With
+    ``S = n_filters + 3`` series per time (the filters, then T, R, L)::
+
+        fixed    = 8 (n_q + 1) S n_times + 20 S n_times + 4096
+        per time = S (8 n_samples + n_q (56 + 8 * 2048) + 4 max(2048, n_q 2^b))
+
+    with ``b`` the largest of 4 ... 11 for which ``n_q 2^b`` four-byte counters fit 48 KiB of LDS."""
+    b = 4
+    while b < 11 and (n_q << (b + 1)) * 4 <= 48 * 1024:
+        b += 1
+    series = n_filters + THERMAL_SERIES
+    fixed = 8 * (n_q + 1) * series * n_times + 20 * series * n_times + 4096
+    return fixed + tile * series * (8 * n_samples + n_q * (56 + 8 * 2048) + 4 * max(2048, n_q << b))
+
+
+def predict_custom(grid_engine, samples, percentiles, T_floor=None, workspace_bytes=None):
+    """``lcf_predict_custom``: percentiles over all samples of a custom model's light curves and of the T, R and L
+    behind them, on the dense filters x distinct-times grid of ``grid_engine`` (an evaluation engine of a
+    ``CustomModel``), with the valid and dark counts and -- with ``T_floor`` -- the samples colder than it per time.
+    ``samples``: a host array (n, ld); at most ``PREDICT_MAX_SEARCHES`` percentiles.  The state function runs once per
+    (sample, time) and every value is kept as a key: see :func:`custom_workspace` for the memory.  Returns
+    ``(quantiles[n_q, n_f + 3, n_t], n_valid[n_f + 3, n_t], n_dark[n_f, n_t], n_cold[n_t] or None)``, filters in the
+    engine's order, then T, R, L; times ascending."""
+    lib = load_library()
+    q = _f64(percentiles)
+    P = _f64(samples)
+    if P.ndim != 2:
+        raise ValueError('samples must have shape (n, n_columns)')
+    n_f = grid_engine.nfilters
+    n_t = grid_engine.npoints // max(n_f, 1)
+    out = np.empty((len(q), n_f + THERMAL_SERIES, n_t))
+    n_valid = np.empty((n_f + THERMAL_SERIES, n_t), dtype=np.int64)
+    n_dark = np.empty((n_f, n_t), dtype=np.int64)
+    n_cold = None if T_floor is None else np.empty(n_t, dtype=np.int64)
+    ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    _check(lib.lcf_predict_custom(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], _ptr(q), len(q),
+                                  -1. if T_floor is None else float(T_floor), ws, _ptr(out), _i64p(n_valid),
+                                  _i64p(n_dark), None if n_cold is None else _i64p(n_cold)))
+    return out, n_valid, n_dark, n_cold
 
 
 #: limits of the corner entry points (include/lcf.h)

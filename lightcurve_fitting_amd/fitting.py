@@ -9,6 +9,8 @@ every sample of the chain instead of 100 random draws, computed on the device wi
 grid point).  :func:`thermal_predictive` does the same for what those light curves are made from -- the blackbody
 temperature, radius and bolometric luminosity -- and counts, time by time, the samples that are colder than the models
 allow or outside their validity window: the check the reference's usage guide asks for after every shock-cooling fit.
+:func:`luminosity_predictive` is the first of the two for the central-engine models, :func:`custom_predictive` both of
+them for a model the user wrote (``CustomModel``).
 The numbers behind ``lightcurve_corner`` (fitting.py:241-253) are :func:`posterior_corner`: the marginal histogram of
 every parameter, the joint histogram of every pair and the counts of the contour levels, with the reference's ``t_0``
 offset, counted on the device over every sample.  The numbers behind the chain plots of ``lightcurve_mcmc(show=True)``
@@ -306,8 +308,8 @@ def _refuse_custom(model, what):
     if isinstance(model, CustomModel):
         from .engine import LcfError
         raise LcfError(5, f'{what} is compiled per built-in model and does not take a CustomModel; its fit (the '
-                          'tempered route, TemperedSampler) gives the chain, and model(t, filters, *p) evaluates '
-                          'any of its rows')
+                          'tempered route, TemperedSampler) gives the chain, custom_predictive the bands of its light '
+                          'curves, T, R and L over that chain, and model(t, filters, *p) evaluates any of its rows')
     if isinstance(model, BaseCentralEngine):
         from .engine import LcfError
         raise LcfError(5, f'{what} is compiled per photometric model and does not take a central-engine model (Arnett, '
@@ -546,6 +548,95 @@ def luminosity_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t
         res.n_peak_first = int(np.sum(i_peak == 0))
         res.n_peak_last = int(np.sum(i_peak == len(distinct) - 1))
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# bands of a custom model (its light curves and the T, R, L behind them: does the fit go through the data, and is the
+# photosphere the user wrote physical over the whole chain)
+# ---------------------------------------------------------------------------------------------------------------
+class CustomPredictive:
+    """Result of :func:`custom_predictive`: ``t`` (nt,), ``filters`` (nf Filter objects), ``percentiles`` (nq,),
+    ``n_samples``; ``quantiles`` (nq, nf, nt) of the model light curves, ``n_valid`` (nf, nt) -- the samples whose
+    value is not NaN -- and ``n_dark`` (nf, nt) -- those whose value is exactly ``+0.0``: no photosphere yet;
+    ``temperature`` [kK], ``radius`` [1000 Rsun] and ``luminosity`` [W], each (nq, nt), with ``n_valid_thermal`` (3, nt)
+    in that order; with a ``T_floor``, ``n_cold`` (nt,) -- the samples with a temperature below it -- else ``None``."""
+    __slots__ = ('t', 'filters', 'percentiles', 'n_samples', 'quantiles', 'n_valid', 'n_dark', 'temperature', 'radius',
+                 'luminosity', 'n_valid_thermal', 'n_cold')
+
+    def __init__(self, t, filters, percentiles, n_samples, quantiles, n_valid, n_dark, temperature, radius, luminosity,
+                 n_valid_thermal, n_cold=None):
+        self.t, self.filters, self.percentiles, self.n_samples = t, filters, percentiles, n_samples
+        self.quantiles, self.n_valid, self.n_dark = quantiles, n_valid, n_dark
+        self.temperature, self.radius, self.luminosity = temperature, radius, luminosity
+        self.n_valid_thermal, self.n_cold = n_valid_thermal, n_cold
+
+    @property
+    def frac_cold(self):
+        """Fraction of the samples with a temperature that are below the floor, per time (NaN where none has one);
+        ``None`` without a ``T_floor``."""
+        if self.n_cold is None:
+            return None
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self.n_cold / self.n_valid_thermal[0]
+
+    def __repr__(self):
+        return (f'<CustomPredictive: {len(self.percentiles)} percentiles x ({len(self.filters)} filters + T, R, L) x '
+                f'{len(self.t)} times over {self.n_samples} samples>')
+
+
+def custom_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=None, tmin=None, tmax=None, num=1000,
+                      xscale='linear', filters_to_model=None, discard=0, thin=1, use_sigma=False, T_floor=None,
+                      workspace_bytes=None):
+    """Percentile bands of the light curves of a :class:`~lightcurve_fitting_amd.models.CustomModel` over ALL samples
+    of a chain, on the dense ``filters x times`` grid of :func:`predictive_grid`, and of the temperature [kK], radius
+    [1000 Rsun] and bolometric luminosity [W] its state function returned for them: :func:`posterior_predictive` and
+    :func:`thermal_predictive` for the models the user writes.
+
+    ``samples``: a host array ``(n_samples, n_columns)`` (``discard`` / ``thin`` do not apply), or any object with
+    ``get_chain`` -- the :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` that ``lightcurve_mcmc`` returned --:
+    rows ``discard::thin`` of its cold rung, uploaded.  ``use_sigma``: the last column is the scatter and does not enter
+    the model.  ``T_floor`` [kK]: count per time the samples colder than it (``n_cold``, ``frac_cold``; a temperature of
+    exactly 0 -- no photosphere yet -- counts, a NaN does not); ``None``: no count.
+
+    Every band is ``np.nanpercentile(values, percentiles, axis=samples)`` with NumPy's default method, NaN where no
+    sample has a value: of ``model(t, filters, *p)``, of ``model.temperature_radius(t, *p)`` and of
+    ``bolometric.stefan_boltzmann(T, R)`` of every (sample, time) pair.  The state function is evaluated once per pair
+    on the device and its ``nf + 3`` values are kept there as 8-byte keys while the percentiles of their time are
+    searched; the times are worked through in tiles that keep device memory beyond the samples below
+    ``workspace_bytes`` (default 1 GiB; ``engine.custom_workspace``).  A sample's values do not depend on the samples
+    evaluated with it; results are bitwise reproducible and do not depend on ``workspace_bytes``.  Returns a
+    :class:`CustomPredictive`."""
+    from . import engine as _eng
+    if not isinstance(model, CustomModel):
+        raise _eng.LcfError(5, 'custom_predictive takes a CustomModel; the bands of a built-in photometric model are '
+                               'posterior_predictive and thermal_predictive, those of a central-engine model '
+                               'luminosity_predictive')
+    q = _percentile_array(percentiles)
+    if not isinstance(samples, np.ndarray) and hasattr(samples, 'get_chain'):
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        samples = samples.get_chain(discard=discard, thin=thin, flat=True)
+        if len(samples) == 0:
+            raise ValueError(f'discard={discard} leaves no steps of the stored chain')
+        discard, thin = 0, 1
+    _, P, n_samples = _model_samples(model, samples, discard, thin, use_sigma)
+    times, filters = predictive_grid(lc, t, tmin, tmax, num, xscale, filters_to_model)
+    distinct, where = np.unique(times, return_inverse=True)     # the engine holds every (time, filter) pair once
+    held = list(dict.fromkeys(filters))
+    which = [held.index(f) for f in filters]
+
+    grid_engine, _ = Model._eval_engine(model, distinct, held, False)   # the dense grid, filter-major
+    nf = len(held)
+    per_call = _eng.PREDICT_MAX_SEARCHES
+    parts = [_eng.predict_custom(grid_engine, P, q[k:k + per_call], T_floor if k == 0 else None, workspace_bytes)
+             for k in range(0, len(q), per_call)]
+    bands = np.concatenate([part[0] for part in parts])[:, :, where]
+    _, n_valid, n_dark, n_cold = parts[0]
+    n_valid = n_valid[:, where]
+    return CustomPredictive(times, filters, q, n_samples, bands[:, :nf][:, which], n_valid[:nf][which],
+                            n_dark[:, where][which], bands[:, nf], bands[:, nf + 1], bands[:, nf + 2], n_valid[nf:],
+                            None if n_cold is None else n_cold[where])
 
 
 # ---------------------------------------------------------------------------------------------------------------

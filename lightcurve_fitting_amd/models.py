@@ -560,7 +560,8 @@ class CustomModel(Model):
     ``log_likelihood``, ``evaluate`` / ``__call__``, ``temperature_radius``, ``make_log_posterior`` and
     ``lightcurve_mcmc`` work as for every model; the fit runs through :class:`~lightcurve_fitting_amd.sampler.
     TemperedSampler` (one rung at ``beta = 1`` unless a ladder is asked for), since the resident sampler's kernels,
-    ``posterior_predictive`` and ``thermal_predictive`` are compiled per built-in model and raise ``LcfError`` here.
+    ``posterior_predictive`` and ``thermal_predictive`` are compiled per built-in model and raise ``LcfError`` here;
+    :func:`~lightcurve_fitting_amd.fitting.custom_predictive` gives the bands of its light curves, T, R and L over a chain.
     The source is compiled on first use (:meth:`compile`); an error in it raises ``LcfError`` with the compiler's log,
     which names the source's own lines as ``user_model:<line>``."""
     model_id = _eng.MODEL_CUSTOM
