@@ -711,6 +711,33 @@ lcf_status lcf_predict_custom(lcf_engine* grid, const double* P, int64_t n, int3
                               int64_t* n_dark /* [n_filters][n_times]: model value exactly +0 */,
                               int64_t* n_cold /* [n_times] or NULL */);
 
+/* ---- upper limits: non-detections as censored terms of the likelihood ---------------------------------------------- */
+/* By default a non-detection is what the reference makes of it: a row with y = 0 and dy = limit / nondetSigmas in the
+ * Gaussian sum.  With limits attached, the engine `e` holds the DETECTIONS only and its log-likelihood gains, per limit
+ * j, the probability that the flux was below the limit:
+ *   ln L(p) = [the Gaussian log-likelihood of e's points] + sum_j ln Phi(z_j),   z_j = (L_lim[j] - m_j(p)) / sigma_j(p),
+ * m_j(p) = the model at the limit's time and filter, bit for bit what lcf_model_evaluate(at, ...) returns;
+ * sigma_j = dy[j] without use_sigma, else sqrt(dy[j]^2 + (s u_j)^2) with s the row's last column and u_j = dy[j]
+ * (LCF_SIGMA_RELATIVE) or e's own median dy (LCF_SIGMA_ABSOLUTE); z is one subtraction and one division.
+ * ln Phi(z) = log(erfcx(-z / sqrt 2) / 2) - z^2 / 2 for z <= 0 and log1p(-erfc(z / sqrt 2) / 2) for z > 0: accurate
+ * in both tails (ln Phi(+inf) = 0, ln Phi(-inf) = -inf, -inf once z^2 overflows, NaN for a NaN model value).  The terms
+ * are added in a fixed order: a row's value does not depend on the rows evaluated with it.  The sum belongs to the
+ * likelihood: lcf_log_likelihood, lcf_log_posterior, their _dev forms and, through lcf_log_likelihood_dev,
+ * lcf_tempered_* include it (a rung multiplies it by its beta); a row the prior excludes stays -inf.
+ * Attach upper limits to a photometric engine: `at` is an engine of the same model, constants, n_par, use_sigma and
+ * device on the limits' (t, filter) in the caller's order (its y, dy are not read); L_lim[n_lim], dy[n_lim] finite,
+ * dy > 0, n_lim <= 2^20.  at = NULL or n_lim = 0 detaches.  The caller keeps `at` alive as long as `e` uses it, and
+ * hands it to one engine only (its workspace holds the rows' coefficients between the launches).
+ * What computes the likelihood inside kernels of its own would drop the limits silently and therefore returns
+ * LCF_ERR_UNSUPPORTED for an engine with limits attached, naming the lcf_tempered_* route: lcf_sampler_create (and with
+ * it every lcf_sampler_* and population run) and lcf_profile_loglike_kernel; so does attaching limits to an engine that
+ * a live lcf_sampler uses, and to a central-engine model (a bolometric table has no non-detections).  Engines that do
+ * not match, non-finite values and dy <= 0: LCF_ERR_INVALID_ARGUMENT. */
+lcf_status lcf_engine_set_limits(lcf_engine* e, lcf_engine* at, int64_t n_lim, const double* L_lim, const double* dy);
+/* out[n][n_lim]: ln Phi term of every (row, limit); rows as lcf_log_likelihood takes them.  LCF_ERR_STATE for an engine
+ * without limits. */
+lcf_status lcf_limit_terms(lcf_engine* e, int64_t n, const double* P, double* out);
+
 #ifdef __cplusplus
 }
 #endif

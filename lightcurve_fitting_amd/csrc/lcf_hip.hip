@@ -3012,6 +3012,27 @@ lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout,
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, e->wpart,
                        e->wlprior, dout);
     LCF_HIP(hipGetLastError());
+    if (e->lim_at) return limits_add(e, n, dP, dout, st);   // (upper limits: the censored terms, lcf_limits.hip)
+    return LCF_OK;
+}
+
+lcf_status limits_model(lcf_engine* e, int64_t n, int64_t lo, int64_t m, const double* dP, bool prepare, hipStream_t st) {
+    lcf_engine* at = e->lim_at;
+    if (at->dp.model == LCF_MODEL_CUSTOM)
+        if (lcf_status s = custom_ready(at)) return s;
+    // The rows' coefficients are a function of the model, its constants and the row (walker_coefficients), all of which
+    // the two engines share: the limit engine's launches read the ones this engine's k_prepare wrote.
+    if (prepare) {
+        const int bs = 128;
+        hipLaunchKernelGGL(k_prepare, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, dP, e->wcoef,
+                           e->wlprior, 0);
+    }
+    if (at->dp.model == LCF_MODEL_CUSTOM) {
+        if (lcf_status s = custom_launch(at, 1, (int)lo, (int)m, dP, e->wlprior, e->lim_m, nullptr, st)) return s;
+    } else {
+        launch_points<1>(at, (int)lo, (int)m, dP, e->wcoef, e->wlprior, at->wtherm, e->lim_m, nullptr, st);
+    }
+    LCF_HIP(hipGetLastError());
     return LCF_OK;
 }
 }  // namespace lcf
@@ -3667,6 +3688,7 @@ extern "C" lcf_status lcf_profile_loglike_kernel(lcf_engine* e, int64_t n, const
     if (!e || n <= 0 || !P || reps <= 0 || !avg_ms) return fail(LCF_ERR_INVALID_ARGUMENT, "bad argument");
     if (lcf_status st = custom_refuse(e, "lcf_profile_loglike_kernel")) return st;
     if (lcf_status st = central_refuse(e, "lcf_profile_loglike_kernel")) return st;
+    if (lcf_status st = limits_refuse(e, "lcf_profile_loglike_kernel")) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (lcf_status st = e->reserve(n)) return st;
     LCF_HIP(hipMemcpyAsync(e->wP, P, n * e->dp.n_dim * sizeof(double), hipMemcpyHostToDevice, e->stream));

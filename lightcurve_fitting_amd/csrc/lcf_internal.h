@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -233,12 +234,22 @@ struct lcf_engine {
     // scratch for evaluate-type calls
     size_t big_bytes = 0;
     double* wbig = nullptr;
+    // upper limits (lcf_engine_set_limits, lcf_limits.hip): the caller's engine on the limits' points, L_lim and dy of the
+    // n_lim limits on the device, and the model values of lim_rows rows at a time, [lim_rows][n_lim] (reserve)
+    lcf_engine* lim_at = nullptr;
+    int64_t n_lim = 0, lim_rows = 0;
+    double *lim_L = nullptr, *lim_dy = nullptr, *lim_m = nullptr;
+    // live lcf_samplers on this engine (their kernels compute the likelihood themselves: limits are refused while there
+    // are any).  Shared with them: a sampler may be destroyed after its engine.
+    std::shared_ptr<int> samplers = std::make_shared<int>(0);
 
     ~lcf_engine() {
         hipSetDevice(device);
         for (void* p : owned) hipFree(p);
         free_ws();
         if (wbig) hipFree(wbig);
+        for (double* p : {lim_L, lim_dy, lim_m})
+            if (p) hipFree(p);
         if (stream) hipStreamDestroy(stream);
     }
     void free_ws() {
@@ -250,7 +261,10 @@ struct lcf_engine {
         wtherm = nullptr;
         cap = 0;
     }
+    lcf_status reserve_limits(int64_t n);   // lcf_limits.hip: the limit engine's workspace and lim_m for n rows
     lcf_status reserve(int64_t n) {
+        if (lim_at)
+            if (lcf_status st = reserve_limits(n)) return st;
         if (n <= cap) return LCF_OK;
         LCF_HIP(hipStreamSynchronize(stream));
         free_ws();
@@ -296,11 +310,21 @@ lcf_status central_engine_create(const lcf_problem* pr, int32_t device, lcf_engi
 lcf_status central_refuse(const lcf_engine* e, const char* what);
 lcf_status central_launch(lcf_engine* e, int mode, int w_lo, int n, const double* dP, const double* lprior, double* out0,
                           hipStream_t st);
+// lcf_limits.hip: engines with upper limits attached (lcf_engine_set_limits).  limits_refuse: as custom_refuse, for what
+// computes the likelihood in kernels of its own; limits_add: the censored terms of rows [0, n) added to dout, enqueued
+// on st behind the launches that wrote dout (rows whose e->wlprior is -inf are left alone).
+lcf_status limits_refuse(const lcf_engine* e, const char* what);
+lcf_status limits_add(lcf_engine* e, int64_t n, const double* dP, double* dout, hipStream_t st);
+// lcf_hip.hip: the model at the limits' points -- rows [lo, lo + m) of dP through e->lim_at, the launches of
+// lcf_model_evaluate, enqueued on st -> e->lim_m[m][n_lim]; `prepare`: the coefficients of all n rows first (k_prepare into
+// e's workspace, no prior), for callers that have not just evaluated the rows' likelihood.
+lcf_status limits_model(lcf_engine* e, int64_t n, int64_t lo, int64_t m, const double* dP, bool prepare, hipStream_t st);
 }  // namespace lcf
 
 struct lcf_sampler {
     lcf_engine* e = nullptr;
     int device = 0;           // e->device, kept for the destructor
+    std::shared_ptr<int> engine_samplers;   // e->samplers, counted down when this sampler goes
     DevSampler ds{};
     std::vector<void*> owned;
     double *coef = nullptr, *lprior = nullptr;
@@ -400,6 +424,7 @@ struct lcf_sampler {
     ~lcf_sampler() {
         // (the device is remembered here: a garbage collector may destroy the engine first, and nothing below needs it)
         hipSetDevice(device);
+        if (engine_samplers) --*engine_samplers;
         for (void* p : owned) hipFree(p);
         if (ds.chain) hipFree(ds.chain);
         if (ds.chain_lp) hipFree(ds.chain_lp);

@@ -194,6 +194,8 @@ SIGNATURES = [
     ('lcf_custom_destroy', None, [C.c_void_p]),
     ('lcf_engine_set_custom', C.c_int, [C.c_void_p, C.c_void_p]),
     ('lcf_engine_set_custom_redshift', C.c_int, [C.c_void_p, C.c_double]),
+    ('lcf_engine_set_limits', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _dp, _dp]),
+    ('lcf_limit_terms', C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
 ]
 
 
@@ -355,6 +357,28 @@ class Engine:
         _check(self._lib.lcf_engine_set_custom(self._h, program.handle))
         _check(self._lib.lcf_engine_set_custom_redshift(self._h, float(redshift)))
         self.program = program   # (kept alive with the engine)
+
+    def set_limits(self, at, L_lim, dy):
+        """Attach upper limits (``lcf_engine_set_limits``): ``at`` is an engine of the same model, constants and sigma
+        mode on the limits' (t, filter); ``L_lim`` and ``dy`` have one entry per limit.  ``at=None`` detaches.  The
+        log-likelihood then carries ``sum_j ln Phi((L_lim[j] - model_j) / sigma_j)``; the resident samplers refuse such
+        an engine (``LcfError``, status 5), :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` takes it."""
+        if at is None:
+            _check(self._lib.lcf_engine_set_limits(self._h, None, 0, None, None))
+            self.limits, self.nlimits = None, 0
+            return
+        L_lim, dy = _f64(L_lim), _f64(dy)
+        if L_lim.ndim != 1 or L_lim.shape != dy.shape:
+            raise ValueError('L_lim and dy must be 1-D and of equal length')
+        _check(self._lib.lcf_engine_set_limits(self._h, at.handle, len(L_lim), _ptr(L_lim), _ptr(dy)))
+        self.limits, self.nlimits = at, len(L_lim)   # (the limits' engine is kept alive with this one)
+
+    def limit_terms(self, P):
+        """``(n, n_limits)``: the ``ln Phi`` term of every (row, limit) of an engine with limits attached."""
+        P = self._block(P)
+        out = np.empty((len(P), getattr(self, 'nlimits', 0)))
+        _check(self._lib.lcf_limit_terms(self._h, len(P), _ptr(P), _ptr(out)))
+        return out
 
     def _block(self, P):
         P = _f64(P)

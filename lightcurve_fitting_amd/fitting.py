@@ -30,12 +30,13 @@ PRIOR_WARNING = 'The p_max/p_min keywords are deprecated. Use the priors keyword
 MODEL_KWARGS_WARNING = 'The model_kwargs keyword is deprecated. These are now included in the model intialization.'
 
 
-def make_log_posterior(lc, model, priors=None, use_sigma=False, sigma_type='relative'):
+def make_log_posterior(lc, model, priors=None, use_sigma=False, sigma_type='relative', nondet='gaussian'):
     """The ``log_posterior`` callable that the reference builds inside ``lightcurve_mcmc`` (fitting.py:121-128), backed
     by the device engine.  ``f(p)`` with ``p`` of shape ``(ndim,)`` returns a float, exactly like the reference's
     closure; with a C-contiguous ``(n, ndim)`` block it returns ``(n,)`` -- the form
-    ``emcee.EnsembleSampler(nwalkers, ndim, f, vectorize=True)`` calls once per half-step."""
-    engine = model.engine_for(lc, use_sigma=use_sigma, sigma_type=sigma_type, priors=priors)
+    ``emcee.EnsembleSampler(nwalkers, ndim, f, vectorize=True)`` calls once per half-step.  ``nondet='censored'``
+    (extension): non-detections enter as upper limits, see ``Model.log_likelihood``."""
+    engine = model.engine_for(lc, use_sigma=use_sigma, sigma_type=sigma_type, priors=priors, nondet=nondet)
 
     def log_posterior(p):
         p = np.asarray(p, dtype=np.float64)
@@ -89,7 +90,7 @@ def _check_start_box(names, priors, p_lo, p_up):
 def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p_up=None,
                     nwalkers=100, nsteps=1000, nsteps_burnin=1000, model_kwargs=None,
                     show=False, save_plot_as='', save_sampler_as='', use_sigma=False, sigma_type='relative',
-                    seed=None, ntemps=None, betas=None, Tmax=None, adapt=False, moves=None):
+                    seed=None, ntemps=None, betas=None, Tmax=None, adapt=False, moves=None, nondet='gaussian'):
     """Fit an analytical model to observed photometry with an affine-invariant ensemble sampler on the GPU.
 
     Arguments as in the reference (fitting.py:16-58).  ``seed`` (extension) keys the counter-based RNG; by default
@@ -117,6 +118,14 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     (:class:`~lightcurve_fitting_amd.models.Arnett`, :class:`~lightcurve_fitting_amd.models.Magnetar`), whose ``lc`` is a
     bolometric light curve (``MJD``, ``L_bol``, ``dL_bol``; no magnitudes are converted).
 
+    ``nondet`` (extension; ``'gaussian'``: the call is what it always was): with ``'censored'`` the rows of ``lc`` whose
+    ``nondet`` is true are upper limits -- each adds ``ln Phi((limit - model) / sigma)`` to the likelihood instead of
+    entering the Gaussian sum as a measurement of zero (``Model.log_likelihood`` has the definition).  The resident
+    sampler's kernels compute the likelihood themselves and do not know the term, so a light curve that has such rows
+    is fitted by :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` as well -- on one rung at ``beta = 1`` unless
+    a ladder or ``moves`` is asked for -- and a ladder tempers the term with the rest of the likelihood.  Without a
+    true ``nondet`` row the fit is the default one.
+
     Returns the sampler (``.chain`` (nwalkers, nsteps, ndim), ``.flatchain``, ``.run_mcmc``, ``.reset``).
     """
     import time
@@ -142,14 +151,14 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
 
     # log_posterior of fitting.py:121-128 lives on the device: priors are baked into the engine
     marks.append(('checks', time.perf_counter()))
-    engine = model.engine_for(lc, use_sigma=use_sigma, sigma_type=sigma_type, priors=priors)
+    engine = model.engine_for(lc, use_sigma=use_sigma, sigma_type=sigma_type, priors=priors, nondet=nondet)
     marks.append(('engine', time.perf_counter()))
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
-    if (isinstance(model, (CustomModel, BaseCentralEngine)) or moves is not None) and ntemps is None and betas is None \
-            and Tmax is None:
-        # the resident sampler's kernels are compiled per photometric model and make the stretch move: one rung is the
-        # same ensemble
+    if (isinstance(model, (CustomModel, BaseCentralEngine)) or moves is not None or getattr(engine, 'nlimits', 0)) \
+            and ntemps is None and betas is None and Tmax is None:
+        # the resident sampler's kernels are compiled per photometric model, make the stretch move and know no upper
+        # limits: one rung is the same ensemble
         betas = [1.]
     if ntemps is not None or betas is not None or Tmax is not None:
         from .sampler import TemperedSampler

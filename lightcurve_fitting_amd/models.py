@@ -15,7 +15,8 @@ constants, computes the SiFTO spline coefficients once, and caches one engine pe
 There is no NumPy fallback for the model mathematics: without the native library and a GPU these calls raise.
 
 Extension over the reference: ``p`` may be a C-contiguous ``(n, ndim)`` block (what emcee passes with
-``vectorize=True``); the result then has shape ``(n,)``.
+``vectorize=True``); the result then has shape ``(n,)``.  ``nondet='censored'`` (``log_likelihood``, ``engine_for``;
+``limit_terms``) makes the rows whose ``nondet`` is true upper limits instead of measurements of zero.
 """
 import numpy as np
 
@@ -125,6 +126,47 @@ class _BoundEngine:
         return filters.shape == self.filters.shape and bool(np.all(filters == self.filters))
 
 
+NONDET_MODES = ('gaussian', 'censored')
+
+
+def _check_nondet_mode(nondet):
+    if nondet not in NONDET_MODES:
+        raise ValueError(f"nondet must be 'gaussian' (a non-detection is a measurement of zero, as in the reference) or "
+                         f"'censored' (an upper limit: the probability that the flux was below it), not {nondet!r}")
+
+
+def _nondet_mask(lc):
+    """The ``nondet`` column of ``lc`` as a boolean array, or None when ``lc`` has none or no row of it is true."""
+    names = getattr(lc, 'colnames', None)
+    if not ('nondet' in names if names is not None else 'nondet' in lc):
+        return None
+    mask = np.asarray(_column(lc, 'nondet')).astype(bool)
+    return mask if mask.any() else None
+
+
+class LimitSplit:
+    """The rows of a light curve split by its ``nondet`` column (``nondet='censored'``): ``det`` / ``lim`` are the
+    boolean masks of the detections and the upper limits, ``dy`` the limits' ``d<quantity>`` (which ``calcLum`` /
+    ``calcFlux`` set to ``limit / nondetSigmas``), ``L_lim = nondetSigmas * dy`` the limits themselves, and
+    ``sigma_unit_abs`` the median ``d<quantity>`` of the detections (the unit of an ``'absolute'`` fitted sigma)."""
+
+    def __init__(self, lc, quantity, mask=None):
+        mask = _nondet_mask(lc) if mask is None else mask
+        dy = np.asarray(_column(lc, 'd' + quantity), dtype=np.float64)
+        if mask is None:
+            mask = np.zeros(len(dy), dtype=bool)
+        if mask.shape != dy.shape:
+            raise ValueError('the nondet column must have one entry per row')
+        if mask.all():
+            raise ValueError("nondet='censored' needs at least one detection: every row of the light curve is a "
+                             "non-detection")
+        self.lim, self.det = mask, ~mask
+        self.nondet_sigmas = float(getattr(lc, 'nondetSigmas', 3.))
+        self.dy = dy[mask]
+        self.L_lim = self.nondet_sigmas * self.dy
+        self.sigma_unit_abs = float(np.median(dy[self.det]))
+
+
 def _index_filters(filts):
     """Distinct filters (first-seen order) and the per-point index into them."""
     uniq = list(dict.fromkeys(filts))
@@ -218,41 +260,77 @@ class Model:
         eng.timings = {'tables_s': t1 - t0, 'create_s': time.perf_counter() - t1, 'levels': sorted(set(tabs.levels_from))}
         return eng
 
-    def engine_for(self, lc, use_sigma=False, sigma_type='relative', priors=None):
+    def engine_for(self, lc, use_sigma=False, sigma_type='relative', priors=None, nondet='gaussian'):
         """Engine bound to the photometry ``lc`` holds NOW (sigma mode and prior set as given).
 
         The reference reads the light-curve columns on every ``log_likelihood`` call (models.py:116-119); an engine
         copies them to the device once.  Engines are therefore cached by the CONTENT of the four columns, compared on
         every call: editing ``lc['lum']`` in place, or a new light-curve object at a recycled address, gets a new
         engine.  An engine that leaves the cache is only dropped, never destroyed here -- samplers and closures that
-        were handed it keep it alive."""
+        were handed it keep it alive.
+
+        ``nondet='censored'`` (extension; see :meth:`log_likelihood`): the engine holds the rows whose ``nondet`` is
+        false, with the true rows attached as upper limits (a second engine on their times and filters); the cache key
+        gains the mode, the column's content and ``nondetSigmas``.  Without a true ``nondet`` row it is the plain engine."""
         if sigma_type not in ('relative', 'absolute'):
             raise Exception('sigma_type must either be "relative" or "absolute"')
+        _check_nondet_mode(nondet)
         t = np.asarray(_column(lc, 'MJD'), dtype=np.float64)
         y = np.asarray(_column(lc, self.output_quantity), dtype=np.float64)
         dy = np.asarray(_column(lc, 'd' + self.output_quantity), dtype=np.float64)
         filt_col = np.asarray(_column(lc, 'filter'), dtype=object)
         mode = (bool(use_sigma), sigma_type, None if priors is None else tuple(p.descriptor() for p in priors))
+        split = None
+        mask = _nondet_mask(lc) if nondet == 'censored' else None
+        if mask is not None:
+            split = LimitSplit(lc, self.output_quantity, mask)
+            mode += ('censored', mask.tobytes(), split.nondet_sigmas)
         for k, bound in enumerate(self._bound):
             if bound.mode == mode and bound.holds(t, filt_col, y, dy):
                 if k:  # most recently used first
                     self._bound.insert(0, self._bound.pop(k))
                 return bound.engine
         filts = [as_filter(f) for f in filt_col]
-        eng = self.make_engine(t, filts, y, dy, use_sigma, sigma_type, priors)
+        if split is None:
+            eng = self.make_engine(t, filts, y, dy, use_sigma, sigma_type, priors)
+        else:
+            det, lim = np.nonzero(split.det)[0], np.nonzero(split.lim)[0]
+            eng = self.make_engine(t[det], [filts[i] for i in det], y[det], dy[det], use_sigma, sigma_type, priors)
+            at = self.make_engine(t[lim], [filts[i] for i in lim], np.zeros(len(lim)), split.dy, use_sigma, sigma_type)
+            eng.set_limits(at, split.L_lim, split.dy)
         self._bound.insert(0, _BoundEngine(eng, mode, t, filt_col, y, dy))
         del self._bound[self.max_bound_engines:]
         return eng
 
     # --- the reference's public surface --------------------------------------------------------------------------
-    def log_likelihood(self, lc, p, use_sigma=False, sigma_type='relative'):
+    def log_likelihood(self, lc, p, use_sigma=False, sigma_type='relative', nondet='gaussian'):
         """Gaussian log-likelihood of the photometry in ``lc`` given parameters ``p`` (models.py:93-136).
 
-        ``p`` 1-D -> float; ``p`` of shape (n, ndim) -> array (n,)."""
-        eng = self.engine_for(lc, use_sigma, sigma_type)
+        ``p`` 1-D -> float; ``p`` of shape (n, ndim) -> array (n,).
+
+        ``nondet`` (extension): ``'gaussian'``, the default, is the reference's treatment -- a row whose ``nondet`` is
+        true enters with ``y = 0`` and ``dy = limit / nondetSigmas`` like a measurement of zero.  ``'censored'`` makes it
+        an upper limit: the Gaussian sum runs over the detections only, and every non-detection ``j`` adds
+        ``ln Phi((L_lim,j - m_j(p)) / sigma_j(p))``, the probability that the flux was below the limit -- with
+        ``L_lim,j = nondetSigmas * dy_j``, ``m_j`` the model at its time and filter, ``sigma_j = dy_j`` or, with
+        ``use_sigma``, ``sqrt(dy_j^2 + (s u_j)^2)`` where ``u_j = dy_j`` (``'relative'``) or the detections' median ``dy``
+        (``'absolute'``).  ``lc`` needs a boolean ``nondet`` column for it (an ``LC`` or a dict); without one, or without
+        a true row, the call is the default one.  No detection at all raises ``ValueError``."""
+        eng = self.engine_for(lc, use_sigma, sigma_type, nondet=nondet)
         p = np.asarray(p, dtype=np.float64)
         out = eng.log_likelihood(p)
         return float(out[0]) if p.ndim == 1 else out
+
+    def limit_terms(self, lc, p, use_sigma=False, sigma_type='relative'):
+        """The censored term ``ln Phi((L_lim,j - m_j(p)) / sigma_j(p))`` of every non-detection of ``lc``, in the order
+        of its ``nondet`` rows: which limits a fit with ``nondet='censored'`` leans on.
+
+        ``p`` 1-D -> (n_lim,); ``p`` of shape (n, ndim) -> (n, n_lim).  Their sum over the limits plus the
+        log-likelihood of the detections alone is ``log_likelihood(..., nondet='censored')``."""
+        eng = self.engine_for(lc, use_sigma, sigma_type, nondet='censored')
+        p = np.asarray(p, dtype=np.float64)
+        out = eng.limit_terms(p) if getattr(eng, 'nlimits', 0) else np.empty((len(eng._block(p)), 0))
+        return out[0] if p.ndim == 1 else out
 
     def _eval_engine(self, t_in, f, scalar_params=True):
         """Engine for model evaluation at (t, f): pointwise when the lengths agree and the parameters are scalars
@@ -668,11 +746,16 @@ class BaseCentralEngine(Model):
                            use_sigma=use_sigma, sigma_type=st, priors=pri,
                            device=self.device if device is None else device)
 
-    def engine_for(self, lc, use_sigma=False, sigma_type='relative', priors=None):
+    def engine_for(self, lc, use_sigma=False, sigma_type='relative', priors=None, nondet='gaussian'):
         """Engine bound to the columns ``MJD``, ``ycol`` and ``dycol`` as ``lc`` holds them NOW (cached by content, as
-        :meth:`Model.engine_for`)."""
+        :meth:`Model.engine_for`).  A bolometric table has no non-detections: ``nondet='censored'`` with a true ``nondet``
+        row raises ``LcfError`` (status 5)."""
         if sigma_type not in ('relative', 'absolute'):
             raise Exception('sigma_type must either be "relative" or "absolute"')
+        _check_nondet_mode(nondet)
+        if nondet == 'censored' and _nondet_mask(lc) is not None:
+            raise _eng.LcfError(5, 'a central-engine model (Arnett, Magnetar) fits a bolometric table, which has no '
+                                   'non-detections: upper limits belong to photometric models')
         t = np.asarray(_column(lc, 'MJD'), dtype=np.float64)
         y = np.asarray(_column(lc, self.output_quantity), dtype=np.float64)
         dy = np.asarray(_column(lc, self.dycol), dtype=np.float64)
