@@ -25,6 +25,7 @@
 
 #include "lcf_internal.h"
 #include "lcf_keys.h"
+#include "lcf_plan.h"
 
 namespace {
 
@@ -250,25 +251,10 @@ lcf_status central_engine_create(const lcf_problem* pr, int32_t device, lcf_engi
         return fail(LCF_ERR_INVALID_ARGUMENT, "the redshift (consts[0]) must be finite and above -1");
     const int N = (int)pr->n_points;
     const int n_dim = pr->n_par + (pr->use_sigma ? 1 : 0);
-    if (pr->priors)
-        for (int i = 0; i < n_dim; ++i)
-            if (pr->priors[i].kind < 0 || pr->priors[i].kind > 2) return fail(LCF_ERR_INVALID_ARGUMENT, "bad prior kind");
+    if (lcf_status st = check_prior_kinds(*pr, n_dim)) return st;
 
-    if (lcf_status st = use_device(device)) return st;
-
-    auto* e = new lcf_engine();
-    e->device = device;
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->n_cus = cus;
-    }
-    lcf_status st = LCF_OK;
-    auto bail = [&](lcf_status s) {
-        delete e;
-        return s;
-    };
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(LCF_ERR_HIP, "hipStreamCreate failed"));
+    std::unique_ptr<lcf_engine> e;
+    if (lcf_status st = engine_shell(device, &e)) return st;
 
     DevProblem& dp = e->dp;
     dp.model = pr->model;
@@ -289,42 +275,24 @@ lcf_status central_engine_create(const lcf_problem* pr, int32_t device, lcf_engi
         dp.part_col0[j] = 0;
     }
     std::memcpy(dp.consts, pr->consts, sizeof(dp.consts));
-    double lognorm = 0.;
-    for (int i = 0; i < N; ++i) lognorm += std::log(2. * M_PI * pr->dy[i] * pr->dy[i]);  // caller order, like np.sum
-    dp.log_norm_const = lognorm;
-    std::vector<double> sorted_dy(pr->dy, pr->dy + N);
-    double med = 0.;
-    if (N > 0) {  // np.median
-        std::sort(sorted_dy.begin(), sorted_dy.end());
-        med = (N & 1) ? sorted_dy[N / 2] : 0.5 * (sorted_dy[N / 2 - 1] + sorted_dy[N / 2]);
-    }
-    dp.sigma_unit_abs = med;
+    noise_constants(pr->dy, N, &dp.log_norm_const, &dp.sigma_unit_abs);
     e->samples_per_eval = (int64_t)N * 2 * kCentralNodes;   // (quadrature nodes of one evaluation)
 
     std::vector<double> ht(pr->t, pr->t + N), hy(pr->y, pr->y + N), hdy(pr->dy, pr->dy + N), hinv(N);
     std::vector<double2> hyd(N);
     for (int i = 0; i < N; ++i) {
         hinv[i] = 1. / hdy[i];
-        hyd[i] = make_double2(hy[i], pr->use_sigma ? hdy[i] : hinv[i]);
+        hyd[i] = scaled_pair(hy[i], hdy[i], pr->use_sigma);
     }
-    double *dt = nullptr, *dy_ = nullptr, *ddy = nullptr, *dinv = nullptr;
-    double2* dyd = nullptr;
-    PriorDev* dpri = nullptr;
+    const std::vector<PriorDev> hp = prior_rows(*pr, n_dim);
     UploadArena arena(e->owned, (size_t)4096 + (size_t)N * 64);
-#define UP(h, d) if ((st = upload(h, &d, arena)) != LCF_OK) return bail(st)
-    UP(ht, dt); UP(hy, dy_); UP(hdy, ddy); UP(hinv, dinv); UP(hyd, dyd);
-    if (pr->priors) {
-        std::vector<PriorDev> hp(n_dim);
-        for (int i = 0; i < n_dim; ++i)
-            hp[i] = PriorDev{pr->priors[i].kind, 0, pr->priors[i].p_min, pr->priors[i].p_max, pr->priors[i].mean,
-                             pr->priors[i].stddev};
-        UP(hp, dpri);
-    }
-#undef UP
-    dp.t = dt; dp.y = dy_; dp.dy = ddy; dp.inv_dy = dinv; dp.pt_yd = dyd; dp.priors = dpri;
-    if ((st = arena.flush()) != LCF_OK) return bail(st);
-    if ((st = e->sync_dp()) != LCF_OK) return bail(st);
-    *out = e;
+    lcf_status st = LCF_OK;
+    const auto up = [&](const auto& h, auto** d) {
+        if (st == LCF_OK) st = put_array(arena, h, d);
+    };
+    up(ht, &dp.t); up(hy, &dp.y); up(hdy, &dp.dy); up(hinv, &dp.inv_dy); up(hyd, &dp.pt_yd); up(hp, &dp.priors);
+    if (st || (st = arena.flush()) || (st = e->sync_dp())) return st;
+    *out = e.release();
     return LCF_OK;
 }
 

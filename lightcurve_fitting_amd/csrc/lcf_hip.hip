@@ -3066,526 +3066,6 @@ int32_t lcf_device_count(void) {
     return n;
 }
 
-lcf_status lcf_engine_create(const lcf_problem* pr, int32_t device, lcf_engine** out) {
-    if (!pr || !out) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    if (pr->abi_version != LCF_ABI_VERSION) return fail(LCF_ERR_INVALID_ARGUMENT, "abi_version mismatch");
-    if (is_central(pr->model)) return central_engine_create(pr, device, out);   // (no filters: an engine of its own making)
-    switch (pr->model) {
-        case LCF_MODEL_SHOCK_COOLING: case LCF_MODEL_SHOCK_COOLING2: case LCF_MODEL_SHOCK_COOLING3:
-        case LCF_MODEL_SHOCK_COOLING4:
-        case LCF_MODEL_COMPANION_SHOCKING: case LCF_MODEL_COMPANION_SHOCKING2: case LCF_MODEL_COMPANION_SHOCKING3:
-        case LCF_MODEL_BLACKBODY:
-        case LCF_MODEL_CUSTOM:
-            break;
-        default:
-            return fail(LCF_ERR_UNSUPPORTED, "unknown or unsupported model id");
-    }
-    static const int kNPar[9] = {0, 5, 4, 7, 5, 8, 7, 7, 2};
-    // (a custom model has as many parameters as its state function reads: the caller says how many)
-    if (pr->model == LCF_MODEL_CUSTOM ? pr->n_par < 0 : pr->n_par != kNPar[pr->model])
-        return fail(LCF_ERR_INVALID_ARGUMENT, "n_par does not match the model");
-    const int n_dim = pr->n_par + (pr->use_sigma ? 1 : 0);
-    if (n_dim > kMaxDim) return fail(LCF_ERR_INVALID_ARGUMENT, "too many parameters");
-    if (pr->n_points < 0 || pr->n_points > (1 << 26) || pr->n_filters <= 0)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "bad n_points / n_filters");
-    if (pr->n_points > 0 && (!pr->t || !pr->y || !pr->dy || !pr->filt_idx))
-        return fail(LCF_ERR_INVALID_ARGUMENT, "null photometry");
-    if (!pr->tab_off || !pr->tab_a || !pr->tab_w) return fail(LCF_ERR_INVALID_ARGUMENT, "null band tables");
-    const bool reddened = pr->model == LCF_MODEL_SHOCK_COOLING3;
-    if (reddened && !pr->tab_ext) return fail(LCF_ERR_INVALID_ARGUMENT, "ShockCooling3 needs tab_ext");
-    if (pr->sigma_type != LCF_SIGMA_RELATIVE && pr->sigma_type != LCF_SIGMA_ABSOLUTE)
-        return fail(LCF_ERR_INVALID_ARGUMENT, "sigma_type must be relative or absolute");
-    const int N = (int)pr->n_points, NF = pr->n_filters;
-    if (pr->tab_off[0] != 0) return fail(LCF_ERR_INVALID_ARGUMENT, "tab_off[0] must be 0");
-    for (int f = 0; f < NF; ++f)
-        if (pr->tab_off[f + 1] < pr->tab_off[f]) return fail(LCF_ERR_INVALID_ARGUMENT, "tab_off must be non-decreasing");
-    for (int i = 0; i < N; ++i)
-        if (pr->filt_idx[i] < 0 || pr->filt_idx[i] >= NF) return fail(LCF_ERR_INVALID_ARGUMENT, "filt_idx out of range");
-    const bool companion = pr->model >= LCF_MODEL_COMPANION_SHOCKING && pr->model <= LCF_MODEL_COMPANION_SHOCKING3;
-    if (companion) {
-        if (!pr->filt_kasen_par || !pr->filt_sifto_par || !pr->filt_dt_par || !pr->spline_knots || !pr->spline_coef ||
-            pr->n_knots < 2)
-            return fail(LCF_ERR_INVALID_ARGUMENT, "companion-shocking model needs spline and factor tables");
-        for (int f = 0; f < NF; ++f)
-            for (const int32_t* a : {pr->filt_kasen_par, pr->filt_sifto_par, pr->filt_dt_par})
-                if (a[f] < -1 || a[f] >= n_dim) return fail(LCF_ERR_INVALID_ARGUMENT, "factor parameter index out of range");
-    }
-
-    if (lcf_status st = use_device(device)) return st;
-
-    auto* e = new lcf_engine();
-    e->device = device;
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->n_cus = cus;
-    }
-    lcf_status st = LCF_OK;
-    auto bail = [&](lcf_status s) {
-        delete e;
-        return s;
-    };
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(LCF_ERR_HIP, "hipStreamCreate failed"));
-
-    // ---- order the points: n_parts contiguous ranges of observation epochs ("parts", one workgroup per walker
-    // each), sorted by filter inside a part (waves then share a band table).  A part owning whole epochs means its
-    // workgroup needs the thermal states of those epochs only. ----
-    // distinct observation times (exact equality): the thermal state depends on (walker, time) only
-    const bool all_finite_t = std::all_of(pr->t, pr->t + N, [](double v) { return std::isfinite(v); });
-    // (with a non-finite time there is no strict weak order to sort by: every point is then its own epoch, in the
-    // caller's order, and nothing below compares times)
-    std::vector<double> epochs(pr->t, pr->t + N);
-    if (all_finite_t) {
-        std::sort(epochs.begin(), epochs.end());
-        epochs.erase(std::unique(epochs.begin(), epochs.end()), epochs.end());
-    }
-    const int n_chunks_all = std::max(1, (N + kBlock - 1) / kBlock);
-    std::vector<int> order(N);
-    std::iota(order.begin(), order.end(), 0);
-    auto epoch_of = [&](int i) {
-        return all_finite_t ? (int)(std::lower_bound(epochs.begin(), epochs.end(), pr->t[i]) - epochs.begin()) : i;
-    };
-    std::vector<int> ep_of(N);
-    for (int i = 0; i < N; ++i) ep_of[i] = epoch_of(i);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ep_of[a] < ep_of[b]; });
-    // Thermal states per (walker, observation time) ahead of the points.  With >= 2 points per distinct time that is
-    // sharing; without any (real multi-band photometry: every observation has its own time) it still is what puts a
-    // light curve on the fast path -- log-space states, interpolated band sums, k_solo.  LCF_SHARED_EPOCHS_ONLY=1
-    // restores the round-1 rule, sharing or nothing (read at every engine creation: the tests of the
-    // state-inside-the-point-loop kernels set it).
-    const bool shared_only = std::getenv("LCF_SHARED_EPOCHS_ONLY") != nullptr;
-    const bool sharing = 2 * (long long)epochs.size() <= N;
-    const bool epochs_ahead = all_finite_t && N > 0 && (sharing || !shared_only);
-    // ---- the epoch-major copy the likelihood walks (DevProblem::em_*): COLUMNS = an observation time with up to em_k of
-    // its points in filter order; an epoch with more points than that takes several columns (em_k = the most points of
-    // an epoch, but at most twice the mean, so that ragged photometry does not pad the arrays beyond ~3 N entries) ----
-    int em_k = 1, em_dense = 0;
-    std::vector<int> col_epoch, col_first;   // per column: its epoch, its first point in em_order
-    std::vector<int> em_order;               // points by (epoch, filter, caller's index)
-    std::vector<int> ep_col0;                // first column of every epoch (+ one past the last)
-    if (epochs_ahead) {
-        em_order = order;
-        std::stable_sort(em_order.begin(), em_order.end(), [&](int a, int b) {
-            return ep_of[a] != ep_of[b] ? ep_of[a] < ep_of[b] : pr->filt_idx[a] < pr->filt_idx[b];
-        });
-        const int n_ep = (int)epochs.size();
-        std::vector<int> cnt(n_ep, 0);
-        for (int i = 0; i < N; ++i) ++cnt[ep_of[i]];
-        const int kmax = *std::max_element(cnt.begin(), cnt.end());
-        em_k = std::min(kmax, std::max(2, (int)((2LL * N + n_ep - 1) / n_ep)));
-        ep_col0.assign(n_ep + 1, 0);
-        for (int e = 0, at = 0; e < n_ep; ++e) {
-            ep_col0[e] = (int)col_epoch.size();
-            for (int k = 0; k < cnt[e]; k += em_k) {
-                col_epoch.push_back(e);
-                col_first.push_back(at + k);
-            }
-            at += cnt[e];
-        }
-        ep_col0[n_ep] = (int)col_epoch.size();
-        em_dense = em_k == NF && (long long)n_ep * NF == N;
-        for (int i = 0; em_dense && i < N; ++i)   // every epoch holds filters 0 .. NF-1, one point each
-            if (pr->filt_idx[em_order[i]] != i % NF) em_dense = 0;
-    }
-    const int n_cols = (int)col_epoch.size();
-    // workgroups per walker ("parts"): every one repeats the prologue (table staging; in the fused sampler kernel also
-    // the serial part of the half-step), so few of them.  Epoch-major engines: a part is what 256 lanes walk, one
-    // column each and round -- one part per 256 columns; else two parts up to 16 chunks of points, then one per 8
-    // (measured on the 1024-walker, 3000-point fit in round 1: 2 parts 52 us/step, 4 parts 61, 8 parts 83)
-    int n_parts = std::min(n_chunks_all, std::min(kMaxParts, std::max(2, (n_chunks_all + 7) / 8)));
-    if (epochs_ahead) {
-        // ... or, beyond kMaxParts x 256 columns, one part per 256 r columns with the smallest r that fits: a part's
-        // 256 lanes then make r full rounds (3000 single-point columns: 6 parts of 500, not 8 of 375 whose second round
-        // is half empty)
-        int rounds = 1;
-        while ((n_cols + kBlock * rounds - 1) / (kBlock * rounds) > kMaxParts) ++rounds;
-        n_parts = std::max(n_cols > 64 ? 2 : 1, (n_cols + kBlock * rounds - 1) / (kBlock * rounds));
-    }
-    if (const char* env = std::getenv("LCF_PARTS"))
-        n_parts = std::max(1, std::min(std::min(epochs_ahead ? n_cols : n_chunks_all, kMaxParts), std::atoi(env)));
-    std::vector<int> part_start(kMaxParts + 1, N), part_col0(kMaxParts + 1, n_cols);
-    part_start[0] = 0;
-    part_col0[0] = 0;
-    {
-        int made = 0;
-        for (int j = 1; j < n_parts; ++j) {
-            int b;  // boundary j: the first epoch change at or after the equal split (of the columns / of the points)
-            if (epochs_ahead) {
-                int cb = (int)((long long)n_cols * j / n_parts);
-                while (cb < n_cols && cb > 0 && col_epoch[cb] == col_epoch[cb - 1]) ++cb;
-                b = cb < n_cols ? col_first[cb] : N;   // (`order` and em_order agree on where an epoch starts)
-                if (b > part_start[made] && b < N) part_col0[made + 1] = cb;
-            } else {
-                b = (int)((long long)N * j / n_parts);
-                while (b < N && b > 0 && ep_of[order[b]] == ep_of[order[b - 1]]) ++b;
-            }
-            if (b > part_start[made] && b < N) part_start[++made] = b;
-        }
-        n_parts = made + 1;
-        for (int j = n_parts; j <= kMaxParts; ++j) {
-            part_start[j] = N;
-            part_col0[j] = n_cols;
-        }
-    }
-    for (int j = 0; j < n_parts; ++j)
-        std::stable_sort(order.begin() + part_start[j], order.begin() + part_start[j + 1],
-                         [&](int a, int b) { return pr->filt_idx[a] < pr->filt_idx[b]; });
-    std::vector<double> ht(N), hy(N), hdy(N);
-    std::vector<int> hfilt(N), horig(N);
-    double lognorm = 0.;
-    int64_t samples = 0;
-    // device table: per filter [full | compressed], each padded to a multiple of four samples with zero weights
-    // (exactly 0 contribution)
-    // (a reddened model reweights the samples per walker: the compressed tables do not apply)
-    const bool have_ctab = pr->ctab_off && pr->ctab_a && pr->ctab_w && pr->ctab_tmin && !reddened;
-    const bool have_htab = have_ctab && pr->htab_off && pr->htab_a && pr->htab_w && pr->htab_tmin;
-    const bool have_itab = !reddened && pr->itab_coef && pr->itab_tmin && pr->itab_m > 0 && pr->itab_h > 0.;
-    if (have_itab) {
-        if (pr->itab_m > 4096 || !(pr->itab_u0 > 0.) || !std::isfinite(pr->itab_h))
-            return bail(fail(LCF_ERR_INVALID_ARGUMENT, "interpolants: 0 < itab_m <= 4096, itab_u0 > 0 (T >= 1 kK), finite itab_h"));
-        for (int f = 0; f < NF; ++f) {
-            if (!(pr->itab_tmin[f] > 0.)) return bail(fail(LCF_ERR_INVALID_ARGUMENT, "itab_tmin must be > 0 (+inf: none)"));
-            if (std::isfinite(pr->itab_tmin[f]))
-                for (int k = 0; k < pr->itab_m * 8; ++k)
-                    if (!std::isfinite(pr->itab_coef[(size_t)f * pr->itab_m * 8 + k]))
-                        return bail(fail(LCF_ERR_INVALID_ARGUMENT, "non-finite interpolant coefficient"));
-        }
-    }
-    if (have_htab) {
-        if (pr->htab_off[0] != 0) return bail(fail(LCF_ERR_INVALID_ARGUMENT, "htab_off[0] must be 0"));
-        for (int f = 0; f < NF; ++f)
-            if (pr->htab_off[f + 1] < pr->htab_off[f] || pr->htab_off[f + 1] - pr->htab_off[f] > 252)
-                return bail(fail(LCF_ERR_INVALID_ARGUMENT, "htab_off must be non-decreasing, <= 252 samples a filter"));
-    }
-    if (have_ctab) {
-        if (pr->ctab_off[0] != 0) return bail(fail(LCF_ERR_INVALID_ARGUMENT, "ctab_off[0] must be 0"));
-        for (int f = 0; f < NF; ++f)
-            if (pr->ctab_off[f + 1] < pr->ctab_off[f])
-                return bail(fail(LCF_ERR_INVALID_ARGUMENT, "ctab_off must be non-decreasing"));
-    }
-    std::vector<int> pfull(2 * NF, 0), pcomp(2 * NF, 0), phot(2 * NF, 0);  // (offset, count) pairs
-    std::vector<double> ptmin(NF, INFINITY), ptmin2(NF, INFINITY);
-    std::vector<double2> htab;
-    std::vector<double> hext;  // reddened models: 0.4 log2(10) A_k / E(B-V), aligned with htab
-    auto append = [&](const double* a, const double* w, int k0, int k1, int* slot) -> bool {
-        slot[0] = (int)htab.size();
-        for (int k = k0; k < k1; ++k) {
-            if (!(a[k] > 0.) || !std::isfinite(a[k]) || !std::isfinite(w[k])) return false;
-            htab.push_back(make_double2(a[k], w[k]));
-            if (reddened) {
-                if (!std::isfinite(pr->tab_ext[k])) return false;
-                hext.push_back(0.4 * 3.321928094887362 * pr->tab_ext[k]);
-            }
-        }
-        const double apad = k1 > k0 ? a[k1 - 1] : 1.;
-        while ((htab.size() - slot[0]) % 4) {
-            htab.push_back(make_double2(apad, 0.));
-            if (reddened) hext.push_back(0.);
-        }
-        slot[1] = (int)htab.size() - slot[0];
-        return true;
-    };
-    // device table = [compressed levels of every filter | full tables of every filter]: when everything does not fit
-    // in LDS the (short) compressed part still does, and only points colder than its validity read global memory
-    for (int f = 0; f < NF; ++f) {
-        bool ok = true;
-        if (ok && have_ctab && pr->ctab_off[f + 1] > pr->ctab_off[f]) {
-            ok = append(pr->ctab_a, pr->ctab_w, pr->ctab_off[f], pr->ctab_off[f + 1], &pcomp[2 * f]);
-            ptmin[f] = pr->ctab_tmin[f];
-            if (!(ptmin[f] >= 0.)) ok = false;
-        }
-        if (ok && have_htab && pr->htab_off[f + 1] > pr->htab_off[f]) {
-            ok = append(pr->htab_a, pr->htab_w, pr->htab_off[f], pr->htab_off[f + 1], &phot[2 * f]);
-            ptmin2[f] = pr->htab_tmin[f];
-            // the hot level must not claim a wider range than the cool one (selection tests it first)
-            if (!(ptmin2[f] >= 0.) || (pcomp[2 * f + 1] > 0 && ptmin2[f] < ptmin[f])) ok = false;
-        }
-        if (!ok)
-            return bail(fail(LCF_ERR_INVALID_ARGUMENT,
-                             "band tables need finite a_k > 0, finite W_k, t_min >= 0 (hot level: t_min >= the cool one's)"));
-    }
-    const int n_compressed = (int)htab.size();
-    for (int f = 0; f < NF; ++f)
-        if (!append(pr->tab_a, pr->tab_w, pr->tab_off[f], pr->tab_off[f + 1], &pfull[2 * f]))
-            return bail(fail(LCF_ERR_INVALID_ARGUMENT, "band tables need finite a_k > 0 and finite W_k"));
-    for (int i = 0; i < N; ++i) {
-        const int o = order[i], f = pr->filt_idx[o];
-        ht[i] = pr->t[o];
-        hy[i] = pr->y[o];
-        hdy[i] = pr->dy[o];
-        hfilt[i] = f;
-        horig[i] = o;
-        samples += pr->tab_off[f + 1] - pr->tab_off[f];
-    }
-    for (int i = 0; i < N; ++i) lognorm += std::log(2. * M_PI * pr->dy[i] * pr->dy[i]);  // caller order, like np.sum
-    std::vector<double> sorted_dy(pr->dy, pr->dy + N);
-    double med = 0.;
-    if (N > 0) {  // np.median
-        std::sort(sorted_dy.begin(), sorted_dy.end());
-        med = (N & 1) ? sorted_dy[N / 2] : 0.5 * (sorted_dy[N / 2 - 1] + sorted_dy[N / 2]);
-    }
-    std::vector<int> hepoch(N);
-    for (int i = 0; i < N; ++i) hepoch[i] = ep_of[horig[i]];
-    int n_chunks = 0, cpb = 1;  // chunks of kBlock points: total over the parts, and the most in one part
-    for (int j = 0; j < n_parts; ++j) {
-        const int c = (part_start[j + 1] - part_start[j] + kBlock - 1) / kBlock;
-        n_chunks += c;
-        cpb = std::max(cpb, c);
-    }
-    std::vector<int> htaboff(pfull);
-    if (htab.empty()) htab.push_back(make_double2(1., 0.));
-    std::vector<double> hinvdy(N);
-    for (int i = 0; i < N; ++i) hinvdy[i] = 1. / hdy[i];
-    std::vector<FiltDesc> hfd(NF);  // per filter: where its tables are and from which temperature each is valid
-    for (int f = 0; f < NF; ++f)
-        hfd[f] = FiltDesc{pfull[2 * f], pfull[2 * f + 1], pcomp[2 * f], pcomp[2 * f + 1], phot[2 * f], phot[2 * f + 1],
-                          // the interpolant holds from max(its proved t_min, the table's first interval)
-                          (have_itab && std::isfinite(pr->itab_tmin[f]))
-                              ? std::nextafter((float)std::max((std::log(pr->itab_tmin[f]) - pr->itab_u0) / pr->itab_h, 0.),
-                                               INFINITY)
-                              : INFINITY,
-                          have_itab ? f * pr->itab_m * 8 : 0,
-                          pcomp[2 * f + 1] > 0 ? 1. / ptmin[f] : 0.,  // t_min = 0 -> inf: always valid
-                          phot[2 * f + 1] > 0 ? 1. / ptmin2[f] : 0.,
-                          companion ? pr->filt_kasen_par[f] : -1, companion ? pr->filt_sifto_par[f] : -1,
-                          companion ? pr->filt_dt_par[f] : -1, 0};
-    std::vector<double> hexp(kExpTabSize);
-    for (int j = 0; j < kExpTabSize; ++j) hexp[j] = std::exp2(j / (double)kExpTabSize);
-
-    DevProblem& dp = e->dp;
-    dp.model = pr->model;
-    dp.n_points = N;
-    dp.n_chunks = n_chunks;
-    dp.n_parts = n_parts;
-    dp.cpb = cpb;
-    for (int j = 0; j <= kMaxParts; ++j) dp.part_start[j] = part_start[j];
-    for (int j = 0; j <= kMaxParts; ++j)  // epochs were sorted, so a part's epoch range starts at its first point's
-        dp.part_ep0[j] = (j < n_parts && part_start[j] < N && all_finite_t) ? ep_of[order[part_start[j]]]
-                                                                              : (int)epochs.size();
-    if (all_finite_t && N > 0) {
-        // `order` is filter-sorted inside a part: the part's first epoch is the minimum over its points
-        for (int j = 0; j < n_parts; ++j) {
-            int lo = (int)epochs.size();
-            for (int i = part_start[j]; i < part_start[j + 1]; ++i) lo = std::min(lo, hepoch[i]);
-            dp.part_ep0[j] = lo;
-        }
-    }
-    dp.n_tab = (int)htab.size();
-    dp.n_filters = NF;
-    dp.n_dim = n_dim;
-    dp.n_par = pr->n_par;
-    dp.use_sigma = pr->use_sigma ? 1 : 0;
-    dp.sigma_abs = pr->sigma_type == LCF_SIGMA_ABSOLUTE;
-    dp.n_knots = companion ? pr->n_knots : 0;
-    dp.has_priors = pr->priors ? 1 : 0;
-    // LDS holds the first n_lds_tab samples of the table array: all of it, or the compressed levels only
-    int lds_tab_max = kLdsTabMax;
-    if (const char* env = std::getenv("LCF_LDS_TAB_MAX")) lds_tab_max = std::max(0, std::min(9500, std::atoi(env)));
-    dp.n_lds_tab = NF > kLdsFiltMax ? 0
-                   : (int)htab.size() <= lds_tab_max ? (int)htab.size()
-                   : (n_compressed > 0 && n_compressed <= lds_tab_max) ? n_compressed : 0;
-    // reddened weights are made while staging the FULL tables; when those do not fit nothing is staged and the
-    // reddening is applied on the fly (slow path)
-    dp.redden_slow = reddened && dp.n_lds_tab != (int)htab.size();
-    if (dp.redden_slow) dp.n_lds_tab = 0;
-    dp.tab_in_lds = dp.n_lds_tab > 0;
-    dp.n_epochs = (int)epochs.size();
-    dp.use_therm = epochs_ahead;
-    dp.em_k = em_k;
-    dp.em_cols = n_cols;
-    dp.em_dense = em_dense;
-    for (int j = 0; j <= kMaxParts; ++j) dp.part_col0[j] = part_col0[j];
-    dp.variant = 1;
-    dp.use_ctab = have_ctab ? 1 : 0;
-    e->have_ctab = have_ctab;
-    // third level: interpolants of ln S(ln T), staged in LDS behind the descriptors when they take <= 40 KiB
-    // (six to ten filters), else read from global memory (L2)
-    // (engines whose points share no epochs keep the thermal state inside the point loop, in linear space)
-    const bool have_itab_here = have_itab && epochs_ahead;
-    e->have_itab = have_itab_here;
-    dp.use_itab = have_itab_here ? 1 : 0;
-    dp.itab_m = have_itab ? pr->itab_m : 0;
-    dp.itab_u0 = have_itab ? pr->itab_u0 : 0.;
-    dp.itab_inv_h = have_itab ? 1. / pr->itab_h : 0.;
-    dp.itab_umax = have_itab ? pr->itab_u0 + pr->itab_h * pr->itab_m : 0.;
-    const size_t n_itab = have_itab_here ? (size_t)NF * pr->itab_m * 8 : 0;
-    // ... and only where a workgroup walks enough points to pay for staging them (a part of >= 1024 points; the
-    // population launches of 600-point transients read the 64 bytes a point needs from L2 instead: staging 24 KiB per
-    // workgroup cost them 20 %)
-    dp.n_itab_lds = (dp.tab_in_lds && n_itab * sizeof(double) <= 40 * 1024 && N >= 1024 * n_parts) ? (int)n_itab : 0;
-    dp.itab_uniform = have_itab ? 1 : 0;
-    for (int f = 0; have_itab && f < NF; ++f)
-        if (!(pr->itab_tmin[f] <= std::exp(pr->itab_u0) * (1. + 1e-12))) dp.itab_uniform = 0;
-    // ... and a companion-shocking model's template splines behind those, when their knots are exactly k0 + i h (the
-    // device then needs no knot) and everything still leaves room for two workgroups per CU (80 KiB each): 26 KiB for
-    // the eight SiFTO filters -- a point's template costs two LDS reads instead of a chain of dependent loads from L2
-    dp.n_spl_lds = 0;
-    if (companion && dp.tab_in_lds) {
-        const double h1 = pr->spline_knots[1] - pr->spline_knots[0];
-        bool exact = h1 > 0.;
-        for (int k = 0; exact && k < pr->n_knots; ++k) exact = pr->spline_knots[k] == pr->spline_knots[0] + k * h1;
-        const size_t n_spl = (size_t)NF * (pr->n_knots - 1) * 4;
-        const size_t before = kLdsHead * sizeof(double) + ((size_t)dp.n_lds_tab + kFdD2 * NF) * sizeof(double2) +
-                              (size_t)dp.n_itab_lds * sizeof(double);
-        if (exact && before + n_spl * sizeof(double) + 2048 <= 80 * 1024) dp.n_spl_lds = (int)n_spl;
-    }
-    dp.stage_d2 = dp.n_lds_tab + kFdD2 * NF + dp.n_itab_lds / 2 + dp.n_spl_lds / 2;
-    std::memcpy(dp.consts, pr->consts, sizeof(dp.consts));
-    if (pr->model == LCF_MODEL_SHOCK_COOLING || pr->model == LCF_MODEL_SHOCK_COOLING3)
-        dp.consts[11] = pr->consts[1] > 0. ? std::log(pr->consts[1] / 19.5) : 0.;  // hoisted out of the half-step
-    if (pr->model == LCF_MODEL_SHOCK_COOLING) {  // logarithms of the two amplitudes' constant factors (log-space state)
-        dp.consts[9] = std::log(pr->consts[6] * pr->consts[7] / kKB);
-        dp.consts[10] = std::log(kC3sq * pr->consts[5] * pr->consts[0]);
-    }
-    dp.log_norm_const = lognorm;
-    dp.sigma_unit_abs = med;
-    e->samples_per_eval = samples * (pr->model == LCF_MODEL_SHOCK_COOLING4 ? 2 : 1);
-    e->lds_bytes = kLdsHead * sizeof(double) + (dp.tab_in_lds ? (size_t)dp.stage_d2 * sizeof(double2) : 0);
-
-    double *dt, *dy_, *ddy, *dkn = nullptr, *dspl = nullptr;
-    int *dfilt, *dorig;
-    double2* dtab;
-    PriorDev* dpri = nullptr;
-    // (one block, one copy: the photometry in its layouts, the tables and the staging image; sized for the light curve)
-    UploadArena arena(e->owned, (size_t)256 * 1024 + (size_t)N * 256);
-#define UP(h, d) if ((st = upload(h, &d, arena)) != LCF_OK) return bail(st)
-    UP(ht, dt); UP(hy, dy_); UP(hdy, ddy); UP(hfilt, dfilt); UP(horig, dorig);
-    UP(htab, dtab); UP(htaboff, e->d_tab_off);
-    if (reddened) {
-        double* dext;
-        UP(hext, dext);
-        dp.tab_ext = dext;
-    }
-    if (have_itab) {
-        std::vector<double> hit(pr->itab_coef, pr->itab_coef + (size_t)NF * pr->itab_m * 8);
-        for (double& v : hit)
-            if (!std::isfinite(v)) v = 0.;  // (filters without an interpolant: never read, u_min = +inf)
-        double* dit;
-        UP(hit, dit);
-        dp.itab = dit;
-    }
-    int* depoch;
-    FiltDesc* dfd;
-    double *dexp, *depocht, *dinvdy;
-    UP(hexp, dexp); UP(hepoch, depoch); UP(epochs, depocht);
-    {   // the image of the kernels' staged LDS (see kLdsHead / stage_tables)
-        std::vector<double2> himg(kLdsHead / 2, make_double2(0., 0.));
-        std::memcpy(himg.data(), hexp.data(), kExpTabSize * sizeof(double));
-        if (dp.tab_in_lds) {
-            himg.insert(himg.end(), htab.begin(), htab.begin() + dp.n_lds_tab);
-            const double2* fd2 = reinterpret_cast<const double2*>(hfd.data());
-            himg.insert(himg.end(), fd2, fd2 + kFdD2 * NF);
-            for (int k = 0; k < dp.n_itab_lds; k += 2) {
-                const double a = pr->itab_coef[k], b = pr->itab_coef[k + 1];
-                himg.push_back(make_double2(std::isfinite(a) ? a : 0., std::isfinite(b) ? b : 0.));
-            }
-            for (int k = 0; k < dp.n_spl_lds; k += 2) himg.push_back(make_double2(pr->spline_coef[k], pr->spline_coef[k + 1]));
-        }
-        double2* dimg;
-        UP(himg, dimg);
-        dp.stage_image = dimg;
-        dp.stage_n16 = (int)himg.size();
-    }
-    {   // observation and the factor its residual is scaled with, side by side
-        std::vector<double2> hyd(N);
-        for (int i = 0; i < N; ++i) hyd[i] = make_double2(hy[i], pr->use_sigma ? hdy[i] : hinvdy[i]);
-        double2* dyd;
-        UP(hyd, dyd);
-        dp.pt_yd = dyd;
-    }
-    if (epochs_ahead) {   // the epoch-major copy: [em_k][n_cols], a column's points in filter order
-        std::vector<double> hct(n_cols);
-        std::vector<double2> hcyd((size_t)em_k * n_cols, make_double2(0., 0.));
-        std::vector<int> hcf((size_t)em_k * n_cols, -1);
-        for (int cidx = 0; cidx < n_cols; ++cidx) {
-            const int ep = col_epoch[cidx];
-            hct[cidx] = epochs[ep];
-            for (int k = 0; k < em_k; ++k) {
-                const int at = col_first[cidx] + k;
-                if (at >= N || ep_of[em_order[at]] != ep) break;
-                const int o = em_order[at];
-                hcyd[(size_t)k * n_cols + cidx] = make_double2(pr->y[o], pr->use_sigma ? pr->dy[o] : 1. / pr->dy[o]);
-                hcf[(size_t)k * n_cols + cidx] = pr->filt_idx[o];
-            }
-        }
-        double* dct;
-        double2* dcyd;
-        int* dcf;
-        UP(hct, dct); UP(hcyd, dcyd); UP(hcf, dcf);
-        dp.em_t = dct;
-        dp.em_yd = dcyd;
-        dp.em_filt = dcf;
-    }
-    if (NF <= 64) {  // filter and epoch of a point in one word (epochs < 2^26 = the most points an engine takes)
-        std::vector<int> hfe(N);
-        for (int i = 0; i < N; ++i) hfe[i] = (int)((unsigned int)hfilt[i] | ((unsigned int)hepoch[i] << 6));
-        int* dfe;
-        UP(hfe, dfe);
-        dp.pt_fe = dfe;
-    }
-    UP(hfd, dfd); UP(hinvdy, dinvdy); UP(pcomp, e->d_ctab_off); UP(ptmin, e->d_ctmin);
-    dp.f_desc = dfd;
-    dp.inv_dy = dinvdy;
-    dp.pt_epoch = depoch;
-    dp.epoch_t = depocht;
-    dp.exp2tab = dexp;
-    if (companion) {
-        std::vector<double> hkn(pr->spline_knots, pr->spline_knots + pr->n_knots),
-            hsp(pr->spline_coef, pr->spline_coef + (size_t)NF * (pr->n_knots - 1) * 4);
-        for (int k = 1; k < pr->n_knots; ++k)
-            if (!(hkn[k] > hkn[k - 1])) return bail(fail(LCF_ERR_INVALID_ARGUMENT, "spline knots must ascend"));
-        const double h = (hkn.back() - hkn.front()) / (pr->n_knots - 1);
-        bool uniform = true;
-        for (int k = 0; k < pr->n_knots; ++k)
-            uniform = uniform && std::fabs(hkn[k] - (hkn.front() + k * h)) <= 1e-9 * h;
-        dp.knot_inv_h = uniform ? 1. / h : 0.;
-        // knots that ARE k0 + i h in float64 (SiFTO: integer days): interval by arithmetic, no knot read on the device
-        const double h1 = hkn[1] - hkn[0];
-        bool exact = pr->n_knots >= 2 && h1 > 0.;
-        for (int k = 0; exact && k < pr->n_knots; ++k) exact = hkn[k] == hkn[0] + k * h1;
-        dp.knot0 = hkn.front();
-        dp.knot_last = hkn.back();
-        dp.knot_h = exact ? h1 : 0.;
-        if (exact) dp.knot_inv_h = 1. / h1;
-        UP(hkn, dkn); UP(hsp, dspl);
-    }
-    if (pr->priors) {
-        std::vector<PriorDev> hp(n_dim);
-        for (int i = 0; i < n_dim; ++i) {
-            if (pr->priors[i].kind < 0 || pr->priors[i].kind > 2) return bail(fail(LCF_ERR_INVALID_ARGUMENT, "bad prior kind"));
-            hp[i] = PriorDev{pr->priors[i].kind, 0, pr->priors[i].p_min, pr->priors[i].p_max, pr->priors[i].mean,
-                             pr->priors[i].stddev};
-        }
-        UP(hp, dpri);
-    }
-#undef UP
-    dp.t = dt; dp.y = dy_; dp.dy = ddy; dp.pt_filt = dfilt; dp.pt_orig = dorig;
-    dp.tab = dtab;
-    dp.knots = dkn; dp.spl = dspl; dp.priors = dpri;
-    if ((st = arena.flush()) != LCF_OK) return bail(st);
-    if ((st = e->sync_dp()) != LCF_OK) return bail(st);
-    *out = e;
-    return LCF_OK;
-}
-
-void lcf_engine_destroy(lcf_engine* e) { delete e; }
-int32_t lcf_engine_ndim(const lcf_engine* e) { return e ? e->dp.n_dim : 0; }
-int64_t lcf_engine_npoints(const lcf_engine* e) { return e ? e->dp.n_points : 0; }
-int64_t lcf_engine_samples_per_eval(const lcf_engine* e) { return e ? e->samples_per_eval : 0; }
-
-lcf_status lcf_engine_set_variant(lcf_engine* e, int32_t variant) {
-    if (!e || variant < 0 || variant > 3) return fail(LCF_ERR_INVALID_ARGUMENT, "variant must be 0, 1, 2 or 3");
-    if (variant >= 2 && !e->have_ctab) return fail(LCF_ERR_INVALID_ARGUMENT, "no compressed tables were given");
-    if (variant == 3 && !e->have_itab) return fail(LCF_ERR_INVALID_ARGUMENT, "no interpolants were given");
-    e->dp.variant = variant == 0 ? 0 : 1;
-    e->dp.use_ctab = variant >= 2 ? 1 : 0;
-    e->dp.use_itab = variant == 3 ? 1 : 0;
-    LCF_HIP(hipSetDevice(e->device));
-    LCF_HIP(hipStreamSynchronize(e->stream));   // (launches in flight read the old copy)
-    return e->sync_dp();
-}
-
 lcf_status lcf_log_likelihood(lcf_engine* e, int64_t n, const double* P, double* out) {
     return logprob_host(e, n, P, out, 0);
 }

@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "lcf.h"
@@ -106,9 +108,26 @@ struct UploadArena {
     }
 };
 
-template <class T>
-lcf_status upload(const std::vector<T>& h, T** d, UploadArena& arena) {
+// `h` into an arena (put(src, bytes, &place): UploadArena, or one that only looks at the bytes); *d: its place.
+template <class Arena, class T, class P>
+lcf_status put_array(Arena& arena, const std::vector<T>& h, P** d) {
+    static_assert(std::is_same<typename std::remove_const<P>::type, T>::value, "the array's own element type");
     return arena.put(h.data(), h.size() * sizeof(T), (void**)d);
+}
+
+// One filter's band-table samples (a_k, W_k), k in [k0, k1), behind `tab`, padded to a multiple of four samples with
+// zero weights (exactly 0 contribution); *off, *cnt: where they are and how many with the padding.  False: a sample
+// that is not a finite a_k > 0 with a finite W_k.
+inline bool append_quads(std::vector<double2>& tab, const double* a, const double* w, int k0, int k1, int* off, int* cnt) {
+    *off = (int)tab.size();
+    for (int k = k0; k < k1; ++k) {
+        if (!(a[k] > 0.) || !std::isfinite(a[k]) || !std::isfinite(w[k])) return false;
+        tab.push_back(make_double2(a[k], w[k]));
+    }
+    const double apad = k1 > k0 ? a[k1 - 1] : 1.;
+    while ((tab.size() - *off) % 4) tab.push_back(make_double2(apad, 0.));
+    *cnt = (int)tab.size() - *off;
+    return true;
 }
 
 // ---- what a chain analysis is made of --------------------------------------------------------------------------------

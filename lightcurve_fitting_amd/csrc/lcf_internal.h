@@ -1,6 +1,7 @@
-// What lcf_hip.hip (kernels, engine, launches, runs over ranks and populations), lcf_sampler.hip (the bookkeeping of
-// runs) and lcf_tempered.hip (the tempered driver beside the sampler) share: what the sampler's kernels and the host
-// exchange, the engine and the sampler behind the C ABI's opaque pointers, and the host functions that cross the files.
+// What lcf_hip.hip (kernels, launches, runs over ranks and populations), lcf_engine.hip (engine creation), lcf_sampler.hip
+// (the bookkeeping of runs) and lcf_tempered.hip (the tempered driver beside the sampler) share: what the sampler's
+// kernels and the host exchange, the engine and the sampler behind the C ABI's opaque pointers, and the host functions
+// that cross the files.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -295,6 +296,8 @@ namespace lcf {
 // polled_alloc: `bytes` of it on the current device, cleared (complete on return).
 void polled_give(int dev, bool uncached, size_t bytes, void* p);
 lcf_status polled_alloc(int dev, bool uncached, size_t bytes, void** out);
+// lcf_engine.hip: an engine on `device` with nothing in it yet -- the device current, its compute units, its stream.
+lcf_status engine_shell(int32_t device, std::unique_ptr<lcf_engine>* out);
 // lcf_custom.hip: engines of LCF_MODEL_CUSTOM.  custom_refuse: LCF_ERR_UNSUPPORTED, naming the supported route, for what is
 // compiled per model (`what` names the caller); LCF_OK for every other engine.
 lcf_status custom_refuse(const lcf_engine* e, const char* what);

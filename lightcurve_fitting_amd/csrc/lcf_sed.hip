@@ -399,22 +399,11 @@ lcf_status lcf_sed_create(int32_t n_filters, const int32_t* tab_off, const doubl
     std::vector<float2> htab32;
     std::vector<int4> hdesc(n_filters);
     std::vector<double> hinvt(n_filters, 0.);
-    auto append = [&](const double* a, const double* w, int k0, int k1, int& off, int& cnt) -> bool {
-        off = (int)htab.size();
-        for (int k = k0; k < k1; ++k) {
-            if (!(a[k] > 0.) || !std::isfinite(a[k]) || !std::isfinite(w[k])) return false;
-            htab.push_back(make_double2(a[k], w[k]));
-        }
-        const double apad = k1 > k0 ? a[k1 - 1] : 1.;
-        while ((htab.size() - off) % 4) htab.push_back(make_double2(apad, 0.));
-        cnt = (int)htab.size() - off;
-        return true;
-    };
     for (int f = 0; f < n_filters; ++f) {
         int4 d = make_int4(0, 0, 0, 0);
-        bool ok = append(tab_a, tab_w, tab_off[f], tab_off[f + 1], d.x, d.y);
+        bool ok = append_quads(htab, tab_a, tab_w, tab_off[f], tab_off[f + 1], &d.x, &d.y);
         if (ok && have_ctab && ctab_off[f + 1] > ctab_off[f]) {
-            ok = append(ctab_a, ctab_w, ctab_off[f], ctab_off[f + 1], d.z, d.w) && ctab_tmin[f] >= 0.;
+            ok = append_quads(htab, ctab_a, ctab_w, ctab_off[f], ctab_off[f + 1], &d.z, &d.w) && ctab_tmin[f] >= 0.;
             hinvt[f] = 1. / ctab_tmin[f];
         }
         if (!ok) return fail(LCF_ERR_INVALID_ARGUMENT, "band tables need finite a_k > 0, finite W_k, t_min >= 0");
@@ -439,7 +428,7 @@ lcf_status lcf_sed_create(int32_t n_filters, const int32_t* tab_off, const doubl
             const double a = itab_coef[2 * k], b = itab_coef[2 * k + 1];
             hitab[k] = make_double2(std::isfinite(a) ? a : 0., std::isfinite(b) ? b : 0.);
         }
-        for (int f = 0; f < n_filters; ++f)   // (the same threshold the light-curve engine uses: lcf_engine_create)
+        for (int f = 0; f < n_filters; ++f)   // (the same threshold the light-curve engine uses: pack_tables, lcf_plan.h)
             if (std::isfinite(itab_tmin[f]))
                 s->rmin[f] = std::nextafter((float)std::max((std::log(itab_tmin[f]) - itab_u0) / itab_h, 0.), INFINITY);
     }

@@ -251,6 +251,76 @@ def _handles(native_samplers):
     return (C.c_void_p * len(native_samplers))(*[s._h for s in native_samplers])
 
 
+def make_problem(model_id, n_par, consts, t, y, dy, filt_idx, tab_off, tab_a, tab_w, use_sigma=False,
+                 sigma_type=SIGMA_RELATIVE, priors=None, companion=None, ctab=None, tab_ext=None, htab=None, itab=None):
+    """``(problem, keep)``: the ``lcf_problem`` of :class:`Engine`'s arguments and the arrays its pointers point into
+    (``keep`` must live as long as the problem is used)."""
+    no_filters = tab_off is None
+    if no_filters:
+        filt_idx, tab_off, tab_a, tab_w = np.zeros(len(_f64(t)), dtype=np.int32), [0], [], []
+    keep = [_f64(t), _f64(y), _f64(dy), _i32(filt_idx), _i32(tab_off), _f64(tab_a), _f64(tab_w)]
+    pr = LcfProblem()
+    pr.abi_version = LCF_ABI_VERSION
+    pr.model = int(model_id)
+    pr.n_par = int(n_par)
+    pr.use_sigma = int(bool(use_sigma))
+    pr.sigma_type = int(sigma_type)
+    pr.n_filters = len(keep[4]) - 1
+    pr.n_points = len(keep[0])
+    if not (len(keep[1]) == len(keep[2]) == len(keep[3]) == pr.n_points):
+        raise ValueError('t, y, dy, filt_idx must have the same length')
+    cs = list(consts) + [0.] * (N_CONSTS - len(consts))
+    pr.consts = (C.c_double * N_CONSTS)(*cs)
+    pr.t, pr.y, pr.dy = _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2])
+    if not no_filters:
+        pr.filt_idx, pr.tab_off = _ptr(keep[3], _ip), _ptr(keep[4], _ip)
+        pr.tab_a, pr.tab_w = _ptr(keep[5]), _ptr(keep[6])
+    if tab_ext is not None:  # A_lambda / E(B-V) per table sample (ShockCooling3)
+        ext = _f64(tab_ext)
+        if len(ext) != len(keep[5]):
+            raise ValueError('tab_ext must have one entry per table sample')
+        keep.append(ext)
+        pr.tab_ext = _ptr(ext)
+    if ctab is not None:  # (coff, ca, cw, ctmin): Gauss-compressed companions of the band tables
+        cx = [_i32(ctab[0]), _f64(ctab[1]), _f64(ctab[2]), _f64(ctab[3])]
+        if len(cx[0]) != pr.n_filters + 1 or len(cx[3]) != pr.n_filters or len(cx[1]) != len(cx[2]):
+            raise ValueError('inconsistent compressed tables')
+        keep += cx
+        pr.ctab_off, pr.ctab_a, pr.ctab_w, pr.ctab_tmin = _ptr(cx[0], _ip), _ptr(cx[1]), _ptr(cx[2]), _ptr(cx[3])
+    if htab is not None:  # (hoff, ha, hw, htmin): the shorter "hot" level (needs ctab)
+        hx = [_i32(htab[0]), _f64(htab[1]), _f64(htab[2]), _f64(htab[3])]
+        if len(hx[0]) != pr.n_filters + 1 or len(hx[3]) != pr.n_filters or len(hx[1]) != len(hx[2]):
+            raise ValueError('inconsistent hot-level tables')
+        keep += hx
+        pr.htab_off, pr.htab_a, pr.htab_w, pr.htab_tmin = _ptr(hx[0], _ip), _ptr(hx[1]), _ptr(hx[2]), _ptr(hx[3])
+    if itab is not None:  # (coef[n_filters, m, 8], tmin[n_filters], u0, h): interpolants of ln S(ln T)
+        ic, it = _f64(itab[0]), _f64(itab[1])
+        if ic.ndim != 3 or ic.shape[0] != pr.n_filters or ic.shape[2] != 8 or it.shape != (pr.n_filters,):
+            raise ValueError('inconsistent interpolant tables')
+        keep += [ic, it]
+        pr.itab_coef, pr.itab_tmin, pr.itab_m = _ptr(ic), _ptr(it), ic.shape[1]
+        pr.itab_u0, pr.itab_h = float(itab[2]), float(itab[3])
+    if companion is not None:
+        kp, sp, dtp, knots, coef = companion
+        extra = [_i32(kp), _i32(sp), _i32(dtp), _f64(knots), _f64(coef)]
+        if extra[4].shape != (pr.n_filters, len(extra[3]) - 1, 4):
+            raise ValueError('spline_coef must have shape (n_filters, n_knots - 1, 4)')
+        keep += extra
+        pr.filt_kasen_par, pr.filt_sifto_par, pr.filt_dt_par = (_ptr(x, _ip) for x in extra[:3])
+        pr.n_knots = len(extra[3])
+        pr.spline_knots, pr.spline_coef = _ptr(extra[3]), _ptr(extra[4])
+    n_dim = pr.n_par + pr.use_sigma
+    if priors is not None:
+        if len(priors) != n_dim:
+            raise ValueError(f'priors must have length {n_dim}')
+        arr = (LcfPrior * n_dim)()
+        for i, (kind, lo, hi, mean, std) in enumerate(priors):
+            arr[i].kind, arr[i].p_min, arr[i].p_max, arr[i].mean, arr[i].stddev = int(kind), lo, hi, mean, std
+        keep.append(arr)
+        pr.priors = arr
+    return pr, keep
+
+
 class Engine:
     """One light curve + one model instance resident on one MI355X.
 
@@ -261,80 +331,22 @@ class Engine:
     def __init__(self, model_id, n_par, consts, t, y, dy, filt_idx, tab_off, tab_a, tab_w, use_sigma=False,
                  sigma_type=SIGMA_RELATIVE, priors=None, companion=None, device=0, ctab=None, tab_ext=None,
                  htab=None, itab=None):
-        lib = load_library()
-        self._lib = lib
+        self._lib = load_library()
         self._h = C.c_void_p()
-        no_filters = tab_off is None
-        if no_filters:
-            filt_idx, tab_off, tab_a, tab_w = np.zeros(len(_f64(t)), dtype=np.int32), [0], [], []
-        keep = [_f64(t), _f64(y), _f64(dy), _i32(filt_idx), _i32(tab_off), _f64(tab_a), _f64(tab_w)]
-        pr = LcfProblem()
-        pr.abi_version = LCF_ABI_VERSION
-        pr.model = int(model_id)
-        pr.n_par = int(n_par)
-        pr.use_sigma = int(bool(use_sigma))
-        pr.sigma_type = int(sigma_type)
-        pr.n_filters = len(keep[4]) - 1
-        pr.n_points = len(keep[0])
-        if not (len(keep[1]) == len(keep[2]) == len(keep[3]) == pr.n_points):
-            raise ValueError('t, y, dy, filt_idx must have the same length')
-        cs = list(consts) + [0.] * (N_CONSTS - len(consts))
-        pr.consts = (C.c_double * N_CONSTS)(*cs)
-        pr.t, pr.y, pr.dy = _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2])
-        if not no_filters:
-            pr.filt_idx, pr.tab_off = _ptr(keep[3], _ip), _ptr(keep[4], _ip)
-            pr.tab_a, pr.tab_w = _ptr(keep[5]), _ptr(keep[6])
-        if tab_ext is not None:  # A_lambda / E(B-V) per table sample (ShockCooling3)
-            ext = _f64(tab_ext)
-            if len(ext) != len(keep[5]):
-                raise ValueError('tab_ext must have one entry per table sample')
-            keep.append(ext)
-            pr.tab_ext = _ptr(ext)
-        if ctab is not None:  # (coff, ca, cw, ctmin): Gauss-compressed companions of the band tables
-            cx = [_i32(ctab[0]), _f64(ctab[1]), _f64(ctab[2]), _f64(ctab[3])]
-            if len(cx[0]) != pr.n_filters + 1 or len(cx[3]) != pr.n_filters or len(cx[1]) != len(cx[2]):
-                raise ValueError('inconsistent compressed tables')
-            keep += cx
-            pr.ctab_off, pr.ctab_a, pr.ctab_w, pr.ctab_tmin = _ptr(cx[0], _ip), _ptr(cx[1]), _ptr(cx[2]), _ptr(cx[3])
-        if htab is not None:  # (hoff, ha, hw, htmin): the shorter "hot" level (needs ctab)
-            hx = [_i32(htab[0]), _f64(htab[1]), _f64(htab[2]), _f64(htab[3])]
-            if len(hx[0]) != pr.n_filters + 1 or len(hx[3]) != pr.n_filters or len(hx[1]) != len(hx[2]):
-                raise ValueError('inconsistent hot-level tables')
-            keep += hx
-            pr.htab_off, pr.htab_a, pr.htab_w, pr.htab_tmin = _ptr(hx[0], _ip), _ptr(hx[1]), _ptr(hx[2]), _ptr(hx[3])
-        if itab is not None:  # (coef[n_filters, m, 8], tmin[n_filters], u0, h): interpolants of ln S(ln T)
-            ic, it = _f64(itab[0]), _f64(itab[1])
-            if ic.ndim != 3 or ic.shape[0] != pr.n_filters or ic.shape[2] != 8 or it.shape != (pr.n_filters,):
-                raise ValueError('inconsistent interpolant tables')
-            keep += [ic, it]
-            pr.itab_coef, pr.itab_tmin, pr.itab_m = _ptr(ic), _ptr(it), ic.shape[1]
-            pr.itab_u0, pr.itab_h = float(itab[2]), float(itab[3])
-        if companion is not None:
-            kp, sp, dtp, knots, coef = companion
-            extra = [_i32(kp), _i32(sp), _i32(dtp), _f64(knots), _f64(coef)]
-            if extra[4].shape != (pr.n_filters, len(extra[3]) - 1, 4):
-                raise ValueError('spline_coef must have shape (n_filters, n_knots - 1, 4)')
-            keep += extra
-            pr.filt_kasen_par, pr.filt_sifto_par, pr.filt_dt_par = (_ptr(x, _ip) for x in extra[:3])
-            pr.n_knots = len(extra[3])
-            pr.spline_knots, pr.spline_coef = _ptr(extra[3]), _ptr(extra[4])
-        n_dim = pr.n_par + pr.use_sigma
-        if priors is not None:
-            if len(priors) != n_dim:
-                raise ValueError(f'priors must have length {n_dim}')
-            arr = (LcfPrior * n_dim)()
-            for i, (kind, lo, hi, mean, std) in enumerate(priors):
-                arr[i].kind, arr[i].p_min, arr[i].p_max, arr[i].mean, arr[i].stddev = int(kind), lo, hi, mean, std
-            keep.append(arr)
-            pr.priors = arr
-        _check(lib.lcf_engine_create(C.byref(pr), int(device), C.byref(self._h)))
-        self.ndim = n_dim
+        pr, _keep = make_problem(model_id, n_par, consts, t, y, dy, filt_idx, tab_off, tab_a, tab_w, use_sigma,
+                                 sigma_type, priors, companion, ctab, tab_ext, htab, itab)
+        self.ndim = pr.n_par + pr.use_sigma
         self.npoints = pr.n_points
         self.nfilters = pr.n_filters
         #: the prior descriptors the engine was created with (None: none)
         self.priors = None if priors is None else [tuple(p) for p in priors]
         self.device = int(device)
-        self.samples_per_eval = lib.lcf_engine_samples_per_eval(self._h)
+        self._create(pr)
+
+    def _create(self, pr):
+        """The native engine of ``pr`` on ``self.device`` (the engine copies what it keeps of the problem)."""
+        _check(self._lib.lcf_engine_create(C.byref(pr), self.device, C.byref(self._h)))
+        self.samples_per_eval = self._lib.lcf_engine_samples_per_eval(self._h)
 
     def close(self):
         h = getattr(self, '_h', None)

@@ -14,6 +14,7 @@ The reference of every case is ``O.stretch_move_run(oracle_log_posterior(pb), ..
 Run as a program (a fresh process per process-wide switch: ``LCF_NO_SOLO=1 python tests/sampler_cases.py 6:auto ...``)
 it prints one JSON line per ``case:form`` with the SHA-256 of the chain, log-probabilities, counts and state."""
 import contextlib
+import ctypes as C
 import hashlib
 import json
 import os
@@ -299,16 +300,63 @@ def engine_keywords(case):
     return dict(use_sigma=True, sigma_type=case.sigma) if case.sigma else {}
 
 
-def make_engine(case, nwalkers=None):
-    """A new engine of the case: LCF_PARTS is read when it is created, the band-sum level is set on it."""
+def _create_engine(case, nwalkers=None):
+    """``(engine, model)`` of the case as it is created: LCF_PARTS is read then."""
     h = host(case, nwalkers)
     model, lc = make_model(case, h)
     with environment(LCF_PARTS=None if case.parts is None else str(case.parts)):
-        eng = model.engine_for(lc, priors=case.priors, **engine_keywords(case))
+        return model.engine_for(lc, priors=case.priors, **engine_keywords(case)), model
+
+
+def make_engine(case, nwalkers=None):
+    """A new engine of the case, the band-sum level set on it."""
+    eng, model = _create_engine(case, nwalkers)
     if case.variant != 3:
         eng.set_variant(case.variant)
     eng.model = model    # (keeps the model, and with it its cache of engines, alive as long as the engine)
     return eng
+
+
+# the integers of lcf_debug_engine_layout (csrc/lcf_engine.hip), in its order; part_start, part_col0, part_ep0 follow
+LAYOUT_FIELDS = ('n_points', 'n_epochs', 'use_therm', 'em_k', 'em_cols', 'em_dense', 'n_parts', 'n_chunks', 'cpb',
+                 'n_tab', 'n_lds_tab', 'tab_in_lds', 'redden_slow', 'use_ctab', 'use_itab', 'itab_uniform',
+                 'n_itab_lds', 'n_spl_lds', 'stage_d2', 'stage_n16')
+
+
+def problem_layout(pr):
+    """The layout ``lcf_engine_create`` plans for an ``LcfProblem``, computed without a device: the fields above, the
+    three arrays of the parts (nine entries each) and ``hash``, FNV-1a over every array the engine would upload."""
+    fn = E.load_library().lcf_debug_engine_layout
+    fn.restype, fn.argtypes = C.c_int32, [C.POINTER(E.LcfProblem), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64)]
+    n = len(LAYOUT_FIELDS)
+    out, h = (C.c_int32 * (n + 27))(), C.c_uint64()
+    E._check(fn(C.byref(pr), out, len(out), C.byref(h)))
+    return dict(zip(LAYOUT_FIELDS, out[:n]), part_start=out[n:n + 9], part_col0=out[n + 9:n + 18],
+                part_ep0=out[n + 18:n + 27], hash=h.value)
+
+
+@contextlib.contextmanager
+def planned_engines():
+    """Inside, ``E.Engine`` asks for no device: every engine's problem is planned only, and its layout appended to the
+    list this yields.  (Such an engine has no native handle: nothing can be evaluated with it.)"""
+    layouts = []
+
+    def plan(self, pr):
+        layouts.append(problem_layout(pr))
+        self._h = None
+    create, E.Engine._create = E.Engine._create, plan
+    try:
+        yield layouts
+    finally:
+        E.Engine._create = create
+
+
+def engine_layout(case):
+    """The layout of the case's engine as the library plans it (:func:`engine_shape` restates the rules)."""
+    with planned_engines() as layouts:
+        _create_engine(case)
+    assert len(layouts) == 1
+    return layouts[0]
 
 
 def run_single(case, form, engine=None):
@@ -439,7 +487,7 @@ def engine_shape(case):
         n_lds = 0
     itmin = tabs.interpolants()[1]
     return dict(n_points=n_pts, n_filters=nf, n_epochs=len(epochs), em_k=em_k, n_cols=n_cols, em_dense=bool(dense),
-                n_parts=len(start), tab_in_lds=n_lds > 0, have_itab=not reddened, filters=uniq, itab_tmin=itmin,
+                n_parts=len(start), start=start, tab_in_lds=n_lds > 0, have_itab=not reddened, filters=uniq, itab_tmin=itmin,
                 itab_uniform=bool(not reddened and np.all(itmin <= np.exp(tabs.iu0) * (1. + 1e-12))), counts=cnt,
                 names=names, t=t)
 

@@ -187,6 +187,23 @@ def test_engine_argument_validation_precedes_device_use():
         M.ShockCooling().make_engine([1.], ['g'], [1.], [1.], sigma_type='bogus')
     assert lib.lcf_log_likelihood(None, 1, None, None) == 1
     assert lib.lcf_sampler_create(None, 4, 0, 2.0, ctypes.byref(h)) == 1
+    # ... and so does every check of the tables, the knots and the priors: LCF_ERR_INVALID_ARGUMENT and its message
+    # wherever the test runs, never LCF_ERR_NO_DEVICE
+    base = dict(model_id=E.MODEL_SHOCK_COOLING, n_par=5, consts=[], t=[1., 2.], y=[1., 1.], dy=[1., 1.], filt_idx=[0, 0],
+                tab_off=[0, 2], tab_a=[1., 2.], tab_w=[1., 1.])
+    ctab = ([0, 1], [1.], [1.], [1.])
+    bad_coef = np.zeros((1, 4, 8))
+    bad_coef[0, 2, 5] = np.inf
+    companion = dict(base, model_id=E.MODEL_COMPANION_SHOCKING, n_par=8)
+    for message, kw in (
+            ('non-finite interpolant coefficient', dict(base, itab=(bad_coef, [1.], 0.5, 0.1))),
+            ('<= 252 samples a filter', dict(base, ctab=ctab, htab=([0, 253], np.ones(253), np.ones(253), [2.]))),
+            ('band tables need finite a_k > 0 and finite W_k', dict(base, tab_a=[1., 0.])),
+            ('spline knots must ascend', dict(companion, companion=([-1], [-1], [-1], [0., 2., 1.], np.zeros((1, 2, 4))))),
+            ('bad prior kind', dict(base, priors=[(3, 0., 1., 0., 1.)] * 5))):
+        pr, _keep = E.make_problem(**kw)
+        assert lib.lcf_engine_create(ctypes.byref(pr), 0, ctypes.byref(h)) == 1, message
+        assert message.encode() in lib.lcf_last_error()
 
 
 def test_rng_and_shards():
