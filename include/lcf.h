@@ -415,6 +415,35 @@ lcf_status lcf_sampler_predict_quantiles(lcf_engine* grid, lcf_sampler* s, int64
                                          int32_t component, const double* q, int32_t n_q, int64_t workspace_bytes,
                                          double* out, int64_t* n_valid);
 
+/* ---- colour bands and per-band peaks: the model's colours with their uncertainty, over ALL samples ---------------- */
+/* `grid` is an evaluation engine on the dense grid, filter-major: point f * n_times + t is filter f of the engine at
+ * the t-th of n_times distinct times (dummy photometry, no sigma, no priors; at most 16 filters).  Colour c is the pair
+ * of engine filters a = pairs[2 c], b = pairs[2 c + 1] with the zero-point difference dzp[c] = m0_a - m0_b.  With
+ * Y[f][t][s] the model value lcf_predict_quantiles ranks,
+ *     C[c][t][s] = dzp[c] - 2.5 log10(Y[a][t][s] / Y[b][t][s])   if both values are finite and > 0, else NaN
+ * (not exploded yet: Y == 0; NaN; a negative SiFTO tail), and out / n_valid are the percentiles and non-NaN counts of C
+ * over the samples (definition, workspace, tiling and reproducibility as for lcf_predict_quantiles; n_c * n_q <= 512).
+ * Every filter is evaluated once per (sample, time) and pass, whatever the number of colours it occurs in.
+ * y_peak / peak_index (both or neither): per filter and sample the largest non-NaN Y over the times walked in ascending
+ * order and the caller's index t of the first time it is attained (strict >; NaN and -1 when every value is NaN; 0 at
+ * the earliest time for a sample that has not exploded anywhere).  The two arrays are results per sample and lie OUTSIDE
+ * workspace_bytes: 12 n_filters n bytes of device memory while the call runs.
+ * Every argument is checked before a device is asked for: a pair index outside the engine's filters is
+ * LCF_ERR_INVALID_ARGUMENT; n_c * n_q > 512, more than 16 filters, and an engine of LCF_MODEL_CUSTOM or of a
+ * central-engine model are LCF_ERR_UNSUPPORTED (the last two naming the route such an engine does take).
+ * Over n host samples P[n][ld] (the first n_par columns are used): */
+lcf_status lcf_predict_colors(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t n_c,
+                              const int32_t* pairs /* [n_c][2] */, const double* dzp /* [n_c] */, const double* q,
+                              int32_t n_q, int64_t workspace_bytes, double* out /* [n_q][n_c][n_times] */,
+                              int64_t* n_valid /* [n_c][n_times] */, double* y_peak /* [n_filters][n] or NULL */,
+                              int32_t* peak_index /* [n_filters][n] or NULL */);
+/* The same over rows discard, discard + thin, ... of the sampler's last stored run, read in place; status codes as
+ * for lcf_sampler_predict_quantiles. */
+lcf_status lcf_sampler_predict_colors(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, int32_t n_c,
+                                      const int32_t* pairs, const double* dzp, const double* q, int32_t n_q,
+                                      int64_t workspace_bytes, double* out, int64_t* n_valid, double* y_peak,
+                                      int32_t* peak_index);
+
 /* ---- thermal bands and validity: T, R_bb, L_bol of the blackbody behind the light curves, over ALL samples -------- */
 /* `grid` is an evaluation engine with one point per distinct time and any single filter (what temperature_radius is
  * evaluated on); the model is any but LCF_MODEL_BLACKBODY.  Per (sample, time): T [kK] and R_bb [1000 Rsun] as

@@ -40,6 +40,14 @@
 // its state function once per (sample, time) and writes the keys of every filter's light curve, T, R and L
 // (lcf_custom_keys, lcf_custom_kernel.h), keys[tile time][series][n].  A (time, series) pair is a selection unit --
 // what a time is to k_kq_pass, which reads the keys as it reads the luminosity form's -- and a tile is whole times.
+// The colour form (DESIGN.md "Colour bands and peaks") recomputes, as the light-curve form does, but its selection units
+// are colours, not filters:
+//   k_cq_pass     the geometry and modes of k_pq_pass: thermal state once per (sample, time), every filter of the grid
+//                 ONCE into LDS as [filter][lane], then per colour (a, b) the value
+//                 (m0_a - m0_b) - 2.5 log10(Y_a / Y_b) -- NaN unless both are finite and > 0 -- as series c of the time.
+//   k_cq_peak     lane = sample: walks the tile's times in ascending order, recomputes the filters' values and keeps
+//                 per filter the sample's largest non-NaN value and the first time it is attained (strict >), in LDS
+//                 as [filter][lane]; read from and written to device memory across tiles, as k_lq_peak's are.
 // k_pq_pick and k_pq_finish serve all forms; the host driver (quantile_run) differs in the launches only.
 #include <hip/hip_runtime.h>
 
@@ -332,6 +340,136 @@ __global__ __launch_bounds__(kPqThreads) void k_pq_pass(const DevProblem pb, con
     }
     __syncthreads();
     pq_merge(a, lds, search, ns, n_hist, tid);
+}
+
+// ---- the colour form: the filters of a time once, the colours between them as its series -----------------------------
+constexpr int kCqMaxFilters = 16;          // filters of a colour call: 4 KiB of LDS each in a pass workgroup
+constexpr int kCqPeakThreads = 256;
+constexpr size_t kCqLdsPerCU = 160 * 1024; // LDS of a gfx950 CU: what a pass workgroup's words must stay under
+
+struct CqArgs {
+    const int* pairs;            // [n_c][2]: the colour's two filters of the engine
+    const double* dzp;           // [n_c]: m0_a - m0_b
+    int n_c;
+};
+
+struct CqPeak {
+    double* best;                // [n_filters][n] largest non-NaN value so far (meaningless while at is -1)
+    int* at;                     // [n_filters][n] the first epoch it was attained at, -1: none yet
+    int n_ep;                    // times of the tile
+};
+
+// The thermal state of (sample, time) in the encoding pq_point reads: what k_pq_pass computes in front of its filters.
+template <int MODEL>
+__device__ __forceinline__ void cq_state(const DevProblem& pb, const double* __restrict__ c, double t_in, bool log_state,
+                                         const ExpTab et, double& x, double& p) {
+    x = -0.;
+    p = 0.;
+    if (log_state) {
+        thermal_state_log<MODEL>(pb, c, t_in, x, p, et);
+    } else {
+        double T, invT, pref;
+        thermal_state<MODEL>(pb, c, t_in, T, invT, pref);
+        encode_linear(invT, pref, x, p);
+    }
+}
+
+// The colour of two model values in magnitudes; NaN unless both are finite and positive (not exploded yet: 0; NaN; a
+// negative SiFTO tail).  Two roundings, as the NumPy expression has.
+__device__ __forceinline__ double cq_color(double ya, double yb, double dzp) {
+    const bool ok = ya > 0. && yb > 0. && ya < INFINITY && yb < INFINITY;
+    return ok ? __dsub_rn(dzp, __dmul_rn(2.5, log10(ya / yb))) : qnan();
+}
+
+// blockIdx.x = time of the tile, blockIdx.y = chunk of samples.  Dynamic LDS: exp table | the filters' values of every
+// lane, [filter][lane] (a lane reads what it wrote: no barrier) | per search prefix, successor, prefix bits, collect
+// flag | histogram counters.
+template <int MODEL>
+__global__ __launch_bounds__(kPqThreads) void k_cq_pass(const DevProblem pb, const PqArgs a, const CqArgs cq) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nf = pb.n_filters, nc = cq.n_c, ns = nc * a.n_q;
+    double* exptab = reinterpret_cast<double*>(smem);
+    double* yv = exptab + kExpTabSize;
+
+    const int model = MODEL ? MODEL : pb.model;
+    const bool companion = model >= kCompanion && model <= kCompanion3;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ep = a.ep0 + blockIdx.x;
+    const int n_hist = a.mode == 0 ? nc << a.bits : a.mode == 1 ? ns << a.bits : 0;
+    PqSearch* search = a.search + (size_t)blockIdx.x * ns;
+    for (int k = tid; k < kExpTabSize; k += kPqThreads) exptab[k] = pb.exp2tab[k];
+    const PqLds lds = pq_lds_setup(a, yv + (size_t)nf * kPqThreads, search, ns, n_hist, tid);
+    __syncthreads();
+
+    const ExpTab et{exptab};
+    const double t_in = pb.epoch_t[ep];
+    const bool log_state = pb.variant != 0 && pb.use_itab && model != kShockCooling3;
+    const unsigned int mask = (1u << a.bits) - 1u;
+    const long long s0 = (long long)blockIdx.y * a.chunk, s1 = min(a.n, s0 + a.chunk);
+    for (long long sb = s0; sb < s1; sb += kPqThreads) {
+        const long long s = sb + tid;
+        if (s >= s1) continue;
+        double c[kNCoef];
+#pragma unroll
+        for (int i = 0; i < kNCoef; ++i) c[i] = a.coef[(long long)i * a.n + s];
+        const double* prow = companion ? pq_row(a, s) : a.base;
+        double x, p;
+        cq_state<MODEL>(pb, c, t_in, log_state, et, x, p);
+        for (int f = 0; f < nf; ++f) yv[f * kPqThreads + tid] = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, 0);
+        for (int k = 0; k < nc; ++k) {
+            const double ya = yv[cq.pairs[2 * k] * kPqThreads + tid], yb = yv[cq.pairs[2 * k + 1] * kPqThreads + tid];
+            pq_consume(a, lds, search, ns, k, cq_color(ya, yb, cq.dzp[k]), lane, mask);
+        }
+    }
+    __syncthreads();
+    pq_merge(a, lds, search, ns, n_hist, tid);
+}
+
+// blockIdx.x = chunk of kCqPeakThreads samples, lanes = samples.  Dynamic LDS: best[filter][lane] | at[filter][lane].
+template <int MODEL>
+__global__ __launch_bounds__(kCqPeakThreads) void k_cq_peak(const DevProblem pb, const PqArgs a, const CqPeak pk) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double exptab[kExpTabSize];
+    const int nf = pb.n_filters;
+    double* best = reinterpret_cast<double*>(smem);
+    int* at = reinterpret_cast<int*>(best + (size_t)nf * kCqPeakThreads);
+
+    const int model = MODEL ? MODEL : pb.model;
+    const bool companion = model >= kCompanion && model <= kCompanion3;
+    const int tid = threadIdx.x;
+    for (int k = tid; k < kExpTabSize; k += kCqPeakThreads) exptab[k] = pb.exp2tab[k];
+    __syncthreads();
+    const long long s = (long long)blockIdx.x * kCqPeakThreads + tid;
+    if (s >= a.n) return;
+
+    const ExpTab et{exptab};
+    const bool log_state = pb.variant != 0 && pb.use_itab && model != kShockCooling3;
+    double c[kNCoef];
+#pragma unroll
+    for (int i = 0; i < kNCoef; ++i) c[i] = a.coef[(long long)i * a.n + s];
+    const double* prow = companion ? pq_row(a, s) : a.base;
+    for (int f = 0; f < nf; ++f) {
+        best[f * kCqPeakThreads + tid] = pk.best[(long long)f * a.n + s];
+        at[f * kCqPeakThreads + tid] = pk.at[(long long)f * a.n + s];
+    }
+    for (int i = 0; i < pk.n_ep; ++i) {
+        const int ep = a.ep0 + i;
+        const double t_in = pb.epoch_t[ep];
+        double x, p;
+        cq_state<MODEL>(pb, c, t_in, log_state, et, x, p);
+        for (int f = 0; f < nf; ++f) {
+            const double v = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, 0);
+            const int k = f * kCqPeakThreads + tid;
+            if (v == v && (at[k] < 0 || v > best[k])) {   // (as k_lq_peak: the first occurrence wins)
+                best[k] = v;
+                at[k] = ep;
+            }
+        }
+    }
+    for (int f = 0; f < nf; ++f) {
+        pk.best[(long long)f * a.n + s] = best[f * kCqPeakThreads + tid];
+        pk.at[(long long)f * a.n + s] = at[f * kCqPeakThreads + tid];
+    }
 }
 
 // ---- the thermal form: T, R_bb, L_bol as the three series of a time, and the validity counters -----------------------
@@ -643,6 +781,7 @@ struct PqForm {
     size_t sample_bytes;   // device memory per sample ...
     size_t time_bytes;     // ... and per time of the whole grid, beyond what every form needs
     size_t tile_bytes = 0; // ... and per time of a TILE, beyond the searches' (the stored keys)
+    size_t call_bytes = 0; // ... and per call (the colour form's pairs and zero-point differences)
     int gran = 1;          // a tile is a whole multiple of this many "times" (the custom form's units of one time)
     size_t lds_head;       // dynamic LDS of a pass in front of the searches' words and the histograms
     bool coef = true;      // the samples' walker_coefficients are wanted ([kNCoef][n], part of sample_bytes)
@@ -795,6 +934,63 @@ struct CustomForm : PqForm {
     }
 };
 
+// The colours of a time are its series; the filters they are made from are recomputed in every pass, once per (sample,
+// time).  The peaks of every (sample, filter) are taken tile by tile in front of the tile's first pass; their two arrays
+// are the caller's results and lie outside the workspace.
+struct ColorForm : PqForm {
+    const DevProblem& dp;
+    const int32_t* pairs_host;
+    const double* dzp_host;
+    const bool peak;
+    CqArgs cq{};
+    CqPeak pk{};
+    ColorForm(const DevProblem& d, int32_t n_c, const int32_t* pairs, const double* dzp, bool want_peak)
+        : dp(d), pairs_host(pairs), dzp_host(dzp), peak(want_peak) {
+        nf = n_c;
+        sample_bytes = kNCoef * sizeof(double);
+        time_bytes = 0;
+        call_bytes = (size_t)n_c * (2 * sizeof(int) + sizeof(double));
+        lds_head = (kExpTabSize + (size_t)d.n_filters * kPqThreads) * sizeof(double);
+        cq.n_c = n_c;
+    }
+    lcf_status prepare(DevBuf& mem, PqArgs& a, double* d_coef) override {
+        int* d_pairs;
+        double* d_dzp;
+        lcf_status st;
+        if ((st = mem.put(&d_pairs, pairs_host, (size_t)2 * cq.n_c)) || (st = mem.put(&d_dzp, dzp_host, (size_t)cq.n_c)))
+            return st;
+        cq.pairs = d_pairs;
+        cq.dzp = d_dzp;
+        hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
+        LCF_HIP(hipGetLastError());
+        if (peak) {
+            const size_t n_pk = (size_t)dp.n_filters * a.n;
+            if ((st = mem.alloc(&pk.best, n_pk)) || (st = mem.alloc(&pk.at, n_pk))) return st;
+            LCF_HIP(hipMemset(pk.best, 0, n_pk * sizeof(double)));
+            LCF_HIP(hipMemset(pk.at, 0xff, n_pk * sizeof(int)));   // -1
+        }
+        return LCF_OK;
+    }
+    template <int MODEL>
+    lcf_status launch(const PqArgs& a, int n_ep, size_t lds) {
+        if (a.mode == 0 && peak) {   // the tile's first pass: the peaks so far (all on the null stream, in order)
+            pk.n_ep = n_ep;
+            const size_t peak_lds = (size_t)dp.n_filters * kCqPeakThreads * (sizeof(double) + sizeof(int));
+            hipLaunchKernelGGL(k_cq_peak<MODEL>, dim3((unsigned)((a.n + kCqPeakThreads - 1) / kCqPeakThreads)),
+                               dim3(kCqPeakThreads), peak_lds, 0, dp, a, pk);
+            LCF_HIP(hipGetLastError());
+        }
+        // (at most 2 KiB + 16 x 4 KiB + 512 x 24 bytes + kPqHistBytes = 126 KiB: whatever bits quantile_run chose)
+        if (lds > kCqLdsPerCU) return fail(LCF_ERR_UNSUPPORTED, "a colour pass needs more LDS than a compute unit has");
+        LCF_HIP(prepare_kernel(k_cq_pass<MODEL>, lds));
+        return launch_pass(k_cq_pass<MODEL>, dp, a, n_ep, lds, cq);
+    }
+    lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
+        if (dp.model == kShockCooling) return launch<kShockCooling>(a, n_ep, lds);
+        return launch<0>(a, n_ep, lds);
+    }
+};
+
 // The searches of every point (time x series of `form`), the times in tiles that fit the workspace, over the walkers of
 // the kept steps of `chain` (device memory) as samples.  orig_host[n_ep_all][nf]: where the point's results go, -1 = no
 // such point.  out[n_q][n_points], n_valid[n_points] (host).
@@ -809,7 +1005,7 @@ lcf_status quantile_run(int32_t device, PqForm& form, int n_ep_all, long long n_
     const size_t lds_head = form.lds_head + (size_t)ns * 24;
     // device memory: per sample the coefficients (and window), per point the results, per time of a tile the rest
     const size_t fixed = (size_t)n_samples * form.sample_bytes + (size_t)n_points * (n_q + 1) * 8 +
-                         (size_t)n_ep_all * (nf * 4 + form.time_bytes) + 4096;
+                         (size_t)n_ep_all * (nf * 4 + form.time_bytes) + form.call_bytes + 4096;
     const size_t hist_ep = std::max((size_t)nf << bits0, (size_t)ns << bits1) * 4;
     const size_t per_ep = hist_ep + (size_t)ns * (sizeof(PqSearch) + (size_t)kPqCap * 8) + form.tile_bytes;
     const size_t gran = (size_t)form.gran;
@@ -1059,6 +1255,75 @@ lcf_status custom_run(lcf_engine* grid, const ChainView& in, int64_t discard, in
     return LCF_OK;
 }
 
+// What both colour entry points check before the device is touched.
+lcf_status color_check(const lcf_engine* grid, int32_t n_c, const int32_t* pairs, const double* dzp, const double* q,
+                       int32_t n_q, const double* out, const int64_t* n_valid, const double* y_peak,
+                       const int32_t* peak_index) {
+    if (!grid || !pairs || !dzp || !q || !out || !n_valid) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if ((y_peak == nullptr) != (peak_index == nullptr))
+        return fail(LCF_ERR_INVALID_ARGUMENT, "y_peak and peak_index are given together or not at all");
+    if (lcf_status st = custom_refuse(grid, "a colour band (lcf_predict_colors, lcf_sampler_predict_colors)")) return st;
+    if (lcf_status st = central_refuse(grid, "a colour band (lcf_predict_colors, lcf_sampler_predict_colors)")) return st;
+    if (lcf_status st = check_percentiles(q, n_q, kPqMaxSearch, "need between 1 and 512 percentiles")) return st;
+    if (n_c < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one colour");
+    if ((long long)n_c * n_q > kPqMaxSearch)
+        return fail(LCF_ERR_UNSUPPORTED, "colours x percentiles of one call must not exceed 512");
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no points");
+    if (grid->dp.n_filters > kCqMaxFilters)
+        return fail(LCF_ERR_UNSUPPORTED, "a colour call takes a grid engine of at most 16 filters");
+    for (int32_t k = 0; k < 2 * n_c; ++k)
+        if (pairs[k] < 0 || pairs[k] >= grid->dp.n_filters)
+            return fail(LCF_ERR_INVALID_ARGUMENT, "pairs: an index that is not a filter of the grid engine");
+    return LCF_OK;
+}
+
+// The colour form on the dense filters x distinct-times grid of the grid engine, given filter-major (caller's point
+// f * n_times + t is filter f of the engine at the caller's time t).  out[n_q][n_c][n_times], n_valid[n_c][n_times],
+// y_peak / peak_index[n_filters][samples] or both nullptr (host); times in the caller's order, peaks walked in
+// ascending time.
+lcf_status color_run(lcf_engine* grid, const ChainView& in, int64_t discard, int64_t thin, int32_t n_c,
+                     const int32_t* pairs, const double* dzp, const double* q, int32_t n_q, int64_t workspace_bytes,
+                     double* out, int64_t* n_valid, double* y_peak, int32_t* peak_index) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points, NF = dp.n_filters, nt = dp.n_epochs;
+    if ((long long)N != (long long)nt * NF)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine must hold every filter at every distinct time");
+    if ((long long)nt * n_c > INT32_MAX) return fail(LCF_ERR_INVALID_ARGUMENT, "too many (time, colour) pairs");
+    std::vector<int> filt(N), orig(N), epoch(N);
+    LCF_HIP(hipMemcpy(filt.data(), dp.pt_filt, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int32_t> time_orig(nt, -1);   // the time's index in the caller's order
+    std::vector<char> seen((size_t)nt * NF, 0);
+    for (int i = 0; i < N; ++i) {
+        char& slot = seen[(size_t)epoch[i] * NF + filt[i]];
+        int32_t& t_o = time_orig[epoch[i]];
+        if (slot) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine holds a (time, filter) pair twice");
+        slot = 1;
+        if (orig[i] / nt != filt[i] || (t_o >= 0 && t_o != orig[i] % nt))
+            return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine's points must be the dense grid, filter-major");
+        t_o = orig[i] % nt;
+    }
+    std::vector<int32_t> table((size_t)nt * n_c);   // the colours take the place of a time's filters
+    for (int ep = 0; ep < nt; ++ep)
+        for (int c = 0; c < n_c; ++c) table[(size_t)ep * n_c + c] = c * nt + time_orig[ep];
+    const int64_t n = kept_steps(in, discard, thin).samples;
+    ColorForm form(dp, n_c, pairs, dzp, y_peak != nullptr);
+    DevBuf mem;
+    if (lcf_status st = quantile_run(grid->device, form, nt, (long long)n_c * nt, in, discard, thin, table.data(), 0, q,
+                                     n_q, workspace_bytes, mem, out, n_valid))
+        return st;
+    if (y_peak) {
+        LCF_HIP(hipMemcpy(y_peak, form.pk.best, (size_t)NF * n * sizeof(double), hipMemcpyDeviceToHost));
+        LCF_HIP(hipMemcpy(peak_index, form.pk.at, (size_t)NF * n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < (int64_t)NF * n; ++k) {
+            if (peak_index[k] < 0) y_peak[k] = std::nan("");
+            else peak_index[k] = time_orig[peak_index[k]];
+        }
+    }
+    return LCF_OK;
+}
+
 // n host samples P[n][ld] as one step of n walkers, on the grid engine's device for as long as `mem` lives.
 lcf_status uploaded_samples(const lcf_engine* grid, const double* P, int64_t n, int32_t ld, DevBuf& mem, ChainView* in) {
     if (!P || n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
@@ -1118,6 +1383,26 @@ lcf_status lcf_sampler_predict_thermal(lcf_engine* grid, lcf_sampler* s, int64_t
     ChainView in;
     if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
     return thermal_run(grid, in, discard, thin, q, n_q, T_floor, workspace_bytes, out, n_valid, n_cold, n_inside);
+}
+
+lcf_status lcf_predict_colors(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t n_c, const int32_t* pairs,
+                              const double* dzp, const double* q, int32_t n_q, int64_t workspace_bytes, double* out,
+                              int64_t* n_valid, double* y_peak, int32_t* peak_index) {
+    if (lcf_status st = color_check(grid, n_c, pairs, dzp, q, n_q, out, n_valid, y_peak, peak_index)) return st;
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return color_run(grid, in, 0, 1, n_c, pairs, dzp, q, n_q, workspace_bytes, out, n_valid, y_peak, peak_index);
+}
+
+lcf_status lcf_sampler_predict_colors(lcf_engine* grid, lcf_sampler* s, int64_t discard, int64_t thin, int32_t n_c,
+                                      const int32_t* pairs, const double* dzp, const double* q, int32_t n_q,
+                                      int64_t workspace_bytes, double* out, int64_t* n_valid, double* y_peak,
+                                      int32_t* peak_index) {
+    if (lcf_status st = color_check(grid, n_c, pairs, dzp, q, n_q, out, n_valid, y_peak, peak_index)) return st;
+    ChainView in;
+    if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
+    return color_run(grid, in, discard, thin, n_c, pairs, dzp, q, n_q, workspace_bytes, out, n_valid, y_peak, peak_index);
 }
 
 lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,

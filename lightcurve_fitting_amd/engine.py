@@ -147,6 +147,10 @@ SIGNATURES = [
                                         _dp, C.POINTER(C.c_int64)]),
     ('lcf_sampler_predict_quantiles', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp,
                                                 C.c_int32, C.c_int64, _dp, C.POINTER(C.c_int64)]),
+    ('lcf_predict_colors', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, C.c_int32, _ip, _dp, _dp, C.c_int32,
+                                     C.c_int64, _dp, C.POINTER(C.c_int64), _dp, _ip]),
+    ('lcf_sampler_predict_colors', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _ip, _dp, _dp,
+                                             C.c_int32, C.c_int64, _dp, C.POINTER(C.c_int64), _dp, _ip]),
     ('lcf_predict_thermal', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, C.c_int64, _dp,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ('lcf_sampler_predict_thermal', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double,
@@ -1019,6 +1023,73 @@ def predict_thermal(grid_engine, samples, percentiles, T_floor=8.12, workspace_b
     _predict_call(lib, 'predict_thermal', grid_engine, samples, discard, thin,
                   (_ptr(q), len(q), float(T_floor), ws, _ptr(out), _i64p(n_valid), _i64p(n_cold), _i64p(n_inside)))
     return out, n_valid, n_cold, n_inside
+
+
+#: filters of one native colour call (include/lcf.h): 4 KiB of LDS each in a pass workgroup
+COLOR_MAX_FILTERS = 16
+
+
+def _hist_bits(n_series):
+    """The largest of 4 ... 11 bits for which ``n_series 2^b`` four-byte counters fit 48 KiB of LDS."""
+    b = 4
+    while b < 11 and (n_series << (b + 1)) * 4 <= 48 * 1024:
+        b += 1
+    return b
+
+
+def color_workspace(n_samples, n_times, n_colors, n_q, tile=1):
+    """Device memory [bytes] beyond the samples that :func:`predict_colors` needs to work through ``tile`` times at
+    once -- the least ``workspace_bytes`` for that tile (DESIGN.md, "Colour bands and peaks")::
+
+        fixed    = 64 n_samples + 8 (n_q + 1) n_colors n_times + 4 n_colors n_times + 16 n_colors + 4096
+        per time = n_colors n_q (56 + 8 * 2048) + 4 max(n_colors 2^b0, n_colors n_q 2^b1)
+
+    with ``b0`` / ``b1`` the largest of 4 ... 11 for which ``n_colors 2^b0`` / ``n_colors n_q 2^b1`` four-byte counters
+    fit 48 KiB of LDS.  Nothing is stored per (sample, time).  The peaks are results per sample and lie OUTSIDE the
+    workspace: :func:`color_peak_bytes`."""
+    ns = n_colors * n_q
+    fixed = 64 * n_samples + 8 * (n_q + 1) * n_colors * n_times + 4 * n_colors * n_times + 16 * n_colors + 4096
+    hist = 4 * max(n_colors << _hist_bits(n_colors), ns << _hist_bits(ns))
+    return fixed + tile * (ns * (56 + 8 * 2048) + hist)
+
+
+def color_peak_bytes(n_samples, n_filters):
+    """Device memory [bytes] of the peaks of :func:`predict_colors` while the call runs, beyond ``workspace_bytes``: a
+    float64 and an int32 per (sample, filter)."""
+    return 12 * n_samples * n_filters
+
+
+def predict_colors(grid_engine, samples, pairs, dzp, percentiles, workspace_bytes=None, peak=True, discard=0, thin=1):
+    """``lcf_predict_colors`` / ``lcf_sampler_predict_colors``: percentiles over all samples of the colours ``pairs``
+    (n_c, 2) -- indices into the filters of ``grid_engine``, an evaluation engine on the dense grid, filter-major --
+    with the zero-point differences ``dzp`` (n_c,), and with ``peak`` every (sample, filter)'s largest value and the
+    first time it is attained.  ``samples`` as for :func:`predict_quantiles`; ``n_c * n_q <= PREDICT_MAX_SEARCHES``.
+    Returns ``(color[n_q, n_c, n_t], n_valid[n_c, n_t], y_peak[n_f, n] or None, peak_index[n_f, n] or None)``."""
+    lib = load_library()
+    q = _f64(percentiles)
+    pairs, dzp = _i32(pairs), _f64(dzp)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or dzp.shape != (len(pairs),):
+        raise ValueError('pairs must have shape (n_c, 2) and dzp shape (n_c,)')
+    n_c, n_f = len(pairs), grid_engine.nfilters
+    n_t = grid_engine.npoints // max(n_f, 1)
+    if not peak:
+        n = 0
+    elif isinstance(samples, NativeSampler):   # (the peaks are per sample: their number has to be known here)
+        n_steps, stored = getattr(samples, '_last', (0, False))
+        if not stored or int(discard) < 0 or int(thin) < 1 or int(discard) >= n_steps:
+            raise ValueError('the sampler\'s last run stored no chain, or discard / thin leave none of it')
+        n = len(range(int(discard), n_steps, int(thin))) * samples.nwalkers
+    else:
+        n = np.shape(samples)[0]
+    out = np.empty((len(q), n_c, n_t))
+    n_valid = np.empty((n_c, n_t), dtype=np.int64)
+    y_peak = np.empty((n_f, n)) if peak else None
+    peak_index = np.empty((n_f, n), dtype=np.int32) if peak else None
+    ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    _predict_call(lib, 'predict_colors', grid_engine, samples, discard, thin,
+                  (n_c, _ptr(pairs, _ip), _ptr(dzp), _ptr(q), len(q), ws, _ptr(out), _i64p(n_valid),
+                   _ptr(y_peak) if peak else None, _ptr(peak_index, _ip) if peak else None))
+    return out, n_valid, y_peak, peak_index
 
 
 def luminosity_workspace(n_samples, n_times, n_q, tile=1, peak=True):

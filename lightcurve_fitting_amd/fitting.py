@@ -389,6 +389,149 @@ def posterior_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# colour bands and per-band peaks (the model's side of calc_colors / plot_color_curves, bolometric.py:559-605)
+# ---------------------------------------------------------------------------------------------------------------
+class ColorPredictive:
+    """Result of :func:`color_predictive`: ``t`` (nt,), ``colors`` (nc pairs of Filter objects), ``color_names`` (nc
+    strings ``'X-Y'``), ``filters`` (nf Filter objects: the distinct filters of the colours, sorted), ``percentiles``
+    (nq,), ``color`` [mag] (nq, nc, nt), ``n_valid`` (nc, nt) -- the samples that have the colour at the time -- and
+    ``n_samples``.  With ``peak=True``, per sample and filter over the times in ascending order: ``y_peak`` (n, nf) in
+    the model's ``output_quantity``, ``peak_index`` (n, nf) int32 into ``t`` (-1: NaN everywhere), ``t_peak`` (n, nf),
+    ``M_peak`` (n, nf) [mag] (NaN where ``y_peak`` is not positive), and the counts ``n_peak_first`` / ``n_peak_last``
+    (nf,) of samples that peak at an edge of the grid (their true peak may lie outside it); else all ``None``."""
+    __slots__ = ('t', 'colors', 'color_names', 'filters', 'percentiles', 'color', 'n_valid', 'n_samples', 'y_peak',
+                 'peak_index', 't_peak', 'M_peak', 'n_peak_first', 'n_peak_last')
+
+    def __init__(self, t, colors, color_names, filters, percentiles, color, n_valid, n_samples):
+        self.t, self.colors, self.color_names, self.filters = t, colors, color_names, filters
+        self.percentiles, self.color, self.n_valid, self.n_samples = percentiles, color, n_valid, n_samples
+        self.y_peak = self.peak_index = self.t_peak = self.M_peak = self.n_peak_first = self.n_peak_last = None
+
+    def set_peaks(self, y_peak, peak_index, zero_points):
+        """Attach the peaks: ``y_peak`` / ``peak_index`` (n, nf) as the device returns them, ``zero_points`` (nf,) the
+        magnitude of a unit value per filter.  Everything else follows on the host."""
+        y_peak = np.asarray(y_peak, dtype=np.float64)
+        peak_index = np.asarray(peak_index, dtype=np.int32)
+        self.y_peak, self.peak_index = y_peak, peak_index
+        self.t_peak = np.where(peak_index < 0, np.nan, np.asarray(self.t)[np.maximum(peak_index, 0)])
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mag = np.asarray(zero_points, dtype=np.float64) - 2.5 * np.log10(y_peak)
+        self.M_peak = np.where(y_peak > 0., mag, np.nan)
+        self.n_peak_first = np.sum(peak_index == 0, axis=0)
+        self.n_peak_last = np.sum(peak_index == len(self.t) - 1, axis=0)
+
+    def peak_summary(self, percentiles=(15.87, 50., 84.14)):
+        """``{'M_peak': (nq, nf), 't_peak': (nq, nf)}``: ``np.nanpercentile`` over the samples, per filter."""
+        if self.peak_index is None:
+            raise ValueError('the peaks were not computed: call color_predictive with peak=True')
+        q = _percentile_array(percentiles)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)   # (every sample NaN: NaN)
+            return {name: np.nanpercentile(getattr(self, name), q, axis=0) for name in ('M_peak', 't_peak')}
+
+    def __repr__(self):
+        return (f'<ColorPredictive: {len(self.percentiles)} percentiles x {len(self.colors)} colours x '
+                f'{len(self.t)} times over {self.n_samples} samples'
+                + ('' if self.peak_index is None else f', with peaks in {len(self.filters)} filters') + '>')
+
+
+def parse_colors(colors):
+    """The colours of :func:`color_predictive`: each ``'X-Y'``, split at the first ``-`` and looked up in ``filtdict``
+    (as ``calc_colors`` does), or a ``(filter, filter)`` pair of names or ``Filter`` objects.  Returns ``(pairs, names,
+    filters, index, dzp)``: the (Filter, Filter) pairs, their ``'X-Y'`` names, the distinct filters sorted, the pairs
+    as indices (nc, 2) into them, and ``m0_a - m0_b`` per colour.  ``ValueError`` for an empty list, an unknown filter,
+    a filter without a zero point, a colour of a filter with itself and more than 16 distinct filters."""
+    from .engine import COLOR_MAX_FILTERS
+    from .filters import Filter, filtdict
+    if isinstance(colors, str):
+        colors = [colors]
+    colors = list(colors)
+    if len(colors) == 0:
+        raise ValueError('colors must not be empty')
+
+    def lookup(f, color):
+        if isinstance(f, Filter):
+            return f
+        try:
+            return filtdict[str(f)]
+        except KeyError:
+            raise ValueError(f'colour {color!r}: unrecognised filter {f!r}') from None
+
+    pairs = []
+    for color in colors:
+        if isinstance(color, str):
+            if '-' not in color:
+                raise ValueError(f"colour {color!r} is not of the form 'X-Y'")
+            ends = color.split('-', 1)
+        else:
+            ends = list(color)
+            if len(ends) != 2:
+                raise ValueError(f'colour {color!r} is not a pair of filters')
+        a, b = lookup(ends[0], color), lookup(ends[1], color)
+        for f in (a, b):
+            if not np.isfinite(f.m0):
+                raise ValueError(f'colour {color!r}: filter {f.name!r} has no zero point')
+        if a == b:
+            raise ValueError(f'colour {color!r} is of a filter with itself')
+        pairs.append((a, b))
+    filters = sorted(set(f for pair in pairs for f in pair))
+    if len(filters) > COLOR_MAX_FILTERS:
+        raise ValueError(f'the colours name {len(filters)} distinct filters: at most {COLOR_MAX_FILTERS}')
+    where = {f: i for i, f in enumerate(filters)}
+    index = np.array([[where[a], where[b]] for a, b in pairs], dtype=np.int32)
+    dzp = np.array([a.m0 - b.m0 for a, b in pairs], dtype=np.float64)
+    return pairs, [f'{a.name}-{b.name}' for a, b in pairs], filters, index, dzp
+
+
+def color_predictive(lc, model, samples, colors=('B-V', 'g-r', 'r-i'), percentiles=(15.87, 50., 84.14), t=None,
+                     tmin=None, tmax=None, num=1000, xscale='linear', discard=0, thin=1, use_sigma=False, peak=True,
+                     workspace_bytes=None):
+    """Percentile bands of the model's colour curves over ALL samples of a chain, and every sample's peak in every
+    filter the colours name: the model's side of ``calc_colors`` / ``plot_color_curves``, with its uncertainty.
+
+    ``samples``, ``discard``, ``thin``, ``use_sigma``, ``workspace_bytes`` and the time grid ``t`` ... ``xscale`` as in
+    :func:`posterior_predictive`; ``model``: every model it takes.  ``colors``: see :func:`parse_colors`; the grid's
+    filters are the distinct filters of all colours, sorted, and a filter may occur in several colours.
+
+    With ``Y[f, t, s] = model(t, filters, *p_s)`` -- the value :func:`posterior_predictive` ranks, in the model's
+    ``output_quantity`` -- the colour ``(a, b)`` of a sample at a time is ``(m0_a - m0_b) - 2.5 log10(Y_a / Y_b)`` where
+    both values are finite and positive, else NaN (not exploded yet; a NaN; a negative SiFTO tail), and ``color`` is
+    ``np.nanpercentile`` of it over the samples: a property of the two filters' joint distribution, sample by sample,
+    not a difference of per-filter percentiles.  ``n_valid`` counts the samples that have the colour; ``color`` is NaN
+    where none has.  With ``peak=True`` the largest non-NaN ``Y`` of every (sample, filter) and the first time it is
+    attained, the times walked in ascending order (``np.nanargmax`` on a sorted grid): a sample that has not exploded
+    anywhere has ``y_peak == 0`` at the earliest time.  ``M_peak = zp - 2.5 log10(y_peak)`` with ``zp`` the filter's
+    ``M0`` for a ``'lum'`` model and ``m0`` for a ``'flux'`` one.  Nothing is stored per (sample, time) except the
+    peaks, 12 bytes per (sample, filter) beyond ``workspace_bytes`` (``engine.color_workspace``).  Results are bitwise
+    reproducible and do not depend on ``workspace_bytes``.  Returns a :class:`ColorPredictive`."""
+    from . import engine as _eng
+    _refuse_custom(model, 'color_predictive')
+    q = _percentile_array(percentiles)
+    pairs, names, filters, index, dzp = parse_colors(colors)
+    if len(pairs) > _eng.PREDICT_MAX_SEARCHES:
+        raise ValueError(f'at most {_eng.PREDICT_MAX_SEARCHES} colours')
+    sampler, P, n_samples = _model_samples(model, samples, discard, thin, use_sigma)
+    times, _ = predictive_grid(lc, t, tmin, tmax, num, xscale, filters)
+
+    grid_engine, _ = Model._eval_engine(model, times, filters, False)   # the dense grid, filter-major
+    source = _sample_source(sampler, P, discard, thin)
+    per_call = max(1, _eng.PREDICT_MAX_SEARCHES // len(pairs))
+    bands, n_valid, y_peak, i_peak = [], None, None, None
+    for k in range(0, len(q), per_call):
+        out, n_valid, y_pk, i_pk = _eng.predict_colors(grid_engine, source, index, dzp, q[k:k + per_call],
+                                                       workspace_bytes, peak=bool(peak) and k == 0,
+                                                       discard=int(discard), thin=int(thin))
+        bands.append(out)
+        if k == 0:
+            y_peak, i_peak = y_pk, i_pk
+    res = ColorPredictive(times, pairs, names, filters, q, np.concatenate(bands), n_valid, n_samples)
+    if peak:
+        zero = [f.M0 if model.output_quantity == 'lum' else f.m0 for f in filters]
+        res.set_peaks(y_peak.T, i_peak.T, zero)      # (views: the device's [filter][sample] arrays are not copied)
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # thermal bands and validity (temperature_radius over the whole chain; t_min / t_max, the 0.7 eV floor)
 # ---------------------------------------------------------------------------------------------------------------
 class ThermalPredictive:
