@@ -767,6 +767,45 @@ lcf_status lcf_engine_set_limits(lcf_engine* e, lcf_engine* at, int64_t n_lim, c
  * without limits. */
 lcf_status lcf_limit_terms(lcf_engine* e, int64_t n, const double* P, double* out);
 
+/* ---- second component: a stretched template added to the model ----------------------------------------------------- */
+/* A double-peaked light curve: the engine's model (a shock-cooling model, or a custom model) plus a second peak given as
+ * a template per filter, which the fit may shift, stretch and scale -- what the companion-shocking models do with the
+ * SiFTO template, for any photometric engine and any template.  With a template attached the model at point j, of
+ * filter f, is
+ *   m_j(p) = base_j(p[0 .. n_par)) + r_f S_f((t_j - t_max - dt_f) / s),
+ * base_j bit for bit what lcf_model_evaluate of the engine without the template returns; S_f the piecewise cubic
+ *   S_f(x) = ((c0 dx + c1) dx + c2) dx + c3,  dx = x - knots[i],  c = coef[f][i],  knots[i] <= x (< knots[i + 1]),
+ * 0 for x outside [knots[0], knots[n_knots - 1]] and for a NaN x; the argument is evaluated as (t_j - t_max - dt_f) *
+ * (1 / s), as the companion-shocking kernels do: s = 0 and a NaN s give an infinite or NaN argument, hence no template;
+ * s < 0 mirrors the template; t is the observed time (not redshifted, as in the reference).  The likelihood is that of
+ * every model (models.py:116-136) on m_j, with the engine's sigma mode, added in a fixed order: a row's value does
+ * not depend on the rows evaluated with it.  A NaN model value gives NaN; a row the prior excludes stays -inf.
+ * The rows gain n_extra >= 2 columns behind the model's own n_par, in front of sigma: lcf_engine_ndim then returns
+ * n_par + n_extra + use_sigma (at most 16).  tmax_par and s_par are the columns of t_max and s; filt_factor_par[n_filters]
+ * and filt_offset_par[n_filters] the columns of each filter's r_f and dt_f, -1 where the filter has none (r = 1,
+ * dt = 0); all of them among the extra columns.  knots[n_knots] finite and strictly increasing, 4 <= n_knots <= 65536;
+ * coef[n_filters][n_knots - 1][4], highest power first, finite.  priors: NULL, or the priors of ALL columns of the grown
+ * row (they replace the ones the engine was created with).  knots = NULL or n_knots = 0 detaches: the engine is as it
+ * was created, its own priors included.  Attach before anything that sizes itself by lcf_engine_ndim is created on the
+ * engine (lcf_tempered_create).
+ * Served: lcf_log_likelihood, lcf_log_posterior, their _dev forms (k_prepare, the engine's own model values into scratch
+ * -- at most 256 MiB per pass, rows in chunks -- and one kernel more) and through them lcf_tempered_*; lcf_model_evaluate
+ * (the sum), lcf_temperature_radius (the base model's) and lcf_template_evaluate.  What computes the likelihood inside
+ * kernels of its own would drop the template silently and therefore returns LCF_ERR_UNSUPPORTED for such an engine,
+ * naming the lcf_tempered_* route: lcf_sampler_create (and with it every lcf_sampler_* and population run),
+ * lcf_profile_loglike_kernel and lcf_engine_set_limits (limits together with a template are out of scope); so does
+ * attaching a template to an engine that a live lcf_sampler uses, that has limits attached, to a central-engine model (no
+ * filters) and to a companion-shocking model (it has its template).  Everything else that does not fit:
+ * LCF_ERR_INVALID_ARGUMENT. */
+lcf_status lcf_engine_set_template(lcf_engine* e, int32_t n_knots, const double* knots, const double* coef,
+                                   const int32_t* filt_factor_par, const int32_t* filt_offset_par, int32_t tmax_par,
+                                   int32_t s_par, int32_t n_extra, const lcf_prior* priors);
+enum { LCF_TEMPLATE_TOTAL = 1, LCF_TEMPLATE_BASE = 2, LCF_TEMPLATE_TEMPLATE = 3 };
+/* out[n][n_points], the caller's order of the points: the model (LCF_TEMPLATE_TOTAL), the base model alone (_BASE) or the
+ * template term alone (_TEMPLATE) of rows as lcf_log_likelihood takes them.  LCF_ERR_STATE for an engine without a
+ * template. */
+lcf_status lcf_template_evaluate(lcf_engine* e, int64_t n, const double* P, int32_t component, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3002,6 +3002,7 @@ lcf_status logprob_dev(lcf_engine* e, int64_t n, const double* dP, double* dout,
     const int bs = 128;
     hipLaunchKernelGGL(k_prepare, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, dP, e->wcoef,
                        e->wlprior, with_prior);
+    if (e->tpl) return template_loglike(e, n, dP, dout, st);   // (a second component: model values, then k_template)
     if (custom) {
         if (lcf_status s = custom_launch(e, 0, 0, (int)n, dP, e->wlprior, e->wpart, nullptr, st)) return s;
     } else if (central) {
@@ -3031,6 +3032,24 @@ lcf_status limits_model(lcf_engine* e, int64_t n, int64_t lo, int64_t m, const d
         if (lcf_status s = custom_launch(at, 1, (int)lo, (int)m, dP, e->wlprior, e->lim_m, nullptr, st)) return s;
     } else {
         launch_points<1>(at, (int)lo, (int)m, dP, e->wcoef, e->wlprior, at->wtherm, e->lim_m, nullptr, st);
+    }
+    LCF_HIP(hipGetLastError());
+    return LCF_OK;
+}
+
+lcf_status prepare_rows(lcf_engine* e, int64_t n, const double* dP, hipStream_t st) {
+    const int bs = 128;
+    hipLaunchKernelGGL(k_prepare, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, e->dp, (int)n, dP, e->wcoef,
+                       e->wlprior, 0);
+    LCF_HIP(hipGetLastError());
+    return LCF_OK;
+}
+
+lcf_status template_model(lcf_engine* e, int64_t lo, int64_t m, const double* dP, double* out, hipStream_t st) {
+    if (e->dp.model == LCF_MODEL_CUSTOM) {
+        if (lcf_status s = custom_launch(e, 1, (int)lo, (int)m, dP, e->wlprior, out, nullptr, st)) return s;
+    } else {
+        launch_points<1>(e, (int)lo, (int)m, dP, e->wcoef, e->wlprior, e->wtherm, out, nullptr, st);
     }
     LCF_HIP(hipGetLastError());
     return LCF_OK;
@@ -3126,6 +3145,7 @@ static lcf_status evaluate_impl(lcf_engine* e, int64_t n, const double* P, doubl
 }
 
 lcf_status lcf_model_evaluate(lcf_engine* e, int64_t n, const double* P, double* y_fit) {
+    if (e && e->tpl) return lcf_template_evaluate(e, n, P, LCF_TEMPLATE_TOTAL, y_fit);   // (both components)
     return evaluate_impl(e, n, P, y_fit, nullptr, 1);
 }
 lcf_status lcf_temperature_radius(lcf_engine* e, int64_t n, const double* P, double* T_K, double* R_bb) {
@@ -3169,6 +3189,7 @@ extern "C" lcf_status lcf_profile_loglike_kernel(lcf_engine* e, int64_t n, const
     if (lcf_status st = custom_refuse(e, "lcf_profile_loglike_kernel")) return st;
     if (lcf_status st = central_refuse(e, "lcf_profile_loglike_kernel")) return st;
     if (lcf_status st = limits_refuse(e, "lcf_profile_loglike_kernel")) return st;
+    if (lcf_status st = template_refuse(e, "lcf_profile_loglike_kernel")) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (lcf_status st = e->reserve(n)) return st;
     LCF_HIP(hipMemcpyAsync(e->wP, P, n * e->dp.n_dim * sizeof(double), hipMemcpyHostToDevice, e->stream));

@@ -240,9 +240,24 @@ struct lcf_engine {
     lcf_engine* lim_at = nullptr;
     int64_t n_lim = 0, lim_rows = 0;
     double *lim_L = nullptr, *lim_dy = nullptr, *lim_m = nullptr;
-    // live lcf_samplers on this engine (their kernels compute the likelihood themselves: limits are refused while there
-    // are any).  Shared with them: a sampler may be destroyed after its engine.
+    // live lcf_samplers on this engine (their kernels compute the likelihood themselves: limits and a template are
+    // refused while there are any).  Shared with them: a sampler may be destroyed after its engine.
     std::shared_ptr<int> samplers = std::make_shared<int>(0);
+    // second component (lcf_engine_set_template, lcf_template.hip): a stretched template added to the model.  The rows
+    // then have tpl_extra columns more than the engine was created with (dp.n_dim has grown; sigma stays last, dp.priors
+    // points at tpl_priors); base_* are what creation set, for detaching.  On the device: the knots, the per-filter cubic
+    // coefficients [n_filters][tpl_nk - 1][4], per filter the row columns of its factor and offset (-1: none), the
+    // photometry in the CALLER'S order (the order of the points launch's output) and the model values of tpl_rows rows
+    // at a time, [tpl_rows][n_points] (reserve).
+    bool tpl = false;
+    int tpl_nk = 0, tpl_extra = 0, tpl_tmax = -1, tpl_s = -1;
+    int base_n_dim = 0, base_has_priors = 0;
+    const PriorDev* base_priors = nullptr;
+    double tpl_inv_h = 0.;
+    int64_t tpl_rows = 0;
+    double *tpl_knots = nullptr, *tpl_coef = nullptr, *tpl_t = nullptr, *tpl_y = nullptr, *tpl_dy = nullptr, *tpl_m = nullptr;
+    int *tpl_filt = nullptr, *tpl_fac = nullptr, *tpl_off = nullptr;
+    PriorDev* tpl_priors = nullptr;
 
     ~lcf_engine() {
         hipSetDevice(device);
@@ -251,6 +266,7 @@ struct lcf_engine {
         if (wbig) hipFree(wbig);
         for (double* p : {lim_L, lim_dy, lim_m})
             if (p) hipFree(p);
+        free_template();
         if (stream) hipStreamDestroy(stream);
     }
     void free_ws() {
@@ -262,10 +278,22 @@ struct lcf_engine {
         wtherm = nullptr;
         cap = 0;
     }
+    void free_template() {
+        for (void* p : {(void*)tpl_knots, (void*)tpl_coef, (void*)tpl_t, (void*)tpl_y, (void*)tpl_dy, (void*)tpl_m,
+                        (void*)tpl_filt, (void*)tpl_fac, (void*)tpl_off, (void*)tpl_priors})
+            if (p) hipFree(p);
+        tpl_knots = tpl_coef = tpl_t = tpl_y = tpl_dy = tpl_m = nullptr;
+        tpl_filt = tpl_fac = tpl_off = nullptr;
+        tpl_priors = nullptr;
+        tpl_rows = 0;
+    }
     lcf_status reserve_limits(int64_t n);   // lcf_limits.hip: the limit engine's workspace and lim_m for n rows
+    lcf_status reserve_template(int64_t n); // lcf_template.hip: tpl_m for n rows
     lcf_status reserve(int64_t n) {
         if (lim_at)
             if (lcf_status st = reserve_limits(n)) return st;
+        if (tpl)
+            if (lcf_status st = reserve_template(n)) return st;
         if (n <= cap) return LCF_OK;
         LCF_HIP(hipStreamSynchronize(stream));
         free_ws();
@@ -322,6 +350,17 @@ lcf_status limits_add(lcf_engine* e, int64_t n, const double* dP, double* dout, 
 // lcf_model_evaluate, enqueued on st -> e->lim_m[m][n_lim]; `prepare`: the coefficients of all n rows first (k_prepare into
 // e's workspace, no prior), for callers that have not just evaluated the rows' likelihood.
 lcf_status limits_model(lcf_engine* e, int64_t n, int64_t lo, int64_t m, const double* dP, bool prepare, hipStream_t st);
+// lcf_template.hip: engines with a second component attached (lcf_engine_set_template).  template_refuse: as
+// limits_refuse; template_loglike: what logprob_dev enqueues behind its k_prepare for such an engine -- per chunk of
+// e->tpl_rows rows the model values (template_model) and k_template, which writes dout.
+lcf_status template_refuse(const lcf_engine* e, const char* what);
+lcf_status template_loglike(lcf_engine* e, int64_t n, const double* dP, double* dout, hipStream_t st);
+// lcf_hip.hip: the engine's own model at its own points -- rows [lo, lo + m) of dP through the launches of
+// lcf_model_evaluate (k_thermal first where epochs are shared), enqueued on st -> out[m][n_points], the caller's order
+// of the points; the rows' coefficients are in e->wcoef (k_prepare has run).  prepare_rows: k_prepare of rows [0, n)
+// into e's workspace, no prior, for callers that have not just evaluated the rows' likelihood.
+lcf_status prepare_rows(lcf_engine* e, int64_t n, const double* dP, hipStream_t st);
+lcf_status template_model(lcf_engine* e, int64_t lo, int64_t m, const double* dP, double* out, hipStream_t st);
 }  // namespace lcf
 
 struct lcf_sampler {

@@ -120,6 +120,7 @@ lcf_status lcf_engine_set_limits(lcf_engine* e, lcf_engine* at, int64_t n_lim, c
     if (is_central(e->dp.model))
         return fail(LCF_ERR_UNSUPPORTED, "a central-engine model (Arnett, Magnetar) fits a bolometric table, which has no "
                                          "non-detections: upper limits belong to photometric engines");
+    if (lcf_status st = template_refuse(e, "lcf_engine_set_limits")) return st;
     LCF_HIP(hipSetDevice(e->device));
     if (!at || n_lim == 0) {   // detach
         LCF_HIP(hipStreamSynchronize(e->stream));

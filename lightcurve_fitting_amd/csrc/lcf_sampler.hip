@@ -619,6 +619,7 @@ lcf_status lcf_sampler_create(lcf_engine* e, int32_t n_walkers, uint64_t seed, d
     if (lcf_status st = custom_refuse(e, "the resident ensemble sampler (lcf_sampler_*, population runs)")) return st;
     if (lcf_status st = central_refuse(e, "the resident ensemble sampler (lcf_sampler_*, population runs)")) return st;
     if (lcf_status st = limits_refuse(e, "the resident ensemble sampler (lcf_sampler_*, population runs)")) return st;
+    if (lcf_status st = template_refuse(e, "the resident ensemble sampler (lcf_sampler_*, population runs)")) return st;
     if (n_walkers < 2) return fail(LCF_ERR_INVALID_ARGUMENT, "n_walkers must be >= 2");
     if (!(a > 1.)) return fail(LCF_ERR_INVALID_ARGUMENT, "stretch scale a must be > 1");
     LCF_HIP(hipSetDevice(e->device));

@@ -200,7 +200,13 @@ SIGNATURES = [
     ('lcf_engine_set_custom_redshift', C.c_int, [C.c_void_p, C.c_double]),
     ('lcf_engine_set_limits', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _dp, _dp]),
     ('lcf_limit_terms', C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    ('lcf_engine_set_template', C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _ip, _ip, C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(LcfPrior)]),
+    ('lcf_template_evaluate', C.c_int, [C.c_void_p, C.c_int64, _dp, C.c_int32, _dp]),
 ]
+
+#: `component` of `lcf_template_evaluate` (include/lcf.h: LCF_TEMPLATE_*)
+TEMPLATE_COMPONENTS = {'total': 1, 'base': 2, 'template': 3}
 
 
 def load_library(path=None):
@@ -394,6 +400,50 @@ class Engine:
         P = self._block(P)
         out = np.empty((len(P), getattr(self, 'nlimits', 0)))
         _check(self._lib.lcf_limit_terms(self._h, len(P), _ptr(P), _ptr(out)))
+        return out
+
+    def set_template(self, knots, coef, factor_par, offset_par, tmax_par, s_par, n_extra, priors=None):
+        """Attach a second component (``lcf_engine_set_template``): a template per filter, the cubic coefficients ``coef``
+        ``(n_filters, n_knots - 1, 4)`` on ``knots``, added to the model as ``r_f S_f((t - t_max - dt_f) / s)``.  The rows
+        gain ``n_extra`` columns behind the model's own (in front of sigma): ``tmax_par`` and ``s_par`` are the columns of
+        ``t_max`` and ``s``, ``factor_par`` / ``offset_par`` per filter those of its ``r_f`` / ``dt_f`` (-1: none).
+        ``priors``: descriptors of ALL columns of the grown row, or None.  ``knots=None`` detaches.  ``ndim`` follows the
+        engine's; the resident samplers refuse such an engine (``LcfError``, status 5),
+        :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` takes it."""
+        if knots is None:
+            _check(self._lib.lcf_engine_set_template(self._h, 0, None, None, None, None, -1, -1, 0, None))
+            self.template = None
+            self.priors = getattr(self, '_created_priors', self.priors)
+        else:
+            if not getattr(self, '_template_extra', 0):
+                self._created_priors = self.priors
+            knots, coef = _f64(knots), _f64(coef)
+            fp, op = _i32(factor_par), _i32(offset_par)
+            if knots.ndim != 1 or coef.shape != (self.nfilters, max(len(knots), 1) - 1, 4):
+                raise ValueError('coef must have shape (n_filters, n_knots - 1, 4)')
+            if fp.shape != (self.nfilters,) or op.shape != (self.nfilters,):
+                raise ValueError('factor_par and offset_par must have one entry per filter')
+            arr = None
+            if priors is not None:
+                arr = (LcfPrior * len(priors))()
+                for i, (kind, lo, hi, mean, std) in enumerate(priors):
+                    arr[i].kind, arr[i].p_min, arr[i].p_max, arr[i].mean, arr[i].stddev = int(kind), lo, hi, mean, std
+                want = self._lib.lcf_engine_ndim(self._h) - getattr(self, '_template_extra', 0) + int(n_extra)
+                if len(priors) != want:
+                    raise ValueError(f'priors must have length {want}')
+            _check(self._lib.lcf_engine_set_template(self._h, len(knots), _ptr(knots), _ptr(coef), _ptr(fp, _ip),
+                                                     _ptr(op, _ip), int(tmax_par), int(s_par), int(n_extra), arr))
+            self.template = (knots, coef)
+            self.priors = None if priors is None else [tuple(p) for p in priors]
+        self._template_extra = 0 if knots is None else int(n_extra)
+        self.ndim = int(self._lib.lcf_engine_ndim(self._h))
+
+    def evaluate_components(self, P, component='total'):
+        """``(n, npoints)``: the model (``'total'``), the base model alone (``'base'``) or the template term alone
+        (``'template'``) of an engine with a second component attached (``lcf_template_evaluate``)."""
+        P = self._block(P)
+        out = np.empty((len(P), self.npoints))
+        _check(self._lib.lcf_template_evaluate(self._h, len(P), _ptr(P), TEMPLATE_COMPONENTS[component], _ptr(out)))
         return out
 
     def _block(self, P):

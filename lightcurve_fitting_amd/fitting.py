@@ -22,7 +22,8 @@ import warnings
 
 import numpy as np
 
-from .models import BaseCentralEngine, BaseCompanionShocking, Blackbody, CustomModel, Model, UniformPrior, _column
+from .models import (BaseCentralEngine, BaseCompanionShocking, Blackbody, CustomModel, Model, UniformPrior, WithTemplate,
+                     _column)
 from .filters import as_filter
 from .sampler import EnsembleSampler
 
@@ -126,6 +127,10 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     a ladder or ``moves`` is asked for -- and a ladder tempers the term with the rest of the likelihood.  Without a
     true ``nondet`` row the fit is the default one.
 
+    A :class:`~lightcurve_fitting_amd.models.WithTemplate` model (a shock model plus a stretched template) is fitted by
+    :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` for the same reason, on one rung at ``beta = 1`` unless a
+    ladder or ``moves`` is asked for; ``nondet='censored'`` with it raises ``ValueError`` (out of scope).
+
     Returns the sampler (``.chain`` (nwalkers, nsteps, ndim), ``.flatchain``, ``.run_mcmc``, ``.reset``).
     """
     import time
@@ -155,10 +160,10 @@ def lightcurve_mcmc(lc, model, priors=None, p_min=None, p_max=None, p_lo=None, p
     marks.append(('engine', time.perf_counter()))
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
-    if (isinstance(model, (CustomModel, BaseCentralEngine)) or moves is not None or getattr(engine, 'nlimits', 0)) \
-            and ntemps is None and betas is None and Tmax is None:
-        # the resident sampler's kernels are compiled per photometric model, make the stretch move and know no upper
-        # limits: one rung is the same ensemble
+    if (isinstance(model, (CustomModel, BaseCentralEngine, WithTemplate)) or moves is not None
+            or getattr(engine, 'nlimits', 0)) and ntemps is None and betas is None and Tmax is None:
+        # the resident sampler's kernels are compiled per photometric model, make the stretch move and know neither
+        # upper limits nor a second component: one rung is the same ensemble
         betas = [1.]
     if ntemps is not None or betas is not None or Tmax is not None:
         from .sampler import TemperedSampler
@@ -313,7 +318,8 @@ def _percentile_array(percentiles):
 
 def _refuse_custom(model, what):
     """The predictive kernels are compiled per built-in photometric model: a ``CustomModel`` and the central-engine
-    models (``Arnett``, ``Magnetar``) are refused before anything is built."""
+    models (``Arnett``, ``Magnetar``) are refused before anything is built, and so is a ``WithTemplate`` model."""
+    _refuse_template(model, what)
     if isinstance(model, CustomModel):
         from .engine import LcfError
         raise LcfError(5, f'{what} is compiled per built-in model and does not take a CustomModel; its fit (the '
@@ -324,6 +330,16 @@ def _refuse_custom(model, what):
         raise LcfError(5, f'{what} is compiled per photometric model and does not take a central-engine model (Arnett, '
                           'Magnetar); its fit (the tempered route, TemperedSampler) gives the chain, model(t, *p) '
                           'evaluates any of its rows, and luminosity_predictive gives the bands of L(t)')
+
+
+def _refuse_template(model, what):
+    """The predictive kernels evaluate the model themselves and do not know a second component."""
+    if isinstance(model, WithTemplate):
+        from .engine import LcfError
+        raise LcfError(5, f'{what} computes the model in kernels of its own, which do not know a second component: bands '
+                          'and colours of a WithTemplate model are out of scope; its fit (the tempered route, '
+                          'TemperedSampler) gives the chain, and model(t, f, *p) on a thinned chain evaluates its rows '
+                          '(model.components(t, f, *p) the two terms)')
 
 
 def _model_samples(model, samples, discard, thin, use_sigma):
@@ -669,6 +685,7 @@ def luminosity_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t
     ``workspace_bytes`` (default 1 GiB; ``engine.luminosity_workspace``).  Results are bitwise reproducible and do not
     depend on ``workspace_bytes``.  Returns a :class:`LuminosityPredictive`."""
     from . import engine as _eng
+    _refuse_template(model, 'luminosity_predictive')
     if not isinstance(model, BaseCentralEngine):
         raise _eng.LcfError(5, 'luminosity_predictive takes a central-engine model (Arnett, Magnetar); the bands of a '
                                'photometric model are posterior_predictive and thermal_predictive')
@@ -759,6 +776,7 @@ def custom_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=Non
     evaluated with it; results are bitwise reproducible and do not depend on ``workspace_bytes``.  Returns a
     :class:`CustomPredictive`."""
     from . import engine as _eng
+    _refuse_template(model, 'custom_predictive')
     if not isinstance(model, CustomModel):
         raise _eng.LcfError(5, 'custom_predictive takes a CustomModel; the bands of a built-in photometric model are '
                                'posterior_predictive and thermal_predictive, those of a central-engine model '

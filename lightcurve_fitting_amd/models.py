@@ -17,6 +17,7 @@ There is no NumPy fallback for the model mathematics: without the native library
 Extension over the reference: ``p`` may be a C-contiguous ``(n, ndim)`` block (what emcee passes with
 ``vectorize=True``); the result then has shape ``(n,)``.  ``nondet='censored'`` (``log_likelihood``, ``engine_for``;
 ``limit_terms``) makes the rows whose ``nondet`` is true upper limits instead of measurements of zero.
+``WithTemplate`` adds a stretched template -- a second peak -- to a shock model or a ``CustomModel``.
 """
 import numpy as np
 
@@ -680,6 +681,178 @@ class CustomModel(Model):
         eng = super().make_engine(t, filts, y, dy, use_sigma, sigma_type, priors, device)
         eng.set_custom(self.compile(device=eng.device), self.z)
         return eng
+
+
+def _parse_template(template):
+    """``(epochs, {column: values})`` of a template given in either form (see :class:`WithTemplate`), checked."""
+    if isinstance(template, tuple) and len(template) == 2 and isinstance(template[1], dict):
+        epochs = np.array(template[0], dtype=np.float64)
+        cols = {str(k): np.array(v, dtype=np.float64) for k, v in template[1].items()}
+    else:
+        tab = np.asarray(template, dtype=np.float64)
+        if tab.ndim != 2 or tab.shape[1] != len(_SIFTO_COLUMNS):
+            raise ValueError('a template is (epochs, {column: values}) or a 2-D array with the columns of '
+                             f'sifto_template(): {", ".join(_SIFTO_COLUMNS)}')
+        epochs = tab[:, 0].copy()
+        cols = {name: tab[:, k].copy() for k, name in enumerate(_SIFTO_COLUMNS) if k}
+    if epochs.ndim != 1 or len(epochs) < 4:
+        raise ValueError('a template needs at least 4 epochs (the smallest not-a-knot spline)')
+    if not np.all(np.isfinite(epochs)) or not np.all(np.diff(epochs) > 0.):
+        raise ValueError('the epochs of a template must be finite and strictly increasing')
+    for name, v in cols.items():
+        if v.shape != epochs.shape or not np.all(np.isfinite(v)):
+            raise ValueError(f'template column {name!r} must have one finite value per epoch')
+    return epochs, cols
+
+
+class WithTemplate(Model):
+    """A shock model plus a second peak from a template (extension): ``base`` -- a :class:`ShockCooling`,
+    :class:`ShockCooling2`, :class:`ShockCooling3`, :class:`ShockCooling4` or :class:`CustomModel` instance -- and, per
+    filter of ``lc``, a template light curve that the fit may shift, stretch and scale.  What
+    :class:`BaseCompanionShocking` does with SiFTO (models.py:665-845), for any base model and any template: the
+    double-peaked core-collapse light curves, a shock-cooling peak followed by the nickel-powered main peak.
+
+    At a data point ``j`` of filter ``f``::
+
+        m_j(p) = base_j(p_base) + r_f * S_f((t_j - t_max - dt_f) / s)
+
+    ``S_f`` is the not-a-knot cubic spline through the template column of ``f``, 0 outside the template's epochs (and
+    for a NaN argument); ``t`` is the observed time (the reference does not redshift it either); ``r_f`` is a parameter
+    for the filters whose ``char`` is in ``factors`` and 1 for the others, ``dt_f`` one for those in ``offsets`` and 0
+    for the others.  Parameters: ``base.input_names + ['t_\\\\mathrm{max}', 's'] + ['r_X' ...] + ['\\\\Delta t_X' ...]``
+    (then ``\\\\sigma`` where ``use_sigma`` appends it).
+
+    ``template``: ``(epochs, {column_name: values})``, or a 2-D array with the columns of :func:`sifto_template`
+    (``Epoch, U, B, V, g, r, i``); at least 4 epochs, finite and strictly increasing (``ValueError``).  ``columns`` maps a
+    filter of ``lc`` (object or name) to a template column, by default ``filter.char``; a filter of ``lc`` without a
+    column raises as the reference does for SiFTO.  ``scale='peak'``: every filter's column is multiplied by
+    ``max(lc[quantity] over the filter's rows) / max(column)`` (models.py:701-717); ``scale={filter: value}`` gives the
+    peak values instead.
+
+    ``log_likelihood``, ``make_log_posterior``, ``engine_for``, ``lightcurve_mcmc`` and ``model(t, f, *p)`` work as for
+    every model; :meth:`components` gives the two terms, ``temperature_radius`` is the base's.  The fit runs through
+    :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` (one rung at ``beta = 1`` unless a ladder or ``moves`` is
+    asked for): the resident samplers, population runs and the predictive functions compute the model in kernels of
+    their own and raise ``LcfError`` for it; ``model(t, f, *p)`` on a thinned chain gives the curves.  Non-detections
+    are measurements of zero, as in the reference: ``nondet='censored'`` raises ``ValueError`` (out of scope)."""
+
+    def __init__(self, base, template, lc, columns=None, factors=(), offsets=(), scale='peak'):
+        if not isinstance(base, (ShockCooling, ShockCooling2, ShockCooling3, ShockCooling4, CustomModel)):
+            raise TypeError('the base of WithTemplate is a ShockCooling, ShockCooling2, ShockCooling3, ShockCooling4 or '
+                            f'CustomModel instance, not {type(base).__name__}: companion-shocking models have a template '
+                            'of their own, central-engine models have no filters')
+        super().__init__(None, redshift=0.)
+        self.base = base
+        self.z = base.z
+        self.output_quantity = base.output_quantity
+        self.model_id = base.model_id
+        self.device = base.device
+        self.factors, self.offsets = tuple(factors), tuple(offsets)
+        for what, chars in (('factors', self.factors), ('offsets', self.offsets)):
+            if len(set(chars)) != len(chars) or not all(isinstance(x, str) for x in chars):
+                raise ValueError(f'{what} must be distinct filter characters')
+        n_base = base.n_model_params
+        self.input_names = (list(base.input_names[:n_base]) + ['t_\\mathrm{max}', 's']
+                            + ['r_' + x for x in self.factors] + ['\\Delta t_' + x for x in self.offsets])
+        self.units = list(base.units[:n_base]) + ['d', ''] + [''] * len(self.factors) + ['d'] * len(self.offsets)
+        self._n_par = len(self.input_names)
+        self._n_base = n_base
+        if self._n_par + 1 > 16:
+            raise ValueError('the base model, t_max, s, the factors, the offsets and a fitted sigma take at most 16 columns')
+        self._knots, cols = _parse_template(template)
+        columns = {} if columns is None else {as_filter(k): str(v) for k, v in columns.items()}
+        peaks = None if isinstance(scale, str) else {as_filter(k): float(v) for k, v in scale.items()}
+        if peaks is None and scale != 'peak':
+            raise ValueError("scale must be 'peak' or a dict {filter: peak value}")
+        filts = [as_filter(f) for f in _column(lc, 'filter')]
+        if peaks is None:
+            names = getattr(lc, 'colnames', None)
+            if hasattr(lc, 'calcAbsMag') and names is not None and self.output_quantity not in names:
+                for method in {'flux': ('calcFlux',), 'lum': ('calcAbsMag', 'calcLum')}.get(self.output_quantity, ()):
+                    getattr(lc, method)()
+            y = np.asarray(_column(lc, self.output_quantity), dtype=np.float64)
+        self.template = {}
+        for filt in dict.fromkeys(filts):  # models.py:701-717
+            column = columns.get(filt, filt.char)
+            if column not in cols:
+                raise Exception('No template for filter ' + filt.name)
+            col = cols[column]
+            if peaks is None:
+                peak = np.max(y[[f == filt for f in filts]])
+            elif filt in peaks:
+                peak = peaks[filt]
+            else:
+                raise ValueError('scale has no peak value for filter ' + filt.name)
+            self.template[filt] = not_a_knot_coefficients(self._knots, col * peak / np.max(col))
+
+    @property
+    def n_model_params(self):
+        return self._n_par
+
+    def __repr__(self):
+        return f'<{self.__class__.__name__}: {self.base!r} + template of {len(self._knots)} epochs>'
+
+    def _template_tables(self, uniq_filters):
+        """What ``Engine.set_template`` takes for these filters: coefficients, factor and offset columns."""
+        coef = np.zeros((len(uniq_filters), len(self._knots) - 1, 4))
+        fac, off = [], []
+        first = self._n_base + 2
+        for i, f in enumerate(uniq_filters):
+            if f not in self.template:
+                raise Exception('No template for filter ' + f.name)
+            coef[i] = self.template[f]
+            fac.append(first + self.factors.index(f.char) if f.char in self.factors else -1)
+            off.append(first + len(self.factors) + self.offsets.index(f.char) if f.char in self.offsets else -1)
+        return coef, fac, off
+
+    def make_engine(self, t, filts, y, dy, use_sigma=False, sigma_type='relative', priors=None, device=None):
+        """The base model's engine on this photometry with the template attached (``Engine.set_template``)."""
+        filts = [as_filter(f) for f in filts]
+        uniq, _ = _index_filters(filts)
+        coef, fac, off = self._template_tables(uniq)   # (raises before anything is built)
+        pri = None if priors is None else [p.descriptor() for p in priors]
+        if pri is not None and len(pri) != self._n_par + bool(use_sigma):
+            raise ValueError(f'priors must have length {self._n_par + bool(use_sigma)}')
+        eng = self.base.make_engine(t, filts, y, dy, use_sigma, sigma_type, None, device)
+        eng.set_template(self._knots, coef, fac, off, self._n_base, self._n_base + 1, self._n_par - self._n_base, pri)
+        return eng
+
+    def engine_for(self, lc, use_sigma=False, sigma_type='relative', priors=None, nondet='gaussian'):
+        """As :meth:`Model.engine_for`; ``nondet='censored'`` raises ``ValueError``: upper limits together with a template
+        are out of scope."""
+        _check_nondet_mode(nondet)
+        if nondet == 'censored':
+            raise ValueError("nondet='censored' is out of scope for a WithTemplate model: its non-detections enter as "
+                             "measurements of zero ('gaussian'), as in the reference")
+        return super().engine_for(lc, use_sigma, sigma_type, priors)
+
+    def _component(self, component, t_in, f, *params):
+        if len(params) != self.n_model_params:
+            raise TypeError(f'{type(self).__name__} takes {self.n_model_params} parameters, got {len(params)}')
+        cols = np.broadcast_arrays(*[np.asarray(x, dtype=np.float64) for x in params])
+        scalar = cols[0].ndim == 0
+        eng, shape = self._eval_engine(t_in, f, scalar)
+        P = np.column_stack([np.atleast_1d(c).ravel() for c in cols])
+        y = eng.evaluate_components(P, component)  # (n, npoints)
+        y = y[0] if scalar else y.T
+        if shape is not None:
+            y = y.reshape(shape if scalar else shape + (len(P),))
+        return y
+
+    def evaluate(self, t_in, f, *params):
+        """Model light curve(s), both components; shapes as :meth:`Model.evaluate`."""
+        return self._component('total', t_in, f, *params)
+
+    def components(self, t_in, f, *params):
+        """``(base, template)``: the two terms of :meth:`evaluate`, in its shapes."""
+        return self._component('base', t_in, f, *params), self._component('template', t_in, f, *params)
+
+    def temperature_radius(self, t_in, *params):
+        """The base model's photosphere (the template has none): ``params`` as the base's ``temperature_radius`` takes
+        them; of a whole row of this model, the base's columns are passed on."""
+        if len(params) == self._n_par:
+            params = params[:self._n_base]
+        return self.base.temperature_radius(t_in, *params)
 
 
 class BaseCentralEngine(Model):
