@@ -806,6 +806,34 @@ enum { LCF_TEMPLATE_TOTAL = 1, LCF_TEMPLATE_BASE = 2, LCF_TEMPLATE_TEMPLATE = 3 
  * template. */
 lcf_status lcf_template_evaluate(lcf_engine* e, int64_t n, const double* P, int32_t component, double* out);
 
+/* ---- bands and features of a template fit: both components and their sum, over ALL samples ------------------------ */
+/* `grid` is an evaluation engine with a second component attached, on the dense grid, filter-major: point f * n_times + t
+ * is filter f of the engine at the t-th of n_times distinct times (dummy photometry, no sigma, no priors; at most 16
+ * filters; the model one of the built-in shock-cooling models).  Per sample s (a row of n_par + n_extra columns, as
+ * lcf_log_likelihood takes it), filter f and time t, defined exactly as lcf_template_evaluate defines them:
+ *     B  = the base model's value (what lcf_predict_quantiles ranks for the engine without the template),
+ *     Tm = r_f S_f((t - t_max - dt_f) * (1 / s)),    Y = B + Tm.
+ * components: a non-empty sum of the LCF_TEMPLATE_MASK_* values; the n_comp components asked for come out in the order
+ * total (Y), base (B), template (Tm).  out / n_valid are the percentiles q[n_q] and the non-NaN counts of each over the
+ * samples (definition, workspace, tiling and reproducibility as for lcf_predict_quantiles; n_comp * n_filters * n_q <=
+ * 512), n_dark the samples whose B is exactly +0.0: the shock has not started.  Nothing is stored per (sample, time).
+ * Every argument is checked before a device is asked for: LCF_ERR_STATE for an engine without a template,
+ * LCF_ERR_UNSUPPORTED for an engine of LCF_MODEL_CUSTOM or of a central-engine model (naming the route such an engine
+ * does take), for more than 16 filters and for more than 512 searches; everything else LCF_ERR_INVALID_ARGUMENT. */
+enum { LCF_TEMPLATE_MASK_TOTAL = 1, LCF_TEMPLATE_MASK_BASE = 2, LCF_TEMPLATE_MASK_TEMPLATE = 4 };
+lcf_status lcf_predict_template(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t components,
+                                const double* q, int32_t n_q, int64_t workspace_bytes,
+                                double* out /* [n_q][n_comp][n_points] */, int64_t* n_valid /* [n_comp][n_points] */,
+                                int64_t* n_dark /* [n_points] */);
+/* Per sample and filter of the same grid, over the times walked in ascending order; the first occurrence always wins,
+ * comparisons are on values and a NaN never wins one.  indices[0], [1]: where the largest non-NaN B and the largest
+ * non-NaN Tm are (-1: none); [2]: the first time with Tm > B (-1: none); [3]: where the smallest non-NaN Y over the
+ * times from indices[0] to indices[1] inclusive is, defined only when 0 <= indices[0] < indices[1] in the walk (else -1).
+ * values[0], [1], [2]: B, Tm and Y there, NaN where the index is -1.  Indices are the caller's t.  One launch over all
+ * samples, (64 + 40 n_filters) n bytes of device memory beyond the samples; checks and status codes as above. */
+lcf_status lcf_template_features(lcf_engine* grid, const double* P, int64_t n, int32_t ld,
+                                 double* values /* [3][n_filters][n] */, int32_t* indices /* [4][n_filters][n] */);
+
 #ifdef __cplusplus
 }
 #endif

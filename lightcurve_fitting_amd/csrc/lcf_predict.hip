@@ -48,6 +48,17 @@
 //   k_cq_peak     lane = sample: walks the tile's times in ascending order, recomputes the filters' values and keeps
 //                 per filter the sample's largest non-NaN value and the first time it is attained (strict >), in LDS
 //                 as [filter][lane]; read from and written to device memory across tiles, as k_lq_peak's are.
+// The template form (DESIGN.md "Bands and features of a template fit") is for an engine with a second component attached
+// (lcf_engine_set_template): per (sample, time, filter) the base model's value B -- pq_point -- and the template term
+// Tm = r_f S_f((t - t_max - dt_f) (1 / s)), with Y = B + Tm the operations of k_template in its order.
+//   k_tq_pass     the geometry and modes of k_pq_pass: thermal state once per (sample, time), then per filter B and Tm;
+//                 the series of a time are component x filter (Y, B, Tm: those the caller's mask names).  The knots and
+//                 the cubic coefficients of every filter are staged in LDS where they fit beside the histograms (lanes
+//                 are samples: their spline intervals diverge).  In mode 0 it also counts, per (time, filter), the
+//                 samples whose B is exactly +0 (the shock has not started), as k_kq_pass counts its dark ones.
+//   k_tq_features lane = sample, one launch over all samples: per filter the times are walked once in ascending order
+//                 for the largest non-NaN B and Tm (first occurrence, strict >) and the first time with Tm > B, then the
+//                 times between the two peaks for the smallest non-NaN Y (the dip), B and Tm recomputed.
 // k_pq_pick and k_pq_finish serve all forms; the host driver (quantile_run) differs in the launches only.
 #include <hip/hip_runtime.h>
 
@@ -59,6 +70,7 @@
 #include "lcf_host.h"
 #include "lcf_internal.h"
 #include "lcf_keys.h"
+#include "lcf_template.h"
 
 using namespace lcf;
 
@@ -469,6 +481,166 @@ __global__ __launch_bounds__(kCqPeakThreads) void k_cq_peak(const DevProblem pb,
     for (int f = 0; f < nf; ++f) {
         pk.best[(long long)f * a.n + s] = best[f * kCqPeakThreads + tid];
         pk.at[(long long)f * a.n + s] = at[f * kCqPeakThreads + tid];
+    }
+}
+
+// ---- the template form: base, template term and their sum as the series of a (time, filter) -------------------------
+constexpr int kTqMaxFilters = 16;          // filters of a template call: a dark counter each in a pass workgroup
+constexpr int kTqFeatThreads = 256;
+constexpr int kTqValues = 3, kTqIndices = 4;   // per (filter, sample): y_peak_base, y_peak_template, y_dip | their indices, i_cross
+enum { kTqTotal = LCF_TEMPLATE_MASK_TOTAL, kTqBase = LCF_TEMPLATE_MASK_BASE, kTqTemplate = LCF_TEMPLATE_MASK_TEMPLATE };
+
+struct TqArgs {
+    TemplateDev tp;
+    int mask, n_comp;                // the components that are ranked (kTq*), and how many
+    int stage;                       // the knots and coefficients are read from LDS
+    unsigned long long* n_dark;      // [n_epochs][n_filters] samples whose B is exactly +0
+};
+
+struct TqFeatures {
+    double* values;                  // [kTqValues][n_filters][n]
+    int* indices;                    // [kTqIndices][n_filters][n]: epochs, -1 = none
+};
+
+// The knots and every filter's coefficients behind `at` (doubles): n_knots + n_filters (n_knots - 1) 4 of them.  The
+// caller synchronises.
+__device__ __forceinline__ void tq_stage(const TemplateDev& tp, int nf, double* at, int tid, int threads) {
+    const int nk = tp.n_knots, nc = nf * (nk - 1) * 4;
+    for (int k = tid; k < nk; k += threads) at[k] = tp.knots[k];
+    for (int k = tid; k < nc; k += threads) at[nk + k] = tp.coef[k];
+}
+
+// The template term of (row p, filter f) at time t_in: the operations of k_template, in its order.
+__device__ __forceinline__ double tq_term(const TemplateDev& tp, const double* __restrict__ knots,
+                                          const double* __restrict__ coef, const double* __restrict__ p, int f,
+                                          double t_in, double t_max, double inv_s) {
+    const int fp = tp.fac[f], op = tp.off[f];
+    const double fac = fp >= 0 ? p[fp] : 1.;
+    const double dt = op >= 0 ? p[op] : 0.;
+    const double x = (t_in - t_max - dt) * inv_s;
+    return __dmul_rn(fac, spline_eval(knots, tp.n_knots, coef + (size_t)f * (tp.n_knots - 1) * 4, x, tp.inv_h));
+}
+
+// blockIdx.x = time of the tile, blockIdx.y = chunk of samples.  Dynamic LDS: exp table | dark counters [kTqMaxFilters]
+// | knots and coefficients (tq.stage) | per search prefix, successor, prefix bits, collect flag | histogram counters.
+template <int MODEL>
+__global__ __launch_bounds__(kPqThreads) void k_tq_pass(const DevProblem pb, const PqArgs a, const TqArgs tq) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nf = pb.n_filters, nk = tq.tp.n_knots, ns = tq.n_comp * nf * a.n_q;
+    double* exptab = reinterpret_cast<double*>(smem);
+    unsigned int* s_dark = reinterpret_cast<unsigned int*>(exptab + kExpTabSize);
+    double* l_knots = exptab + kExpTabSize + kTqMaxFilters / 2;
+    double* l_coef = l_knots + nk;
+    double* words = tq.stage ? l_coef + (size_t)nf * (nk - 1) * 4 : l_knots;
+
+    const int model = MODEL ? MODEL : pb.model;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ep = a.ep0 + blockIdx.x;
+    const int n_hist = a.mode == 0 ? (tq.n_comp * nf) << a.bits : a.mode == 1 ? ns << a.bits : 0;
+    PqSearch* search = a.search + (size_t)blockIdx.x * ns;
+    for (int k = tid; k < kExpTabSize; k += kPqThreads) exptab[k] = pb.exp2tab[k];
+    if (tid < kTqMaxFilters) s_dark[tid] = 0u;
+    if (tq.stage) tq_stage(tq.tp, nf, l_knots, tid, kPqThreads);
+    const PqLds lds = pq_lds_setup(a, words, search, ns, n_hist, tid);
+    __syncthreads();
+
+    const ExpTab et{exptab};
+    const double t_in = pb.epoch_t[ep];
+    const bool log_state = pb.variant != 0 && pb.use_itab && model != kShockCooling3;
+    const unsigned int mask = (1u << a.bits) - 1u;
+    const long long s0 = (long long)blockIdx.y * a.chunk, s1 = min(a.n, s0 + a.chunk);
+    for (long long sb = s0; sb < s1; sb += kPqThreads) {
+        const long long s = sb + tid;
+        if (s >= s1) continue;
+        double c[kNCoef];
+#pragma unroll
+        for (int i = 0; i < kNCoef; ++i) c[i] = a.coef[(long long)i * a.n + s];
+        const double* prow = pq_row(a, s);
+        const double t_max = prow[tq.tp.i_tmax];
+        const double inv_s = 1. / prow[tq.tp.i_s];
+        double x, p;
+        cq_state<MODEL>(pb, c, t_in, log_state, et, x, p);
+        for (int f = 0; f < nf; ++f) {
+            const double B = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, 0);
+            const double Tm = tq.stage ? tq_term(tq.tp, l_knots, l_coef, prow, f, t_in, t_max, inv_s)
+                                       : tq_term(tq.tp, tq.tp.knots, tq.tp.coef, prow, f, t_in, t_max, inv_s);
+            if (a.mode == 0) {   // (wave-uniform: one LDS add per wave and filter)
+                const unsigned long long dark = __builtin_amdgcn_ballot_w64(__double_as_longlong(B) == 0LL);
+                if (dark && lane == (int)__builtin_ctzll(dark)) atomicAdd(&s_dark[f], (unsigned int)__popcll(dark));
+            }
+            int k = 0;
+            if (tq.mask & kTqTotal) pq_consume(a, lds, search, ns, k++ * nf + f, __dadd_rn(B, Tm), lane, mask);
+            if (tq.mask & kTqBase) pq_consume(a, lds, search, ns, k++ * nf + f, B, lane, mask);
+            if (tq.mask & kTqTemplate) pq_consume(a, lds, search, ns, k * nf + f, Tm, lane, mask);
+        }
+    }
+    __syncthreads();
+    pq_merge(a, lds, search, ns, n_hist, tid);
+    if (a.mode == 0 && tid < nf && s_dark[tid]) atomicAdd(&tq.n_dark[(size_t)ep * nf + tid], (unsigned long long)s_dark[tid]);
+}
+
+// blockIdx.x = chunk of kTqFeatThreads samples, lanes = samples; every time of the grid, whatever the tiling of the
+// passes.  Filters outermost, the running state of one filter in registers; the thermal state is recomputed per filter.
+// Dynamic LDS: knots and coefficients (tq.stage).
+template <int MODEL>
+__global__ __launch_bounds__(kTqFeatThreads) void k_tq_features(const DevProblem pb, const PqArgs a, const TqArgs tq,
+                                                               const TqFeatures ft) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double exptab[kExpTabSize];
+    const int nf = pb.n_filters, nk = tq.tp.n_knots, n_ep = pb.n_epochs;
+    double* l_knots = reinterpret_cast<double*>(smem);
+    double* l_coef = l_knots + nk;
+
+    const int model = MODEL ? MODEL : pb.model;
+    const int tid = threadIdx.x;
+    for (int k = tid; k < kExpTabSize; k += kTqFeatThreads) exptab[k] = pb.exp2tab[k];
+    if (tq.stage) tq_stage(tq.tp, nf, l_knots, tid, kTqFeatThreads);
+    __syncthreads();
+    const long long s = (long long)blockIdx.x * kTqFeatThreads + tid;
+    if (s >= a.n) return;
+
+    const ExpTab et{exptab};
+    const bool log_state = pb.variant != 0 && pb.use_itab && model != kShockCooling3;
+    double c[kNCoef];
+#pragma unroll
+    for (int i = 0; i < kNCoef; ++i) c[i] = a.coef[(long long)i * a.n + s];
+    const double* prow = pq_row(a, s);
+    const double t_max = prow[tq.tp.i_tmax];
+    const double inv_s = 1. / prow[tq.tp.i_s];
+    const size_t plane = (size_t)nf * a.n;
+    for (int f = 0; f < nf; ++f) {
+        double best_b = 0., best_t = 0., best_y = 0.;
+        int at_b = -1, at_t = -1, at_x = -1, at_y = -1;
+        for (int i = 0; i < n_ep; ++i) {
+            const double t_in = pb.epoch_t[i];
+            double x, p;
+            cq_state<MODEL>(pb, c, t_in, log_state, et, x, p);
+            const double B = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, 0);
+            const double Tm = tq.stage ? tq_term(tq.tp, l_knots, l_coef, prow, f, t_in, t_max, inv_s)
+                                       : tq_term(tq.tp, tq.tp.knots, tq.tp.coef, prow, f, t_in, t_max, inv_s);
+            if (B == B && (at_b < 0 || B > best_b)) best_b = B, at_b = i;   // (as k_lq_peak: the first occurrence wins)
+            if (Tm == Tm && (at_t < 0 || Tm > best_t)) best_t = Tm, at_t = i;
+            if (at_x < 0 && Tm > B) at_x = i;
+        }
+        if (at_b >= 0 && at_b < at_t)
+            for (int i = at_b; i <= at_t; ++i) {
+                const double t_in = pb.epoch_t[i];
+                double x, p;
+                cq_state<MODEL>(pb, c, t_in, log_state, et, x, p);
+                const double B = pq_point<MODEL>(pb, c, prow, t_in, f, x, p, et, 0);
+                const double Tm = tq.stage ? tq_term(tq.tp, l_knots, l_coef, prow, f, t_in, t_max, inv_s)
+                                           : tq_term(tq.tp, tq.tp.knots, tq.tp.coef, prow, f, t_in, t_max, inv_s);
+                const double Y = __dadd_rn(B, Tm);
+                if (Y == Y && (at_y < 0 || Y < best_y)) best_y = Y, at_y = i;
+            }
+        const size_t o = (size_t)f * a.n + s;
+        ft.values[o] = best_b;
+        ft.values[plane + o] = best_t;
+        ft.values[2 * plane + o] = best_y;
+        ft.indices[o] = at_b;
+        ft.indices[plane + o] = at_t;
+        ft.indices[2 * plane + o] = at_x;
+        ft.indices[3 * plane + o] = at_y;
     }
 }
 
@@ -991,6 +1163,49 @@ struct ColorForm : PqForm {
     }
 };
 
+// Bytes of the knots and of every filter's coefficients of the engine's template: what a kernel stages in LDS.
+size_t template_table_bytes(const lcf_engine* e) {
+    return ((size_t)e->tpl_nk + (size_t)e->dp.n_filters * (e->tpl_nk - 1) * 4) * sizeof(double);
+}
+
+// The series of a time are component x filter; B and Tm of every (sample, time, filter) are recomputed in every pass,
+// the thermal state once per (sample, time).
+struct TemplateForm : PqForm {
+    const DevProblem& dp;
+    TqArgs tq{};
+    TemplateForm(const lcf_engine* e, int mask) : dp(e->dp) {
+        tq.tp = template_dev(e);
+        tq.mask = mask;
+        tq.n_comp = __builtin_popcount((unsigned)mask);
+        nf = tq.n_comp * dp.n_filters;
+        sample_bytes = kNCoef * sizeof(double);
+        time_bytes = (size_t)dp.n_filters * sizeof(unsigned long long);   // the dark counters
+        lds_head = kExpTabSize * sizeof(double) + kTqMaxFilters * sizeof(unsigned int);
+        // the table goes to LDS when a pass workgroup with the most search words and counters still fits a compute unit
+        const size_t most = lds_head + (size_t)kPqMaxSearch * 24 + kPqHistBytes;
+        tq.stage = most + template_table_bytes(e) <= kCqLdsPerCU;
+        if (tq.stage) lds_head += template_table_bytes(e);
+    }
+    lcf_status prepare(DevBuf& mem, PqArgs& a, double* d_coef) override {
+        const size_t n_cnt = (size_t)dp.n_epochs * dp.n_filters;
+        if (lcf_status st = mem.alloc(&tq.n_dark, n_cnt)) return st;
+        LCF_HIP(hipMemset(tq.n_dark, 0, n_cnt * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
+        LCF_HIP(hipGetLastError());
+        return LCF_OK;
+    }
+    template <int MODEL>
+    lcf_status launch(const PqArgs& a, int n_ep, size_t lds) {
+        if (lds > kCqLdsPerCU) return fail(LCF_ERR_UNSUPPORTED, "a template pass needs more LDS than a compute unit has");
+        LCF_HIP(prepare_kernel(k_tq_pass<MODEL>, lds));
+        return launch_pass(k_tq_pass<MODEL>, dp, a, n_ep, lds, tq);
+    }
+    lcf_status pass(const PqArgs& a, int n_ep, size_t lds) override {
+        if (dp.model == kShockCooling) return launch<kShockCooling>(a, n_ep, lds);
+        return launch<0>(a, n_ep, lds);
+    }
+};
+
 // The searches of every point (time x series of `form`), the times in tiles that fit the workspace, over the walkers of
 // the kept steps of `chain` (device memory) as samples.  orig_host[n_ep_all][nf]: where the point's results go, -1 = no
 // such point.  out[n_q][n_points], n_valid[n_points] (host).
@@ -1344,6 +1559,124 @@ lcf_status stored_samples(const lcf_engine* grid, lcf_sampler* s, int64_t discar
     return LCF_OK;
 }
 
+// What both template entry points check before the device is touched (`what` names the caller).
+lcf_status template_check(const lcf_engine* grid, const double* P, int64_t n, int32_t ld, const char* what) {
+    if (!grid || !P) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = custom_refuse(grid, what)) return st;
+    if (lcf_status st = central_refuse(grid, what)) return st;
+    if (!grid->tpl)
+        return fail(LCF_ERR_STATE, std::string(what) + " takes an engine with a second component: call "
+                                   "lcf_engine_set_template first (the bands of the model alone are lcf_predict_quantiles)");
+    if (grid->dp.n_points < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine has no points");
+    if (grid->dp.n_filters > kTqMaxFilters)
+        return fail(LCF_ERR_UNSUPPORTED, std::string(what) + " takes a grid engine of at most 16 distinct filters, this "
+                                         "one has " + std::to_string(grid->dp.n_filters) + ": split the filters over calls");
+    if (n < 1) return fail(LCF_ERR_INVALID_ARGUMENT, "need at least one sample");
+    if (ld < grid->dp.n_par + grid->tpl_extra)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "ld is smaller than the model's parameter count with the template's columns");
+    return LCF_OK;
+}
+
+// The engine's points as the dense filters x distinct-times grid, filter-major (color_run's requirement): time_orig[ep]
+// is the caller's index of the engine's time ep (the engine's are ascending).
+lcf_status template_grid(const lcf_engine* grid, std::vector<int32_t>* time_orig) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points, NF = dp.n_filters, nt = dp.n_epochs;
+    if ((long long)N != (long long)nt * NF)
+        return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine must hold every filter at every distinct time");
+    std::vector<int> filt(N), orig(N), epoch(N);
+    LCF_HIP(hipMemcpy(filt.data(), dp.pt_filt, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(orig.data(), dp.pt_orig, N * sizeof(int), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(epoch.data(), dp.pt_epoch, N * sizeof(int), hipMemcpyDeviceToHost));
+    time_orig->assign(nt, -1);
+    std::vector<char> seen((size_t)nt * NF, 0);
+    for (int i = 0; i < N; ++i) {
+        if (epoch[i] < 0 || epoch[i] >= nt || filt[i] < 0 || filt[i] >= NF || orig[i] < 0 || orig[i] >= N)
+            return fail(LCF_ERR_STATE, "the engine's point order is inconsistent");
+        char& slot = seen[(size_t)epoch[i] * NF + filt[i]];
+        int32_t& t_o = (*time_orig)[epoch[i]];
+        if (slot) return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine holds a (time, filter) pair twice");
+        slot = 1;
+        if (orig[i] / nt != filt[i] || (t_o >= 0 && t_o != orig[i] % nt))
+            return fail(LCF_ERR_INVALID_ARGUMENT, "the grid engine's points must be the dense grid, filter-major");
+        t_o = orig[i] % nt;
+    }
+    return LCF_OK;
+}
+
+// The template form on the dense grid.  out[n_q][n_comp][n_filters][n_times], n_valid[n_comp][n_filters][n_times],
+// n_dark[n_filters][n_times] (host); the components in the order total, base, template; times in the caller's order.
+lcf_status template_run(lcf_engine* grid, const ChainView& in, int32_t mask, const double* q, int32_t n_q,
+                        int64_t workspace_bytes, double* out, int64_t* n_valid, int64_t* n_dark) {
+    const DevProblem& dp = grid->dp;
+    const int N = dp.n_points, NF = dp.n_filters, nt = dp.n_epochs;
+    std::vector<int32_t> time_orig;
+    if (lcf_status st = template_grid(grid, &time_orig)) return st;
+    TemplateForm form(grid, mask);
+    const int nser = form.nf;
+    if ((long long)N * form.tq.n_comp > INT32_MAX) return fail(LCF_ERR_INVALID_ARGUMENT, "too many (point, component) pairs");
+    std::vector<int32_t> table((size_t)nt * nser);   // component x filter take the place of a time's filters
+    for (int ep = 0; ep < nt; ++ep)
+        for (int k = 0; k < nser; ++k) table[(size_t)ep * nser + k] = (k / NF) * N + (k % NF) * nt + time_orig[ep];
+    DevBuf mem;
+    if (lcf_status st = quantile_run(grid->device, form, nt, (long long)form.tq.n_comp * N, in, 0, 1, table.data(), 0, q,
+                                     n_q, workspace_bytes, mem, out, n_valid))
+        return st;
+    std::vector<unsigned long long> cnt((size_t)nt * NF);
+    LCF_HIP(hipMemcpy(cnt.data(), form.tq.n_dark, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int ep = 0; ep < nt; ++ep)
+        for (int f = 0; f < NF; ++f) n_dark[(size_t)f * nt + time_orig[ep]] = (int64_t)cnt[(size_t)ep * NF + f];
+    return LCF_OK;
+}
+
+// The features of every (sample, filter) on the dense grid, one launch.  values[3][n_filters][n] (NaN where the index is
+// -1), indices[4][n_filters][n] in the caller's order of the times (host).
+lcf_status features_run(lcf_engine* grid, const ChainView& in, double* values, int32_t* indices) {
+    const DevProblem& dp = grid->dp;
+    const int NF = dp.n_filters;
+    std::vector<int32_t> time_orig;
+    if (lcf_status st = template_grid(grid, &time_orig)) return st;
+    const KeptSteps kept = kept_steps(in, 0, 1);
+    const long long n = kept.samples;
+    const size_t plane = (size_t)NF * n;
+    DevBuf mem;
+    double* d_coef;
+    TqFeatures ft{};
+    lcf_status st;
+    if ((st = mem.alloc(&d_coef, (size_t)n * kNCoef)) || (st = mem.alloc(&ft.values, kTqValues * plane)) ||
+        (st = mem.alloc(&ft.indices, kTqIndices * plane)))
+        return st;
+    PqArgs a{};
+    a.base = kept.base;
+    a.n = n;
+    a.n_w = in.n_w;
+    a.step_stride = kept.step_stride;
+    a.ld = in.ld;
+    a.coef = d_coef;
+    TqArgs tq{};
+    tq.tp = template_dev(grid);
+    const size_t table = template_table_bytes(grid);
+    tq.stage = table <= 60 * 1024;   // (beside the kernel's own exp table, within the 64 KiB every launch may ask for)
+    const size_t lds = tq.stage ? table : 0;
+    const unsigned blocks = (unsigned)((n + kTqFeatThreads - 1) / kTqFeatThreads);
+    hipLaunchKernelGGL(k_pq_coef, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dp, a, d_coef);
+    LCF_HIP(hipGetLastError());
+    if (dp.model == kShockCooling)
+        hipLaunchKernelGGL(k_tq_features<kShockCooling>, dim3(blocks), dim3(kTqFeatThreads), lds, 0, dp, a, tq, ft);
+    else
+        hipLaunchKernelGGL(k_tq_features<0>, dim3(blocks), dim3(kTqFeatThreads), lds, 0, dp, a, tq, ft);
+    LCF_HIP(hipGetLastError());
+    LCF_HIP(hipMemcpy(values, ft.values, kTqValues * plane * sizeof(double), hipMemcpyDeviceToHost));
+    LCF_HIP(hipMemcpy(indices, ft.indices, kTqIndices * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int of_index[kTqValues] = {0, 1, 3};   // y_peak_base, y_peak_template, y_dip belong to i_peak_base, .., i_dip
+    for (int v = 0; v < kTqValues; ++v)
+        for (size_t k = 0; k < plane; ++k)
+            if (indices[of_index[v] * plane + k] < 0) values[v * plane + k] = std::nan("");
+    for (size_t k = 0; k < kTqIndices * plane; ++k)
+        if (indices[k] >= 0) indices[k] = time_orig[indices[k]];
+    return LCF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1403,6 +1736,35 @@ lcf_status lcf_sampler_predict_colors(lcf_engine* grid, lcf_sampler* s, int64_t 
     ChainView in;
     if (lcf_status st = stored_samples(grid, s, discard, thin, &in)) return st;
     return color_run(grid, in, discard, thin, n_c, pairs, dzp, q, n_q, workspace_bytes, out, n_valid, y_peak, peak_index);
+}
+
+lcf_status lcf_predict_template(lcf_engine* grid, const double* P, int64_t n, int32_t ld, int32_t components,
+                                const double* q, int32_t n_q, int64_t workspace_bytes, double* out, int64_t* n_valid,
+                                int64_t* n_dark) {
+    if (!q || !out || !n_valid || !n_dark) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = template_check(grid, P, n, ld, "a band of a template fit (lcf_predict_template)")) return st;
+    const int32_t all = LCF_TEMPLATE_MASK_TOTAL | LCF_TEMPLATE_MASK_BASE | LCF_TEMPLATE_MASK_TEMPLATE;
+    if (components < 1 || (components & ~all))
+        return fail(LCF_ERR_INVALID_ARGUMENT, "components: a non-empty sum of LCF_TEMPLATE_MASK_TOTAL, _BASE and _TEMPLATE");
+    if (lcf_status st = check_percentiles(q, n_q, kPqMaxSearch, "need between 1 and 512 percentiles")) return st;
+    const long long searches = (long long)__builtin_popcount((unsigned)components) * grid->dp.n_filters * n_q;
+    if (searches > kPqMaxSearch)
+        return fail(LCF_ERR_UNSUPPORTED, "components x filters x percentiles of one call must not exceed 512, this call has " +
+                                         std::to_string(searches) + ": split the percentiles over calls");
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return template_run(grid, in, components, q, n_q, workspace_bytes, out, n_valid, n_dark);
+}
+
+lcf_status lcf_template_features(lcf_engine* grid, const double* P, int64_t n, int32_t ld, double* values,
+                                 int32_t* indices) {
+    if (!values || !indices) return fail(LCF_ERR_INVALID_ARGUMENT, "null argument");
+    if (lcf_status st = template_check(grid, P, n, ld, "the features of a template fit (lcf_template_features)")) return st;
+    DevBuf mem;
+    ChainView in;
+    if (lcf_status st = uploaded_samples(grid, P, n, ld, mem, &in)) return st;
+    return features_run(grid, in, values, indices);
 }
 
 lcf_status lcf_predict_luminosity(lcf_engine* grid, const double* P, int64_t n, int32_t ld, const double* q, int32_t n_q,

@@ -20,19 +20,14 @@
 #include <cmath>
 
 #include "lcf_internal.h"
+#include "lcf_template.h"
 
 namespace {
 
 constexpr size_t kTemplateScratch = 256u << 20;   // bytes of model values per pass (as lcf_model_evaluate bounds its own)
 constexpr int kMaxKnots = 1 << 16;
 
-// What k_template reads about the engine (by value).
-struct TemplateDev {
-    int n_points, n_knots, n_dim, use_sigma, sigma_abs, i_tmax, i_s, pad;
-    double unit_abs, log_norm_const, inv_h;
-    const double *knots, *coef, *t, *y, *dy;   // the photometry in the caller's order, as m is
-    const int *filt, *fac, *off;               // per point: its filter; per filter: the columns of its r and dt, -1: none
-};
+// (What k_template reads about the engine, by value: TemplateDev / template_dev, lcf_template.h.)
 
 enum { kLogLike = 0, kTotal = LCF_TEMPLATE_TOTAL, kBase = LCF_TEMPLATE_BASE, kTemplate = LCF_TEMPLATE_TEMPLATE };
 
@@ -92,17 +87,6 @@ __global__ __launch_bounds__(64) void k_template(const TemplateDev a, int n_rows
 const char kRoute[] = "an engine with a second component attached (lcf_engine_set_template) is evaluated by "
                       "lcf_log_likelihood / lcf_log_posterior (and _dev) and lcf_template_evaluate, and sampled through "
                       "lcf_tempered_* (TemperedSampler; one rung at beta = 1 is the ensemble sampler)";
-
-TemplateDev template_dev(const lcf_engine* e) {
-    const DevProblem& pb = e->dp;
-    TemplateDev a{};
-    a.n_points = pb.n_points, a.n_knots = e->tpl_nk, a.n_dim = pb.n_dim, a.use_sigma = pb.use_sigma;
-    a.sigma_abs = pb.sigma_abs, a.i_tmax = e->tpl_tmax, a.i_s = e->tpl_s;
-    a.unit_abs = pb.sigma_unit_abs, a.log_norm_const = pb.log_norm_const, a.inv_h = e->tpl_inv_h;
-    a.knots = e->tpl_knots, a.coef = e->tpl_coef, a.t = e->tpl_t, a.y = e->tpl_y, a.dy = e->tpl_dy;
-    a.filt = e->tpl_filt, a.fac = e->tpl_fac, a.off = e->tpl_off;
-    return a;
-}
 
 void launch_template(const lcf_engine* e, int64_t lo, int64_t m, int mode, const double* dP, const double* lprior,
                      double* values, double* dout, hipStream_t st) {

@@ -203,10 +203,15 @@ SIGNATURES = [
     ('lcf_engine_set_template', C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _ip, _ip, C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(LcfPrior)]),
     ('lcf_template_evaluate', C.c_int, [C.c_void_p, C.c_int64, _dp, C.c_int32, _dp]),
+    ('lcf_predict_template', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int64, _dp,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('lcf_template_features', C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, _dp, _ip]),
 ]
 
 #: `component` of `lcf_template_evaluate` (include/lcf.h: LCF_TEMPLATE_*)
 TEMPLATE_COMPONENTS = {'total': 1, 'base': 2, 'template': 3}
+#: `components` of `lcf_predict_template` (include/lcf.h: LCF_TEMPLATE_MASK_*), in the order the results come out
+TEMPLATE_MASK = {'total': 1, 'base': 2, 'template': 4}
 
 
 def load_library(path=None):
@@ -1222,6 +1227,86 @@ def predict_custom(grid_engine, samples, percentiles, T_floor=None, workspace_by
                                   -1. if T_floor is None else float(T_floor), ws, _ptr(out), _i64p(n_valid),
                                   _i64p(n_dark), None if n_cold is None else _i64p(n_cold)))
     return out, n_valid, n_dark, n_cold
+
+
+#: filters of one native template call (include/lcf.h)
+TEMPLATE_MAX_FILTERS = 16
+#: per (filter, sample): the values and the indices of :func:`template_features`, in their order
+TEMPLATE_FEATURE_VALUES = ('y_peak_base', 'y_peak_template', 'y_dip')
+TEMPLATE_FEATURE_INDICES = ('i_peak_base', 'i_peak_template', 'i_cross', 'i_dip')
+
+
+def template_components(components):
+    """``(names in the order the results come out, mask)`` of the ``components`` of :func:`predict_template`: a name or
+    a non-empty sequence of distinct names out of ``'total'``, ``'base'``, ``'template'``."""
+    if isinstance(components, str):
+        components = (components,)
+    components = tuple(components)
+    bad = [c for c in components if c not in TEMPLATE_MASK]
+    if len(components) == 0 or bad or len(set(components)) != len(components):
+        raise ValueError("components must be a non-empty selection of distinct names out of 'total', 'base', 'template'"
+                         + (f', not {bad[0]!r}' if bad else ''))
+    names = tuple(c for c in TEMPLATE_MASK if c in components)
+    return names, sum(TEMPLATE_MASK[c] for c in names)
+
+
+def template_workspace(n_samples, n_times, n_filters, n_components, n_q, tile=1):
+    """Device memory [bytes] beyond the samples that :func:`predict_template` needs to work through ``tile`` times at
+    once -- the least ``workspace_bytes`` for that tile ("Bands and features of a template fit").  With
+    ``S = n_components n_filters`` series per time::
+
+        fixed    = 64 n_samples + 8 (n_q + 1) S n_times + (4 S + 8 n_filters) n_times + 4096
+        per time = S n_q (56 + 8 * 2048) + 4 max(S 2^b0, S n_q 2^b1)
+
+    with ``b0`` / ``b1`` the largest of 4 ... 11 for which ``S 2^b0`` / ``S n_q 2^b1`` four-byte counters fit 48 KiB of
+    LDS.  Nothing is stored per (sample, time).  The features of :func:`template_features` are a call of their own:
+    ``(64 + 40 n_filters) n_samples`` bytes."""
+    series = n_components * n_filters
+    ns = series * n_q
+    fixed = 64 * n_samples + 8 * (n_q + 1) * series * n_times + (4 * series + 8 * n_filters) * n_times + 4096
+    hist = 4 * max(series << _hist_bits(series), ns << _hist_bits(ns))
+    return fixed + tile * (ns * (56 + 8 * 2048) + hist)
+
+
+def _template_samples(grid_engine, samples):
+    P = _f64(samples)
+    if P.ndim != 2:
+        raise ValueError('samples must have shape (n, n_columns)')
+    n_f = grid_engine.nfilters
+    return P, n_f, grid_engine.npoints // max(n_f, 1)
+
+
+def predict_template(grid_engine, samples, percentiles, components=('total', 'base', 'template'), workspace_bytes=None):
+    """``lcf_predict_template``: percentiles over all samples of the sum, the base model's term and the template term of
+    an engine with a second component attached, on the dense filters x distinct-times grid of ``grid_engine``
+    (filter-major), with the valid counts and the samples whose base term is exactly ``+0.0``.  ``samples``: a host
+    array (n, ld); ``n_components * n_filters * n_q <= PREDICT_MAX_SEARCHES``.  Returns ``(quantiles[n_q, n_c, n_f, n_t],
+    n_valid[n_c, n_f, n_t], n_dark[n_f, n_t], names)``, the components in the order ``names`` (total, base, template)."""
+    lib = load_library()
+    q = _f64(percentiles)
+    names, mask = template_components(components)
+    P, n_f, n_t = _template_samples(grid_engine, samples)
+    out = np.empty((len(q), len(names), n_f, n_t))
+    n_valid = np.empty((len(names), n_f, n_t), dtype=np.int64)
+    n_dark = np.empty((n_f, n_t), dtype=np.int64)
+    ws = PREDICT_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    _check(lib.lcf_predict_template(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], mask, _ptr(q), len(q), ws,
+                                    _ptr(out), _i64p(n_valid), _i64p(n_dark)))
+    return out, n_valid, n_dark, names
+
+
+def template_features(grid_engine, samples):
+    """``lcf_template_features``: per sample and filter of the same grid, over the times in ascending order, the two
+    components' peaks, the first time the template term exceeds the base term and the dip of the sum between the peaks.
+    Returns ``(values[3, n_f, n], indices[4, n_f, n])`` in the order of ``TEMPLATE_FEATURE_VALUES`` /
+    ``TEMPLATE_FEATURE_INDICES``: a value is NaN where its index is -1."""
+    lib = load_library()
+    P, n_f, _ = _template_samples(grid_engine, samples)
+    values = np.empty((len(TEMPLATE_FEATURE_VALUES), n_f, P.shape[0]))
+    indices = np.empty((len(TEMPLATE_FEATURE_INDICES), n_f, P.shape[0]), dtype=np.int32)
+    _check(lib.lcf_template_features(grid_engine.handle, _ptr(P), P.shape[0], P.shape[1], _ptr(values),
+                                     _ptr(indices, _ip)))
+    return values, indices
 
 
 #: limits of the corner entry points (include/lcf.h)

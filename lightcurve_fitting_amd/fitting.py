@@ -336,10 +336,11 @@ def _refuse_template(model, what):
     """The predictive kernels evaluate the model themselves and do not know a second component."""
     if isinstance(model, WithTemplate):
         from .engine import LcfError
-        raise LcfError(5, f'{what} computes the model in kernels of its own, which do not know a second component: bands '
-                          'and colours of a WithTemplate model are out of scope; its fit (the tempered route, '
-                          'TemperedSampler) gives the chain, and model(t, f, *p) on a thinned chain evaluates its rows '
-                          '(model.components(t, f, *p) the two terms)')
+        raise LcfError(5, f'{what} computes the model in kernels of its own, which do not know a second component: '
+                          'template_predictive gives the bands of a WithTemplate model, of its two terms, and the dip '
+                          'and hand-over between them, over the chain its fit (the tempered route, TemperedSampler) '
+                          'gives; its colours and thermal bands are out of scope, and model(t, f, *p) on a thinned chain '
+                          'evaluates its rows (model.components(t, f, *p) the two terms)')
 
 
 def _model_samples(model, samples, discard, thin, use_sigma):
@@ -807,6 +808,149 @@ def custom_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=Non
     return CustomPredictive(times, filters, q, n_samples, bands[:, :nf][:, which], n_valid[:nf][which],
                             n_dark[:, where][which], bands[:, nf], bands[:, nf + 1], bands[:, nf + 2], n_valid[nf:],
                             None if n_cold is None else n_cold[where])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# bands and features of a template fit (a WithTemplate model: how much of the light is shock cooling and how much the
+# second peak, when the second component takes over, where and how deep the dip between the peaks is)
+# ---------------------------------------------------------------------------------------------------------------
+class TemplatePredictive:
+    """Result of :func:`template_predictive`: ``t`` (nt,), ``filters`` (nf Filter objects), ``percentiles`` (nq,),
+    ``n_samples``, ``components`` (the names asked for, in the order total, base, template); ``quantiles[c]`` (nq, nf, nt)
+    and ``n_valid[c]`` (nf, nt) -- the samples whose value is not NaN -- per component ``c`` (also ``.total``, ``.base``,
+    ``.template``: ``None`` where not asked for); ``n_dark`` (nf, nt): the samples whose base term is exactly ``+0.0``,
+    the shock has not started.  With ``features=True``, per filter and sample (nf, n), over the times in ascending order
+    (the first occurrence wins, comparisons are on values, a NaN never wins): ``y_peak_base`` / ``i_peak_base`` and
+    ``y_peak_template`` / ``i_peak_template`` -- the largest non-NaN base and template term and its index into ``t``
+    (NaN and -1: none); ``i_cross`` -- the first index with template > base (-1: none); ``y_dip`` / ``i_dip`` -- the
+    smallest non-NaN sum from the base's peak to the template's inclusive, defined only when the base peaks first (else
+    NaN and -1); the times ``t_peak_base``, ``t_peak_template``, ``t_cross``, ``t_dip`` (NaN where the index is -1) and the
+    counts ``n_cross_none``, ``n_dip_none`` (nf,); else all ``None``."""
+    FEATURE_TIMES = ('t_peak_base', 't_peak_template', 't_cross', 't_dip')
+    FEATURE_VALUES = ('y_peak_base', 'y_peak_template', 'y_dip')
+    FEATURE_INDICES = ('i_peak_base', 'i_peak_template', 'i_cross', 'i_dip')
+    __slots__ = ('t', 'filters', 'percentiles', 'n_samples', 'components', 'quantiles', 'n_valid', 'n_dark',
+                 'n_cross_none', 'n_dip_none') + FEATURE_TIMES + FEATURE_VALUES + FEATURE_INDICES
+
+    def __init__(self, t, filters, percentiles, n_samples, components, quantiles, n_valid, n_dark):
+        self.t, self.filters, self.percentiles, self.n_samples = t, filters, percentiles, n_samples
+        self.components, self.quantiles, self.n_valid, self.n_dark = components, quantiles, n_valid, n_dark
+        for name in self.__slots__[8:]:
+            setattr(self, name, None)
+
+    total = property(lambda self: self.quantiles.get('total'))
+    base = property(lambda self: self.quantiles.get('base'))
+    template = property(lambda self: self.quantiles.get('template'))
+
+    def set_features(self, values, indices):
+        """Attach the features: ``values`` (3, nf, n) and ``indices`` (4, nf, n) into ``t``, in the order of
+        ``FEATURE_VALUES`` / ``FEATURE_INDICES``.  The times and the counts follow on the host."""
+        t = np.asarray(self.t, dtype=np.float64)
+        for name, v in zip(self.FEATURE_VALUES, values):
+            setattr(self, name, v)
+        for name, t_name, i in zip(self.FEATURE_INDICES, self.FEATURE_TIMES, indices):
+            setattr(self, name, i)
+            setattr(self, t_name, np.where(i < 0, np.nan, t[np.maximum(i, 0)]))
+        self.n_cross_none = np.sum(self.i_cross < 0, axis=1)
+        self.n_dip_none = np.sum(self.i_dip < 0, axis=1)
+
+    def feature_summary(self, percentiles=(15.87, 50., 84.14)):
+        """``{name: (nq, nf)}`` for the four times and the three values: ``np.nanpercentile`` over the samples, per
+        filter (NaN where no sample has the feature)."""
+        if self.i_cross is None:
+            raise ValueError('the features were not computed: call template_predictive with features=True')
+        q = _percentile_array(percentiles)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)   # (every sample NaN: NaN)
+            return {name: np.nanpercentile(getattr(self, name), q, axis=1)
+                    for name in self.FEATURE_TIMES + self.FEATURE_VALUES}
+
+    def __repr__(self):
+        return (f'<TemplatePredictive: {len(self.percentiles)} percentiles x {len(self.components)} components x '
+                f'{len(self.filters)} filters x {len(self.t)} times over {self.n_samples} samples'
+                + ('' if self.i_cross is None else ', with features') + '>')
+
+
+def _template_model(model):
+    """``template_predictive`` takes a ``WithTemplate`` over a built-in shock-cooling base; everything else is refused
+    before anything is built, naming the function that does take it."""
+    from .engine import LcfError
+    if isinstance(model, WithTemplate):
+        if isinstance(model.base, CustomModel):
+            raise LcfError(5, 'template_predictive computes the base model in kernels compiled per built-in model, and the '
+                              'base of this WithTemplate is a CustomModel, compiled at run time: out of scope; '
+                              'model(t, f, *p) and model.components(t, f, *p) on a thinned chain evaluate its rows and '
+                              'their two terms')
+        return
+    if isinstance(model, CustomModel):
+        route = 'custom_predictive gives the bands of a CustomModel'
+    elif isinstance(model, BaseCentralEngine):
+        route = 'luminosity_predictive gives the bands of a central-engine model (Arnett, Magnetar)'
+    else:
+        route = (f'posterior_predictive gives the bands of a {type(model).__name__} (thermal_predictive and '
+                 'color_predictive its T, R, L and colours)')
+    raise LcfError(5, f'template_predictive takes a WithTemplate model, which has two terms to tell apart; {route}')
+
+
+def template_predictive(lc, model, samples, percentiles=(15.87, 50., 84.14), t=None, tmin=None, tmax=None, num=1000,
+                        xscale='linear', filters_to_model=None, discard=0, thin=1, use_sigma=False,
+                        components=('total', 'base', 'template'), features=True, workspace_bytes=None):
+    """Percentile bands of a :class:`~lightcurve_fitting_amd.models.WithTemplate` fit over ALL samples of a chain, on the
+    dense ``filters x times`` grid of :func:`predictive_grid` -- of the model, of its base term and of its template term
+    -- and, per sample, what only the two curves jointly tell: the two peaks, when the template takes over, and the dip
+    between the peaks.
+
+    ``model``: a ``WithTemplate`` whose base is a ``ShockCooling``, ``ShockCooling2``, ``ShockCooling3`` or
+    ``ShockCooling4`` (a ``CustomModel`` base and every other model raise ``LcfError`` naming their route).  ``samples``:
+    a host array ``(n_samples, n_columns)`` (``discard`` / ``thin`` do not apply), or any object with ``get_chain`` -- the
+    :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` that ``lightcurve_mcmc`` returned --: rows ``discard::thin``
+    of its cold rung, uploaded.  ``use_sigma``: the last column is the scatter and does not enter the model.
+    ``components``: which of ``'total'``, ``'base'``, ``'template'`` to rank.
+
+    Per sample, filter ``f`` and time, exactly as ``model.components`` defines them: ``B`` the base model's value,
+    ``Tm = r_f S_f((t - t_max - dt_f) (1 / s))`` the template term and ``Y = B + Tm``.  Every band is
+    ``np.nanpercentile(values, percentiles, axis=samples)`` with NumPy's default method, NaN where no sample has a value;
+    no value is stored per (sample, time): device memory beyond the samples stays below ``workspace_bytes`` (default
+    1 GiB; ``engine.template_workspace``), the times being worked through in tiles.  With ``features`` one more launch
+    walks every sample's curves (:class:`TemplatePredictive` has the definitions; 40 bytes per (sample, filter)).  At most
+    16 distinct filters.  Results are bitwise reproducible and do not depend on ``workspace_bytes``.  Returns a
+    :class:`TemplatePredictive`."""
+    from . import engine as _eng
+    _template_model(model)
+    q = _percentile_array(percentiles)
+    names, _ = _eng.template_components(components)
+    if not isinstance(samples, np.ndarray) and hasattr(samples, 'get_chain'):
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError('need discard >= 0 and thin >= 1')
+        samples = samples.get_chain(discard=discard, thin=thin, flat=True)
+        if len(samples) == 0:
+            raise ValueError(f'discard={discard} leaves no steps of the stored chain')
+        discard, thin = 0, 1
+    _, P, n_samples = _model_samples(model, samples, discard, thin, use_sigma)
+    times, filters = predictive_grid(lc, t, tmin, tmax, num, xscale, filters_to_model)
+    distinct, first, where = np.unique(times, return_index=True, return_inverse=True)   # every (time, filter) pair once
+    held = list(dict.fromkeys(filters))
+    which = [held.index(f) for f in filters]
+    if len(held) > _eng.TEMPLATE_MAX_FILTERS:
+        raise ValueError(f'the grid has {len(held)} distinct filters: template_predictive takes at most '
+                         f'{_eng.TEMPLATE_MAX_FILTERS} per call')
+
+    grid_engine, _ = Model._eval_engine(model, distinct, held, False)   # the dense grid, filter-major, template attached
+    per_call = max(1, _eng.PREDICT_MAX_SEARCHES // (len(names) * len(held)))
+    parts = [_eng.predict_template(grid_engine, P, q[k:k + per_call], names, workspace_bytes)
+             for k in range(0, len(q), per_call)]
+    bands = np.concatenate([part[0] for part in parts])[:, :, which][..., where]
+    _, n_valid, n_dark, _ = parts[0]
+    n_valid = n_valid[:, which][..., where]
+    res = TemplatePredictive(times, filters, q, n_samples, names, {c: bands[:, k] for k, c in enumerate(names)},
+                             {c: n_valid[k] for k, c in enumerate(names)}, n_dark[which][:, where])
+    if features:
+        values, indices = _eng.template_features(grid_engine, P)
+        # (an index is into the distinct times, ascending: to the first place of that time in t)
+        indices = np.where(indices < 0, -1, first[np.maximum(indices, 0)]).astype(np.int32)
+        res.set_features(values[:, which], indices[:, which])
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -732,8 +732,10 @@ class WithTemplate(Model):
     ``log_likelihood``, ``make_log_posterior``, ``engine_for``, ``lightcurve_mcmc`` and ``model(t, f, *p)`` work as for
     every model; :meth:`components` gives the two terms, ``temperature_radius`` is the base's.  The fit runs through
     :class:`~lightcurve_fitting_amd.sampler.TemperedSampler` (one rung at ``beta = 1`` unless a ladder or ``moves`` is
-    asked for): the resident samplers, population runs and the predictive functions compute the model in kernels of
-    their own and raise ``LcfError`` for it; ``model(t, f, *p)`` on a thinned chain gives the curves.  Non-detections
+    asked for): the resident samplers, population runs and the other predictive functions compute the model in kernels of
+    their own and raise ``LcfError`` for it.  :func:`~lightcurve_fitting_amd.fitting.template_predictive` gives the
+    bands of the model and of its two terms over a whole chain, and per sample the two peaks, the hand-over and the dip
+    between them (built-in bases); ``model(t, f, *p)`` on a thinned chain gives single curves.  Non-detections
     are measurements of zero, as in the reference: ``nondet='censored'`` raises ``ValueError`` (out of scope)."""
 
     def __init__(self, base, template, lc, columns=None, factors=(), offsets=(), scale='peak'):
