@@ -189,7 +189,10 @@ struct Window {
             finish(first_false, tau_ff);
         } else if (next == n_t) {
             if (!any_true) finish(n_t - 1, taus);
-            else finish(0, tau0);   // every m[k] true: argmin is 0
+            // every m[k] true: argmin is 0.  That needs taus[n_t - 1] > 0, and in exact arithmetic the normalised
+            // autocorrelations of a mean-subtracted series sum to taus[n_t - 1] = 0, so no honest chain comes here
+            // and no test does.
+            else finish(0, tau0);
         }
     }
     void finish(long long w, double t) {
